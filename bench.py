@@ -3,6 +3,7 @@
 Gauss-Newton kernel and a CPU baseline (BASELINE.json metric).
 
   python bench.py --gpus 1 --steps 600 --warmup 30
+  python bench.py --gpus 1 --steps 600 --warmup 30 --full --dump-outputs bench_outputs
   python bench.py --gpus N ...            (starts its N ranks itself through torch.distributed.run)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
@@ -15,6 +16,11 @@ static scene, rank r object r): rank 0 broadcasts the frame (RCCL), every rank p
 processFrame for the model it owns (mmf_fusion_set_shard), poses are all-gathered; value = model-frames/s over all
 ranks (weak scaling).  MMF_BENCH_WORKLOAD=config5 runs that workload at N = 1 too (the like-for-like base of the curve).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the line (value, ms_per_step).  --full adds everything else
+after the timed region: the roofline of the Gauss-Newton iteration kernel and the chain, the stand-alone ICP kernel, the surfel
+passes, the 8(f) extras, the mature map, the 1 .. 8-model sweep, the host upload, 1280x960, the CPU baseline and (N > 1) config5.
+--dump-outputs DIR writes what the last timed step handed its caller (poses, surfel map) as DIR/<name>.npy.
 """
 import argparse
 import gc
@@ -100,7 +106,27 @@ def self_launch(args):
            str(args.steps), "--warmup", str(args.warmup), "--roofline-frames", str(args.roofline_frames)]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
+    if args.full:
+        cmd.append("--full")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     return subprocess.call(cmd)
+
+
+def dump_outputs(out_dir, mmf, pose, budget=64 << 20):
+    """--dump-outputs: what the last timed processFrame handed its caller, as float32 .npy files -- `pose` (the step's pose),
+    `model_poses` (every active model's, list order) and `surfels` (the background model's map, Model::downloadMap, [count, 12];
+    a fixed seeded sample of its rows, in store order, when the files would exceed `budget` bytes)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"pose": np.asarray(pose, np.float32).reshape(4, 4),
+              "model_poses": np.stack([m.getPose() for m in mmf.getModels()]).astype(np.float32)}
+    surfels = mmf.getBackgroundModel().downloadMap()
+    room = max(0, budget - sum(a.nbytes for a in arrays.values()) - 1024) // (12 * 4)
+    if surfels.shape[0] > room:
+        surfels = surfels[np.sort(np.random.default_rng(0).choice(surfels.shape[0], room, replace=False))]
+    arrays["surfels"] = np.ascontiguousarray(surfels, np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(frames, K, W, H):
@@ -242,6 +268,9 @@ def main():
     ap.add_argument("--extras", action="store_true", default=True, help="also time the SURVEY 8(f) kernels beside the path: descriptor "
                     "matcher and SuperPoint (MFMA), super-pixel resampling (on by default: a few seconds)")
     ap.add_argument("--no-extras", dest="extras", action="store_false")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline after the timed region "
+                    "(roofline, surfel passes, extras, mature map, model sweep, host upload, 1280x960, CPU baseline, config5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))
@@ -617,39 +646,42 @@ def main():
         assert ranks_seen == world, f"{ranks_seen} ranks answered, {world} expected"
         assert all(g_["tracked_a_model_in_the_first_timed_step"] for g_ in gathered), \
             f"a rank had no model to track at the start of the timed region: {gathered}"
+    if rank == 0 and args.dump_outputs:  # before anything else runs a frame
+        dump_outputs(args.dump_outputs, mmf, last_pose)
+    t_err = None
+    if rank == 0 and not config5:  # accuracy sanity of the last timed frame against the known trajectory (relative to frame 0)
+        k = pingpong(state["frame"] - 1, len(frames))
+        gt = np.linalg.inv(poses[0]) @ poses[k]
+        t_err = float(np.linalg.norm(last_pose[:3, 3] - gt[:3, 3]))
 
-    # ---- roofline of the dominant kernel of the frame: the level-0 producer launch of the Gauss-Newton loop
-    # (track_producer_kernel: ICP J^T J reduction + photometric correspondence pass), timed INSIDE processFrame by
-    # start / stop HIP events on each launch (the dispatch's own timestamps, on the stream it is launched on).
-    # Every rank runs these extra frames (they contain the collectives); rank 0 reports its own model's kernels.
-    own = rank if config5 else 0
-    odom = mmf.getModelOdometry(own) if own < len(mmf.getModels()) else None
-    if odom is not None:
-        odom.enableTiming(2)
-    for i in range(args.roofline_frames):
-        step(args.warmup + args.steps + i)
-    fence()
-    tm = odom.getTiming() if odom is not None else None
-    if odom is not None:
-        odom.enableTiming(1)  # the chain as a whole, without the per-kernel events (they stretch it)
-    for i in range(args.roofline_frames):
-        step(args.warmup + args.steps + args.roofline_frames + i)
-    fence()
-    if odom is not None:
-        tm["chain_us"] = odom.getTiming()["chain_us"]
-        odom.enableTiming(0)
+    if args.full:
+        # ---- roofline of the dominant kernel of the frame: the level-0 producer launch of the Gauss-Newton loop
+        # (track_producer_kernel: ICP J^T J reduction + photometric correspondence pass), timed INSIDE processFrame by
+        # start / stop HIP events on each launch (the dispatch's own timestamps, on the stream it is launched on).
+        # Every rank runs these extra frames (they contain the collectives); rank 0 reports its own model's kernels.
+        own = rank if config5 else 0
+        odom = mmf.getModelOdometry(own) if own < len(mmf.getModels()) else None
+        if odom is not None:
+            odom.enableTiming(2)
+        for i in range(args.roofline_frames):
+            step(args.warmup + args.steps + i)
+        fence()
+        tm = odom.getTiming() if odom is not None else None
+        if odom is not None:
+            odom.enableTiming(1)  # the chain as a whole, without the per-kernel events (they stretch it)
+        for i in range(args.roofline_frames):
+            step(args.warmup + args.steps + args.roofline_frames + i)
+        fence()
+        if odom is not None:
+            tm["chain_us"] = odom.getTiming()["chain_us"]
+            odom.enableTiming(0)
 
     result = None
     if rank == 0:
         n0 = W * H
         model = mmf.getBackgroundModel()
         n_surfels = model.lastCount()
-        t_err = None
-        if not config5:  # accuracy sanity of the last tracked frame against the known trajectory (relative to frame 0)
-            k = pingpong(state["frame"] - 1, len(frames))
-            gt = np.linalg.inv(poses[0]) @ poses[k]
-            t_err = float(np.linalg.norm(last_pose[:3, 3] - gt[:3, 3]))
-
+    if rank == 0 and args.full:
         us = tm["producer_l0"]["mean_us"]
         fused = tm["rgb_step_l0"]["launches"] == 0  # the chain ran as one launch per iteration (csrc/gn_fused.hpp)
         if fused:
@@ -738,6 +770,7 @@ def main():
             "combinedPredict": {"us": us_spl, "bytes": b_spl, "GBps": b_spl / us_spl / 1e3, "frac": b_spl / us_spl / 1e3 / HBM_PEAK_GBPS,
                                 "kernels": "splat_kernel + splat_resolve_kernel"},
         }
+    if rank == 0:
         result = {
             "metric": f"frames/sec @ {W}x{H} (dense ICP+RGB tracking + surfel fusion); Gauss-Newton iteration kernel (ICP + RGB JtJ-reduce) achieved HBM GB/s vs peak",
             "value": world * args.steps / elapsed,
@@ -755,21 +788,19 @@ def main():
             "data": "synthetic",
             "config": {"workload": workload, "width": W, "height": H, "models_per_gpu": models_per_gpu,
                        "parallelism": f"model-shard x{world}"},
-            "roofline": roofline,
-            "gn_chain": gn_chain,
+            **({"roofline": roofline, "gn_chain": gn_chain} if args.full else {}),
             **({"per_rank": per_rank, "slowest_rank": max(per_rank, key=lambda r_: r_["step_ms"])["rank"],
                 "per_rank_what": "host wall clock per step inside the timed region: post_frame = starting the broadcasts, wait_frame = "
                                  "mmf_shard_wait_frame (or the torch work handles), gather_poses_end = picking up the all-gather of two steps "
                                  "ago, process_frame = the call itself (it ends when the rank's pose is on the host)"} if per_rank else {}),
-            "icp_kernel_standalone": icp_standalone,
-            "surfel_passes": surfel_passes,
+            **({"icp_kernel_standalone": icp_standalone, "surfel_passes": surfel_passes} if args.full else {}),
             "device": ctx.device_name(),
             "surfels": n_surfels,
             "icp_inliers_last": mmf.getFrameOdometry().lastICPCount,
         }
         if t_err is not None:
             result["last_frame_translation_error_m"] = t_err
-        if args.extras and not config5:
+        if args.full and args.extras and not config5:
             # the keypoint descriptor matcher: 1024 x 1024 descriptors of 256 floats on v_mfma_f32_32x32x2_f32
             gen = torch.Generator(device="cpu").manual_seed(0)
             dq = torch.nn.functional.normalize(torch.randn(1024, 256, generator=gen), dim=1).to(dev)
@@ -802,12 +833,12 @@ def main():
             result["slic_downsample"] = {"us": timed(slic_raw, reps=50), "superpixels": (H // S) * (W // S), "bytes_in": 8 * n0}
         if config5 and world > 1:
             result["config"]["scaling_note"] = ("weak scaling: the frame size is the N = 1 metric's (640x480) and every GPU runs one rigid-body "
-                                                "model; BASELINE.json configs[4] (1280x960) on the same ranks is the `config5` object of this "
-                                                "line, its N = 1 counterpart `MMF_BENCH_WORKLOAD=config5 python bench.py` (profiles/)")
+                                                "model; BASELINE.json configs[4] (1280x960) on the same ranks is the `config5` object of the "
+                                                "--full line, its N = 1 counterpart `MMF_BENCH_WORKLOAD=config5 python bench.py` (profiles/)")
 
     # MMF_BENCH_HEADLINE_ONLY=1: only the frames of the N = 1 metric (for profiler runs whose per-kernel statistics must
     # not mix in the 1 .. 8-model sweep and the host-upload variant below)
-    if rank == 0 and world == 1 and not config5 and os.environ.get("MMF_BENCH_HEADLINE_ONLY", "") != "1":
+    if args.full and rank == 0 and world == 1 and not config5 and os.environ.get("MMF_BENCH_HEADLINE_ONLY", "") != "1":
         # ---- a MATURE map at the metric's frame size (SURVEY 8(d) states the surfel-pass bytes at ~1 M surfels; the headline
         # loop resets its map every 30 frames).  The map of the sequence so far is replicated 1 + 3 times, the copies pushed
         # 2, 4 and 6 cm along the viewing rays behind the surfaces (occluded: what a store that has seen a room from many sides is
@@ -968,7 +999,7 @@ def main():
         if not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(frames, K, W, H)
     fence()
-    if world > 1 and env_workload != "config5" and os.environ.get("MMF_BENCH_SKIP_CONFIG5", "") != "1":
+    if args.full and world > 1 and env_workload != "config5" and os.environ.get("MMF_BENCH_SKIP_CONFIG5", "") != "1":
         # ---- BASELINE.json configs[4] on the same ranks, outside the contract's timed region: 1280x960, one rigid body per GPU
         mmf.close()
         c5_mmf, c5_step, c5_fence, c5_text = make_shard_workload(1280, 960)

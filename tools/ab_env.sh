@@ -5,7 +5,7 @@ reps=$1; shift
 for r in $(seq 1 $reps); do
   for cfg in "$@"; do
     c="$cfg"; [ "$c" = "-" ] && c="MMF_NOP=1"
-    env $c MMF_BENCH_HEADLINE_ONLY=1 timeout -k 10 120 python bench.py --steps 150 --warmup 20 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+    env $c MMF_BENCH_HEADLINE_ONLY=1 timeout -k 10 120 python bench.py --full --steps 150 --warmup 20 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read().strip().splitlines()[-1]); p=d['gn_chain']['per_level']

@@ -4,7 +4,7 @@
 reps=$1; shift
 for r in $(seq 1 $reps); do
   for lib in "$@"; do
-    MMF_HIP_LIB=$PWD/$lib MMF_BENCH_HEADLINE_ONLY=1 timeout -k 10 120 python bench.py --steps 150 --warmup 20 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+    MMF_HIP_LIB=$PWD/$lib MMF_BENCH_HEADLINE_ONLY=1 timeout -k 10 120 python bench.py --full --steps 150 --warmup 20 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read().strip().splitlines()[-1]); p=d['gn_chain']['per_level']
