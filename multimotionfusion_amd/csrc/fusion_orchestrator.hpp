@@ -1264,6 +1264,11 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
                                                f->frame_depth, f->depth_filtered, g.outlier_coeff, wts);
             }
             if (rc) return rc;
+            // the other objects' streams continue behind the batch: a model left out of the predict batch below (a deep store,
+            // mmf_debug_set_splat_bound) is predicted on its own stream, and a predict batch led by another object joins the
+            // lanes as they stand -- both read the maps this batch writes
+            MMF_HIP_TRY(hipEventRecord(objs[0]->ev_done, st));
+            for (size_t k = 1; k < objs.size(); ++k) MMF_HIP_TRY(hipStreamWaitEvent(objs[k]->lane->stream, objs[0]->ev_done, 0));
         }
     }
     stamp(3);

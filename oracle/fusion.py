@@ -62,6 +62,7 @@ class OracleFusion:
         self.models = [OracleModel(self._next_model_id(True), conf, w, h, K, True)]
         self.inactive = []
         self.tick = 1  # MultiMotionFusion.cpp:36
+        self.clean_log = []  # (tick, model id, orc.clean's rule counts, surfels removed) of every clean pass
         self.mask = np.zeros((h, w), np.uint8)  # textures[MASK]
         self.last_image_ring = None
 
@@ -99,6 +100,19 @@ class OracleFusion:
         for m in self.models:
             self._predict_model(m, rgb, fil)
 
+    def adopt(self, model_index, surfels, pose, rgb, filtered_depth):
+        """Take over a model's state between two frames (a map and a pose from elsewhere, e.g. the GPU's): set them, then
+        render the predicted and fill-in images as the end-of-frame predict() of the previous frame did -- from that frame's
+        rgb and filtered depth, at that call's tick (tick - 1 of the counter, which has advanced since)."""
+        m = self.models[model_index]
+        m.surfels = np.ascontiguousarray(surfels, np.float32).reshape(-1, 12).copy()
+        m.override_pose(pose)
+        self.tick -= 1
+        try:
+            self._predict_model(m, rgb, filtered_depth)
+        finally:
+            self.tick += 1
+
     # -- predictIndices / fuse / predictIndices / clean of one model (:791-816) -------------------------------
     def _fuse_clean_model(self, m, rgb, depth, fil, weight, second_predict=True):
         index, vc, ct, nr = orc.predict_indices(m.surfels, m.pose, self.K, self.w, self.h, self.max_depth, self.tick,
@@ -109,8 +123,9 @@ class OracleFusion:
         if second_predict:
             index, vc, ct, nr = orc.predict_indices(s_upd, m.pose, self.K, self.w, self.h, self.max_depth, self.tick,
                                                     self.time_delta)
-        m.surfels = orc.clean(s_upd, new, m.pose, self.K, self.w, self.h, self.tick, self.time_delta, m.conf,
-                              self.outlier_coeff, m.id, index, vc, ct, fil, self.mask)
+        m.surfels, stats = orc.clean(s_upd, new, m.pose, self.K, self.w, self.h, self.tick, self.time_delta, m.conf,
+                                     self.outlier_coeff, m.id, index, vc, ct, fil, self.mask, with_stats=True)
+        self.clean_log.append((self.tick, m.id, stats, s_upd.shape[0] + new.shape[0] - m.surfels.shape[0]))
 
     # -- Model::performTracking (Model.cpp:409-433) with Model::initICP (:390-407) ----------------------------
     def _perform_tracking(self, m, rgb, fil, do_fill_in):
@@ -127,14 +142,20 @@ class OracleFusion:
                                                    self.pyramid, self.fast_odom, self.so3)
         m.pose = np.eye(4, dtype=np.float32)
         m.pose[:3, :3], m.pose[:3, 3] = R, t
+        m.tracked_pose, m.tracked_stats = m.pose.copy(), m.odom.stats()
 
     def process_frame(self, rgb, depth, timestamp=0, in_pose=None, weight_multiplier=1.0, bootstrap=False,
                       init_transform=None, init_transforms=None, icp_refine=True, mask=None, has_new_label=False,
-                      model_data=None):
+                      model_data=None, substitute_poses=None):
         """mask / has_new_label / model_data: the SegmentationResult of this frame (fullSegmentation, hasNewLabel,
-        modelData as dicts with id, super_pixel_count, avg_confidence, depth_mean, depth_std)."""
+        modelData as dicts with id, super_pixel_count, avg_confidence, depth_mean, depth_std).
+        substitute_poses: one 4x4 per model (a single 4x4: the first model) that replaces the pose each model's own
+        tracking arrives at -- the tracking still runs and leaves its result in `tracked_pose` / `tracked_stats`, and
+        `last_pose` stays the pose before it, so computeFusionWeight sees the substituted motion (in_pose would reset it)."""
         if init_transform is not None:
             init_transforms = [init_transform]
+        if substitute_poses is not None and np.ndim(substitute_poses) == 2:
+            substitute_poses = [substitute_poses]
         fil = orc.bilateral_filter(depth, self.depth_cutoff)  # filterDepth (:262)
         if not self.enable_multiple_models:
             self.mask = np.zeros((self.h, self.w), np.uint8)  # :268-275
@@ -161,6 +182,8 @@ class OracleFusion:
                         do_fill = m.fill_in and bool(orc.requires_fill_in(m.image, 0.75))  # requiresFillIn (:877-895)
                         m.fill_in_taken = do_fill
                         self._perform_tracking(m, rgb, fil, do_fill)
+                        if substitute_poses is not None and k < len(substitute_poses):
+                            m.pose = np.array(substitute_poses[k], np.float32).reshape(4, 4).copy()
                 if bootstrap:  # :397-400
                     g.override_pose(orc.matmul4f(g.pose, np.asarray(in_pose, np.float32).reshape(4, 4)))
                 if self.enable_multiple_models:  # :407-622

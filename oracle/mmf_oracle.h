@@ -188,6 +188,13 @@ int orc_clean(const orc_surfel *s, int count, const orc_surfel *new_unstable, in
               float confThreshold, float outlierCoeff, uint8_t maskID, const uint32_t *index,
               const float *vertConf, const float *colorTime, const float *depth_filtered, const uint8_t *mask,
               orc_surfel *out);
+enum { ORC_CLEAN_KEPT, ORC_CLEAN_WINDOW_COUNT, ORC_CLEAN_Z_COUNT, ORC_CLEAN_UNSTABLE, ORC_CLEAN_COL_W, ORC_CLEAN_KEPT_TIME_DELTA,
+       ORC_CLEAN_RULES };
+int orc_clean_stats(const orc_surfel *s, int count, const orc_surfel *new_unstable, int nnew, const float pose[16],
+                    float cx, float cy, float fx, float fy, int cols, int rows, int time, int timeDelta,
+                    float confThreshold, float outlierCoeff, uint8_t maskID, const uint32_t *index,
+                    const float *vertConf, const float *colorTime, const float *depth_filtered, const uint8_t *mask,
+                    orc_surfel *out, int stats[ORC_CLEAN_RULES]);
 void orc_fill_in(const float *vertex_pred, const float *normal_pred, const uint8_t *image_pred_rgba,
                  const float *depth_filtered, const uint8_t *rgb, int cols, int rows, float cx, float cy,
                  float fx, float fy, int passthrough_geom, int passthrough_rgb, float *vertex_out,

@@ -502,7 +502,7 @@ int orc_fuse(orc_surfel *s, int count, const uint8_t *rgb, const float *depth_ra
 static int clean_one(orc_surfel *v, const float t_inv[16], float cx, float cy, float fx, float fy, int cols, int rows,
                      int time, int timeDelta, float confThreshold, float outlierCoeff, uint8_t maskID,
                      const uint32_t *index, const float *vertConf, const float *colorTime, const float *depth_in,
-                     const uint8_t *mask) {
+                     const uint8_t *mask, int *rule) {
     int test = 1;
     const float scale = 1.0f;
     const v3 localPos = m4point(t_inv, V3(v->pos[0], v->pos[1], v->pos[2]));
@@ -543,8 +543,14 @@ static int clean_one(orc_surfel *v, const float t_inv[16], float cx, float cy, f
     }
     if (count > 8 || zCount > 4) test = 0;
     if (v->col[3] == -2) v->col[3] = (float)time;
-    if ((v->col[3] == -1 || (((float)time - v->col[3]) > 20 && v->pos[3] < confThreshold))) test = 0;
-    if (v->col[3] > 0 && (float)time - v->col[3] > (float)timeDelta) test = 1;
+    const int unstable = ((float)time - v->col[3]) > 20 && v->pos[3] < confThreshold;
+    if ((v->col[3] == -1 || unstable)) test = 0;
+    const int outside = v->col[3] > 0 && (float)time - v->col[3] > (float)timeDelta;
+    if (outside) test = 1;
+    /* which rule decided (orc_clean_stats): the first removal rule that holds, in the order of ORC_CLEAN_* */
+    *rule = outside ? ORC_CLEAN_KEPT_TIME_DELTA : test ? ORC_CLEAN_KEPT
+          : count > 8 ? ORC_CLEAN_WINDOW_COUNT : zCount > 4 ? ORC_CLEAN_Z_COUNT
+          : unstable ? ORC_CLEAN_UNSTABLE : ORC_CLEAN_COL_W;
     if (violationCount > 0) {
         avgViolation /= violationCount;
         v->pos[3] *= 1.0f / (1 + outlierCoeff * avgViolation);
@@ -560,6 +566,19 @@ int orc_clean(const orc_surfel *s, int count, const orc_surfel *new_unstable, in
               float cx, float cy, float fx, float fy, int cols, int rows, int time, int timeDelta,
               float confThreshold, float outlierCoeff, uint8_t maskID, const uint32_t *index, const float *vertConf,
               const float *colorTime, const float *depth_filtered, const uint8_t *mask, orc_surfel *out) {
+    return orc_clean_stats(s, count, new_unstable, nnew, pose, cx, cy, fx, fy, cols, rows, time, timeDelta, confThreshold,
+                           outlierCoeff, maskID, index, vertConf, colorTime, depth_filtered, mask, out, NULL);
+}
+
+/* orc_clean, and how many surfels each rule decided: stats[ORC_CLEAN_*] (ORC_CLEAN_KEPT + ORC_CLEAN_KEPT_TIME_DELTA =
+   the surfels kept, the four others add up to the surfels removed) */
+int orc_clean_stats(const orc_surfel *s, int count, const orc_surfel *new_unstable, int nnew, const float pose[16],
+                    float cx, float cy, float fx, float fy, int cols, int rows, int time, int timeDelta,
+                    float confThreshold, float outlierCoeff, uint8_t maskID, const uint32_t *index, const float *vertConf,
+                    const float *colorTime, const float *depth_filtered, const uint8_t *mask, orc_surfel *out,
+                    int stats[ORC_CLEAN_RULES]) {
+    if (stats)
+        for (int r = 0; r < ORC_CLEAN_RULES; ++r) stats[r] = 0;
     float t_inv[16];
     orc_inverse4f(pose, t_inv);
     int n = 0;
@@ -568,9 +587,11 @@ int orc_clean(const orc_surfel *s, int count, const orc_surfel *new_unstable, in
         const int m = pass == 0 ? count : nnew;
         for (int k = 0; k < m; ++k) {
             orc_surfel v = src[k];
+            int rule;
             if (clean_one(&v, t_inv, cx, cy, fx, fy, cols, rows, time, timeDelta, confThreshold, outlierCoeff, maskID,
-                          index, vertConf, colorTime, depth_filtered, mask))
+                          index, vertConf, colorTime, depth_filtered, mask, &rule))
                 out[n++] = v;
+            if (stats) ++stats[rule];
         }
     }
     return n;

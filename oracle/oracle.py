@@ -478,19 +478,31 @@ def fuse(surfels, rgb, depth_raw, depth_filtered, mask, index, vertConf, normRad
     return s, new[:n].copy()
 
 
+CLEAN_RULES = ("kept", "window_count", "z_count", "unstable", "col_w", "kept_time_delta")  # enum ORC_CLEAN_* (mmf_oracle.h)
+
+
 def clean(surfels, new_unstable, pose, K, cols, rows, time, timeDelta, confThreshold, outlierCoeff, maskID, index,
-          vertConf, colorTime, depth_filtered, mask):
+          vertConf, colorTime, depth_filtered, mask, with_stats=False):
+    """Model::clean.  with_stats: also return how many surfels each rule decided, a dict over CLEAN_RULES -- a removed
+    surfel counts under the first of `count > 8` (window_count), `zCount > 4` (z_count), the 20-frame unstable rule and
+    `col.w == -1` that holds; kept_time_delta: kept by `time - t > timeDelta` (copy_unstable.vert)."""
     s, nu = _surf(surfels), _surf(new_unstable)
     pose = _f(np.reshape(pose, 16))
     index = np.ascontiguousarray(index, np.uint32)
     vc, ct, df = _f(vertConf), _f(colorTime), _f(depth_filtered)
     mask = np.ascontiguousarray(mask, np.uint8)
     out = np.zeros((s.shape[0] + nu.shape[0] + 1, 12), np.float32)
-    lib().orc_clean.restype = C.c_int
-    n = lib().orc_clean(_pf(s), s.shape[0], _pf(nu), nu.shape[0], _pf(pose), _cf(K["cx"]), _cf(K["cy"]), _cf(K["fx"]),
-                        _cf(K["fy"]), cols, rows, int(time), int(timeDelta), _cf(confThreshold), _cf(outlierCoeff),
-                        C.c_uint8(maskID), _pu32(index), _pf(vc), _pf(ct), _pf(df), _pu8(mask), _pf(out))
-    return out[:n].copy()
+    args = (_pf(s), s.shape[0], _pf(nu), nu.shape[0], _pf(pose), _cf(K["cx"]), _cf(K["cy"]), _cf(K["fx"]), _cf(K["fy"]), cols,
+            rows, int(time), int(timeDelta), _cf(confThreshold), _cf(outlierCoeff), C.c_uint8(maskID), _pu32(index), _pf(vc),
+            _pf(ct), _pf(df), _pu8(mask), _pf(out))
+    if not with_stats:
+        lib().orc_clean.restype = C.c_int
+        n = lib().orc_clean(*args)
+        return out[:n].copy()
+    stats = (C.c_int * len(CLEAN_RULES))()
+    lib().orc_clean_stats.restype = C.c_int
+    n = lib().orc_clean_stats(*args, stats)
+    return out[:n].copy(), dict(zip(CLEAN_RULES, list(stats)))
 
 
 def fill_in(vertex_pred, normal_pred, image_pred, depth_filtered, rgb, K, passthrough_geom, passthrough_rgb):

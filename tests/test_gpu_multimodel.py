@@ -560,3 +560,66 @@ def test_object_preparation_by_box_equals_whole_frame_preparation(gpu_ctx, fused
         assert ma.shape == mb.shape and np.array_equal(ma.view(np.uint32), mb.view(np.uint32))
     for ea, eb in zip(a[2], b[2]):
         assert np.array_equal(ea.view(np.uint32), eb.view(np.uint32))
+
+
+@pytest.mark.parametrize("left_out", ["splat_bound", "deep_store"])
+def test_batched_passes_with_models_left_out_of_the_predict_batch(gpu_ctx, left_out):
+    """The object models' fuse / clean batch runs on the first object's stream; a model that is then left out of the predict
+    batch -- every model under mmf_debug_set_splat_bound(1), or one whose store is deep (model_predict_batchable) -- is
+    predicted on its own stream, and must not start before the batch has written its map (csrc/fusion_orchestrator.hpp: the
+    object lanes wait on the batch).  Every model's poses, maps and predicted images, every frame, must be those of the passes
+    model by model (pass_batch 0), bit for bit.  A race need not show on every run: this test keeps it from coming back."""
+    from multimotionfusion_amd.fusion import MultiMotionFusion
+    lib = gpu_ctx.lib
+    w, h, n_obj = 320, 240, 4
+    n_frames = n_obj + 4
+    K, poses, traj, frames, objs = scene(w, h, n_frames, n_obj, seed=39)
+    rgb, depth = [dev(f["rgb"]) for f in frames], [dev(f["depth"]) for f in frames]
+    deep_at, deep_model = 2, 2  # after frame 2 the SECOND object (not the one whose stream the batches run on) turns deep
+
+    def run(batch):
+        lib.mmf_debug_set_pass_batch(batch)
+        lib.mmf_debug_set_splat_bound(1 if left_out == "splat_bound" else -1)
+        g = MultiMotionFusion(gpu_ctx, w, h, K["cx"], K["cy"], K["fx"], K["fy"], enable_multiple_models=1, preallocated_models=n_obj)
+        known, keep, out = [0], [], []
+        try:
+            for i, f in enumerate(frames):
+                spawn = 1 <= i <= n_obj
+                if spawn:
+                    known.append(i)
+                keep.append(dev(gt_mask(f["ids"], known)))
+                nxt = (rgb[i + 1], depth[i + 1]) if i + 1 < n_frames else None
+                g.processFrame(rgb[i], depth[i], timestamp=i, mask=keep[-1], hasNewLabel=spawn, next=nxt)
+                torch.cuda.synchronize()
+                models = g.getModels()
+                out.append(([m.getPose() for m in models], [m.downloadMap() for m in models],
+                            [[m.texture(n).cpu().numpy().copy() for n in ("image", "vertexConf", "normalRadius")] for m in models]))
+                if left_out == "deep_store" and i == deep_at:
+                    # copies of its map 1 km to the side: never in view, never cleaned within the sequence, and a store of at
+                    # least two surfels per pixel (deep: its combinedPredict is not batched)
+                    m = models[deep_model]
+                    s = m.downloadMap()
+                    reps = -(-2 * w * h // s.shape[0])
+                    far = np.tile(s, (reps, 1))
+                    far[:, 0] += np.float32(1000.0)
+                    m.uploadMap(np.concatenate([s, far]))
+            if left_out == "deep_store":
+                assert g.getModels()[deep_model].lastCount() >= 2 * w * h
+        finally:
+            g.close()
+            lib.mmf_debug_set_splat_bound(-1)
+            lib.mmf_debug_set_pass_batch(-1)
+        return out
+
+    ref = run(0)
+    assert len(ref[-1][0]) == n_obj + 1 and all(m.shape[0] > 100 for m in ref[-1][1])
+    for batch in (1, 2):
+        got = run(batch)
+        for i in range(n_frames):
+            (pa, ma, ta), (pb, mb, tb) = ref[i], got[i]
+            assert len(pa) == len(pb), (batch, i)
+            for k in range(len(pa)):
+                assert np.array_equal(pa[k], pb[k]), (batch, i, k)
+                assert ma[k].shape == mb[k].shape and np.array_equal(ma[k].view(np.uint32), mb[k].view(np.uint32)), (batch, i, k)
+                for x, y in zip(ta[k], tb[k]):
+                    assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), (batch, i, k)

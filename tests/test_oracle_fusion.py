@@ -119,3 +119,87 @@ def test_object_tracking_is_sensitive_to_one_ulp_noise():
     obj = max(float(np.abs(p - q).max()) for x, y in zip(a, b) for p, q in zip(x[1:], y[1:]))
     assert glob < 1e-6, glob
     assert obj > 20 * glob, (glob, obj)  # measured: 1e-5 .. 1e-3 against < 1e-7
+
+
+def _tracked_run(w, h, n, conf=10.0, seed=7, adopt_at=(), substitute=None):
+    """A free-running oracle orchestration; before the frames in `adopt_at` the oracle takes over its own state
+    (OracleFusion.adopt); `substitute`: the poses to hand in after each frame's tracking (substitute_poses)."""
+    K = synth.intrinsics(w, h)
+    poses = synth.trajectory(n, seed=seed)
+    frames = [synth.render(p, w, h, seed=i) for i, p in enumerate(poses)]
+    o = OracleFusion(w, h, K, conf=conf)
+    out = []
+    for i, f in enumerate(frames):
+        if i in adopt_at:
+            m = o.models[0]
+            before = [m.image, m.vertexConf, m.normalRadius, m.time_tex, m.fillVertex, m.fillNormal, m.fillImage]
+            prev = frames[i - 1]
+            o.adopt(0, o.surfels.copy(), o.pose.copy(), prev["rgb"], orc.bilateral_filter(prev["depth"], o.depth_cutoff))
+            after = [m.image, m.vertexConf, m.normalRadius, m.time_tex, m.fillVertex, m.fillNormal, m.fillImage]
+            for a, b in zip(before, after):  # the images the end-of-frame predict() left, regenerated
+                assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8)), i
+        o.process_frame(f["rgb"], f["depth"], substitute_poses=None if substitute is None or i == 0 else substitute[i])
+        out.append((o.pose.copy(), o.surfels.copy(), getattr(o.models[0], "tracked_pose", None), o.models[0].image.copy()))
+    return o, out
+
+
+def test_adopting_its_own_state_changes_no_bit():
+    """OracleFusion.adopt (the re-synchronised GPU tests hand the oracle the device's map and pose before each frame) renders
+    the predicted and fill-in images of the previous frame's end again: with the oracle's own state they are the same bits,
+    and so is everything after.  Threshold 0.5: the splat draws most of the map (at 10 nothing is stable for ~12 frames)."""
+    for conf in (10.0, 0.5):
+        _, a = _tracked_run(160, 120, 6, conf=conf)
+        _, b = _tracked_run(160, 120, 6, conf=conf, adopt_at=(3, 4))
+        assert conf == 10.0 or (a[-1][3][..., 3] > 0).mean() > 0.5  # (non-empty predicted images were regenerated)
+        for i, (x, y) in enumerate(zip(a, b)):
+            assert np.array_equal(x[0], y[0]), (conf, i)
+            assert np.array_equal(x[1].view(np.uint32), y[1].view(np.uint32)), (conf, i)
+
+
+def test_substituting_the_tracked_pose():
+    """process_frame(substitute_poses=...) tracks, keeps the tracker's result in tracked_pose, then goes on with the pose handed
+    in: its own poses give a plain run's bits; another pose moves the map, but not what the tracker found, and the fusion weight
+    sees the substituted motion (last_pose is not reset)."""
+    _, a = _tracked_run(160, 120, 5)
+    _, b = _tracked_run(160, 120, 5, substitute=[x[0] for x in a])
+    for i, (x, y) in enumerate(zip(a, b)):
+        assert np.array_equal(x[0], y[0]) and np.array_equal(x[1].view(np.uint32), y[1].view(np.uint32)), i
+        assert i == 0 or np.array_equal(y[2], x[0]), i
+    nudged = [x[0].copy() for x in a]
+    nudged[2][0, 3] += np.float32(2e-3)
+    o, c = _tracked_run(160, 120, 3, substitute=nudged)
+    assert np.array_equal(c[2][2], a[2][0]) and np.array_equal(c[2][0], nudged[2])
+    assert c[2][1].shape != a[2][1].shape or not np.array_equal(c[2][1], a[2][1])
+    m = o.models[0]
+    assert np.array_equal(m.last_pose, a[1][0]) and orc.compute_fusion_weight(m.pose, m.last_pose, 1.0) < 1.0
+
+
+def test_clean_rule_counts_add_up():
+    """orc_clean_stats: the surfels each rule of Model::clean removed add up to the surfels removed, the kept ones to the map
+    left behind; the plain entry point gives the same bits.  Two dictated sequences that reach the rules: 40 frames (stable
+    surfels from frame 12: the window rules `count > 8` and `zCount > 4`, the 20-frame unstable rule) and a pan with
+    timeDelta 10 (surfels outside the window kept by `time - t > timeDelta`)."""
+    w, h = 160, 120
+    K = synth.intrinsics(w, h)
+    seen = dict.fromkeys(orc.CLEAN_RULES, 0)
+    for poses, td in ((synth.trajectory(40, seed=23), 200),
+                      ([synth.make_pose([0, np.deg2rad(1.5 * i), 0], [0, 0, 0]) for i in range(13)], 10)):
+        o = OracleFusion(w, h, K, time_delta=td)
+        for i, p in enumerate(poses):
+            f = synth.render(p, w, h, seed=i)
+            o.process_frame(f["rgb"], f["depth"], in_pose=None if i == 0 else (np.linalg.inv(poses[0]) @ p).astype(np.float32))
+        for tick, mid, st, removed in o.clean_log:  # every clean of the sequence
+            assert st["window_count"] + st["z_count"] + st["unstable"] + st["col_w"] == removed, (tick, st, removed)
+            for k, v in st.items():
+                seen[k] += v
+        # one more clean by hand: the counts of that call, and the plain entry point's bits
+        m, fil = o.models[0], orc.bilateral_filter(f["depth"], o.depth_cutoff)
+        index, vc, ct, nr = orc.predict_indices(m.surfels, m.pose, K, w, h, o.max_depth, o.tick, td)
+        s_upd, new = orc.fuse(m.surfels, f["rgb"], f["depth"], fil, o.mask, index, vc, nr, m.pose, K, o.tick, 1.0, 0, o.max_depth)
+        args = (s_upd, new, m.pose, K, w, h, o.tick, td, m.conf, o.outlier_coeff, 0, index, vc, ct, fil, o.mask)
+        plain = orc.clean(*args)
+        stat_out, stats = orc.clean(*args, with_stats=True)
+        assert np.array_equal(plain.view(np.uint32), stat_out.view(np.uint32))
+        assert stats["kept"] + stats["kept_time_delta"] == plain.shape[0]
+        assert sum(stats.values()) == s_upd.shape[0] + new.shape[0]
+    assert all(seen[k] > 0 for k in ("window_count", "z_count", "unstable", "kept_time_delta")), seen
