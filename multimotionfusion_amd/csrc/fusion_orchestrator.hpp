@@ -611,12 +611,13 @@ static float seg_max_depth(const mmf_segmentation_model& d) { return (float)((do
 // test / A-B hook: how the object models' passes go out (fusion_batch_mode)
 static std::atomic<int> g_batch_passes{-1};  // -1: MMF_PASS_BATCH / the number of object models decide
 extern "C" int mmf_debug_set_pass_batch(int mode) {
-    g_batch_passes.store(mode < 0 ? -1 : (mode > 2 ? 2 : mode));
+    MMF_REQUIRE(mode == -1 || mode == 0 || mode == 2, "mmf_debug_set_pass_batch: mode must be -1, 0 or 2");
+    g_batch_passes.store(mode);
     return MMF_OK;
 }
-// 0: model by model; 1: one launch per pass, each covering the whole frame (*_batched_kernel); 2: one launch per pass,
-// restricted to where the models are (pass_rect.hpp).  Neither the hook nor MMF_PASS_BATCH says: by the number of object
-// models this GPU runs -- model by model on the models' own streams up to three of them, restricted launches from four on
+// 0: model by model; 2: one launch per pass, restricted to where the models are (pass_rect.hpp).  Neither the hook nor
+// MMF_PASS_BATCH says: by the number of object models this GPU runs -- model by model on the models' own streams up to three
+// of them, restricted launches from four on
 // (measured, LABNOTES r5: 8 models 0.69-0.70 against 0.76-0.78 ms, 5 models 0.60-0.62 against 0.65-0.67, 4 models 0.575-0.58
 // against 0.55-0.59)
 constexpr int kRectPassObjects = 4;
@@ -692,621 +693,684 @@ static hipError_t fusion_wait_unless_done(hipStream_t s, hipEvent_t e) {
 }
 static int fusion_stage_host_rgb(mmf_fusion* f);
 
-static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
-    MMF_REQUIRE(f != nullptr && fr != nullptr, "mmf_fusion_process_frame: null argument");
-    const uint8_t* rgb = fr->rgb;
-    const float* depth = fr->depth;
-    if (!rgb || !depth || fr->timestamp < 0)  // MultiMotionFusion.cpp:209-212
-        return fail(MMF_ERR_INVALID, "invalid image data");
-    mmf_ctx* c = f->ctx;
-    MMF_HIP_TRY(hipSetDevice(c->device));
-    const auto t_begin = std::chrono::steady_clock::now();
-    // MMF_HOST_TRACE=1: where the calling thread is, in us after the call began, at six points of the call (averages over 100 calls)
-    const bool host_trace = tunables().host_trace;
-    auto stamp = [&](int i) {
+// ---- processFrame (MultiMotionFusion.cpp:207-854), stage by stage ----------------------------------------------------------
+// With several models a frame waits for the thread that enqueues its work: which launches, events and waits the stages
+// below enqueue, and in what order, is the frame's speed.
+
+// what the stages of one processFrame call hand on to each other
+struct FrameRun {
+    const mmf_frame* fr = nullptr;
+    std::chrono::steady_clock::time_point t_begin;
+    bool host_trace = false;  // MMF_HOST_TRACE
+    bool have_init = false;   // odom_cfg.init == "kp"
+    bool track = false;       // :299 "regular execution"
+    bool prefetched = false;  // the filter (:262) and the input-side preparation ran on the side stream
+    const OdomState* so3_stage = nullptr;  // this frame's own SO3 pre-alignment, computed ahead
+    // tracking
+    bool one_pass = false;    // one model: its sensor side and model side share the launches of one preparation
+    bool lanes_wait = false;  // other streams wait for ev_frame_ready
+    int owned = 0;            // models this rank runs, before the tracking
+    bool will_batch = false;  // the tracked models will share one chain led by the camera model
+    int early_image = 0;      // where the next frame's image side is enqueued (MMF_EARLY_IMAGE: 2 start, 1 chain, 0 off)
+    bool next_from_host = false, image_early_any = false, image_early_ok = false;
+    std::vector<FusionModel*> tracked;
+    bool batched = false;  // one chain for all tracked models is planned ...
+    bool batch_ok = false;  // ... and runs
+    mmf_model early_snapshot;  // the model's host bookkeeping before the passes enqueued ahead of the pose (fusion_retrack)
+    bool early_snapshot_valid = false;
+    int pass_mode = 0;  // fusion_batch_mode, once the frame's model list is final
+
+    // MMF_HOST_TRACE=1: where the calling thread is, in us after the call began (averages over 100 calls)
+    void stamp(mmf_fusion* f, int i) const {
         if (host_trace) f->trace_us[i] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_begin).count();
-    };
-    f->t_tracking_s = 0;
+    }
+};
+
+// a pose's translation and rotation (row-major 3 x 3), as a tracking starts from them
+static void pose_trans_rot(const float* pose, float* trans, float* rot) {
+    for (int r = 0; r < 3; ++r) {
+        for (int q = 0; q < 3; ++q) rot[r * 3 + q] = pose[r * 4 + q];
+        trans[r] = pose[r * 4 + 3];
+    }
+}
+
+// Model::initICP's model side (initICPModel / initRGBModel, Model.cpp:396-401) of one model from `pose`, into `stages`
+// (side PREP_ALL: this frame's sensor side as well).  requiresFillIn (:380, :877-895) is decided on the device, from the
+// count of covered thumbnail samples the prediction's resolve left (surfel_kernels.hpp: thumbnail_count_px).  `boxed`: an
+// object model notes its extents under ext_gen (extent.hpp) and covers only the box its prediction is non-zero in.  The
+// end-of-frame preparation of a rank's only model is not boxed: that model's odom->sparse may still be set from its tracking
+// (an object model, on a sharded rank).
+static void fusion_collect_prep(mmf_fusion* f, PrepStages& stages, FusionModel* fm, const float* pose, int side, bool boxed,
+                                unsigned ext_gen) {
     const mmf_fusion_config& g = f->cfg;
-    const float weight_multiplier = fr->weight_multiplier;
-    const bool have_init = fr->init_transforms != nullptr && fr->n_init_transforms > 0;  // odom_cfg.init == "kp"
-    FusionModel* global = f->models[0];
-    int rc = MMF_OK;
-    bool prefetched = false;
-    bool next_prefetched = false;  // mmf_frame::next_* has been enqueued
+    const mmf_model* m = fm->model;
+    const uint8_t* pi = (const uint8_t*)((g.frame_to_frame_rgb && fm->fill_in) ? m->fill_image : m->image);
+    odom_prepare_collect(stages, fm->odom, f->depth_filtered, g.max_depth_processed, f->frame_rgb, 3, (const float*)m->vertexConf,
+                         (const float*)m->normalRadius, pi, 4, pose, fm->fill_in ? fusion_thumb_count(m) : nullptr,
+                         (const float*)m->fill_vertex, (const float*)m->fill_normal, (const uint8_t*)m->fill_image, side,
+                         (m->width / 20) * (m->height / 20), 0.75f, boxed && fm->odom->sparse ? ext_gen : 0u,
+                         boxed ? fusion_pred_box(fm, side) : nullptr);
+}
+
+// The Gauss-Newton chains (Model::performTracking, Model.cpp:409-433) of n tracked models, from their poses or, on a retrack,
+// from the poses the frame started with (fm->last_pose).  batch: ONE chain for all of them on the first one's stream
+// (gridDim.y = model), the other models' streams continuing behind it; else one chain per model on the model's stream.
+static int fusion_enqueue_chains(mmf_fusion* f, FusionModel* const* fms, size_t n, bool batch, bool from_last_pose) {
+    const mmf_fusion_config& g = f->cfg;
+    float pose[16];
+    auto start_pose = [&](FusionModel* fm) -> const float* {
+        if (from_last_pose) return fm->last_pose;
+        mmf_model_get_pose(fm->model, pose);
+        return pose;
+    };
+    if (!batch) {
+        for (size_t k = 0; k < n; ++k) {
+            float trans[3], rot[9];
+            pose_trans_rot(start_pose(fms[k]), trans, rot);
+            int rc = odom_enqueue_tracking(fms[k]->odom, trans, rot, g.rgb_only, g.icp_weight, g.pyramid, g.fast_odom, g.so3,
+                                           fms[k]->icp_error, fms[k]->rgb_error);
+            if (rc) return rc;
+        }
+        return MMF_OK;
+    }
+    FusionModel* lead = fms[0];
+    hipStream_t st = lead->lane->stream;
+    TrackBatch tb;
+    tb.n = (int)n;
+    std::memset(&tb.bd, 0, sizeof(tb.bd));
+    for (int k = 0; k < tb.n; ++k) {
+        tb.o[k] = fms[k]->odom;
+        tb.bd.d[k] = (long long)(reinterpret_cast<char*>(fms[k]->odom->slab) - reinterpret_cast<char*>(lead->odom->slab));
+        pose_trans_rot(start_pose(fms[k]), tb.poses.trans[k], tb.poses.rot[k]);
+    }
+    int rc = odom_enqueue_tracking(lead->odom, tb.poses.trans[0], tb.poses.rot[0], g.rgb_only, g.icp_weight, g.pyramid,
+                                   g.fast_odom, g.so3, lead->icp_error, lead->rgb_error, &tb);
+    if (rc) return rc;
+    // the lanes continue after the chain.  With a segmentation every lane waits for ev_frame_ready before its passes anyway,
+    // and that event is recorded on this very stream (the camera model's) behind the chain (the mask's upload, frame_segment):
+    // an event and a wait per model here would be fourteen host calls and seven barrier packets for nothing
+    for (size_t k = 1; k < n && !(g.enable_multiple_models && st == f->ctx->stream); ++k) {
+        MMF_HIP_TRY(hipEventRecord(fms[k]->ev_done, st));
+        MMF_HIP_TRY(hipStreamWaitEvent(fms[k]->lane->stream, fms[k]->ev_done, 0));
+    }
+    return MMF_OK;
+}
+
+// :209-283: the prefetch hand-over, the bilateral filter (:262), the mask, the scheduled deactivations
+static int frame_begin(mmf_fusion* f, FrameRun& r) {
+    const mmf_frame* fr = r.fr;
+    const mmf_fusion_config& g = f->cfg;
+    mmf_ctx* c = f->ctx;
     if (f->pre_valid) {  // whatever was prefetched has to be complete before this frame touches the same buffers
         MMF_HIP_TRY(hipStreamWaitEvent(c->stream, f->ev_prefetch_done, 0));  // (recorded behind BOTH side streams' work)
-        prefetched = f->pre_rgb == rgb && f->pre_depth == depth;
+        r.prefetched = f->pre_rgb == fr->rgb && f->pre_depth == fr->depth;
         f->pre_valid = false;
     }
-    const bool track = f->tick > 1 && (fr->bootstrap || !fr->in_pose);  // :299 "regular execution"
     // a prefetched SO3 pre-alignment only counts for the frame it was computed for, and only when that frame is tracked
     const int so3_ready = f->so3_stage_ready;
     f->so3_stage_ready = -1;
     f->image_pre_rgb = nullptr;
-    const OdomState* const so3_stage =
-        (so3_ready >= 0 && prefetched && track && !(have_init && !fr->icp_refine)) ? f->so3_stage[so3_ready] : nullptr;
+    if (so3_ready >= 0 && r.prefetched && r.track && !(r.have_init && !fr->icp_refine)) r.so3_stage = f->so3_stage[so3_ready];
     for (FusionModel* fm : f->models) fm->odom->so3_prefetched = false, fm->odom->so3_stage = nullptr;
-    if (prefetched) {  // the filter (:262) and the input-side preparation already ran on the side stream
+    if (r.prefetched) {  // the filter (:262) and the input-side preparation already ran on the side stream
         f->cur ^= 1;
         f->depth_filtered = f->filtered[f->cur];
-        odom_adopt_gradients(global->odom);
+        odom_adopt_gradients(f->models[0]->odom);
     } else {
-        rc = mmf_filter_depth(c, depth, f->width, f->height, g.depth_cutoff, f->depth_filtered);  // :262
+        int rc = mmf_filter_depth(c, fr->depth, f->width, f->height, g.depth_cutoff, f->depth_filtered);  // :262
         if (rc) return rc;
     }
-    f->frame_rgb = rgb, f->frame_depth = depth;
-    f->inputs_free_recorded = false;  // (set again by the branches below that record ev_inputs_free)
+    f->frame_rgb = fr->rgb, f->frame_depth = fr->depth;
+    f->inputs_free_recorded = false;  // (set again by the stages that record ev_inputs_free)
     f->host_caught_up = false;
     if (!g.enable_multiple_models && !f->mask_is_zero) {  // :268-275: everything is background
         MMF_HIP_TRY(hipMemsetAsync(f->mask, 0, (size_t)f->width * f->height, c->stream));
         f->mask_is_zero = true;
     }
-
     for (int id : f->scheduled_deactivation)  // :279-283
         if (FusionModel* fm = fusion_find(f, id)) fusion_inactivate(f, fm);
     f->scheduled_deactivation.clear();
+    return MMF_OK;
+}
 
-    if (f->tick == 1) {  // :290-296
-        if (fusion_owns(f, 0)) {
-            rc = mmf_model_initialise(global->model, rgb, depth, f->depth_filtered, f->tick, g.max_depth_processed);
-            if (rc) return rc;
-        }
-        rc = mmf_odom_init_first_rgb(global->odom, rgb, 0, 3);  // sensor side: every rank
+// :290-296
+static int frame_first(mmf_fusion* f, const FrameRun& r) {
+    const mmf_frame* fr = r.fr;
+    mmf_ctx* c = f->ctx;
+    if (fusion_owns(f, 0)) {
+        int rc = mmf_model_initialise(f->models[0]->model, fr->rgb, fr->depth, f->depth_filtered, f->tick, f->cfg.max_depth_processed);
         if (rc) return rc;
-        MMF_HIP_TRY(hipEventRecord(f->ev_inputs_free, c->stream));
-        f->inputs_free_recorded = true;
-        MMF_HIP_TRY(hipEventRecord(f->ev_frame_ready, c->stream));
-    } else {
-        f->tracking_ok = 1;
-        const size_t n_models = f->models.size();
-        if (track) {
-            MMF_REQUIRE(!have_init || !g.frame_to_frame_rgb, "ICP initialisation not supported in frame-to-frame mode");  // :370
-            // generateCUDATextures (:302) + the sensor side of Model::initICP (Model.cpp:402-403: initICP, initRGB), once
-            // for all models.  One model without pose initialisation: sensor side and model side share four launches.
-            const auto t_track = std::chrono::steady_clock::now();
-            for (size_t k = 0; k < n_models; ++k) {  // is last frame's end-of-frame preparation of a model still good?
-                FusionModel* fm = f->models[k];
-                float pose_now[16];
-                mmf_model_get_pose(fm->model, pose_now);
-                fm->spec_hit = fm->spec_valid && fusion_owns(f, k) && !have_init &&
-                               std::memcmp(pose_now, fm->spec_pose, sizeof(pose_now)) == 0 &&
-                               fm->model->tex_gen == fm->spec_tex_gen && fm->spec_f2f == g.frame_to_frame_rgb &&
-                               fm->odom->prep_batched;
-                fm->spec_valid = false;
-                fm->odom->begin_spec_ok = fm->spec_hit;  // (the tracking's beginning rode that preparation: odom_begin_rider)
-                fm->early_done = fm->early_fused = false;
-            }
-            const bool one_pass = n_models == 1 && !have_init && fusion_owns(f, 0) && !global->spec_hit;
-            if (!prefetched && !one_pass) {
-                float identity[16];
-                identity16(identity);
-                rc = odom_prepare_batched(global->odom, f->depth_filtered, g.max_depth_processed, rgb, 3, nullptr, nullptr,
-                                          nullptr, 4, identity, nullptr, nullptr, nullptr, nullptr,
-                                          PREP_INPUT_IMAGE | PREP_INPUT_DEPTH);
-                if (rc) return rc;
-                odom_adopt_gradients(global->odom);
-            }
-            // (waited for by the other models' streams only: one model and no segmentation = no marker on the model's stream)
-            const bool lanes_wait = g.enable_multiple_models || n_models > 1;
-            if (!one_pass && lanes_wait) MMF_HIP_TRY(hipEventRecord(f->ev_frame_ready, c->stream));
-            // Round 3: the IMAGE side of the next frame -- intensity pyramid, gradients, SO3 pre-alignment: sixteen launches --
-            // depends on nothing the chains read or write (the image ring and the gradients are double buffered, the
-            // pre-alignment runs in a state of its own), so it need not wait behind the pose, where its enqueue was the longest
-            // part of the host's tail (93 us) and its stream the last thing the next frame's chain waited for.
-            //   MMF_EARLY_IMAGE=start (default): enqueued HERE, before this frame's chain: the GPU is still working off the
-            //     last frame's tail then, and the image side runs beside that, not beside the latency-bound chain;
-            //   =chain: after the chain's enqueue, while the host would only wait (runs beside the chain: +5..35 us on it);
-            //   =off: at the end of the call with the depth side.
-            // so3_stage: this frame's own pre-alignment ran ahead as well -- inside the chain it reads the LAST frame's level-2
-            // image, the half of the image ring the next frame's pyramid is written to.
-            // (-1, the default: `start` with one or two models on this GPU -- the GPU is still busy when the call begins --,
-            // `chain` from three on: there the GPU waits for the chain's first launch when the call begins, and sixteen
-            // launches enqueued in front of it are 50-80 us of that wait: 4 models 0.617 -> 0.558 ms, 8 models 0.70 -> 0.69)
-            int owned_models = 0;
-            for (size_t k = 0; k < n_models; ++k) owned_models += fusion_owns(f, k) ? 1 : 0;
-            const int early_image = tunables().early_image >= 0 ? tunables().early_image : (owned_models >= 3 ? 1 : 2);
-            const bool next_from_host = f->host_next.slot >= 0 && f->up_dev[0] != nullptr;  // (a frame still being uploaded)
-            const bool image_early_any = fr->next_rgb && fr->next_depth && f->side2 && g.so3 && so3_stage != nullptr;
-            const bool image_early_ok = image_early_any && !next_from_host;
-            if (early_image == 2 && image_early_ok) {
-                // the ring as it will be once this frame's chain is enqueued (RGBDOdometry.cpp:469-473; odom_enqueue_tracking)
-                mmf_odom* go = global->odom;
-                for (int i = 0; i < MMF_NUM_PYRS; ++i) std::swap(go->last_next_image[i], go->next_image[i]);
-                rc = fusion_prefetch_image(f, fr->next_rgb, f->tick + 1, true);
-                for (int i = 0; i < MMF_NUM_PYRS; ++i) std::swap(go->last_next_image[i], go->next_image[i]);
-                if (rc) return rc;
-            }
-            stamp(6);
-            // Several models in one chain (below): an object model's stream gets its next work behind that chain -- it waits for
-            // an event recorded there -- so the wait for the frame's sensor side here would be a second barrier packet per stream
-            // and two host calls per model at the point of the call where the GPU waits for the calling thread.
-            int will_track = 0;
-            for (size_t k = 0; k < n_models; ++k) will_track += fusion_owns(f, k) ? 1 : 0;
-            // (only where the camera model leads the chain: its stream is the one the sensor side and the end-of-frame preparation
-            // are ordered on; a rank of a sharded run that holds object models only keeps every wait)
-            const bool will_batch = will_track > 1 && will_track <= kMaxBatch && !have_init && g.batch_tracking && fusion_owns(f, 0);
-            std::vector<FusionModel*> tracked;
-            for (size_t k = 0; k < n_models; ++k) {  // :312-387, enqueue only
-                FusionModel* fm = f->models[k];
-                fm->tracking = false;
-                if (!fusion_owns(f, k)) continue;
-                if (k > 0) {
-                    if (!will_batch) {
-                        rc = lane_wait(fm, f->ev_frame_ready);
-                        if (rc) return rc;
-                    }
-                    odom_alias_sensor_side(fm->odom, global->odom);
-                }
-                bool do_icp = true;
-                if (have_init) {  // initialise by track transformation (:316-376)
-                    do_icp = fr->icp_refine != 0;
-                    float pose[16], tnew[16];
-                    mmf_model_get_pose(fm->model, pose);
-                    const float* T = fr->init_transforms + 16 * (k < (size_t)fr->n_init_transforms ? k : 0);
-                    if (k >= (size_t)fr->n_init_transforms) {
-                        std::memcpy(tnew, pose, sizeof(pose));  // no transformation for this model: keep its pose
-                    } else if (fm->model->id == 0) {
-                        mmf::host::matmul4(pose, T, tnew);  // Tnew = model->getPose() * T (:331)
-                    } else {
-                        mmf::host::matmul4(T, pose, tnew);  // Tnew = T * model->getPose() (:334)
-                    }
-                    mmf_model_set_pose(fm->model, tnew);  // overridePose: pose = lastPose = Tnew (:350, Model.h:301-304)
-                    std::memcpy(fm->last_pose, tnew, sizeof(tnew));
-                    rc = fusion_predict_model(f, fm);  // :353-355
-                    if (rc) return rc;
-                    // Model::fuse(..., weightMultiplier) applies computeFusionWeight(weightMultiplier) (:359-360, Model.cpp:918)
-                    rc = fusion_fuse_clean_model(f, fm, fusion_weight(tnew, fm->last_pose, weight_multiplier));  // :357-366
-                    if (rc) return rc;
-                }
-                if (!do_icp) continue;  // no refinement, use the initial pose directly (:382-385)
-                // Model::performTracking (Model.cpp:409-433) with Model::initICP (:390-407).  requiresFillIn (:380,
-                // :877-895) is decided on the device: the preparation jobs pick their sources by the count of covered
-                // thumbnail samples the prediction's resolve pass left behind (surfel_kernels.hpp: thumbnail_count_px)
-                float pose[16];
-                mmf_model_get_pose(fm->model, pose);
-                std::memcpy(fm->last_pose, pose, sizeof(pose));  // lastPose = pose (Model.cpp:412)
-                fm->tracking = true;
-                tracked.push_back(fm);
-            }
-            stamp(7);
-            if (so3_stage)  // every chain enqueued below starts from the prefetched pre-alignment
-                for (FusionModel* fm : tracked) fm->odom->so3_prefetched = true, fm->odom->so3_stage = so3_stage;
-            // ONE chain of launches for all tracked models (gridDim.y = model) when every level runs on the fused
-            // producer path and no model went through a pose-initialisation round on its own stream; else one chain
-            // per model on the model's stream.  Either way nothing waits here.
-            const bool batched = tracked.size() > 1 && tracked.size() <= (size_t)kMaxBatch && !have_init && g.batch_tracking;
-            const unsigned ext_gen = ++f->extent_seq;
-            for (FusionModel* fm : tracked) fm->odom->sparse = fm != global && !fm->fill_in;  // an object model: extent.hpp, ChainGeom
-            auto collect_prep = [&](PrepStages& stages, FusionModel* fm, int side) {
-                const mmf_model* m = fm->model;
-                const uint8_t* pi = (const uint8_t*)((g.frame_to_frame_rgb && fm->fill_in) ? m->fill_image : m->image);
-                float pose[16];
-                mmf_model_get_pose(fm->model, pose);
-                odom_prepare_collect(stages, fm->odom, f->depth_filtered, g.max_depth_processed, rgb, 3, (const float*)m->vertexConf,
-                                     (const float*)m->normalRadius, pi, 4, pose,
-                                     fm->fill_in ? fusion_thumb_count(m) : nullptr, (const float*)m->fill_vertex,
-                                     (const float*)m->fill_normal, (const uint8_t*)m->fill_image, side, (m->width / 20) * (m->height / 20),
-                                     0.75f, fm->odom->sparse ? ext_gen : 0u, fusion_pred_box(fm, side));
-            };
-            bool batch_ok = batched;
-            if (batched) {
-                FusionModel* lead = tracked[0];
-                hipStream_t st = lead->lane->stream;
-                for (size_t k = 1; k < tracked.size(); ++k) {  // the other models' last work (previous frame's predict) precedes
-                    // (a model prepared at the end of the last call, behind the join of all streams there, and untouched since:
-                    // nothing enqueued below reads what its stream may still hold)
-                    if (tracked[k]->spec_hit) continue;
-                    MMF_HIP_TRY(hipEventRecord(tracked[k]->ev_done, tracked[k]->lane->stream));
-                    MMF_HIP_TRY(hipStreamWaitEvent(st, tracked[k]->ev_done, 0));
-                }
-                PrepStages stages;
-                stages.set_critical(true);  // the model's stream
-                for (size_t k = 0; k < tracked.size(); ++k) {
-                    if (tracked[k]->spec_hit) {
-                        tracked[k]->odom->depth_l0 = f->depth_filtered;
-                        continue;
-                    }
-                    collect_prep(stages, tracked[k], (k == 0 && tracked[k] == global && one_pass && !prefetched) ? PREP_ALL : PREP_MODEL_SIDE);
-                }
-                rc = stages.launch(st);
-                if (rc) return rc;
-                stamp(8);
-                // (a PREP_ALL collect above prepared this frame's image side as well; NOT when the pending gradients are the
-                // next frame's, from the image side enqueued ahead a few lines up)
-                if (one_pass && !prefetched) odom_adopt_gradients(global->odom);
-                batch_ok = odom_batchable(lead->odom, g.rgb_only, g.icp_weight, g.pyramid, g.fast_odom);
-                if (batch_ok) {
-                    TrackBatch tb;
-                    tb.n = (int)tracked.size();
-                    std::memset(&tb.bd, 0, sizeof(tb.bd));
-                    for (int k = 0; k < tb.n; ++k) {
-                        tb.o[k] = tracked[k]->odom;
-                        tb.bd.d[k] = (long long)(reinterpret_cast<char*>(tracked[k]->odom->slab) - reinterpret_cast<char*>(lead->odom->slab));
-                        float pose[16];
-                        mmf_model_get_pose(tracked[k]->model, pose);
-                        for (int r = 0; r < 3; ++r) {
-                            for (int q = 0; q < 3; ++q) tb.poses.rot[k][r * 3 + q] = pose[r * 4 + q];
-                            tb.poses.trans[k][r] = pose[r * 4 + 3];
-                        }
-                    }
-                    lead->odom->exclusive_chain = true;  // one chain for all of them
-                    rc = odom_enqueue_tracking(lead->odom, tb.poses.trans[0], tb.poses.rot[0], g.rgb_only, g.icp_weight, g.pyramid,
-                                               g.fast_odom, g.so3, lead->icp_error, lead->rgb_error, &tb);
-                    if (rc) return rc;
-                    // the lanes continue after the chain.  With a segmentation every lane waits for ev_frame_ready before its
-                    // passes anyway, and that event is recorded on this very stream (the camera model's) behind the chain (the mask's upload, below):
-                    // an event and a wait per model here would be fourteen host calls and seven barrier packets for nothing
-                    for (size_t k = 1; k < tracked.size() && !(g.enable_multiple_models && st == c->stream); ++k) {
-                        MMF_HIP_TRY(hipEventRecord(tracked[k]->ev_done, st));
-                        MMF_HIP_TRY(hipStreamWaitEvent(tracked[k]->lane->stream, tracked[k]->ev_done, 0));
-                    }
-                }
-            }
-            for (size_t k = 0; k < tracked.size() && !batch_ok; ++k) {
-                FusionModel* fm = tracked[k];
-                if (will_batch && fm != global) {  // (the wait skipped above)
-                    rc = lane_wait(fm, f->ev_frame_ready);
-                    if (rc) return rc;
-                }
-                if (fm->spec_hit) {  // the model side was prepared at the end of the last frame; the sensor side by the prefetch
-                    fm->odom->depth_l0 = f->depth_filtered;  // (or just above)
-                } else if (!batched) {  // (a failed batch has prepared every model already)
-                    PrepStages stages;
-                stages.set_critical(true);  // the model's stream
-                    collect_prep(stages, fm, (fm == global && one_pass && !prefetched) ? PREP_ALL : PREP_MODEL_SIDE);
-                    rc = stages.launch(fm->lane->stream);
-                    if (rc) return rc;
-                    if (fm == global && one_pass && !prefetched) odom_adopt_gradients(global->odom);  // (PREP_ALL: this frame's image side as well)
-                } else if (k > 0) {  // prepared on the leader's stream
-                    MMF_HIP_TRY(hipEventRecord(fm->ev_done, tracked[0]->lane->stream));
-                    MMF_HIP_TRY(hipStreamWaitEvent(fm->lane->stream, fm->ev_done, 0));
-                }
-                float pose[16];
-                mmf_model_get_pose(fm->model, pose);
-                const float trans[3] = {pose[3], pose[7], pose[11]};
-                const float rot[9] = {pose[0], pose[1], pose[2], pose[4], pose[5], pose[6], pose[8], pose[9], pose[10]};
-                fm->odom->exclusive_chain = tracked.size() == 1;  // several chains side by side: no in-launch barriers
-                // The frame's first projection, enqueued right behind this chain (below), carries the hand-over to the host and
-                // the fusion weight on one extra workgroup (frame_rider.hpp): the chain's last launch is the solve alone (13 ->
-                // 5.7 us on the stream a frame waits for).
-                fm->odom->defer_publish = tracked.size() == 1 && !fr->bootstrap && !have_init && !g.rgb_only && f->tracking_ok;
-                rc = odom_enqueue_tracking(fm->odom, trans, rot, g.rgb_only, g.icp_weight, g.pyramid, g.fast_odom, g.so3,
-                                           fm->icp_error, fm->rgb_error);
-                if (rc) return rc;
-            }
-            // One model on the context's stream, nothing between its tracking and its fusion that the host decides: the
-            // frame's first projections -- predict() (:675) and the first predictIndices (:792) -- are enqueued right here,
-            // behind the chain and the copy of its result, with the inverse pose read from the odometry's device state.
-            // They run while the host picks the pose up and prepares the fusion passes (that turnaround used to be ~25 us
-            // of idle GPU per frame).
-            // (With several models it is one model per process in the sharded configuration: the segmentation between
-            // tracking and fusion touches masks, thresholds and the list, none of which a projection reads.)
-            static_assert(std::is_trivially_copyable<mmf_model>::value, "the speculation rollback below copies mmf_model by value");
-            mmf_model early_snapshot;  // the model's host bookkeeping before the passes enqueued ahead of the pose (see `retrack` below)
-            bool early_snapshot_valid = false;
-            if (tracked.size() == 1 && !fr->bootstrap && !have_init && !g.rgb_only && f->tracking_ok) {
-                FusionModel* fm = tracked[0];
-                mmf_model* m = fm->model;
-                early_snapshot = *m, early_snapshot_valid = true;
-                m->abort_dev = &fm->odom->state->gn_fault;
-                // "nothing enqueued so far reads the odometries' sensor-side buffers or the other filtered-depth buffer" holds
-                // HERE, behind the one chain of this process; the passes enqueued next do not read them either.  No event
-                // says so any more (see below: the host knows when it has the pose; a marker behind the chain cost the
-                // model's stream ~4 us in front of the frame's first projection).
-                m->t_inv_dev = fm->odom->state->pose_inv;
-                m->rider = fm->odom->rider;
-                fm->odom->rider = FrameRider();
-                rc = fusion_mid_predict() ? fusion_predict_model(f, fm) : MMF_OK;
-                if (rc == MMF_OK) rc = mmf_model_predict_indices(m, f->tick, g.max_depth_processed, g.time_delta);
-                MMF_REQUIRE(rc != MMF_OK || m->rider.st == nullptr, "mmf_fusion_process_frame: the tracking result was not handed over");
-                fm->early_done = rc == MMF_OK;
-                // Without a segmentation the mask of the frame is known (all zeros) and nothing the host decides lies
-                // between tracking and fusion: fuse -> predictIndices -> clean (:791-816) follow at once, with the pose and
-                // Model::computeFusionWeight taken from the device state (odom_end, odom_fusion_weight_kernel).
-                if (rc == MMF_OK && !g.enable_multiple_models) {
-                    m->pose_dev = fm->odom->state->pose_out, m->weight_dev = &fm->odom->state->fusion_weight;
-                    rc = fusion_fuse_clean_model(f, fm, weight_multiplier, true);
-                    fm->early_fused = rc == MMF_OK;
-                }
-                m->t_inv_dev = m->pose_dev = m->weight_dev = nullptr;
-                m->abort_dev = nullptr;
-                if (rc) return rc;
-            }
-            // the sensor-side image ring (this frame's / last frame's intensity pyramid, RGBDOdometry.cpp:469-473) lives in
-            // the global odometry and advances when its chain is enqueued: when its owner is another rank, the swap
-            // happens here, whether or not this rank tracked anything (every rank's ring must advance with the global model's)
-            const bool global_tracked = global->tracking;
-            const bool global_tracks_somewhere = !(have_init && !fr->icp_refine);
-            if (g.so3 && global_tracks_somewhere && !global_tracked)
-                for (int i = 0; i < MMF_NUM_PYRS; ++i) std::swap(global->odom->last_next_image[i], global->odom->next_image[i]);
-            if (early_image == 1 && image_early_ok && !tracked.empty()) {  // (see above)
-                rc = fusion_prefetch_image(f, fr->next_rgb, f->tick + 1, true);
-                if (rc) return rc;
-            }
-            stamp(0);
-            // a host frame announced for the next call: staged and sent up now, while the GPU tracks and the host would only wait
-            // (its colour image first; the depth image is joined where the depth side is enqueued, behind the pose)
-            rc = fusion_stage_host_rgb(f);
-            if (rc) return rc;
-            // ... and its image side behind the upload (an announced HOST frame cannot have it at the start of the call: its
-            // copy into pinned memory has only just begun then), beside the chain instead of behind the pose
-            if (early_image != 0 && image_early_any && next_from_host && !tracked.empty() && f->host_next.rgb_staged) {
-                MMF_HIP_TRY(fusion_wait_unless_done(f->side2, f->ev_up_rgb[f->host_next.slot]));
-                rc = fusion_prefetch_image(f, fr->next_rgb, f->tick + 1, true);
-                if (rc) return rc;
-            }
-            // The one-launch chain can give up (its count barrier needs every workgroup of a launch resident: another process on
-            // the GPU can prevent that; OdomState::gn_fault).  Then nothing of the chain's result is valid and the passes enqueued
-            // ahead of the pose have done nothing (MMF_SPECULATION_GUARD): the model's host bookkeeping goes back to where it
-            // was, the process stops using that chain, and the frame's tracking is enqueued again -- the two-launch chain, from
-            // the poses the frame started with (fm->last_pose) -- before the results are picked up a second time.
-            auto retrack = [&]() -> int {
-                std::vector<mmf_odom*> odoms;
-                for (FusionModel* fm : tracked) odoms.push_back(fm->odom);
-                odom_retrack_prepare(odoms.data(), (int)odoms.size(), g.so3);
-                if (early_snapshot_valid) {
-                    *tracked[0]->model = early_snapshot;
-                    tracked[0]->early_done = tracked[0]->early_fused = false;
-                    early_snapshot_valid = false;
-                }
-                for (FusionModel* fm : tracked) fm->odom->defer_publish = false, fm->odom->rider = FrameRider();
-                if (batch_ok) {
-                    FusionModel* lead = tracked[0];
-                    TrackBatch tb;
-                    tb.n = (int)tracked.size();
-                    std::memset(&tb.bd, 0, sizeof(tb.bd));
-                    for (int k = 0; k < tb.n; ++k) {
-                        tb.o[k] = tracked[k]->odom;
-                        tb.bd.d[k] = (long long)(reinterpret_cast<char*>(tracked[k]->odom->slab) - reinterpret_cast<char*>(lead->odom->slab));
-                        for (int r = 0; r < 3; ++r) {
-                            for (int q = 0; q < 3; ++q) tb.poses.rot[k][r * 3 + q] = tracked[k]->last_pose[r * 4 + q];
-                            tb.poses.trans[k][r] = tracked[k]->last_pose[r * 4 + 3];
-                        }
-                    }
-                    int rc2 = odom_enqueue_tracking(lead->odom, tb.poses.trans[0], tb.poses.rot[0], g.rgb_only, g.icp_weight, g.pyramid,
-                                                    g.fast_odom, g.so3, lead->icp_error, lead->rgb_error, &tb);
-                    if (rc2) return rc2;
-                    for (size_t k = 1; k < tracked.size() && !(g.enable_multiple_models && lead->lane->stream == c->stream); ++k) {  // (as above)
-                        MMF_HIP_TRY(hipEventRecord(tracked[k]->ev_done, lead->lane->stream));
-                        MMF_HIP_TRY(hipStreamWaitEvent(tracked[k]->lane->stream, tracked[k]->ev_done, 0));
-                    }
-                    return MMF_OK;
-                }
-                for (FusionModel* fm : tracked) {
-                    const float* p = fm->last_pose;
-                    const float trans[3] = {p[3], p[7], p[11]};
-                    const float rot[9] = {p[0], p[1], p[2], p[4], p[5], p[6], p[8], p[9], p[10]};
-                    int rc2 = odom_enqueue_tracking(fm->odom, trans, rot, g.rgb_only, g.icp_weight, g.pyramid, g.fast_odom, g.so3,
-                                                    fm->icp_error, fm->rgb_error);
-                    if (rc2) return rc2;
-                }
-                return MMF_OK;
-            };
-            bool retracked = false;
-            for (size_t k = 0; k < n_models; ++k) {  // the results, model by model
-                FusionModel* fm = f->models[k];
-                float pose[16];
-                mmf_model_get_pose(fm->model, pose);
-                if (fm->tracking) {
-                    float trans[3], rot[9];
-                    rc = odom_finish_tracking(fm->odom, trans, rot);
-                    if (rc == kGnRetry && !retracked) {  // (at most once: the two-launch chain has no way to give up)
-                        // every chain of the frame is void with it (a batch is one chain; chains side by side are two-launch chains)
-                        for (FusionModel* t : tracked)
-                            if (t->tracking && t != fm && t->odom->result_of) {  // drain what the other lanes' chains still publish
-                                float tt[3], rr[9];
-                                (void)odom_finish_tracking(t->odom, tt, rr);
-                            }
-                        rc = retrack();
-                        if (rc) return rc;
-                        retracked = true;
-                        for (FusionModel* t : tracked) {  // poses already taken over from the void chain: back to the frame's start
-                            mmf_model_set_pose(t->model, t->last_pose);
-                            t->tracking = true;
-                        }
-                        k = (size_t)-1;  // pick the results up again, from the first model
-                        continue;
-                    }
-                    if (rc == kGnRetry) return gn_retry_twice();
-                    if (rc) return rc;
-                    for (int r = 0; r < 3; ++r) {
-                        for (int q = 0; q < 3; ++q) pose[r * 4 + q] = rot[r * 3 + q];
-                        pose[r * 4 + 3] = trans[r];
-                    }
-                    mmf_model_set_pose(fm->model, pose);
-                    fm->tracking = false;
-                    if (fm->lane->stream == c->stream) f->host_caught_up = true;
-                }
-            }
-            f->t_tracking_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_track).count();
-            stamp(1);
-            if (fr->bootstrap) {  // :397-400
-                MMF_REQUIRE(fr->in_pose != nullptr, "mmf_fusion_process_frame: bootstrap needs in_pose");
-                float pose[16], np[16];
-                mmf_model_get_pose(global->model, pose);
-                mmf::host::matmul4(pose, fr->in_pose, np);
-                mmf_model_set_pose(global->model, np);  // overridePose
-                std::memcpy(global->last_pose, np, sizeof(np));
-            }
-            // from here on nothing enqueued reads the odometries' sensor-side buffers or the other filtered-depth
-            // buffer, and the HOST knows it: every chain's result has been received, so every chain -- and whatever its
-            // stream held before it, e.g. this frame's own image-side preparation -- has run.  The next frame's side-stream
-            // work, enqueued from here on, needs no event to wait for (inputs_free_recorded stays false).
-            if (one_pass && lanes_wait) MMF_HIP_TRY(hipEventRecord(f->ev_frame_ready, c->stream));
+    }
+    int rc = mmf_odom_init_first_rgb(f->models[0]->odom, fr->rgb, 0, 3);  // sensor side: every rank
+    if (rc) return rc;
+    MMF_HIP_TRY(hipEventRecord(f->ev_inputs_free, c->stream));
+    f->inputs_free_recorded = true;
+    MMF_HIP_TRY(hipEventRecord(f->ev_frame_ready, c->stream));
+    return MMF_OK;
+}
 
-            if (g.enable_multiple_models) {  // :407-622
-                mmf_segmentation seg_cb;
-                const mmf_segmentation* seg = fr->segmentation;
-                if (!seg && f->seg_fn) {  // performSegmentation(frame) (:412)
-                    std::memset(&seg_cb, 0, sizeof(seg_cb));
-                    rc = f->seg_fn(f->seg_user, f, fr, &seg_cb);
-                    if (rc) return fail(MMF_ERR_STATE, "mmf_fusion_process_frame: the segmentation callback failed");
-                    seg = &seg_cb;
-                }
-                MMF_REQUIRE(seg && seg->mask, "mmf_fusion_process_frame: enableMultipleModels needs a segmentation "
-                                              "(mmf_frame::segmentation or mmf_fusion_set_segmentation_callback)");
-                // textures[MASK]->Upload(fullSegmentation) (:416)
-                MMF_HIP_TRY(hipMemcpyAsync(f->mask, seg->mask, (size_t)f->width * f->height, hipMemcpyDeviceToDevice, c->stream));
-                f->mask_is_zero = false;
-                MMF_HIP_TRY(hipEventRecord(f->ev_frame_ready, c->stream));
-                const int n_data = seg->model_data ? seg->n_models : 0;
-                FusionModel* fresh = nullptr;
-                if (seg->has_new_label) {  // :469-487
-                    rc = fusion_spawn(f, &fresh);
-                    if (rc) return rc;
-                    if (n_data > 0)
-                        fresh->model->max_depth = seg_max_depth(seg->model_data[n_data - 1]);
-                }
-                // Set max-depth (:585-586)
-                for (size_t i = 1; i < f->models.size() && (int)i < n_data; ++i)
-                    f->models[i]->model->max_depth = seg_max_depth(seg->model_data[i]);
-                if (fresh && !fusion_owns_model(f, fresh)) {
-                    f->models.push_back(fresh);  // another rank's model: bookkeeping only
-                } else if (fresh) {  // :588-601: the first surfels of the new model, then it joins the list
-                    rc = lane_wait(fresh, f->ev_frame_ready);
-                    if (rc) return rc;
-                    identity16(fresh->last_pose);
-                    float pose[16];
-                    mmf_model_get_pose(fresh->model, pose);
-                    rc = mmf_model_predict_indices(fresh->model, f->tick, g.max_depth_processed, g.time_delta);
-                    if (rc) return rc;
-                    rc = mmf_model_fuse(fresh->model, f->tick, rgb, f->mask, depth, f->depth_filtered, g.max_depth_processed,
-                                        fusion_weight(pose, fresh->last_pose, 100.f));  // fuse(..., 100) (:591-592)
-                    if (rc) return rc;
-                    // (the second predictIndices is commented out in the reference, :594)
-                    rc = mmf_model_clean(fresh->model, f->tick, g.time_delta, g.max_depth_processed, f->depth_filtered, f->mask,
-                                         g.outlier_coeff);
-                    if (rc) return rc;
-                    f->models.push_back(fresh);  // moveNewModelToList (:600)
-                }
-                // unseen models leave the list (:606-613); the confidence of object models rises (:616-620)
-                std::vector<FusionModel*> lost;
-                for (int i = 0; i < n_data; ++i) {
-                    FusionModel* fm = fusion_find(f, (int)seg->model_data[i].id);
-                    if (!fm || fm == fresh) continue;
-                    if (seg->model_data[i].super_pixel_count <= 0 && ++fm->unseen > 0 && fm->model->id != 0) lost.push_back(fm);
-                }
-                for (FusionModel* fm : lost) fusion_inactivate(f, fm);
-                for (size_t i = 1; i < f->models.size() && (int)i < n_data; ++i) {
-                    const float old_conf = f->models[i]->model->conf_threshold;
-                    const float avg = seg->model_data[i].avg_confidence;
-                    const float m1 = old_conf < avg ? avg : old_conf;
-                    f->models[i]->model->conf_threshold = 9.0f < m1 ? 9.0f : m1;
-                }
-            }
-        } else {
-            float pose[16];
-            std::memcpy(pose, fr->in_pose, sizeof(pose));
-            mmf_model_set_pose(global->model, pose);  // globalModel->overridePose(*inPose) (:670)
-            std::memcpy(global->last_pose, pose, sizeof(pose));
-            MMF_HIP_TRY(hipEventRecord(f->ev_inputs_free, c->stream));
-            f->inputs_free_recorded = true;
-            MMF_HIP_TRY(hipEventRecord(f->ev_frame_ready, c->stream));
-        }
+// generateCUDATextures (:302) + the sensor side of Model::initICP (Model.cpp:402-403: initICP, initRGB), once for all models,
+// and the next frame's image side if it goes out before the chains.  One model without pose initialisation: sensor side and
+// model side share four launches.
+static int frame_track_sensor_side(mmf_fusion* f, FrameRun& r) {
+    const mmf_frame* fr = r.fr;
+    const mmf_fusion_config& g = f->cfg;
+    mmf_ctx* c = f->ctx;
+    FusionModel* global = f->models[0];
+    const size_t n_models = f->models.size();
+    for (size_t k = 0; k < n_models; ++k) {  // is last frame's end-of-frame preparation of a model still good?
+        FusionModel* fm = f->models[k];
+        float pose_now[16];
+        mmf_model_get_pose(fm->model, pose_now);
+        fm->spec_hit = fm->spec_valid && fusion_owns(f, k) && !r.have_init && std::memcmp(pose_now, fm->spec_pose, sizeof(pose_now)) == 0 &&
+                       fm->model->tex_gen == fm->spec_tex_gen && fm->spec_f2f == g.frame_to_frame_rgb && fm->odom->prep_batched;
+        fm->spec_valid = false;
+        fm->odom->begin_spec_ok = fm->spec_hit;  // (the tracking's beginning rode that preparation: odom_begin_rider)
+        fm->early_done = fm->early_fused = false;
+    }
+    r.one_pass = n_models == 1 && !r.have_init && fusion_owns(f, 0) && !global->spec_hit;
+    if (!r.prefetched && !r.one_pass) {
+        float identity[16];
+        identity16(identity);
+        int rc = odom_prepare_batched(global->odom, f->depth_filtered, g.max_depth_processed, fr->rgb, 3, nullptr, nullptr, nullptr, 4,
+                                      identity, nullptr, nullptr, nullptr, nullptr, PREP_INPUT_IMAGE | PREP_INPUT_DEPTH);
+        if (rc) return rc;
+        odom_adopt_gradients(global->odom);
+    }
+    // (waited for by the other models' streams only: one model and no segmentation = no marker on the model's stream)
+    r.lanes_wait = g.enable_multiple_models || n_models > 1;
+    if (!r.one_pass && r.lanes_wait) MMF_HIP_TRY(hipEventRecord(f->ev_frame_ready, c->stream));
+    // Round 3: the IMAGE side of the next frame -- intensity pyramid, gradients, SO3 pre-alignment: sixteen launches --
+    // depends on nothing the chains read or write (the image ring and the gradients are double buffered, the
+    // pre-alignment runs in a state of its own), so it need not wait behind the pose, where its enqueue was the longest
+    // part of the host's tail (93 us) and its stream the last thing the next frame's chain waited for.
+    //   MMF_EARLY_IMAGE=start (default): enqueued HERE, before this frame's chain: the GPU is still working off the
+    //     last frame's tail then, and the image side runs beside that, not beside the latency-bound chain;
+    //   =chain: after the chain's enqueue, while the host would only wait (runs beside the chain: +5..35 us on it);
+    //   =off: at the end of the call with the depth side.
+    // so3_stage: this frame's own pre-alignment ran ahead as well -- inside the chain it reads the LAST frame's level-2
+    // image, the half of the image ring the next frame's pyramid is written to.
+    // (-1, the default: `start` with one or two models on this GPU -- the GPU is still busy when the call begins --,
+    // `chain` from three on: there the GPU waits for the chain's first launch when the call begins, and sixteen
+    // launches enqueued in front of it are 50-80 us of that wait: 4 models 0.617 -> 0.558 ms, 8 models 0.70 -> 0.69)
+    r.owned = 0;
+    for (size_t k = 0; k < n_models; ++k) r.owned += fusion_owns(f, k) ? 1 : 0;
+    r.early_image = tunables().early_image >= 0 ? tunables().early_image : (r.owned >= 3 ? 1 : 2);
+    r.next_from_host = f->host_next.slot >= 0 && f->up_dev[0] != nullptr;  // (a frame still being uploaded)
+    r.image_early_any = fr->next_rgb && fr->next_depth && f->side2 && g.so3 && r.so3_stage != nullptr;
+    r.image_early_ok = r.image_early_any && !r.next_from_host;
+    if (r.early_image == 2 && r.image_early_ok) {
+        // the ring as it will be once this frame's chain is enqueued (RGBDOdometry.cpp:469-473; odom_enqueue_tracking)
+        mmf_odom* go = global->odom;
+        for (int i = 0; i < MMF_NUM_PYRS; ++i) std::swap(go->last_next_image[i], go->next_image[i]);
+        int rc = fusion_prefetch_image(f, fr->next_rgb, f->tick + 1, true);
+        for (int i = 0; i < MMF_NUM_PYRS; ++i) std::swap(go->last_next_image[i], go->next_image[i]);
+        if (rc) return rc;
+    }
+    return MMF_OK;
+}
 
-        stamp(2);
-        // The OBJECT models' passes go out as one launch per pass for all of them (models_fuse_clean_batched) on the first
-        // object's stream: ~9 launches per model and frame otherwise, and with seven objects the calling thread's launch rate
-        // set the pace of this part of the frame.  The camera model keeps its own stream and kernels (riders, fill-in).
-        std::vector<FusionModel*> objs;
-        const bool fuse_now = !g.rgb_only && f->tracking_ok;
-        const int pass_mode = fusion_batch_mode(f);
-        for (size_t k = 1; k < f->models.size() && pass_mode != 0 && fuse_now && !fusion_mid_predict(); ++k) {
-            FusionModel* fm = f->models[k];
-            if (!fusion_owns(f, k) || fm->early_done || fm->early_fused || fm->fill_in || (int)objs.size() >= kMaxPassBatch) continue;
-            objs.push_back(fm);
+// :312-387 up to the tracking itself: each model's stream, the initialisation by track transformation, the list of models
+// whose tracking is enqueued next (r.tracked)
+static int frame_init_poses(mmf_fusion* f, FrameRun& r) {
+    const mmf_frame* fr = r.fr;
+    const mmf_fusion_config& g = f->cfg;
+    FusionModel* global = f->models[0];
+    // Several models in one chain (fusion_enqueue_chains): an object model's stream gets its next work behind that chain -- it
+    // waits for an event recorded there -- so the wait for the frame's sensor side here would be a second barrier packet per
+    // stream and two host calls per model at the point of the call where the GPU waits for the calling thread.
+    // (only where the camera model leads the chain: its stream is the one the sensor side and the end-of-frame preparation
+    // are ordered on; a rank of a sharded run that holds object models only keeps every wait)
+    r.will_batch = r.owned > 1 && r.owned <= kMaxBatch && !r.have_init && g.batch_tracking && fusion_owns(f, 0);
+    for (size_t k = 0; k < f->models.size(); ++k) {
+        FusionModel* fm = f->models[k];
+        fm->tracking = false;
+        if (!fusion_owns(f, k)) continue;
+        if (k > 0) {
+            if (!r.will_batch) {
+                int rc = lane_wait(fm, f->ev_frame_ready);
+                if (rc) return rc;
+            }
+            odom_alias_sensor_side(fm->odom, global->odom);
         }
-        if (objs.size() < 2) objs.clear();
-        for (size_t k = 0; k < f->models.size(); ++k) {  // predict() (:675), then :791-816, model by model
-            FusionModel* fm = f->models[k];
-            if (!fusion_owns(f, k)) continue;
-            if (std::find(objs.begin(), objs.end(), fm) != objs.end()) continue;  // (batched below)
-            if (k > 0) {
-                rc = lane_wait(fm, f->ev_frame_ready);
-                if (rc) return rc;
-            }
-            const bool early = fm->early_done;  // its predict + predictIndices are already enqueued
-            fm->early_done = false;
-            if (!early && fusion_mid_predict()) {
-                rc = fusion_predict_model(f, fm);
-                if (rc) return rc;
-            }
-            if (fuse_now && !fm->early_fused) {
-                float pose[16];
-                mmf_model_get_pose(fm->model, pose);
-                rc = fusion_fuse_clean_model(f, fm, fusion_weight(pose, fm->last_pose, weight_multiplier), early);
-                if (rc) return rc;
-            }
-            fm->early_fused = false;
-        }
-        if (!objs.empty()) {
-            hipStream_t st = objs[0]->lane->stream;
-            rc = lane_wait(objs[0], f->ev_frame_ready);
-            if (rc) return rc;
-            rc = fusion_lanes_join(objs, st);
-            if (rc) return rc;
-            mmf_model* ms[kMaxPassBatch];
-            float wts[kMaxPassBatch];
-            for (size_t k = 0; k < objs.size(); ++k) {
-                float pose[16];
-                mmf_model_get_pose(objs[k]->model, pose);
-                ms[k] = objs[k]->model;
-                wts[k] = fusion_weight(pose, objs[k]->last_pose, weight_multiplier);
-            }
-            if (pass_mode >= 2) {
-                rc = fusion_note_mask_boxes(f, st);
-                if (rc) return rc;
-                rc = models_fuse_clean_rect(ms, (int)objs.size(), st, f->tick, g.time_delta, g.max_depth_processed, f->frame_rgb, f->mask,
-                                            f->frame_depth, f->depth_filtered, g.outlier_coeff, wts, f->mask_boxes, f->mask_gen);
+        bool do_icp = true;
+        if (r.have_init) {  // initialise by track transformation (:316-376)
+            do_icp = fr->icp_refine != 0;
+            float pose[16], tnew[16];
+            mmf_model_get_pose(fm->model, pose);
+            const float* T = fr->init_transforms + 16 * (k < (size_t)fr->n_init_transforms ? k : 0);
+            if (k >= (size_t)fr->n_init_transforms) {
+                std::memcpy(tnew, pose, sizeof(pose));  // no transformation for this model: keep its pose
+            } else if (fm->model->id == 0) {
+                mmf::host::matmul4(pose, T, tnew);  // Tnew = model->getPose() * T (:331)
             } else {
-                rc = models_fuse_clean_batched(ms, (int)objs.size(), st, f->tick, g.time_delta, g.max_depth_processed, f->frame_rgb, f->mask,
-                                               f->frame_depth, f->depth_filtered, g.outlier_coeff, wts);
+                mmf::host::matmul4(T, pose, tnew);  // Tnew = T * model->getPose() (:334)
             }
+            mmf_model_set_pose(fm->model, tnew);  // overridePose: pose = lastPose = Tnew (:350, Model.h:301-304)
+            std::memcpy(fm->last_pose, tnew, sizeof(tnew));
+            int rc = fusion_predict_model(f, fm);  // :353-355
             if (rc) return rc;
-            // the other objects' streams continue behind the batch: a model left out of the predict batch below (a deep store,
-            // mmf_debug_set_splat_bound) is predicted on its own stream, and a predict batch led by another object joins the
-            // lanes as they stand -- both read the maps this batch writes
-            MMF_HIP_TRY(hipEventRecord(objs[0]->ev_done, st));
-            for (size_t k = 1; k < objs.size(); ++k) MMF_HIP_TRY(hipStreamWaitEvent(objs[k]->lane->stream, objs[0]->ev_done, 0));
+            // Model::fuse(..., weightMultiplier) applies computeFusionWeight(weightMultiplier) (:359-360, Model.cpp:918)
+            rc = fusion_fuse_clean_model(f, fm, fusion_weight(tnew, fm->last_pose, fr->weight_multiplier));  // :357-366
+            if (rc) return rc;
         }
+        if (!do_icp) continue;  // no refinement, use the initial pose directly (:382-385)
+        // Model::performTracking (Model.cpp:409-433) with Model::initICP (:390-407)
+        float pose[16];
+        mmf_model_get_pose(fm->model, pose);
+        std::memcpy(fm->last_pose, pose, sizeof(pose));  // lastPose = pose (Model.cpp:412)
+        fm->tracking = true;
+        r.tracked.push_back(fm);
     }
-    stamp(3);
-    {  // predict() (:821): the object models without fill-in as one batch, the others one by one
-        std::vector<FusionModel*> objs;
-        const int pass_mode = fusion_batch_mode(f);
-        for (size_t k = 1; k < f->models.size() && pass_mode != 0; ++k) {
-            FusionModel* fm = f->models[k];
-            if (!fusion_owns(f, k) || fm->fill_in || !model_predict_batchable(fm->model) || (int)objs.size() >= kMaxPassBatch) continue;
-            objs.push_back(fm);
-        }
-        if (objs.size() < 2) objs.clear();
-        for (size_t k = 0; k < f->models.size(); ++k) {
-            if (!fusion_owns(f, k)) continue;
-            if (std::find(objs.begin(), objs.end(), f->models[k]) != objs.end()) continue;
-            rc = fusion_predict_model(f, f->models[k]);
-            if (rc) return rc;
-        }
-        if (!objs.empty()) {
-            hipStream_t st = objs[0]->lane->stream;
-            rc = fusion_lanes_join(objs, st);
-            if (rc) return rc;
-            mmf_model* ms[kMaxPassBatch];
-            for (size_t k = 0; k < objs.size(); ++k) ms[k] = objs[k]->model;
-            rc = pass_mode >= 2 ? models_combined_predict_rect(ms, (int)objs.size(), st, g.max_depth_processed, f->tick, f->tick, g.time_delta)
-                                          : models_combined_predict_batched(ms, (int)objs.size(), st, g.max_depth_processed, f->tick, f->tick, g.time_delta);
-            if (rc) return rc;
-            // the other objects' streams continue behind the batch: whatever is enqueued on them next reads what it wrote
-            MMF_HIP_TRY(hipEventRecord(objs[0]->ev_done, st));
-            for (size_t k = 1; k < objs.size(); ++k) MMF_HIP_TRY(hipStreamWaitEvent(objs[k]->lane->stream, objs[0]->ev_done, 0));
-        }
-    }
-    stamp(4);
-    f->tick++;  // :825
+    return MMF_OK;
+}
 
-    // :829-846: pose log (camera->world for the first model, object->world for the others)
+// the tracked models' model-side preparation and chains.  ONE chain of launches for all tracked models (gridDim.y = model)
+// when every level runs on the fused producer path and no model went through a pose-initialisation round on its own stream;
+// else one chain per model on the model's stream.  Either way nothing waits here.
+static int frame_enqueue_tracking(mmf_fusion* f, FrameRun& r) {
+    const mmf_frame* fr = r.fr;
+    const mmf_fusion_config& g = f->cfg;
+    FusionModel* global = f->models[0];
+    const std::vector<FusionModel*>& tracked = r.tracked;
+    if (r.so3_stage)  // every chain enqueued below starts from the prefetched pre-alignment
+        for (FusionModel* fm : tracked) fm->odom->so3_prefetched = true, fm->odom->so3_stage = r.so3_stage;
+    r.batched = tracked.size() > 1 && tracked.size() <= (size_t)kMaxBatch && !r.have_init && g.batch_tracking;
+    const unsigned ext_gen = ++f->extent_seq;
+    for (FusionModel* fm : tracked) fm->odom->sparse = fm != global && !fm->fill_in;  // an object model: extent.hpp, ChainGeom
+    r.batch_ok = r.batched;
+    if (r.batched) {  // (one_pass is one model: a batch is never prepared with the sensor side)
+        FusionModel* lead = tracked[0];
+        hipStream_t st = lead->lane->stream;
+        for (size_t k = 1; k < tracked.size(); ++k) {  // the other models' last work (previous frame's predict) precedes
+            // (a model prepared at the end of the last call, behind the join of all streams there, and untouched since:
+            // nothing enqueued below reads what its stream may still hold)
+            if (tracked[k]->spec_hit) continue;
+            MMF_HIP_TRY(hipEventRecord(tracked[k]->ev_done, tracked[k]->lane->stream));
+            MMF_HIP_TRY(hipStreamWaitEvent(st, tracked[k]->ev_done, 0));
+        }
+        PrepStages stages;
+        stages.set_critical(true);  // the model's stream
+        for (FusionModel* fm : tracked) {
+            if (fm->spec_hit) {
+                fm->odom->depth_l0 = f->depth_filtered;
+                continue;
+            }
+            float pose[16];
+            mmf_model_get_pose(fm->model, pose);
+            fusion_collect_prep(f, stages, fm, pose, PREP_MODEL_SIDE, true, ext_gen);
+        }
+        int rc = stages.launch(st);
+        if (rc) return rc;
+        r.stamp(f, 8);
+        r.batch_ok = odom_batchable(lead->odom, g.rgb_only, g.icp_weight, g.pyramid, g.fast_odom);
+        if (r.batch_ok) {
+            lead->odom->exclusive_chain = true;  // one chain for all of them
+            return fusion_enqueue_chains(f, tracked.data(), tracked.size(), true, false);
+        }
+    }
+    for (size_t k = 0; k < tracked.size(); ++k) {
+        FusionModel* fm = tracked[k];
+        const bool prep_all = fm == global && r.one_pass && !r.prefetched;
+        if (r.will_batch && fm != global) {  // (the wait frame_init_poses skipped)
+            int rc = lane_wait(fm, f->ev_frame_ready);
+            if (rc) return rc;
+        }
+        if (fm->spec_hit) {  // the model side was prepared at the end of the last frame; the sensor side by the prefetch
+            fm->odom->depth_l0 = f->depth_filtered;  // (or in frame_track_sensor_side)
+        } else if (!r.batched) {  // (a failed batch has prepared every model already)
+            PrepStages stages;
+            stages.set_critical(true);  // the model's stream
+            float pose[16];
+            mmf_model_get_pose(fm->model, pose);
+            fusion_collect_prep(f, stages, fm, pose, prep_all ? PREP_ALL : PREP_MODEL_SIDE, true, ext_gen);
+            int rc = stages.launch(fm->lane->stream);
+            if (rc) return rc;
+            if (prep_all) odom_adopt_gradients(global->odom);  // (PREP_ALL: this frame's image side as well)
+        } else if (k > 0) {  // prepared on the leader's stream
+            MMF_HIP_TRY(hipEventRecord(fm->ev_done, tracked[0]->lane->stream));
+            MMF_HIP_TRY(hipStreamWaitEvent(fm->lane->stream, fm->ev_done, 0));
+        }
+        fm->odom->exclusive_chain = tracked.size() == 1;  // several chains side by side: no in-launch barriers
+        // The frame's first projection, enqueued right behind this chain (frame_enqueue_ahead), carries the hand-over to the
+        // host and the fusion weight on one extra workgroup (frame_rider.hpp): the chain's last launch is the solve alone (13
+        // -> 5.7 us on the stream a frame waits for).
+        fm->odom->defer_publish = tracked.size() == 1 && !fr->bootstrap && !r.have_init && !g.rgb_only && f->tracking_ok;
+        int rc = fusion_enqueue_chains(f, &fm, 1, false, false);
+        if (rc) return rc;
+    }
+    return MMF_OK;
+}
+
+// One model on the context's stream, nothing between its tracking and its fusion that the host decides: the frame's first
+// projections -- predict() (:675) and the first predictIndices (:792) -- are enqueued right here, behind the chain and the
+// copy of its result, with the inverse pose read from the odometry's device state.  They run while the host picks the pose
+// up and prepares the fusion passes (that turnaround used to be ~25 us of idle GPU per frame).
+// (With several models it is one model per process in the sharded configuration: the segmentation between tracking and
+// fusion touches masks, thresholds and the list, none of which a projection reads.)
+static int frame_enqueue_ahead(mmf_fusion* f, FrameRun& r) {
+    const mmf_fusion_config& g = f->cfg;
+    static_assert(std::is_trivially_copyable<mmf_model>::value, "the speculation rollback copies mmf_model by value");
+    if (!(r.tracked.size() == 1 && !r.fr->bootstrap && !r.have_init && !g.rgb_only && f->tracking_ok)) return MMF_OK;
+    FusionModel* fm = r.tracked[0];
+    mmf_model* m = fm->model;
+    r.early_snapshot = *m, r.early_snapshot_valid = true;
+    m->abort_dev = &fm->odom->state->gn_fault;
+    // "nothing enqueued so far reads the odometries' sensor-side buffers or the other filtered-depth buffer" holds
+    // HERE, behind the one chain of this process; the passes enqueued next do not read them either.  No event
+    // says so any more (see frame_track: the host knows when it has the pose; a marker behind the chain cost the
+    // model's stream ~4 us in front of the frame's first projection).
+    m->t_inv_dev = fm->odom->state->pose_inv;
+    m->rider = fm->odom->rider;
+    fm->odom->rider = FrameRider();
+    int rc = fusion_mid_predict() ? fusion_predict_model(f, fm) : MMF_OK;
+    if (rc == MMF_OK) rc = mmf_model_predict_indices(m, f->tick, g.max_depth_processed, g.time_delta);
+    MMF_REQUIRE(rc != MMF_OK || m->rider.st == nullptr, "mmf_fusion_process_frame: the tracking result was not handed over");
+    fm->early_done = rc == MMF_OK;
+    // Without a segmentation the mask of the frame is known (all zeros) and nothing the host decides lies
+    // between tracking and fusion: fuse -> predictIndices -> clean (:791-816) follow at once, with the pose and
+    // Model::computeFusionWeight taken from the device state (odom_end, odom_fusion_weight_kernel).
+    if (rc == MMF_OK && !g.enable_multiple_models) {
+        m->pose_dev = fm->odom->state->pose_out, m->weight_dev = &fm->odom->state->fusion_weight;
+        rc = fusion_fuse_clean_model(f, fm, r.fr->weight_multiplier, true);
+        fm->early_fused = rc == MMF_OK;
+    }
+    m->t_inv_dev = m->pose_dev = m->weight_dev = nullptr;
+    m->abort_dev = nullptr;
+    return rc;
+}
+
+// The one-launch chain can give up (its count barrier needs every workgroup of a launch resident: another process on the GPU
+// can prevent that; OdomState::gn_fault).  Then nothing of the chain's result is valid and the passes enqueued ahead of the
+// pose have done nothing (MMF_SPECULATION_GUARD): the model's host bookkeeping goes back to where it was, the process stops
+// using that chain, and the frame's tracking is enqueued again -- the two-launch chain, from the poses the frame started with
+// (fm->last_pose) -- before the results are picked up a second time.
+static int fusion_retrack(mmf_fusion* f, FrameRun& r) {
+    std::vector<mmf_odom*> odoms;
+    for (FusionModel* fm : r.tracked) odoms.push_back(fm->odom);
+    odom_retrack_prepare(odoms.data(), (int)odoms.size(), f->cfg.so3);
+    if (r.early_snapshot_valid) {
+        *r.tracked[0]->model = r.early_snapshot;
+        r.tracked[0]->early_done = r.tracked[0]->early_fused = false;
+        r.early_snapshot_valid = false;
+    }
+    for (FusionModel* fm : r.tracked) fm->odom->defer_publish = false, fm->odom->rider = FrameRider();
+    return fusion_enqueue_chains(f, r.tracked.data(), r.tracked.size(), r.batch_ok, true);
+}
+
+// the tracking results, model by model
+static int frame_pick_up_poses(mmf_fusion* f, FrameRun& r) {
+    bool retracked = false;
+    for (size_t k = 0; k < f->models.size(); ++k) {
+        FusionModel* fm = f->models[k];
+        float pose[16];
+        mmf_model_get_pose(fm->model, pose);
+        if (!fm->tracking) continue;
+        float trans[3], rot[9];
+        int rc = odom_finish_tracking(fm->odom, trans, rot);
+        if (rc == kGnRetry && !retracked) {  // (at most once: the two-launch chain has no way to give up)
+            // every chain of the frame is void with it (a batch is one chain; chains side by side are two-launch chains)
+            for (FusionModel* t : r.tracked)
+                if (t->tracking && t != fm && t->odom->result_of) {  // drain what the other lanes' chains still publish
+                    float tt[3], rr[9];
+                    (void)odom_finish_tracking(t->odom, tt, rr);
+                }
+            rc = fusion_retrack(f, r);
+            if (rc) return rc;
+            retracked = true;
+            for (FusionModel* t : r.tracked) {  // poses already taken over from the void chain: back to the frame's start
+                mmf_model_set_pose(t->model, t->last_pose);
+                t->tracking = true;
+            }
+            k = (size_t)-1;  // pick the results up again, from the first model
+            continue;
+        }
+        if (rc == kGnRetry) return gn_retry_twice();
+        if (rc) return rc;
+        for (int i = 0; i < 3; ++i) {
+            for (int q = 0; q < 3; ++q) pose[i * 4 + q] = rot[i * 3 + q];
+            pose[i * 4 + 3] = trans[i];
+        }
+        mmf_model_set_pose(fm->model, pose);
+        fm->tracking = false;
+        if (fm->lane->stream == f->ctx->stream) f->host_caught_up = true;
+    }
+    return MMF_OK;
+}
+
+// :299-400: every model's tracking, enqueued before the first result is awaited, then the bootstrap
+static int frame_track(mmf_fusion* f, FrameRun& r) {
+    const mmf_frame* fr = r.fr;
+    const mmf_fusion_config& g = f->cfg;
+    FusionModel* global = f->models[0];
+    MMF_REQUIRE(!r.have_init || !g.frame_to_frame_rgb, "ICP initialisation not supported in frame-to-frame mode");  // :370
+    const auto t_track = std::chrono::steady_clock::now();
+    int rc = frame_track_sensor_side(f, r);
+    if (rc) return rc;
+    r.stamp(f, 6);
+    rc = frame_init_poses(f, r);
+    if (rc) return rc;
+    r.stamp(f, 7);
+    rc = frame_enqueue_tracking(f, r);
+    if (rc) return rc;
+    rc = frame_enqueue_ahead(f, r);
+    if (rc) return rc;
+    // the sensor-side image ring (this frame's / last frame's intensity pyramid, RGBDOdometry.cpp:469-473) lives in
+    // the global odometry and advances when its chain is enqueued: when its owner is another rank, the swap
+    // happens here, whether or not this rank tracked anything (every rank's ring must advance with the global model's)
+    const bool global_tracks_somewhere = !(r.have_init && !fr->icp_refine);
+    if (g.so3 && global_tracks_somewhere && !global->tracking)
+        for (int i = 0; i < MMF_NUM_PYRS; ++i) std::swap(global->odom->last_next_image[i], global->odom->next_image[i]);
+    if (r.early_image == 1 && r.image_early_ok && !r.tracked.empty()) {  // (see frame_track_sensor_side)
+        rc = fusion_prefetch_image(f, fr->next_rgb, f->tick + 1, true);
+        if (rc) return rc;
+    }
+    r.stamp(f, 0);
+    // a host frame announced for the next call: staged and sent up now, while the GPU tracks and the host would only wait
+    // (its colour image first; the depth image is joined where the depth side is enqueued, behind the pose)
+    rc = fusion_stage_host_rgb(f);
+    if (rc) return rc;
+    // ... and its image side behind the upload (an announced HOST frame cannot have it at the start of the call: its
+    // copy into pinned memory has only just begun then), beside the chain instead of behind the pose
+    if (r.early_image != 0 && r.image_early_any && r.next_from_host && !r.tracked.empty() && f->host_next.rgb_staged) {
+        MMF_HIP_TRY(fusion_wait_unless_done(f->side2, f->ev_up_rgb[f->host_next.slot]));
+        rc = fusion_prefetch_image(f, fr->next_rgb, f->tick + 1, true);
+        if (rc) return rc;
+    }
+    rc = frame_pick_up_poses(f, r);
+    if (rc) return rc;
+    f->t_tracking_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_track).count();
+    r.stamp(f, 1);
+    if (fr->bootstrap) {  // :397-400
+        MMF_REQUIRE(fr->in_pose != nullptr, "mmf_fusion_process_frame: bootstrap needs in_pose");
+        float pose[16], np[16];
+        mmf_model_get_pose(global->model, pose);
+        mmf::host::matmul4(pose, fr->in_pose, np);
+        mmf_model_set_pose(global->model, np);  // overridePose
+        std::memcpy(global->last_pose, np, sizeof(np));
+    }
+    // from here on nothing enqueued reads the odometries' sensor-side buffers or the other filtered-depth
+    // buffer, and the HOST knows it: every chain's result has been received, so every chain -- and whatever its
+    // stream held before it, e.g. this frame's own image-side preparation -- has run.  The next frame's side-stream
+    // work, enqueued from here on, needs no event to wait for (inputs_free_recorded stays false).
+    if (r.one_pass && r.lanes_wait) MMF_HIP_TRY(hipEventRecord(f->ev_frame_ready, f->ctx->stream));
+    return MMF_OK;
+}
+
+// :407-622: the segmentation's mask, a new model's first surfels, models that leave the list, confidence thresholds
+static int frame_segment(mmf_fusion* f, const FrameRun& r) {
+    const mmf_frame* fr = r.fr;
+    const mmf_fusion_config& g = f->cfg;
+    mmf_ctx* c = f->ctx;
+    mmf_segmentation seg_cb;
+    const mmf_segmentation* seg = fr->segmentation;
+    if (!seg && f->seg_fn) {  // performSegmentation(frame) (:412)
+        std::memset(&seg_cb, 0, sizeof(seg_cb));
+        if (f->seg_fn(f->seg_user, f, fr, &seg_cb)) return fail(MMF_ERR_STATE, "mmf_fusion_process_frame: the segmentation callback failed");
+        seg = &seg_cb;
+    }
+    MMF_REQUIRE(seg && seg->mask, "mmf_fusion_process_frame: enableMultipleModels needs a segmentation "
+                                  "(mmf_frame::segmentation or mmf_fusion_set_segmentation_callback)");
+    // textures[MASK]->Upload(fullSegmentation) (:416)
+    MMF_HIP_TRY(hipMemcpyAsync(f->mask, seg->mask, (size_t)f->width * f->height, hipMemcpyDeviceToDevice, c->stream));
+    f->mask_is_zero = false;
+    MMF_HIP_TRY(hipEventRecord(f->ev_frame_ready, c->stream));
+    const int n_data = seg->model_data ? seg->n_models : 0;
+    FusionModel* fresh = nullptr;
+    if (seg->has_new_label) {  // :469-487
+        int rc = fusion_spawn(f, &fresh);
+        if (rc) return rc;
+        if (n_data > 0) fresh->model->max_depth = seg_max_depth(seg->model_data[n_data - 1]);
+    }
+    // Set max-depth (:585-586)
+    for (size_t i = 1; i < f->models.size() && (int)i < n_data; ++i) f->models[i]->model->max_depth = seg_max_depth(seg->model_data[i]);
+    if (fresh && !fusion_owns_model(f, fresh)) {
+        f->models.push_back(fresh);  // another rank's model: bookkeeping only
+    } else if (fresh) {  // :588-601: the first surfels of the new model, then it joins the list
+        int rc = lane_wait(fresh, f->ev_frame_ready);
+        if (rc) return rc;
+        identity16(fresh->last_pose);
+        float pose[16];
+        mmf_model_get_pose(fresh->model, pose);
+        rc = mmf_model_predict_indices(fresh->model, f->tick, g.max_depth_processed, g.time_delta);
+        if (rc) return rc;
+        rc = mmf_model_fuse(fresh->model, f->tick, f->frame_rgb, f->mask, f->frame_depth, f->depth_filtered, g.max_depth_processed,
+                            fusion_weight(pose, fresh->last_pose, 100.f));  // fuse(..., 100) (:591-592)
+        if (rc) return rc;
+        // (the second predictIndices is commented out in the reference, :594)
+        rc = mmf_model_clean(fresh->model, f->tick, g.time_delta, g.max_depth_processed, f->depth_filtered, f->mask, g.outlier_coeff);
+        if (rc) return rc;
+        f->models.push_back(fresh);  // moveNewModelToList (:600)
+    }
+    // unseen models leave the list (:606-613); the confidence of object models rises (:616-620)
+    std::vector<FusionModel*> lost;
+    for (int i = 0; i < n_data; ++i) {
+        FusionModel* fm = fusion_find(f, (int)seg->model_data[i].id);
+        if (!fm || fm == fresh) continue;
+        if (seg->model_data[i].super_pixel_count <= 0 && ++fm->unseen > 0 && fm->model->id != 0) lost.push_back(fm);
+    }
+    for (FusionModel* fm : lost) fusion_inactivate(f, fm);
+    for (size_t i = 1; i < f->models.size() && (int)i < n_data; ++i) {
+        const float old_conf = f->models[i]->model->conf_threshold;
+        const float avg = seg->model_data[i].avg_confidence;
+        const float m1 = old_conf < avg ? avg : old_conf;
+        f->models[i]->model->conf_threshold = 9.0f < m1 ? 9.0f : m1;
+    }
+    return MMF_OK;
+}
+
+// globalModel->overridePose(*inPose) (:670)
+static int frame_dictated_pose(mmf_fusion* f, const FrameRun& r) {
+    FusionModel* global = f->models[0];
+    float pose[16];
+    std::memcpy(pose, r.fr->in_pose, sizeof(pose));
+    mmf_model_set_pose(global->model, pose);
+    std::memcpy(global->last_pose, pose, sizeof(pose));
+    MMF_HIP_TRY(hipEventRecord(f->ev_inputs_free, f->ctx->stream));
+    f->inputs_free_recorded = true;
+    MMF_HIP_TRY(hipEventRecord(f->ev_frame_ready, f->ctx->stream));
+    return MMF_OK;
+}
+
+// The OBJECT models whose passes go out as one launch per pass for all of them on the first one's stream (pass mode 2): ~9
+// launches per model and frame otherwise, and with seven objects the calling thread's launch rate set the pace of that part
+// of the frame.  At least two, at most kMaxPassBatch, no fill-in: the camera model keeps its own stream and kernels (riders,
+// fill-in).  The fuse / clean batch leaves out a model whose passes went out ahead of its pose; the predict batch leaves out
+// deep stores and models with device-side inputs (model_predict_batchable).  So a model fused in the batch can be predicted
+// on its own stream, and a predict batch can be led by another object: both read the maps the fuse / clean batch wrote, and
+// every object's stream continues behind a batch (fusion_pass_batch).
+static void fusion_pass_batch_members(const mmf_fusion* f, bool predict, std::vector<FusionModel*>& objs) {
+    for (size_t k = 1; k < f->models.size(); ++k) {
+        FusionModel* fm = f->models[k];
+        if (!fusion_owns(f, k) || fm->fill_in || (int)objs.size() >= kMaxPassBatch) continue;
+        if (predict ? !model_predict_batchable(fm->model) : (fm->early_done || fm->early_fused)) continue;
+        objs.push_back(fm);
+    }
+    if (objs.size() < 2) objs.clear();
+}
+// one batch on objs[0]'s stream: it waits for whatever the other objects' streams still hold (fusion_lanes_join),
+// enqueue(models, n, stream) enqueues the passes, and the other objects' streams continue behind the batch
+template <typename Enqueue>
+static int fusion_pass_batch(const std::vector<FusionModel*>& objs, Enqueue&& enqueue) {
+    hipStream_t st = objs[0]->lane->stream;
+    int rc = fusion_lanes_join(objs, st);
+    if (rc) return rc;
+    mmf_model* ms[kMaxPassBatch];
+    for (size_t k = 0; k < objs.size(); ++k) ms[k] = objs[k]->model;
+    rc = enqueue(ms, (int)objs.size(), st);
+    if (rc) return rc;
+    MMF_HIP_TRY(hipEventRecord(objs[0]->ev_done, st));
+    for (size_t k = 1; k < objs.size(); ++k) MMF_HIP_TRY(hipStreamWaitEvent(objs[k]->lane->stream, objs[0]->ev_done, 0));
+    return MMF_OK;
+}
+
+// predict() (:675), then predictIndices -> fuse -> predictIndices -> clean (:791-816) of every model
+static int frame_fuse_clean(mmf_fusion* f, const FrameRun& r) {
+    const mmf_fusion_config& g = f->cfg;
+    const float weight_multiplier = r.fr->weight_multiplier;
+    const bool fuse_now = !g.rgb_only && f->tracking_ok;
+    std::vector<FusionModel*> objs;
+    if (r.pass_mode != 0 && fuse_now && !fusion_mid_predict()) fusion_pass_batch_members(f, false, objs);
+    for (size_t k = 0; k < f->models.size(); ++k) {  // model by model
+        FusionModel* fm = f->models[k];
+        if (!fusion_owns(f, k)) continue;
+        if (std::find(objs.begin(), objs.end(), fm) != objs.end()) continue;  // (batched below)
+        if (k > 0) {
+            int rc = lane_wait(fm, f->ev_frame_ready);
+            if (rc) return rc;
+        }
+        const bool early = fm->early_done;  // its predict + predictIndices are already enqueued
+        fm->early_done = false;
+        if (!early && fusion_mid_predict()) {
+            int rc = fusion_predict_model(f, fm);
+            if (rc) return rc;
+        }
+        if (fuse_now && !fm->early_fused) {
+            float pose[16];
+            mmf_model_get_pose(fm->model, pose);
+            int rc = fusion_fuse_clean_model(f, fm, fusion_weight(pose, fm->last_pose, weight_multiplier), early);
+            if (rc) return rc;
+        }
+        fm->early_fused = false;
+    }
+    if (objs.empty()) return MMF_OK;
+    int rc = lane_wait(objs[0], f->ev_frame_ready);
+    if (rc) return rc;
+    return fusion_pass_batch(objs, [&](mmf_model* const* ms, int n, hipStream_t st) {
+        float wts[kMaxPassBatch];
+        for (int k = 0; k < n; ++k) {
+            float pose[16];
+            mmf_model_get_pose(ms[k], pose);
+            wts[k] = fusion_weight(pose, objs[k]->last_pose, weight_multiplier);
+        }
+        int rc2 = fusion_note_mask_boxes(f, st);
+        if (rc2) return rc2;
+        return models_fuse_clean_rect(ms, n, st, f->tick, g.time_delta, g.max_depth_processed, f->frame_rgb, f->mask, f->frame_depth,
+                                      f->depth_filtered, g.outlier_coeff, wts, f->mask_boxes, f->mask_gen);
+    });
+}
+
+// predict() (:821): the object models in a batch, the others one by one
+static int frame_predict(mmf_fusion* f, const FrameRun& r) {
+    const mmf_fusion_config& g = f->cfg;
+    std::vector<FusionModel*> objs;
+    if (r.pass_mode != 0) fusion_pass_batch_members(f, true, objs);
+    for (size_t k = 0; k < f->models.size(); ++k) {
+        if (!fusion_owns(f, k)) continue;
+        if (std::find(objs.begin(), objs.end(), f->models[k]) != objs.end()) continue;
+        int rc = fusion_predict_model(f, f->models[k]);
+        if (rc) return rc;
+    }
+    if (objs.empty()) return MMF_OK;
+    return fusion_pass_batch(objs, [&](mmf_model* const* ms, int n, hipStream_t st) {
+        return models_combined_predict_rect(ms, n, st, g.max_depth_processed, f->tick, f->tick, g.time_delta);
+    });
+}
+
+// :829-846: pose log (camera->world for the first model, object->world for the others)
+static void frame_log_poses(mmf_fusion* f, const FrameRun& r) {
     float global_pose[16];
-    mmf_model_get_pose(global->model, global_pose);
+    mmf_model_get_pose(f->models[0]->model, global_pose);
     for (size_t k = 0; k < f->models.size(); ++k) {
         FusionModel* fm = f->models[k];
         if (fm->pose_log.capacity() == 0) continue;  // isLoggingPoses()
@@ -1323,100 +1387,141 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
             mmf::host::matmul4(global_pose, inv, T);
         }
         PoseLogItem item;
-        item.ts = fr->timestamp;
+        item.ts = r.fr->timestamp;
         pose_to_log7(T, item.p);
         fm->pose_log.push_back(item);
     }
+}
 
+// the next frame's model-side preparation, at the end of this one (see FusionModel::spec_valid)
+static int frame_prepare_next(mmf_fusion* f, const FrameRun& r) {
+    const mmf_frame* fr = r.fr;
+    const mmf_fusion_config& g = f->cfg;
+    FusionModel* global = f->models[0];
+    FusionModel* only = nullptr;
+    int owned = 0;
+    for (size_t k = 0; k < f->models.size(); ++k)
+        if (fusion_owns(f, k)) only = f->models[k], ++owned;
+    if (owned == 1) {
+        const mmf_model* m = only->model;
+        hipStream_t st = only->lane->stream;
+        PrepStages stages;
+        stages.set_critical(true);  // the model's stream
+        mmf_model_get_pose(only->model, only->spec_pose);
+        fusion_collect_prep(f, stages, only, only->spec_pose, PREP_MODEL_SIDE, false, 0u);
+        // ... and the beginning of that tracking (odom_begin_kernel: the pose it starts from is this one, the pre-alignment
+        // of the next frame sits staged since the start of this call) on one more workgroup of the preparation's last launch
+        BeginRider rider;
+        bool ride = false;
+        if (only == global && !stages.empty() && fr->next_rgb && f->image_pre_rgb == fr->next_rgb && !g.rgb_only) {
+            const OdomState* stage = (g.so3 && f->so3_stage_ready >= 0) ? f->so3_stage[f->so3_stage_ready] : nullptr;
+            if (!g.so3 || stage != nullptr) {
+                if (stage) MMF_HIP_TRY(fusion_wait_unless_done(st, f->ev_prefetch2_done));  // (the staged pre-alignment is complete)
+                ride = odom_begin_rider(only->odom, only->spec_pose, g.rgb_only, g.icp_weight, g.pyramid, g.fast_odom, g.so3, stage, &rider);
+            }
+        }
+        if (!ride) only->odom->begin_spec_valid = false;
+        int rc = stages.launch(st, ride ? &rider : nullptr);
+        if (rc) return rc;
+        only->spec_tex_gen = m->tex_gen;
+        only->spec_f2f = g.frame_to_frame_rgb;
+        only->spec_valid = true;
+    } else if (owned >= std::max(2, tunables().spec_prep_all) && f->shard_world <= 1 && g.batch_tracking && owned <= kMaxBatch && tunables().spec_prep_all) {
+        // Several models on this GPU: the same for all of them, in the launches they will share (the batched chain's
+        // preparation: one set of stages, every model's jobs).  At the start of the next call these ~50 jobs were what the
+        // calling thread enqueued first -- 130 us of it and as much of the GPU's -- while the GPU had nothing else to do; here
+        // they queue up behind the frame's last passes.  A model whose pose or prediction changes before it is tracked
+        // (a pose initialisation, a caller's predict()) is prepared again then (spec_hit).  From two models on (round 4: from
+        // four -- with two or three the early preparation measured 6 % slower while every model's stream was joined by an
+        // event in front of the chain; a model prepared HERE needs no such wait, and it is 4-7 % faster: LABNOTES r5).
+        PrepStages stages;
+        stages.set_critical(true);
+        const unsigned ext_gen = ++f->extent_seq;
+        for (size_t k = 0; k < f->models.size(); ++k) {
+            if (!fusion_owns(f, k)) continue;
+            FusionModel* fm = f->models[k];
+            fm->odom->sparse = fm != global && !fm->fill_in;
+            mmf_model_get_pose(fm->model, fm->spec_pose);
+            fusion_collect_prep(f, stages, fm, fm->spec_pose, PREP_MODEL_SIDE, true, ext_gen);
+            fm->spec_tex_gen = fm->model->tex_gen;
+            fm->spec_f2f = g.frame_to_frame_rgb;
+            fm->spec_valid = true;
+        }
+        int rc = stages.launch(f->ctx->stream);  // (every lane has joined this stream in frame_end)
+        if (rc) return rc;
+    }
+    return MMF_OK;
+}
+
+// the end of the call: the lanes join, the next frame's prefetch, its model-side preparation
+static int frame_end(mmf_fusion* f, const FrameRun& r) {
+    const mmf_frame* fr = r.fr;
     // the fusion's stream continues only after every lane: the next frame's filter, prefetch and mask upload
     // overwrite what the lanes read
     for (size_t k = 1; k < f->models.size(); ++k) {
         FusionModel* fm = f->models[k];
         if (!fusion_owns(f, k)) continue;
         MMF_HIP_TRY(hipEventRecord(fm->ev_done, fm->lane->stream));
-        MMF_HIP_TRY(hipStreamWaitEvent(c->stream, fm->ev_done, 0));
+        MMF_HIP_TRY(hipStreamWaitEvent(f->ctx->stream, fm->ev_done, 0));
     }
-    if (fr->next_rgb && fr->next_depth && !next_prefetched) {  // (first frame, dictated pose, several lanes)
-        rc = fusion_prefetch_impl(f, fr->next_rgb, fr->next_depth, f->tick);
+    if (fr->next_rgb && fr->next_depth) {  // (first frame, dictated pose, several lanes)
+        int rc = fusion_prefetch_impl(f, fr->next_rgb, fr->next_depth, f->tick);
         if (rc) return rc;
     }
-    // next frame's model-side preparation, now (see FusionModel::spec_valid); behind the prefetch's enqueue: the side
-    // streams have the longer way to go
-    {
-        FusionModel* only = nullptr;
-        int owned = 0;
-        for (size_t k = 0; k < f->models.size(); ++k)
-            if (fusion_owns(f, k)) only = f->models[k], ++owned;
-        if (owned == 1) {
-            const mmf_model* m = only->model;
-            hipStream_t st = only->lane->stream;
-            // (requiresFillIn (:380, :877-895) of the next frame: decided on the device from the count this prediction's resolve left)
-            PrepStages stages;
-                stages.set_critical(true);  // the model's stream
-            const uint8_t* pi = (const uint8_t*)((g.frame_to_frame_rgb && only->fill_in) ? m->fill_image : m->image);
-            mmf_model_get_pose(only->model, only->spec_pose);
-            odom_prepare_collect(stages, only->odom, f->depth_filtered, g.max_depth_processed, rgb, 3, (const float*)m->vertexConf,
-                                 (const float*)m->normalRadius, pi, 4, only->spec_pose,
-                                 only->fill_in ? fusion_thumb_count(m) : nullptr, (const float*)m->fill_vertex,
-                                 (const float*)m->fill_normal, (const uint8_t*)m->fill_image, PREP_MODEL_SIDE,
-                                 (m->width / 20) * (m->height / 20), 0.75f);
-            // ... and the beginning of that tracking (odom_begin_kernel: the pose it starts from is this one, the pre-alignment
-            // of the next frame sits staged since the start of this call) on one more workgroup of the preparation's last launch
-            BeginRider rider;
-            bool ride = false;
-            if (only == global && !stages.empty() && fr->next_rgb && f->image_pre_rgb == fr->next_rgb && !g.rgb_only) {
-                const OdomState* stage = (g.so3 && f->so3_stage_ready >= 0) ? f->so3_stage[f->so3_stage_ready] : nullptr;
-                if (!g.so3 || stage != nullptr) {
-                    if (stage) MMF_HIP_TRY(fusion_wait_unless_done(st, f->ev_prefetch2_done));  // (the staged pre-alignment is complete)
-                    ride = odom_begin_rider(only->odom, only->spec_pose, g.rgb_only, g.icp_weight, g.pyramid, g.fast_odom, g.so3, stage, &rider);
-                }
-            }
-            if (!ride) only->odom->begin_spec_valid = false;
-            rc = stages.launch(st, ride ? &rider : nullptr);
-            if (rc) return rc;
-            only->spec_tex_gen = m->tex_gen;
-            only->spec_f2f = g.frame_to_frame_rgb;
-            only->spec_valid = true;
-        } else if (owned >= std::max(2, tunables().spec_prep_all) && f->shard_world <= 1 && g.batch_tracking && owned <= kMaxBatch && tunables().spec_prep_all) {
-            // Several models on this GPU: the same for all of them, in the launches they will share (the batched chain's
-            // preparation: one set of stages, every model's jobs).  At the start of the next call these ~50 jobs were what the
-            // calling thread enqueued first -- 130 us of it and as much of the GPU's -- while the GPU had nothing else to do; here
-            // they queue up behind the frame's last passes.  A model whose pose or prediction changes before it is tracked
-            // (a pose initialisation, a caller's predict()) is prepared again then (spec_hit).  From two models on (round 4: from
-            // four -- with two or three the early preparation measured 6 % slower while every model's stream was joined by an
-            // event in front of the chain; a model prepared HERE needs no such wait, and it is 4-7 % faster: LABNOTES r5).
-            PrepStages stages;
-            stages.set_critical(true);
-            const unsigned ext_gen = ++f->extent_seq;
-            for (size_t k = 0; k < f->models.size(); ++k) {
-                if (!fusion_owns(f, k)) continue;
-                FusionModel* fm = f->models[k];
-                const mmf_model* m = fm->model;
-                const uint8_t* pi = (const uint8_t*)((g.frame_to_frame_rgb && fm->fill_in) ? m->fill_image : m->image);
-                fm->odom->sparse = fm != global && !fm->fill_in;
-                mmf_model_get_pose(fm->model, fm->spec_pose);
-                odom_prepare_collect(stages, fm->odom, f->depth_filtered, g.max_depth_processed, rgb, 3, (const float*)m->vertexConf,
-                                     (const float*)m->normalRadius, pi, 4, fm->spec_pose,
-                                     fm->fill_in ? fusion_thumb_count(m) : nullptr, (const float*)m->fill_vertex,
-                                     (const float*)m->fill_normal, (const uint8_t*)m->fill_image, PREP_MODEL_SIDE,
-                                     (m->width / 20) * (m->height / 20), 0.75f, fm->odom->sparse ? ext_gen : 0u, fusion_pred_box(fm, PREP_MODEL_SIDE));
-                fm->spec_tex_gen = m->tex_gen;
-                fm->spec_f2f = g.frame_to_frame_rgb;
-                fm->spec_valid = true;
-            }
-            rc = stages.launch(c->stream);  // (every lane has joined this stream just above)
+    // behind the prefetch's enqueue: the side streams have the longer way to go
+    return frame_prepare_next(f, r);
+}
+
+static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
+    MMF_REQUIRE(f != nullptr && fr != nullptr, "mmf_fusion_process_frame: null argument");
+    if (!fr->rgb || !fr->depth || fr->timestamp < 0)  // MultiMotionFusion.cpp:209-212
+        return fail(MMF_ERR_INVALID, "invalid image data");
+    MMF_HIP_TRY(hipSetDevice(f->ctx->device));
+    FrameRun r;
+    r.fr = fr;
+    r.t_begin = std::chrono::steady_clock::now();
+    r.host_trace = tunables().host_trace;
+    r.have_init = fr->init_transforms != nullptr && fr->n_init_transforms > 0;
+    r.track = f->tick > 1 && (fr->bootstrap || !fr->in_pose);
+    f->t_tracking_s = 0;
+    int rc = frame_begin(f, r);
+    if (rc) return rc;
+    const bool first = f->tick == 1;
+    if (first) {
+        rc = frame_first(f, r);
+        if (rc) return rc;
+    } else {
+        f->tracking_ok = 1;
+        rc = r.track ? frame_track(f, r) : frame_dictated_pose(f, r);
+        if (rc) return rc;
+        if (r.track && f->cfg.enable_multiple_models) {
+            rc = frame_segment(f, r);
             if (rc) return rc;
         }
+        r.stamp(f, 2);
     }
-    stamp(5);
-    if (host_trace && ++f->trace_calls % 100 == 0) {
+    r.pass_mode = fusion_batch_mode(f);  // (the model list stays as it is from here to the end of the call)
+    if (!first) {
+        rc = frame_fuse_clean(f, r);
+        if (rc) return rc;
+    }
+    r.stamp(f, 3);
+    rc = frame_predict(f, r);
+    if (rc) return rc;
+    r.stamp(f, 4);
+    f->tick++;  // :825
+    frame_log_poses(f, r);
+    rc = frame_end(f, r);
+    if (rc) return rc;
+    r.stamp(f, 5);
+    if (r.host_trace && ++f->trace_calls % 100 == 0) {
         std::fprintf(stderr, "host us from call start: next image side enqueued %.0f, lanes waiting %.0f, preparation enqueued %.0f (batched chains), chains enqueued %.0f, "
                              "poses here %.0f, segmentation handled %.0f, per-model passes enqueued %.0f, final predicts enqueued %.0f, end %.0f\n",
                      f->trace_us[6] / 100, f->trace_us[7] / 100, f->trace_us[8] / 100, f->trace_us[0] / 100, f->trace_us[1] / 100, f->trace_us[2] / 100,
                      f->trace_us[3] / 100, f->trace_us[4] / 100, f->trace_us[5] / 100);
         for (double& a : f->trace_us) a = 0;
     }
-    f->t_frame_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+    f->t_frame_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - r.t_begin).count();
     return MMF_OK;
 }
 

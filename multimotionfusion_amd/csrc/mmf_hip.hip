@@ -2967,138 +2967,6 @@ extern "C" int mmf_model_clean(mmf_model* m, int time, int time_delta, float dep
     return MMF_OK;
 }
 
-// ---- the same passes for SEVERAL models, one launch per pass (surfel_kernels.hpp: *_batched_kernel), all on `st` ----
-// predictIndices -> fuse -> predictIndices -> clean (MultiMotionFusion.cpp:791-816) of n <= kMaxPassBatch models without
-// frame riders, device-side poses or fill-in (object models): what mmf_model_predict_indices, model_fuse(then_index),
-// model_predict_indices(projected) and mmf_model_clean enqueue for each of them, model by model, as seven launches in all.
-static int models_fuse_clean_batched(mmf_model* const* ms, int n, hipStream_t st, int time, int time_delta, float depth_cutoff,
-                                     const uint8_t* rgb, const uint8_t* mask, const float* depth_raw, const float* depth_filtered,
-                                     float outlier_coeff, const float* weighting) {
-    MMF_REQUIRE(ms && n >= 1 && n <= kMaxPassBatch && rgb && mask && depth_raw && depth_filtered && weighting,
-                "models_fuse_clean_batched: bad argument");
-    MMF_HIP_TRY(hipSetDevice(ms[0]->ctx->device));
-    PassBatch<index_map_item> b_map;
-    PassBatch<index_resolve_item> b_res;
-    PassBatch<fuse_data_item> b_fuse;
-    PassBatch<fuse_update_index_item> b_upd;
-    PassBatch<clean_flag_item> b_flag;
-    PassBatch<clean_scatter_item> b_scat;
-    unsigned g_map = 0, g_res = 0, g_fuse = 0, g_upd = 0, g_clean = 0;
-    for (int k = 0; k < n; ++k) {
-        mmf_model* m = ms[k];
-        MMF_REQUIRE(m && m->rider.st == nullptr && !m->t_inv_dev && !m->pose_dev && !m->abort_dev,
-                    "models_fuse_clean_batched: a model with a pending hand-over or a device-side pose");
-        if (int rc0 = model_resolve_count(m)) return rc0;
-        m->idx_nz_known = false;
-        const unsigned npix = (unsigned)(m->width * m->height);
-        const IndexArgs ia = model_index_args(m, time, depth_cutoff, time_delta);
-        index_map_item& im = b_map.m[k];
-        im.s = m->set[m->cur], im.count = (int)m->count, im.a_in = ia, im.keys = m->keys, im.rider = FrameRider();
-        im.grid = (m->count + 255u) / 256u;
-        index_resolve_item& ir = b_res.m[k];
-        ir.s = m->set[m->cur], ir.a_in = ia, ir.keys = m->keys, ir.index = m->index, ir.vertConf = m->vertConf, ir.colorTime = m->colorTime,
-        ir.normRad = m->normRad, ir.rider = FrameRider();
-        ir.grid = (npix + 255u) / 256u;
-        FuseArgs fa;
-        std::memcpy(fa.pose.m, m->pose, sizeof(m->pose));
-        fa.c = make_cam(m, true);
-        fa.cols = m->width, fa.rows = m->height;
-        fa.time = time;
-        fa.weighting = weighting[k];
-        fa.pose_dev = nullptr, fa.weight_dev = nullptr, fa.weight_mult = weighting[k];
-        fa.abort_dev = nullptr;
-        fa.maskID = m->id;
-        fa.maxDepth = depth_cutoff < m->max_depth ? depth_cutoff : m->max_depth;  // std::min(depthCutoff, maxDepth) (Model.cpp:928)
-        fa.count = (int)m->count;
-        fuse_data_item& fd = b_fuse.m[k];
-        fd.rgb = rgb, fd.depth_raw = depth_raw, fd.depth_fil = depth_filtered, fd.mask = mask, fd.index = m->index, fd.vertConf = m->vertConf,
-        fd.normRad = m->normRad, fd.a_in = fa, fd.meas = m->meas, fd.new_flags = m->flags_b, fd.winner = m->winner;
-        fd.grid = ((unsigned)((m->width + 1) / 2) * (unsigned)((m->height + 1) / 2) + 255u) / 256u;
-        fuse_update_index_item& fu = b_upd.m[k];
-        fu.s = m->set[m->cur], fu.count = (int)m->count, fu.meas = m->meas, fu.time = time, fu.winner = m->winner, fu.a_in = ia, fu.keys = m->keys;
-        fu.grid = (m->count + 255u) / 256u;
-        CleanArgs ca;
-        inverse4f_host(m->pose, ca.t_inv.m);
-        ca.t_inv_dev = nullptr, ca.abort_dev = nullptr;
-        ca.c = make_cam(m, false);
-        ca.cols = m->width, ca.rows = m->height;
-        ca.time = time, ca.timeDelta = time_delta;
-        ca.confThreshold = m->conf_threshold;
-        ca.outlierCoeff = outlier_coeff;
-        ca.maskID = m->id;
-        ca.count = (int)m->count;
-        ca.npix = (int)npix;
-        const unsigned nc = m->count + npix;
-        clean_flag_item& cf = b_flag.m[k];
-        cf.s = m->set[m->cur], cf.meas = m->meas, cf.new_flags = m->flags_b, cf.a_in = ca, cf.index = m->index, cf.vertConf = m->vertConf,
-        cf.colorTime = m->colorTime, cf.depth_in = depth_filtered, cf.mask = mask, cf.keep = m->flags_a, cf.conf_time = m->conf_time,
-        cf.block_sums = m->block_sums;
-        cf.grid = (nc + 255u) / 256u;
-        clean_scatter_item& cs = b_scat.m[k];
-        cs.s = m->set[m->cur], cs.meas = m->meas, cs.count = (int)m->count, cs.npix = (int)npix, cs.keep = m->flags_a, cs.block_sums = m->block_sums,
-        cs.conf_time = m->conf_time, cs.dst = m->set[1 - m->cur], cs.capacity = m->capacity, cs.total_out = &m->totals[0],
-        cs.total_host = m->host_totals_dev + kCountWord, cs.seq = ++m->count_seq, cs.abort_dev = nullptr;
-        cs.grid = cf.grid;
-        g_map = std::max(g_map, im.grid), g_res = std::max(g_res, ir.grid), g_fuse = std::max(g_fuse, fd.grid);
-        g_upd = std::max(g_upd, fu.grid), g_clean = std::max(g_clean, cf.grid);
-        // the host's bookkeeping of mmf_model_clean
-        m->count_bound = nc < (unsigned)m->capacity ? nc : (unsigned)m->capacity;
-        m->count_pending = true;
-        m->count_stream = st;
-        m->cur = 1 - m->cur;
-    }
-    const dim3 blk(256);
-    if (g_map) hipLaunchKernelGGL(index_map_batched_kernel, dim3(g_map, n), blk, 0, st, b_map);
-    hipLaunchKernelGGL(index_resolve_batched_kernel, dim3(g_res, n), blk, 0, st, b_res);
-    hipLaunchKernelGGL(fuse_data_batched_kernel, dim3(g_fuse, n), blk, 0, st, b_fuse);
-    if (g_upd) hipLaunchKernelGGL(fuse_update_index_batched_kernel, dim3(g_upd, n), blk, 0, st, b_upd);
-    hipLaunchKernelGGL(index_resolve_batched_kernel, dim3(g_res, n), blk, 0, st, b_res);
-    hipLaunchKernelGGL(clean_flag_batched_kernel, dim3(g_clean, n), blk, 0, st, b_flag);
-    hipLaunchKernelGGL(clean_scatter_batched_kernel, dim3(g_clean, n), blk, 0, st, b_scat);
-    MMF_HIP_TRY(hipGetLastError());
-    return MMF_OK;
-}
-
-// Model::combinedPredict(ACTIVE) (ModelProjection.cpp:187-269) of n models without fill-in, two launches in all
-static int models_combined_predict_batched(mmf_model* const* ms, int n, hipStream_t st, float depth_cutoff, int time, int max_time,
-                                           int time_delta) {
-    MMF_REQUIRE(ms && n >= 1 && n <= kMaxPassBatch, "models_combined_predict_batched: bad argument");
-    MMF_HIP_TRY(hipSetDevice(ms[0]->ctx->device));
-    PassBatch<splat_item> b_splat;
-    PassBatch<splat_resolve_item> b_res;
-    unsigned g_splat = 0, g_res = 0;
-    for (int k = 0; k < n; ++k) {
-        mmf_model* m = ms[k];
-        MMF_REQUIRE(m && m->rider.st == nullptr && !m->t_inv_dev && !m->abort_dev, "models_combined_predict_batched: a model with a device-side pose");
-        ++m->tex_gen;
-        ++m->thumb_gen;
-        m->spl_nz_known = false;
-        SplatArgs a;
-        inverse4f_host(m->pose, a.t_inv.m);
-        a.t_inv_dev = nullptr, a.abort_dev = nullptr;
-        a.c = make_cam(m, false);
-        a.cols = m->width, a.rows = m->height;
-        a.maxDepth = depth_cutoff;
-        a.confThreshold = m->conf_threshold;
-        a.time = time, a.maxTime = max_time, a.timeDelta = time_delta;
-        a.early_z = 0;
-        a.rays = m->rays;
-        const unsigned launch_count = m->count_pending ? m->count_bound : m->count;
-        const size_t npix_s = (size_t)m->width * m->height;
-        splat_item& sp = b_splat.m[k];
-        sp.s = m->set[m->cur], sp.count = (int)launch_count, sp.a_in = a, sp.keys = m->keys, sp.count_dev = m->count_pending ? m->totals : nullptr;
-        sp.grid = launch_count ? splat_grid(launch_count, (size_t)launch_count >= npix_s / 2).x : 0u;
-        splat_resolve_item& sr = b_res.m[k];
-        sr.s = m->set[m->cur], sr.a_in = a, sr.keys = m->keys, sr.image = m->image, sr.vertexConf = m->vertexConf, sr.normalRadius = m->normalRadius,
-        sr.time_out = m->time_tex, sr.thumb = model_thumb_counts(m), sr.gen = (int)(m->thumb_gen & 1);
-        sr.grid = splat_tile_grid(m->width, m->height);
-        g_splat = std::max(g_splat, sp.grid), g_res = std::max(g_res, sr.grid);
-    }
-    if (g_splat) hipLaunchKernelGGL(splat_batched_kernel, dim3(g_splat, n), dim3(256), 0, st, b_splat);
-    hipLaunchKernelGGL(splat_resolve_batched_kernel, dim3(g_res, n), dim3(256), 0, st, b_res);
-    MMF_HIP_TRY(hipGetLastError());
-    return MMF_OK;
-}
 // ---- the same passes RESTRICTED to where the models are (pass_rect.hpp): nine launches for all of them ----
 // mask_boxes: the id image's boxes of this frame (mask_boxes_kernel, generation mask_gen), device
 static int models_fuse_clean_rect(mmf_model* const* ms, int n, hipStream_t st, int time, int time_delta, float depth_cutoff,
@@ -3232,7 +3100,7 @@ static int models_combined_predict_rect(mmf_model* const* ms, int n, hipStream_t
     MMF_HIP_TRY(hipGetLastError());
     return MMF_OK;
 }
-// can a model's combinedPredict go into a batch (models_combined_predict_batched)?  Not a deep store (its rasterising pass is
+// can a model's combinedPredict go into a batch (models_combined_predict_rect)?  Not a deep store (its rasterising pass is
 // another kernel), not one with pending device-side inputs
 static bool model_predict_batchable(const mmf_model* m) {
     const unsigned launch_count = m->count_pending ? m->count_bound : m->count;

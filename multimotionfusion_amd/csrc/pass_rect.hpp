@@ -22,6 +22,15 @@ namespace mmf {
 
 constexpr int kRectGroups = 128;   // workgroups per model of a rect launch (an object's box of 200 x 200: one or two strides each)
 
+// One launch per pass for up to kMaxPassBatch object models (~9 short launches per model and frame otherwise: with seven
+// object models the calling thread's launch rate set the pace).  A *_batched_kernel runs a pass's *_kernel_body
+// (surfel_kernels.hpp) on item blockIdx.y's arguments.
+constexpr int kMaxPassBatch = 7;
+template <typename Item>
+struct PassBatch {
+    Item m[kMaxPassBatch];
+};
+
 // ---- the id image's boxes: one launch per frame for all ids (the segmentation's result is an input of processFrame) ----
 // boxes[id][4] (id 0, the background, is not noted).  64 x 16 pixel tiles; per tile the ids present are few.
 __global__ __launch_bounds__(256) void mask_boxes_kernel(const uint8_t* __restrict__ mask, int cols, int rows, unsigned long long* __restrict__ boxes,

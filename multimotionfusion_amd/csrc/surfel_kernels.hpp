@@ -1664,159 +1664,4 @@ __global__ void aos_to_soa_kernel(const float4* __restrict__ aos, int count, Sur
     s.nrm[k] = aos[3 * k + 2];
 }
 
-
-// ---- the passes of SEVERAL models in one launch each (gridDim.y = model) ----------------------------------------------------
-// An object model's store is a few thousand surfels: its projection / fuse / clean / predict passes (MultiMotionFusion.cpp:791-816,
-// 863-875 loop over the models) are ~9 short launches per model and frame, and with seven object models on a GPU the calling
-// thread's launch rate, not the GPU, set the pace of that part of the frame.  Every pass exists as *_kernel_body(arguments,
-// block, blocks); the *_batched_kernel of a pass runs the bodies of up to kMaxPassBatch models, each on its own arguments and
-// its own number of workgroups (the surplus workgroups of a smaller model leave at once).  Same bodies, same bits.
-constexpr int kMaxPassBatch = 7;
-template <typename Item>
-struct PassBatch {
-    Item m[kMaxPassBatch];
-};
-
-struct index_map_item {
-    SurfelSoA s;
-    int count;
-    IndexArgs a_in;
-    unsigned long long* keys;
-    FrameRider rider;
-    unsigned grid;  // workgroups of this model
-};
-__global__ __launch_bounds__(256) void index_map_batched_kernel(PassBatch<index_map_item> b) {
-    const index_map_item& p = b.m[blockIdx.y];
-    if (blockIdx.x >= p.grid) return;
-    index_map_kernel_body(p.s, p.count, p.a_in, p.keys, p.rider, blockIdx.x, p.grid);
-}
-
-struct index_resolve_item {
-    SurfelSoA s;
-    IndexArgs a_in;
-    unsigned long long* keys;
-    unsigned* index;
-    float4* vertConf;
-    float4* colorTime;
-    float4* normRad;
-    FrameRider rider;
-    unsigned grid;  // workgroups of this model
-};
-__global__ __launch_bounds__(256) void index_resolve_batched_kernel(PassBatch<index_resolve_item> b) {
-    const index_resolve_item& p = b.m[blockIdx.y];
-    if (blockIdx.x >= p.grid) return;
-    index_resolve_kernel_body(p.s, p.a_in, p.keys, p.index, p.vertConf, p.colorTime, p.normRad, p.rider, blockIdx.x, p.grid);
-}
-
-struct fuse_data_item {
-    const uint8_t* rgb;
-    const float* depth_raw;
-    const float* depth_fil;
-    const uint8_t* mask;
-    const unsigned* index;
-    const float4* vertConf;
-    const float4* normRad;
-    FuseArgs a_in;
-    SurfelSoA meas;
-    unsigned* new_flags;
-    unsigned* winner;
-    unsigned grid;  // workgroups of this model
-};
-__global__ __launch_bounds__(256) void fuse_data_batched_kernel(PassBatch<fuse_data_item> b) {
-    const fuse_data_item& p = b.m[blockIdx.y];
-    if (blockIdx.x >= p.grid) return;
-    fuse_data_kernel_body(p.rgb, p.depth_raw, p.depth_fil, p.mask, p.index, p.vertConf, p.normRad, p.a_in, p.meas, p.new_flags, p.winner, blockIdx.x, p.grid);
-}
-
-struct fuse_update_index_item {
-    SurfelSoA s;
-    int count;
-    SurfelSoA meas;
-    int time;
-    unsigned* winner;
-    IndexArgs a_in;
-    unsigned long long* keys;
-    unsigned grid;  // workgroups of this model
-};
-__global__ __launch_bounds__(256) void fuse_update_index_batched_kernel(PassBatch<fuse_update_index_item> b) {
-    const fuse_update_index_item& p = b.m[blockIdx.y];
-    if (blockIdx.x >= p.grid) return;
-    fuse_update_index_kernel_body(p.s, p.count, p.meas, p.time, p.winner, p.a_in, p.keys, blockIdx.x, p.grid);
-}
-
-struct clean_flag_item {
-    SurfelSoA s;
-    SurfelSoA meas;
-    const unsigned* new_flags;
-    CleanArgs a_in;
-    const unsigned* index;
-    const float4* vertConf;
-    const float4* colorTime;
-    const float* depth_in;
-    const uint8_t* mask;
-    unsigned* keep;
-    float2* conf_time;
-    unsigned* block_sums;
-    unsigned grid;  // workgroups of this model
-};
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MMF_CLEAN_WAVES))) void clean_flag_batched_kernel(PassBatch<clean_flag_item> b) {
-    const clean_flag_item& p = b.m[blockIdx.y];
-    if (blockIdx.x >= p.grid) return;
-    clean_flag_kernel_body(p.s, p.meas, p.new_flags, p.a_in, p.index, p.vertConf, p.colorTime, p.depth_in, p.mask, p.keep, p.conf_time, p.block_sums, blockIdx.x, p.grid);
-}
-
-struct clean_scatter_item {
-    SurfelSoA s;
-    SurfelSoA meas;
-    int count;
-    int npix;
-    const unsigned* keep;
-    const unsigned* block_sums;
-    const float2* conf_time;
-    SurfelSoA dst;
-    int capacity;
-    unsigned* total_out;
-    unsigned* total_host;
-    unsigned seq;
-    const int* abort_dev;
-    unsigned grid;  // workgroups of this model
-};
-__global__ __launch_bounds__(256) void clean_scatter_batched_kernel(PassBatch<clean_scatter_item> b) {
-    const clean_scatter_item& p = b.m[blockIdx.y];
-    if (blockIdx.x >= p.grid) return;
-    clean_scatter_kernel_body(p.s, p.meas, p.count, p.npix, p.keep, p.block_sums, p.conf_time, p.dst, p.capacity, p.total_out, p.total_host, p.seq, p.abort_dev, blockIdx.x, p.grid);
-}
-
-struct splat_item {
-    SurfelSoA s;
-    int count;
-    SplatArgs a_in;
-    unsigned long long* keys;
-    const unsigned* count_dev;
-    unsigned grid;  // workgroups of this model
-};
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void splat_batched_kernel(PassBatch<splat_item> b) {
-    const splat_item& p = b.m[blockIdx.y];
-    if (blockIdx.x >= p.grid) return;
-    splat_kernel_body<false>(p.s, p.count, p.a_in, p.keys, p.count_dev, blockIdx.x, p.grid);
-}
-
-struct splat_resolve_item {
-    SurfelSoA s;
-    SplatArgs a_in;
-    unsigned long long* keys;
-    uchar4* image;
-    float4* vertexConf;
-    float4* normalRadius;
-    unsigned short* time_out;
-    unsigned* thumb;
-    int gen;
-    unsigned grid;  // workgroups of this model
-};
-__global__ __launch_bounds__(256) void splat_resolve_batched_kernel(PassBatch<splat_resolve_item> b) {
-    const splat_resolve_item& p = b.m[blockIdx.y];
-    if (blockIdx.x >= p.grid) return;
-    splat_resolve_kernel_body(p.s, p.a_in, p.keys, p.image, p.vertexConf, p.normalRadius, p.time_out, p.thumb, p.gen, blockIdx.x, p.grid);
-}
-
 }  // namespace mmf

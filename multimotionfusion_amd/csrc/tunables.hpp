@@ -34,9 +34,9 @@ struct Tunables {
     // ---- surfel passes ----
     int track_cull = 1;       // MMF_TRACK_CULL=0: object models are tracked like the camera model (whole image, full grids)
     int spec_prep_all = 2;    // MMF_SPEC_PREP_ALL=<n>: from n models per GPU on the next frame's model-side preparation of all models is enqueued at the end of the frame (0: never)
-    int pass_batch = -1;      // MMF_PASS_BATCH=0|1|2: the object models' projection / fuse / clean / predict passes model by model on the models' own
-                              // streams / as one launch per pass covering the whole frame / as one launch per pass restricted to where the models
-                              // are (pass_rect.hpp).  All bit-identical.  -1 (default): 2 from four object models on a GPU, else 0 -- the restricted
+    int pass_batch = -1;      // MMF_PASS_BATCH=0|2: the object models' projection / fuse / clean / predict passes model by model on the models' own
+                              // streams / as one launch per pass restricted to where the models are (pass_rect.hpp).  Bit-identical.  -1 (the
+                              // default, also for any other value): 2 from four object models on a GPU, else 0 -- the restricted
                               // launches do 9 % less GPU work with a fifth of the launches, which pays once the calling thread's ~11 launches per
                               // model are what the GPU waits for (LABNOTES r5)
     bool xcd_blocks = true;   // MMF_XCD=0: the blocks of a surfel pass are dealt to the XCDs round-robin, as the workgroups are (else: a contiguous eighth per XCD)
@@ -78,6 +78,7 @@ inline const Tunables& tunables() {
         v.track_cull = (int)num("MMF_TRACK_CULL", 1);
         v.spec_prep_all = (int)num("MMF_SPEC_PREP_ALL", 2);
         v.pass_batch = (int)num("MMF_PASS_BATCH", -1);
+        if (v.pass_batch != 0 && v.pass_batch != 2) v.pass_batch = -1;
         v.xcd_blocks = flag("MMF_XCD", true);
         v.splat_wgs = (int)num("MMF_SPLAT_WGS", 0);
         if (std::getenv("MMF_SPLAT_BOUND")) v.splat_bound = num("MMF_SPLAT_BOUND", 0) ? 1 : 0;

@@ -117,3 +117,18 @@ def test_compute_fusion_weight_matches_the_oracle_bit_for_bit():
         assert out[0].view(np.uint32) == ref.view(np.uint32), (k, out[0], ref)
         seen.add(float(out[0] / mult))
     assert min(seen) == 0.5 and max(seen) == 1.0 and len(seen) > 20  # both clamps and the range between were hit
+
+
+def test_pass_batch_hook_refuses_modes_it_does_not_have():
+    """mmf_debug_set_pass_batch knows -1 (the default), 0 (model by model) and 2 (restricted launches); any other mode is
+    MMF_ERR_INVALID (no mode falls through to another without a word).  The hook touches no device."""
+    from multimotionfusion_amd import _capi
+    lib = _capi.load()
+    try:
+        for mode in (1, 3, -2):
+            assert lib.mmf_debug_set_pass_batch(mode) == -1, mode
+            assert b"mmf_debug_set_pass_batch" in lib.mmf_last_error()
+        for mode in (0, 2, -1):
+            assert lib.mmf_debug_set_pass_batch(mode) == 0, mode
+    finally:
+        lib.mmf_debug_set_pass_batch(-1)

@@ -453,9 +453,9 @@ def test_batched_passes_equal_passes_model_by_model(gpu_ctx, n_obj):
     """The object models' projection / fuse / clean / predict passes go out as ONE launch per pass for all of them (gridDim.y =
     model) instead of ~9 launches per model on the model's own stream (MultiMotionFusion.cpp:791-816, 863-875 loop over the
     models) -- restricted to where each model is (csrc/pass_rect.hpp: the boxes of its key-image writes, of its non-zero
-    images and of its id in the id image) or covering the whole frame (csrc/surfel_kernels.hpp, *_batched_kernel).  Same
-    per-texel code on the same data: every model's surfels (values AND order), poses, prediction images -- all of the
-    image, also where the restricted passes never go -- and error images must agree bit for bit."""
+    images and of its id in the id image).  Same per-texel code on the same data: every model's surfels (values AND order),
+    poses, prediction images -- all of the image, also where the restricted passes never go -- and error images must agree bit
+    for bit."""
     from multimotionfusion_amd.fusion import MultiMotionFusion
     lib = gpu_ctx.lib
     w, h, n_frames = 320, 240, n_obj + 4
@@ -487,17 +487,10 @@ def test_batched_passes_equal_passes_model_by_model(gpu_ctx, n_obj):
             lib.mmf_debug_set_pass_batch(-1)
         return out, maps, tex, err
 
-    # restricted to where the models are (csrc/pass_rect.hpp) against model by model ... and the batched launches that cover the
-    # whole frame.  Six objects: the DEFAULT (-1: model by model up to three object models on a GPU, restricted launches from the
-    # fourth on -- the mode changes in the middle of the sequence, when the fourth object is spawned) against model by model
+    # restricted to where the models are (csrc/pass_rect.hpp) against model by model.  Six objects: the DEFAULT (-1: model by
+    # model up to three object models on a GPU, restricted launches from the fourth on -- the mode changes in the middle of the
+    # sequence, when the fourth object is spawned) against model by model
     a, b = run(2 if n_obj == 4 else -1), run(0)
-    c = run(1) if n_obj == 4 else a
-    for x, y in ((a, c),):
-        for i in range(n_frames):
-            for pa, pb in zip(x[0][i], y[0][i]):
-                assert np.array_equal(pa, pb), i
-        for ma, mb in zip(x[1], y[1]):
-            assert ma.shape == mb.shape and np.array_equal(ma.view(np.uint32), mb.view(np.uint32))
     assert len(a[1]) == n_obj + 1 and all(m.shape[0] > 100 for m in a[1])
     for i in range(n_frames):
         for k, (pa, pb) in enumerate(zip(a[0][i], b[0][i])):
@@ -568,7 +561,8 @@ def test_batched_passes_with_models_left_out_of_the_predict_batch(gpu_ctx, left_
     batch -- every model under mmf_debug_set_splat_bound(1), or one whose store is deep (model_predict_batchable) -- is
     predicted on its own stream, and must not start before the batch has written its map (csrc/fusion_orchestrator.hpp: the
     object lanes wait on the batch).  Every model's poses, maps and predicted images, every frame, must be those of the passes
-    model by model (pass_batch 0), bit for bit.  A race need not show on every run: this test keeps it from coming back."""
+    model by model (pass_batch 0), bit for bit, under the restricted launches (pass_batch 2).  A race need not show on every
+    run: this test keeps it from coming back."""
     from multimotionfusion_amd.fusion import MultiMotionFusion
     lib = gpu_ctx.lib
     w, h, n_obj = 320, 240, 4
@@ -613,7 +607,7 @@ def test_batched_passes_with_models_left_out_of_the_predict_batch(gpu_ctx, left_
 
     ref = run(0)
     assert len(ref[-1][0]) == n_obj + 1 and all(m.shape[0] > 100 for m in ref[-1][1])
-    for batch in (1, 2):
+    for batch in (2,):
         got = run(batch)
         for i in range(n_frames):
             (pa, ma, ta), (pb, mb, tb) = ref[i], got[i]
