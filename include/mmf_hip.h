@@ -301,10 +301,10 @@ int mmf_model_id(mmf_model *m);
  * .cpp:207-854, 863-875): the global (camera) model plus the object models of the `models` list, each
  * with its own RGBDOdometry, tracked / predicted / fused / cleaned per frame.  With
  * enable_multiple_models == 0 this is the static-scene configuration (all-zero mask, :268-275).
- * The segmentation proper (gSLICr + dense CRF, or the ground-truth id image of
- * Segmentation.cpp:89-150), relocalisation and loop closure stay in the reference's front-end: the
- * segmentation RESULT is handed in per frame (mmf_segmentation) or pulled through a callback at the point
- * where the reference calls performSegmentation (:412).
+ * The segmentation RESULT is handed in per frame (mmf_segmentation: gSLICr + dense CRF of the reference's
+ * front-end, or the ground-truth id image of Segmentation.cpp:89-150), pulled through a callback at the point
+ * where the reference calls performSegmentation (:412), or computed by the built-in dense CRF
+ * (mmf_fusion_set_crf_segmentation, below).  Relocalisation and loop closure stay in the reference's front-end.
  * Every model runs on its own stream ("lane"); every public call returns with the fusion's own
  * stream (the context's) ordered after all lanes.
  * ------------------------------------------------------------------------------------- */
@@ -642,6 +642,71 @@ int mmf_slic_downsample_rgb(mmf_ctx *ctx, const int *labels, int width, int heig
 /* out[i] = map[labels[i]] */
 int mmf_slic_upsample_u8(mmf_ctx *ctx, const int *labels, int width, int height, const uint8_t *map, int nspix,
                          uint8_t *out);
+
+/* ---- dense-CRF motion segmentation (Core/Segmentation/Segmentation.cpp:159-740, performSegmentationCRF) ----------
+ * The segmentation that spawns object models, on the device (csrc/crf_kernels.hpp): super-pixel
+ * means of the raw depth and of every model's ICP-error image and splat confidence, unaries from the ICP error, a
+ * fully connected CRF (two Potts kernels, symmetric normalisation) by mean field, then the reference's post-processing
+ * (largest connected component per label, size and border rules, depth statistics).  The Gaussian sums are EXACT
+ * (densecrf's permutohedral lattice approximates them: DESIGN.md B1).  Labels are gSLICr-like super-pixel indices
+ * (int32 [height][width], values in [0, n)); without them the regular grid min(y/S, H/S-1) * (W/S) + min(x/S, W/S-1)
+ * is used (B3).  When the depth range of the frame is not a finite positive number every cell is background and no
+ * new label is proposed (range_invalid, B4).
+ *   mmf_crf_default_config   the GUI's settings (GUI/Tools/GUI.h:211-226 pushed by MainController.cpp:658-670); the
+ *                        header defaults of Segmentation.h:140-159 are replaced by these before any segmentation runs.
+ *                        Needs no device.
+ *   mmf_crf_segment          stand-alone, synchronous: low_maps = DEVICE [n_models][2][n] {icp, conf} per super-pixel
+ *                        as mmf_shard_gather_maps writes them (model list order); rgb / depth = DEVICE full-resolution
+ *                        frame (u8 x 3, float32 metres); ids = HOST model ids in list order (< 255), next_id = the new
+ *                        label's id, allow_new = spawnOffset >= modelSpawnOffset.  Writes the DEVICE mask_out
+ *                        (width*height u8, fullSegmentation: model id or 255 per pixel), the HOST models_out (capacity
+ *                        n_models + 1: the existing models, then the new label's entry when it survived), *n_models_out
+ *                        and *has_new_label.  At most 32 labels and 16384 super-pixels.
+ *   mmf_crf_last             what the last segmentation on this context computed (for tests and GUIs): the info
+ *                        below, the model data, and optionally (DEVICE pointers, NULL to skip) the unaries [L][n], the
+ *                        final marginals Q [L][n], the raw argmax map and the filtered map [n] (model ids, 255 =
+ *                        removed).  Synchronous. */
+typedef struct {
+    float sigma_rgb, sigma_depth, sigma_pos;   /* pairwise standard deviations: 10, 0.9, 1.8 */
+    float weight_appearance, weight_smoothness; /* 7, 2 */
+    float threshold_new;       /* unaryThresholdNew: 5.5 */
+    float unary_weight_error;  /* 75 */
+    float unary_k_error;       /* 0.0375 */
+    int iterations;            /* mean-field iterations: 10 */
+    float min_rel_size_new, max_rel_size_new; /* 0.005, 0.4 of the super-pixels */
+    int spixel_size;           /* SegmentationConfiguration::sp_size: 16, in (10, 256) */
+    int model_spawn_offset;    /* fusion only: frames between spawns (22) */
+    int inhibit_new;           /* fusion only: setSetInhibit (hasNewLabel forced to 0) */
+} mmf_crf_config;
+
+typedef struct {
+    int n_cells, cells_x, cells_y; /* n = (W/S) (H/S) */
+    int n_labels;       /* L = models + allow_new */
+    int n_models;       /* entries of the model data */
+    int allow_new, has_new_label, range_invalid, n_components;
+    float range;        /* depth range of the super-pixel depth */
+} mmf_crf_info;
+
+int mmf_crf_default_config(mmf_crf_config *cfg);
+int mmf_crf_segment(mmf_ctx *ctx, const mmf_crf_config *cfg, const int *labels, int width, int height, const uint8_t *rgb,
+                    const float *depth, const float *low_maps, const unsigned *ids, int n_models, unsigned next_id,
+                    int allow_new, uint8_t *mask_out, mmf_segmentation_model *models_out, int *n_models_out,
+                    int *has_new_label);
+int mmf_crf_last(mmf_ctx *ctx, mmf_crf_info *info, mmf_segmentation_model *models, int capacity, float *unaries,
+                 float *q, uint8_t *raw_map, uint8_t *map);
+
+/* The built-in segmentation (mmf_crf_segment) for enable_multiple_models, where the reference calls performSegmentation
+ * (:412): precedence mmf_frame::segmentation, then the callback, then this; cfg == NULL switches it off (default).
+ * It reads every model's ICP-error image (error_recording) and the splat of the previous frame, runs on the fusion's
+ * stream behind every model's tracking, and needs world == 1 (MMF_ERR_STATE otherwise; sharded front ends call
+ * mmf_crf_segment in their callback).  spawnOffset (:148, :410, :484) counts the multi-model tracked frames up to
+ * cfg->model_spawn_offset and restarts at every spawn; a new label is proposed only once it has reached it.
+ * mmf_fusion_set_superpixels: DEVICE int32 label image (width x height) for the NEXT frame only (copied); NULL: grid.
+ * mmf_fusion_last_segmentation: mmf_crf_last of the fusion's context. */
+int mmf_fusion_set_crf_segmentation(mmf_fusion *f, const mmf_crf_config *cfg);
+int mmf_fusion_set_superpixels(mmf_fusion *f, const int *labels);
+int mmf_fusion_last_segmentation(mmf_fusion *f, mmf_crf_info *info, mmf_segmentation_model *models, int capacity,
+                                 float *unaries, float *q, uint8_t *raw_map, uint8_t *map);
 
 /* ---- keypoint-based pose initialisation: RigidRANSAC (Core/Utils/RigidRANSAC.h:6-32, .cpp:73-180) ----
  * Host code, like the reference's (a few dozen keypoint tracks): p0, p1 are HOST arrays of n 3-D points

@@ -68,6 +68,20 @@ class mmf_frame(C.Structure):
                 ("segmentation", C.POINTER(mmf_segmentation)), ("next_rgb", C.c_void_p), ("next_depth", C.c_void_p)]
 
 
+class mmf_crf_config(C.Structure):
+    _fields_ = [("sigma_rgb", C.c_float), ("sigma_depth", C.c_float), ("sigma_pos", C.c_float),
+                ("weight_appearance", C.c_float), ("weight_smoothness", C.c_float), ("threshold_new", C.c_float),
+                ("unary_weight_error", C.c_float), ("unary_k_error", C.c_float), ("iterations", C.c_int),
+                ("min_rel_size_new", C.c_float), ("max_rel_size_new", C.c_float), ("spixel_size", C.c_int),
+                ("model_spawn_offset", C.c_int), ("inhibit_new", C.c_int)]
+
+
+class mmf_crf_info(C.Structure):
+    _fields_ = [("n_cells", C.c_int), ("cells_x", C.c_int), ("cells_y", C.c_int), ("n_labels", C.c_int),
+                ("n_models", C.c_int), ("allow_new", C.c_int), ("has_new_label", C.c_int), ("range_invalid", C.c_int),
+                ("n_components", C.c_int), ("range", C.c_float)]
+
+
 SEGMENTATION_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(mmf_frame), C.POINTER(mmf_segmentation))
 
 
@@ -188,6 +202,13 @@ SIGNATURES = {
     "mmf_fusion_set_enable_multiple_models": (_i, [_vp, _i]),
     "mmf_fusion_get_config": (_i, [_vp, C.POINTER(mmf_fusion_config)]),
     "mmf_fusion_set_segmentation_callback": (_i, [_vp, _vp, _vp]),
+    "mmf_fusion_set_crf_segmentation": (_i, [_vp, C.POINTER(mmf_crf_config)]),
+    "mmf_fusion_set_superpixels": (_i, [_vp, _vp]),
+    "mmf_fusion_last_segmentation": (_i, [_vp, C.POINTER(mmf_crf_info), C.POINTER(mmf_segmentation_model), _i, _vp, _vp, _vp, _vp]),
+    "mmf_crf_default_config": (_i, [C.POINTER(mmf_crf_config)]),
+    "mmf_crf_segment": (_i, [_vp, C.POINTER(mmf_crf_config), _vp, _i, _i, _vp, _vp, _vp, C.POINTER(C.c_uint), _i, C.c_uint, _i,
+                             _vp, C.POINTER(mmf_segmentation_model), _ip, _ip]),
+    "mmf_crf_last": (_i, [_vp, C.POINTER(mmf_crf_info), C.POINTER(mmf_segmentation_model), _i, _vp, _vp, _vp, _vp]),
     "mmf_fusion_export_poses": (_i, [_vp, C.c_char_p]),
     "mmf_fusion_pose_log": (_i, [_vp, _i, C.POINTER(C.c_longlong), _fp, _i, _ip]),
     "mmf_compute_fusion_weight": (_i, [_fp, _fp, _f, _fp]),

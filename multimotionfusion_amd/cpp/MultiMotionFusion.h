@@ -5,8 +5,9 @@
 // GPUTexture* arguments / getters keep their place in the signatures (GPUTexture.h: a view of a dense device image
 // instead of an OpenGL texture).  Eigen / OpenCV types of the reference become plain arrays: poses are row-major
 // float[16], FrameData carries raw pointers.  What the front-end pushes per GUI tick (GUI/MainController.cpp:641-670)
-// and per frame (:588) compiles against this header; setters of subsystems that stay in the reference (CRF, model
-// spawning policy, redetection) are kept as recorded no-ops so those call sites need no #ifdef.
+// and per frame (:588) compiles against this header; setters of subsystems that stay in the reference (redetection,
+// ferns) are kept as recorded no-ops so those call sites need no #ifdef; the CRF and spawn setters are recorded and
+// forwarded to the built-in dense-CRF segmentation.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -101,7 +102,7 @@ struct OdometryConfig {  // Core/Model/Model.h:45-61
     bool icp_refine = false;
     int segm_lvl = 0;
 };
-struct SegmentationConfiguration {  // Core/Segmentation/Segmentation.h:72-80 (the segmentation itself stays in the reference)
+struct SegmentationConfiguration {  // Core/Segmentation/Segmentation.h:72-80 ("": the built-in dense CRF; "flow_crf": not here)
     std::string mode;
     int sp_size = 16;
 };
@@ -378,6 +379,8 @@ class MultiMotionFusion {
         : width_(width), height_(height) {
         mmf::check(mmf_fusion_create(ctx.get(), width, height, cx, cy, fx, fy, cfg, &f_), "mmf_fusion_create");
         mmf::check(mmf_fusion_get_config(f_, &cfg_), "mmf_fusion_get_config");
+        mmf::check(mmf_crf_default_config(&crf_), "mmf_crf_default_config");
+        pushCrf();
     }
     // The reference's own argument list (Core/MultiMotionFusion.h:54-61, .cpp:21-97): the frame geometry comes from the
     // Resolution / Intrinsics singletons, the device context is the process-wide default one (device 0, like the reference's
@@ -410,6 +413,11 @@ class MultiMotionFusion {
         const Intrinsics& K = Intrinsics::getInstance();
         mmf::check(mmf_fusion_create(defaultContext().get(), width_, height_, K.cx(), K.cy(), K.fx(), K.fy(), &cfg, &f_), "mmf_fusion_create");
         mmf::check(mmf_fusion_get_config(f_, &cfg_), "mmf_fusion_get_config");
+        // the segmentation of a maskless multi-model frame: the built-in dense CRF in the default mode (""); "flow_crf"
+        // (Farneback flow + keypoint tracks) is not part of this path and keeps the error of a missing segmentation
+        mmf::check(mmf_crf_default_config(&crf_), "mmf_crf_default_config");
+        crf_.model_spawn_offset = (int)modelSpawnOffset, crf_.spixel_size = segm_cfg.sp_size;
+        pushCrf();
     }
     static mmf::Context& defaultContext() {
         static mmf::Context ctx(0);
@@ -542,24 +550,25 @@ class MultiMotionFusion {
     void setEnableMultipleModels(bool v) { mmf::check(mmf_fusion_set_enable_multiple_models(f_, v), "setEnableMultipleModels"); }
     void setTick(const int& v) { mmf::check(mmf_fusion_set_tick(f_, v), "setTick"); }
     void scheduleDeactivation(const ModelPointer& m) { mmf::check(mmf_fusion_schedule_deactivation(f_, (int)m->getID()), "scheduleDeactivation"); }
-    // settings of subsystems that stay in the reference's front-end (segmentation / CRF, spawning policy, redetection,
-    // ferns): recorded, not interpreted here
+    // settings of subsystems that stay in the reference's front-end (spawning policy beyond the CRF, redetection, ferns):
+    // recorded, not interpreted here.  The CRF and spawn settings are recorded too and forwarded to the built-in
+    // segmentation (mmf_fusion_set_crf_segmentation).
     void setFernThresh(const float& v) { other_["fernThresh"] = v; }
-    void setModelSpawnOffset(const unsigned& v) { other_["modelSpawnOffset"] = (float)v; }
+    void setModelSpawnOffset(const unsigned& v) { other_["modelSpawnOffset"] = (float)v, crf_.model_spawn_offset = (int)v, pushCrf(); }
     void setModelDeactivateCount(const unsigned& v) { other_["modelDeactivateCount"] = (float)v; }
-    void setCrfPairwiseSigmaRGB(const float& v) { other_["crfPairwiseSigmaRGB"] = v; }
-    void setCrfPairwiseSigmaPosition(const float& v) { other_["crfPairwiseSigmaPosition"] = v; }
-    void setCrfPairwiseSigmaDepth(const float& v) { other_["crfPairwiseSigmaDepth"] = v; }
-    void setCrfPairwiseWeightAppearance(const float& v) { other_["crfPairwiseWeightAppearance"] = v; }
-    void setCrfPairwiseWeightSmoothness(const float& v) { other_["crfPairwiseWeightSmoothness"] = v; }
-    void setCrfThresholdNew(const float& v) { other_["crfThresholdNew"] = v; }
-    void setCrfUnaryWeightError(const float& v) { other_["crfUnaryWeightError"] = v; }
-    void setCrfIteration(const unsigned& v) { other_["crfIteration"] = (float)v; }
-    void setCrfUnaryKError(const float& v) { other_["crfUnaryKError"] = v; }
-    void setNewModelMinRelativeSize(const float& v) { other_["newModelMinRelativeSize"] = v; }
-    void setNewModelMaxRelativeSize(const float& v) { other_["newModelMaxRelativeSize"] = v; }
+    void setCrfPairwiseSigmaRGB(const float& v) { other_["crfPairwiseSigmaRGB"] = v, crf_.sigma_rgb = v, pushCrf(); }
+    void setCrfPairwiseSigmaPosition(const float& v) { other_["crfPairwiseSigmaPosition"] = v, crf_.sigma_pos = v, pushCrf(); }
+    void setCrfPairwiseSigmaDepth(const float& v) { other_["crfPairwiseSigmaDepth"] = v, crf_.sigma_depth = v, pushCrf(); }
+    void setCrfPairwiseWeightAppearance(const float& v) { other_["crfPairwiseWeightAppearance"] = v, crf_.weight_appearance = v, pushCrf(); }
+    void setCrfPairwiseWeightSmoothness(const float& v) { other_["crfPairwiseWeightSmoothness"] = v, crf_.weight_smoothness = v, pushCrf(); }
+    void setCrfThresholdNew(const float& v) { other_["crfThresholdNew"] = v, crf_.threshold_new = v, pushCrf(); }
+    void setCrfUnaryWeightError(const float& v) { other_["crfUnaryWeightError"] = v, crf_.unary_weight_error = v, pushCrf(); }
+    void setCrfIteration(const unsigned& v) { other_["crfIteration"] = (float)v, crf_.iterations = (int)v, pushCrf(); }
+    void setCrfUnaryKError(const float& v) { other_["crfUnaryKError"] = v, crf_.unary_k_error = v, pushCrf(); }
+    void setNewModelMinRelativeSize(const float& v) { other_["newModelMinRelativeSize"] = v, crf_.min_rel_size_new = v, pushCrf(); }
+    void setNewModelMaxRelativeSize(const float& v) { other_["newModelMaxRelativeSize"] = v, crf_.max_rel_size_new = v, pushCrf(); }
     void setEnableRedetection(bool v) { other_["enableRedetection"] = v; }
-    void setSetInhibit(bool v) { other_["inhibitModels"] = v; }
+    void setSetInhibit(bool v) { other_["inhibitModels"] = v, crf_.inhibit_new = v ? 1 : 0, pushCrf(); }
     void setEnableSmartModelDelete(bool v) { other_["enableSmartModelDelete"] = v; }
     const std::map<std::string, float>& frontEndSettings() const { return other_; }
 
@@ -584,6 +593,9 @@ class MultiMotionFusion {
         mmf::check(rc, what);
         return false;
     }
+    void pushCrf() {
+        mmf::check(mmf_fusion_set_crf_segmentation(f_, segm_cfg_.mode.empty() ? &crf_ : nullptr), "mmf_fusion_set_crf_segmentation");
+    }
     const mmf_fusion_config& refresh() {
         mmf::check(mmf_fusion_get_config(f_, &cfg_), "mmf_fusion_get_config");
         return cfg_;
@@ -597,6 +609,7 @@ class MultiMotionFusion {
     ModelList models_;
     std::map<std::string, GPUTexture*> textures_;
     std::map<std::string, float> other_;
+    mmf_crf_config crf_;
     bool lost_ = false;
     FrameData next_;
 };

@@ -2,9 +2,10 @@
 // 863-875) for a list of rigid-body models: the global (camera) model plus the object models the segmentation
 // spawns.  Textually included at the end of mmf_hip.hip (it uses that file's static helpers).
 //
-// What stays with the caller: the segmentation itself (gSLICr + dense CRF, or a ground-truth id image) -- it is
-// handed in per frame (mmf_segmentation) or pulled through a callback at the point where the reference calls
-// performSegmentation (:412); relocalisation, ferns, deformation (closeLoops / reloc off).
+// The segmentation is handed in per frame (mmf_segmentation: the reference's gSLICr + dense CRF, or a ground-truth id
+// image), pulled through a callback at the point where the reference calls performSegmentation (:412), or computed by the
+// built-in dense CRF (crf_kernels.hpp, mmf_fusion_set_crf_segmentation).  What stays with the caller: relocalisation,
+// ferns, deformation (closeLoops / reloc off).
 //
 // MI355X mapping: every model owns a LANE (a child context: its own stream + reduction scratch), so the
 // latency-bound Gauss-Newton chains of different models (19 x two small launches each) overlap on the device;
@@ -78,6 +79,13 @@ struct mmf_fusion {
     const float* frame_depth = nullptr;
     mmf_segmentation_fn seg_fn = nullptr;
     void* seg_user = nullptr;
+    // the built-in segmentation (mmf_fusion_set_crf_segmentation): off unless configured
+    bool crf_on = false;
+    mmf_crf_config crf_cfg;          // (mmf_crf_default_config at creation: model_spawn_offset is read either way)
+    unsigned spawn_offset = 0;       // MultiMotionFusion::spawnOffset (MultiMotionFusion.h:433)
+    int* sp_labels = nullptr;        // mmf_fusion_set_superpixels: the next frame's label image (a copy)
+    bool sp_next = false;
+    std::vector<mmf_segmentation_model> crf_models;
     hipEvent_t ev_frame_ready = nullptr;  // fusion stream: the frame's shared inputs are complete
     // next-frame prefetch (mmf_fusion_prefetch_frame): the filter and the input-side preparation of frame t+1 run
     // on `side` while frame t is fused on the context's stream.  Two filtered-depth buffers: frame t's fuse /
@@ -263,6 +271,7 @@ extern "C" int mmf_fusion_create(mmf_ctx* c, int width, int height, float cx, fl
         f->cfg = *cfg;
     else
         mmf_fusion_default_config(&f->cfg);
+    mmf_crf_default_config(&f->crf_cfg);
     f->width = width, f->height = height;
     f->cx = cx, f->cy = cy, f->fx = fx, f->fy = fy;
     FusionModel* global = nullptr;
@@ -325,6 +334,7 @@ extern "C" void mmf_fusion_destroy(mmf_fusion* f) {
     (void)hipFree(f->filtered[0]);
     (void)hipFree(f->filtered[1]);
     (void)hipFree(f->mask);
+    (void)hipFree(f->sp_labels);
     (void)hipFree(f->mask_boxes);
     (void)hipFree(f->side_partials);
     (void)hipFree(f->side_ticket);
@@ -491,6 +501,31 @@ extern "C" int mmf_fusion_set_segmentation_callback(mmf_fusion* f, mmf_segmentat
     MMF_REQUIRE(f != nullptr, "mmf_fusion_set_segmentation_callback: null fusion object");
     f->seg_fn = fn, f->seg_user = user;
     return MMF_OK;
+}
+extern "C" int mmf_fusion_set_crf_segmentation(mmf_fusion* f, const mmf_crf_config* cfg) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_set_crf_segmentation: null fusion object");
+    if (!cfg) {
+        f->crf_on = false;
+        return MMF_OK;
+    }
+    if (int rc = crf_check_config(cfg, "mmf_fusion_set_crf_segmentation")) return rc;
+    f->crf_cfg = *cfg, f->crf_on = true;
+    return MMF_OK;
+}
+extern "C" int mmf_fusion_set_superpixels(mmf_fusion* f, const int* labels) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_set_superpixels: null fusion object");
+    f->sp_next = false;
+    if (!labels) return MMF_OK;
+    MMF_HIP_TRY(hipSetDevice(f->ctx->device));
+    if (!f->sp_labels) MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&f->sp_labels), (size_t)f->width * f->height * sizeof(int)));
+    MMF_HIP_TRY(hipMemcpyAsync(f->sp_labels, labels, (size_t)f->width * f->height * sizeof(int), hipMemcpyDeviceToDevice, f->ctx->stream));
+    f->sp_next = true;
+    return MMF_OK;
+}
+extern "C" int mmf_fusion_last_segmentation(mmf_fusion* f, mmf_crf_info* info, mmf_segmentation_model* models, int capacity,
+                                            float* unaries, float* q, uint8_t* raw_map, uint8_t* map) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_last_segmentation: null fusion object");
+    return mmf_crf_last(f->ctx, info, models, capacity, unaries, q, raw_map, map);
 }
 // scheduleDeactivation (MultiMotionFusion.cpp: scheduled_model_deactivation, applied at the next frame :279-283)
 extern "C" int mmf_fusion_schedule_deactivation(mmf_fusion* f, int id) {
@@ -1197,6 +1232,56 @@ static int frame_track(mmf_fusion* f, FrameRun& r) {
     return MMF_OK;
 }
 
+// performSegmentationCRF (Segmentation.cpp:159-740) on the fusion's stream, into textures[MASK]: stage 1 from every model's
+// ICP-error image and the confidence of its splat (the previous frame's prediction), then crf_enqueue; one pinned read of
+// the summary.  `out` points at f->mask and f->crf_models.
+static int fusion_crf_segment(mmf_fusion* f, mmf_segmentation* out) {
+    if (f->shard_world != 1)
+        return fail(MMF_ERR_STATE, "mmf_fusion_process_frame: the built-in segmentation needs world == 1 (a sharded front end "
+                                   "calls mmf_crf_segment in its segmentation callback)");
+    mmf_ctx* c = f->ctx;
+    const mmf_crf_config& cfg = f->crf_cfg;
+    const int M = (int)f->models.size(), W = f->width, H = f->height, S = cfg.spixel_size;
+    std::vector<unsigned> ids((size_t)M);
+    for (int i = 0; i < M; ++i) ids[(size_t)i] = (unsigned)f->models[(size_t)i]->model->id;
+    const unsigned next_id = (unsigned)mmf_fusion_next_model_id(f);
+    const int allow_new = f->spawn_offset >= (unsigned)cfg.model_spawn_offset ? 1 : 0;  // (:148)
+    CrfWs* w = nullptr;
+    const int* labels = nullptr;
+    int rc = crf_begin(c, &cfg, f->sp_next ? f->sp_labels : nullptr, W, H, ids.data(), M, next_id, allow_new,
+                       "mmf_fusion_process_frame (segmentation)", &w, &labels);
+    if (rc) return rc;
+    // behind every model's tracking chain: the chains write the ICP-error images on the models' streams
+    for (FusionModel* fm : f->models) {
+        hipStream_t ls = fm->lane->stream;
+        if (ls == c->stream) continue;
+        MMF_HIP_TRY(hipEventRecord(fm->ev_done, ls));
+        MMF_HIP_TRY(hipStreamWaitEvent(c->stream, fm->ev_done, 0));
+    }
+    const int N = (W / S) * (H / S);
+    rc = mmf_slic_downsample(c, labels, W, H, S, f->frame_depth, 1, 0, 1, 0.02f, w->low_depth, nullptr);  // :178
+    for (int i = 0; i < M && rc == MMF_OK; ++i) {  // :218-219
+        FusionModel* fm = f->models[(size_t)i];
+        if (!fm->icp_error) return fail(MMF_ERR_STATE, "mmf_fusion_process_frame: the built-in segmentation needs error_recording");
+        rc = mmf_slic_downsample(c, labels, W, H, S, fm->icp_error, 1, 0, 0, 0.f, w->maps + (size_t)i * 2 * N, nullptr);
+        if (rc == MMF_OK)
+            rc = mmf_slic_downsample(c, labels, W, H, S, reinterpret_cast<const float*>(fm->model->vertexConf), 4, 3, 0, 0.f,
+                                     w->maps + ((size_t)i * 2 + 1) * N, nullptr);
+    }
+    if (rc) return rc;
+    rc = crf_enqueue(c, w, &cfg, labels, W, H, f->frame_rgb, w->maps, ids.data(), M, next_id, allow_new, f->mask);
+    if (rc) return rc;
+    MMF_HIP_TRY(hipStreamSynchronize(c->stream));
+    const mmf::CrfSummary& s = *w->sum_host;
+    f->crf_models.assign(s.models, s.models + s.n_models_out);
+    std::memset(out, 0, sizeof(*out));
+    out->mask = f->mask;
+    out->has_new_label = s.has_new_label && !cfg.inhibit_new;  // inhibitModels (:413-415): the mask and the entry stay
+    out->n_models = s.n_models_out;
+    out->model_data = f->crf_models.data();
+    return MMF_OK;
+}
+
 // :407-622: the segmentation's mask, a new model's first surfels, models that leave the list, confidence thresholds
 static int frame_segment(mmf_fusion* f, const FrameRun& r) {
     const mmf_frame* fr = r.fr;
@@ -1204,15 +1289,21 @@ static int frame_segment(mmf_fusion* f, const FrameRun& r) {
     mmf_ctx* c = f->ctx;
     mmf_segmentation seg_cb;
     const mmf_segmentation* seg = fr->segmentation;
+    if (f->spawn_offset < (unsigned)f->crf_cfg.model_spawn_offset) f->spawn_offset++;  // (:410)
     if (!seg && f->seg_fn) {  // performSegmentation(frame) (:412)
         std::memset(&seg_cb, 0, sizeof(seg_cb));
         if (f->seg_fn(f->seg_user, f, fr, &seg_cb)) return fail(MMF_ERR_STATE, "mmf_fusion_process_frame: the segmentation callback failed");
         seg = &seg_cb;
+    } else if (!seg && f->crf_on) {
+        int rc = fusion_crf_segment(f, &seg_cb);
+        if (rc) return rc;
+        seg = &seg_cb;
     }
     MMF_REQUIRE(seg && seg->mask, "mmf_fusion_process_frame: enableMultipleModels needs a segmentation "
-                                  "(mmf_frame::segmentation or mmf_fusion_set_segmentation_callback)");
+                                  "(mmf_frame::segmentation, mmf_fusion_set_segmentation_callback or mmf_fusion_set_crf_segmentation)");
     // textures[MASK]->Upload(fullSegmentation) (:416)
-    MMF_HIP_TRY(hipMemcpyAsync(f->mask, seg->mask, (size_t)f->width * f->height, hipMemcpyDeviceToDevice, c->stream));
+    if (seg->mask != f->mask)
+        MMF_HIP_TRY(hipMemcpyAsync(f->mask, seg->mask, (size_t)f->width * f->height, hipMemcpyDeviceToDevice, c->stream));
     f->mask_is_zero = false;
     MMF_HIP_TRY(hipEventRecord(f->ev_frame_ready, c->stream));
     const int n_data = seg->model_data ? seg->n_models : 0;
@@ -1220,6 +1311,7 @@ static int frame_segment(mmf_fusion* f, const FrameRun& r) {
     if (seg->has_new_label) {  // :469-487
         int rc = fusion_spawn(f, &fresh);
         if (rc) return rc;
+        f->spawn_offset = 0;  // (:484)
         if (n_data > 0) fresh->model->max_depth = seg_max_depth(seg->model_data[n_data - 1]);
     }
     // Set max-depth (:585-586)
@@ -1500,6 +1592,7 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
         }
         r.stamp(f, 2);
     }
+    f->sp_next = false;  // (mmf_fusion_set_superpixels: this call's labels only, whichever segmentation ran)
     r.pass_mode = fusion_batch_mode(f);  // (the model list stays as it is from here to the end of the call)
     if (!first) {
         rc = frame_fuse_clean(f, r);

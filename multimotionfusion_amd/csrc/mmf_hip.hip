@@ -95,6 +95,9 @@ extern "C" const char* mmf_last_error(void) { return g_last_error.c_str(); }
 constexpr int kMaxGrid = 2048;
 constexpr int kMaxIcpGrid = 8192;  // the single-pass ICP producer needs one workgroup per BLOCK * PX pixels  // workgroups per reduction launch (grid-stride beyond)
 
+struct CrfWs;
+static void crf_ws_free(CrfWs* w);
+
 struct mmf_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -110,6 +113,7 @@ struct mmf_ctx {
     size_t match_ws_rows = 0;
     void* slic_ws = nullptr;  // super-pixel resampling workspace (boxes, counts, sums), grown on demand
     size_t slic_ws_n = 0;
+    struct CrfWs* crf_ws = nullptr;  // dense-CRF segmentation workspace (crf_kernels.hpp), grown on demand
     char arch[64] = {0};
     int cu_count = 0;  // compute units of the device (the one-launch Gauss-Newton chain needs its grid resident at once)
 };
@@ -184,6 +188,7 @@ extern "C" void mmf_ctx_destroy(mmf_ctx* c) {
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     (void)hipFree(c->match_ws);
     (void)hipFree(c->slic_ws);
+    crf_ws_free(c->crf_ws);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -3428,6 +3433,245 @@ extern "C" int mmf_slic_upsample_u8(mmf_ctx* c, const int* labels, int width, in
     const int npix = width * height;
     hipLaunchKernelGGL(mmf::slic_upsample_u8_kernel, grid1d(npix), dim3(256), 0, c->stream, labels, npix, nspix, map, out);
     MMF_HIP_TRY(hipGetLastError());
+    return MMF_OK;
+}
+
+// ---- dense-CRF motion segmentation (crf_kernels.hpp; Segmentation.cpp:159-740) ---------------------------------------
+#include "crf_kernels.hpp"
+
+struct CrfWs {
+    size_t cells = 0;        // capacity in super-pixels (every per-cell buffer holds kCrfMaxLabels rows where it has labels)
+    size_t partial_n = 0;    // floats of `partial`
+    float *low_depth = nullptr, *maps = nullptr, *U = nullptr, *feat = nullptr, *Q = nullptr, *xs = nullptr, *xa = nullptr;
+    float *Ds = nullptr, *Da = nullptr, *ones = nullptr, *partial = nullptr;
+    int *cstat = nullptr, *cid = nullptr, *flabel = nullptr;
+    uint8_t *raw_map = nullptr, *map = nullptr;
+    mmf::CrfSummary* sum_dev = nullptr;
+    mmf::CrfSummary* sum_host = nullptr;  // pinned
+    int* grid = nullptr;  // B3 labels
+    size_t grid_cap = 0;
+    int grid_w = 0, grid_h = 0, grid_s = 0;
+    bool valid = false;  // a segmentation ran (mmf_crf_last)
+    int cells_x = 0, cells_y = 0;
+};
+
+static void crf_ws_free(CrfWs* w) {
+    if (!w) return;
+    for (void* p : {(void*)w->low_depth, (void*)w->maps, (void*)w->U, (void*)w->feat, (void*)w->Q, (void*)w->xs, (void*)w->xa,
+                    (void*)w->Ds, (void*)w->Da, (void*)w->ones, (void*)w->partial, (void*)w->cstat, (void*)w->cid,
+                    (void*)w->flabel, (void*)w->raw_map, (void*)w->map, (void*)w->sum_dev, (void*)w->grid})
+        (void)hipFree(p);
+    (void)hipHostFree(w->sum_host);
+    delete w;
+}
+
+static int crf_workspace(mmf_ctx* c, size_t n, size_t partial_n, CrfWs** out) {
+    if (!c->crf_ws) {
+        c->crf_ws = new (std::nothrow) CrfWs();
+        MMF_REQUIRE(c->crf_ws != nullptr, "mmf_crf: out of host memory");
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->crf_ws->sum_dev), sizeof(mmf::CrfSummary)));
+        MMF_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->crf_ws->sum_host), sizeof(mmf::CrfSummary), hipHostMallocDefault));
+    }
+    CrfWs* w = c->crf_ws;
+    if (n > w->cells) {
+        MMF_HIP_TRY(hipStreamSynchronize(c->stream));
+        for (void** p : {(void**)&w->low_depth, (void**)&w->maps, (void**)&w->U, (void**)&w->feat, (void**)&w->Q, (void**)&w->xs,
+                         (void**)&w->xa, (void**)&w->Ds, (void**)&w->Da, (void**)&w->ones, (void**)&w->cstat, (void**)&w->cid,
+                         (void**)&w->flabel, (void**)&w->raw_map, (void**)&w->map}) {
+            (void)hipFree(*p);
+            *p = nullptr;
+        }
+        w->cells = 0, w->valid = false;
+        const size_t L = mmf::kCrfMaxLabels;
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->low_depth), n * sizeof(float)));
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->maps), 2 * L * n * sizeof(float)));
+        for (float** p : {&w->U, &w->Q, &w->xs, &w->xa}) MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), L * n * sizeof(float)));
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->feat), 8 * n * sizeof(float)));
+        for (float** p : {&w->Ds, &w->Da, &w->ones}) MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), n * sizeof(float)));
+        MMF_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w->ones), 0x3f800000, n, c->stream));  // 1.0f
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->cstat), 6 * n * sizeof(int)));
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->cid), n * sizeof(int)));
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->flabel), n * sizeof(int)));
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->raw_map), n));
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->map), n));
+        w->cells = n;
+    }
+    if (partial_n > w->partial_n) {
+        MMF_HIP_TRY(hipStreamSynchronize(c->stream));
+        (void)hipFree(w->partial);
+        w->partial = nullptr, w->partial_n = 0;
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->partial), partial_n * sizeof(float)));
+        w->partial_n = partial_n;
+    }
+    *out = w;
+    return MMF_OK;
+}
+
+extern "C" int mmf_crf_default_config(mmf_crf_config* cfg) {
+    MMF_REQUIRE(cfg != nullptr, "mmf_crf_default_config: null argument");
+    // GUI/Tools/GUI.h:211-226, pushed by GUI/MainController.cpp:658-670 before any segmentation runs
+    // (the Segmentation.h:140-159 member defaults 1/30, 1/0.4, 1/8, 40, 40, 5, 0.01, 40, 10, 0.07 / 0.4 never reach a frame)
+    cfg->sigma_rgb = 10.f, cfg->sigma_depth = 0.9f, cfg->sigma_pos = 1.8f;
+    cfg->weight_appearance = 7.f, cfg->weight_smoothness = 2.f;
+    cfg->threshold_new = 5.5f, cfg->unary_weight_error = 75.f, cfg->unary_k_error = 0.0375f;
+    cfg->iterations = 10;
+    cfg->min_rel_size_new = 0.005f, cfg->max_rel_size_new = 0.4f;
+    cfg->spixel_size = 16;  // SegmentationConfiguration::sp_size (Segmentation.h:79)
+    cfg->model_spawn_offset = 22;
+    cfg->inhibit_new = 0;
+    return MMF_OK;
+}
+
+static int crf_check_config(const mmf_crf_config* cfg, const char* who) {
+    MMF_REQUIRE(cfg != nullptr, std::string(who) + ": null configuration");
+    if (!(cfg->sigma_rgb > 0.f && cfg->sigma_depth > 0.f && cfg->sigma_pos > 0.f) || cfg->iterations < 0 ||
+        cfg->model_spawn_offset < 0 || !(cfg->spixel_size > 10 && cfg->spixel_size < 256))
+        return fail(MMF_ERR_INVALID, std::string(who) + ": bad CRF configuration (sigmas > 0, iterations >= 0, spixel_size in (10, 256))");
+    return MMF_OK;
+}
+
+// stages 2-14 on the context's stream, from the stage-1 maps in w->low_depth and `maps`; the summary is copied to pinned
+// memory behind them (the caller synchronises)
+static int crf_enqueue(mmf_ctx* c, CrfWs* w, const mmf_crf_config* cfg, const int* labels, int W, int H, const uint8_t* rgb,
+                       const float* maps, const unsigned* ids, int M, unsigned next_id, int allow_new, uint8_t* mask_out) {
+    using namespace mmf;
+    const int S = cfg->spixel_size, spx = W / S, spy = H / S, N = spx * spy, L = M + (allow_new ? 1 : 0);
+    hipStream_t st = c->stream;
+    CrfParams p;
+    p.scale_rgb = 1.0f / cfg->sigma_rgb, p.scale_depth = 1.0f / cfg->sigma_depth, p.scale_pos = 1.0f / cfg->sigma_pos;
+    p.w_app = cfg->weight_appearance, p.w_smooth = cfg->weight_smoothness;
+    p.thr_new = cfg->threshold_new, p.w_err = cfg->unary_weight_error, p.k_err = cfg->unary_k_error;
+    p.min_rel = cfg->min_rel_size_new, p.max_rel = cfg->max_rel_size_new;
+    hipLaunchKernelGGL(crf_prep_kernel, dim3(1), dim3(1024), 0, st, w->low_depth, maps, rgb, N, spx, M, allow_new, p, w->U, w->feat,
+                       w->sum_dev);
+    const int nsplit = (N + kCrfTJ - 1) / kCrfTJ;
+    const dim3 pgrid((N + kCrfTI - 1) / kCrfTI, nsplit), cgrid((N + 255) / 256);
+    auto pair = [&](int Lp, const float* xs, const float* xa) {
+        if (Lp <= 1) hipLaunchKernelGGL(crf_pair_kernel<1>, pgrid, dim3(256), 0, st, w->feat, N, Lp, xs, xa, w->partial);
+        else if (Lp <= 2) hipLaunchKernelGGL(crf_pair_kernel<2>, pgrid, dim3(256), 0, st, w->feat, N, Lp, xs, xa, w->partial);
+        else if (Lp <= 4) hipLaunchKernelGGL(crf_pair_kernel<4>, pgrid, dim3(256), 0, st, w->feat, N, Lp, xs, xa, w->partial);
+        else if (Lp <= 8) hipLaunchKernelGGL(crf_pair_kernel<8>, pgrid, dim3(256), 0, st, w->feat, N, Lp, xs, xa, w->partial);
+        else if (Lp <= 16) hipLaunchKernelGGL(crf_pair_kernel<16>, pgrid, dim3(256), 0, st, w->feat, N, Lp, xs, xa, w->partial);
+        else hipLaunchKernelGGL(crf_pair_kernel<32>, pgrid, dim3(256), 0, st, w->feat, N, Lp, xs, xa, w->partial);
+    };
+    auto softmax = [&](int mode, const float* part) {
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, cgrid, dim3(256), 0, st, mode, N, L, nsplit, part, (const float*)w->U, p.w_smooth, p.w_app, w->Ds,
+                               w->Da, w->Q, w->xs, w->xa, (const CrfSummary*)w->sum_dev);
+        };
+        if (L <= 2) go(crf_softmax_kernel<2>);
+        else if (L <= 4) go(crf_softmax_kernel<4>);
+        else if (L <= 8) go(crf_softmax_kernel<8>);
+        else if (L <= 16) go(crf_softmax_kernel<16>);
+        else go(crf_softmax_kernel<32>);
+    };
+    const int iters = cfg->iterations;
+    if (iters > 0) pair(1, w->ones, w->ones);
+    softmax(0, iters > 0 ? (const float*)w->partial : nullptr);
+    for (int it = 0; it < iters; ++it) {
+        pair(L, w->xs, w->xa);
+        softmax(1, w->partial);
+    }
+    CrfPostArgs a;
+    a.Q = w->Q, a.low_depth = w->low_depth;
+    a.N = N, a.spx = spx, a.spy = spy, a.W = W, a.H = H, a.S = S, a.L = L, a.M = M, a.allow_new = allow_new ? 1 : 0;
+    a.next_id = next_id;
+    for (int l = 0; l < kCrfMaxLabels; ++l) a.ids[l] = l < M ? ids[l] : (l == M ? next_id : 255u);
+    a.min_rel = p.min_rel, a.max_rel = p.max_rel;
+    a.cstat = w->cstat, a.cid = w->cid, a.flabel = w->flabel, a.raw_map = w->raw_map, a.map = w->map, a.sum = w->sum_dev;
+    const size_t lds = (size_t)N * sizeof(int) + (((size_t)N + 3) & ~(size_t)3);
+    MMF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(crf_post_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(crf_post_kernel, dim3(1), dim3(1024), lds, st, a);
+    hipLaunchKernelGGL(slic_upsample_u8_kernel, grid1d((size_t)W * H), dim3(256), 0, st, labels, W * H, N, (const uint8_t*)w->map, mask_out);
+    MMF_HIP_TRY(hipGetLastError());
+    MMF_HIP_TRY(hipMemcpyAsync(w->sum_host, w->sum_dev, sizeof(CrfSummary), hipMemcpyDeviceToHost, st));
+    w->valid = true, w->cells_x = spx, w->cells_y = spy;
+    return MMF_OK;
+}
+
+// checks shared by the stand-alone call and the fusion; *labels_out = the label image to use (the grid when labels is NULL)
+static int crf_begin(mmf_ctx* c, const mmf_crf_config* cfg, const int* labels, int W, int H, const unsigned* ids, int M,
+                     unsigned next_id, int allow_new, const char* who, CrfWs** ws, const int** labels_out) {
+    if (int rc = crf_check_config(cfg, who)) return rc;
+    const int S = cfg->spixel_size;
+    MMF_REQUIRE(W > 0 && H > 0 && W / S >= 1 && H / S >= 1, std::string(who) + ": the image is smaller than one super-pixel");
+    const int N = (W / S) * (H / S), L = M + (allow_new ? 1 : 0);
+    MMF_REQUIRE(M >= 1 && L <= mmf::kCrfMaxLabels, std::string(who) + ": 1 to 32 labels (models + the new one)");
+    MMF_REQUIRE(N <= mmf::kCrfMaxCells, std::string(who) + ": at most 16384 super-pixels");
+    for (int i = 0; i < M; ++i) {
+        MMF_REQUIRE(ids[i] < 255u, std::string(who) + ": model ids must be below 255");
+        for (int j = 0; j < i; ++j) MMF_REQUIRE(ids[i] != ids[j], std::string(who) + ": duplicate model id");
+        MMF_REQUIRE(!allow_new || ids[i] != next_id, std::string(who) + ": the new label's id is a model's");
+    }
+    MMF_REQUIRE(!allow_new || next_id < 255u, std::string(who) + ": the new label's id must be below 255");
+    const size_t nsplit = (size_t)(N + mmf::kCrfTJ - 1) / mmf::kCrfTJ;
+    CrfWs* w = nullptr;
+    if (int rc = crf_workspace(c, (size_t)N, nsplit * 2 * (size_t)std::max(L, 1) * (size_t)N, &w)) return rc;
+    if (!labels) {  // B3
+        if (w->grid_w != W || w->grid_h != H || w->grid_s != S) {
+            if ((size_t)W * H > w->grid_cap) {
+                MMF_HIP_TRY(hipStreamSynchronize(c->stream));
+                (void)hipFree(w->grid);
+                w->grid = nullptr, w->grid_cap = 0;
+                MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->grid), (size_t)W * H * sizeof(int)));
+                w->grid_cap = (size_t)W * H;
+            }
+            hipLaunchKernelGGL(mmf::crf_grid_labels_kernel, grid1d((size_t)W * H), dim3(256), 0, c->stream, W, H, S, W / S, H / S, w->grid);
+            MMF_HIP_TRY(hipGetLastError());
+            w->grid_w = W, w->grid_h = H, w->grid_s = S;
+        }
+        labels = w->grid;
+    }
+    *ws = w, *labels_out = labels;
+    return MMF_OK;
+}
+
+static void crf_models_out(const mmf::CrfSummary& s, mmf_segmentation_model* models_out, int* n_models_out, int* has_new_label) {
+    if (models_out)
+        for (int i = 0; i < s.n_models_out; ++i) models_out[i] = s.models[i];
+    if (n_models_out) *n_models_out = s.n_models_out;
+    if (has_new_label) *has_new_label = s.has_new_label;
+}
+
+extern "C" int mmf_crf_segment(mmf_ctx* c, const mmf_crf_config* cfg, const int* labels, int width, int height, const uint8_t* rgb,
+                               const float* depth, const float* low_maps, const unsigned* ids, int n_models, unsigned next_id,
+                               int allow_new, uint8_t* mask_out, mmf_segmentation_model* models_out, int* n_models_out,
+                               int* has_new_label) {
+    MMF_REQUIRE(c && rgb && depth && low_maps && ids && mask_out, "mmf_crf_segment: null argument");
+    MMF_HIP_TRY(hipSetDevice(c->device));
+    CrfWs* w = nullptr;
+    const int* lab = nullptr;
+    if (int rc = crf_begin(c, cfg, labels, width, height, ids, n_models, next_id, allow_new, "mmf_crf_segment", &w, &lab)) return rc;
+    // stage 1 of the depth (:178); the models' maps come in
+    if (int rc = mmf_slic_downsample(c, lab, width, height, cfg->spixel_size, depth, 1, 0, 1, 0.02f, w->low_depth, nullptr)) return rc;
+    if (int rc = crf_enqueue(c, w, cfg, lab, width, height, rgb, low_maps, ids, n_models, next_id, allow_new, mask_out)) return rc;
+    MMF_HIP_TRY(hipStreamSynchronize(c->stream));
+    crf_models_out(*w->sum_host, models_out, n_models_out, has_new_label);
+    return MMF_OK;
+}
+
+extern "C" int mmf_crf_last(mmf_ctx* c, mmf_crf_info* info, mmf_segmentation_model* models, int capacity, float* unaries, float* q,
+                            uint8_t* raw_map, uint8_t* map) {
+    MMF_REQUIRE(c != nullptr, "mmf_crf_last: null context");
+    CrfWs* w = c->crf_ws;
+    MMF_REQUIRE(w && w->valid, "mmf_crf_last: no segmentation has run on this context");
+    MMF_HIP_TRY(hipSetDevice(c->device));
+    MMF_HIP_TRY(hipStreamSynchronize(c->stream));
+    const mmf::CrfSummary& s = *w->sum_host;
+    const size_t N = (size_t)s.n_cells, L = (size_t)s.n_labels;
+    if (info) {
+        info->n_cells = s.n_cells, info->cells_x = w->cells_x, info->cells_y = w->cells_y;
+        info->n_labels = s.n_labels, info->n_models = s.n_models_out;
+        info->allow_new = s.allow_new, info->has_new_label = s.has_new_label, info->range_invalid = s.range_invalid;
+        info->n_components = s.n_components, info->range = s.range;
+    }
+    if (models)
+        for (int i = 0; i < s.n_models_out && i < capacity; ++i) models[i] = s.models[i];
+    if (unaries) MMF_HIP_TRY(hipMemcpyAsync(unaries, w->U, L * N * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    if (q) MMF_HIP_TRY(hipMemcpyAsync(q, w->Q, L * N * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    if (raw_map) MMF_HIP_TRY(hipMemcpyAsync(raw_map, w->raw_map, N, hipMemcpyDeviceToDevice, c->stream));
+    if (map) MMF_HIP_TRY(hipMemcpyAsync(map, w->map, N, hipMemcpyDeviceToDevice, c->stream));
+    MMF_HIP_TRY(hipStreamSynchronize(c->stream));
     return MMF_OK;
 }
 

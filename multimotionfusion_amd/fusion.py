@@ -209,6 +209,60 @@ class MultiMotionFusion:
     def setConfidenceThreshold(self, v): self._set("confidence_threshold", float(v))
     def setEnableMultipleModels(self, v): self._set("enable_multiple_models", int(bool(v)))
 
+    # ----- the built-in dense-CRF segmentation (segmentation.py) and the settings of MultiMotionFusion.h:243-261 that feed it
+    def setCrfSegmentation(self, cfg=True):
+        """cfg: a segmentation.CrfConfig (True: the current settings); None / False: off (the default).  With it on and no
+        mask or callback, processFrame computes the segmentation of every multi-model tracked frame itself."""
+        from .segmentation import CrfConfig
+        if cfg is None or cfg is False:
+            self._crf_on = False
+            check(self.ctx.lib.mmf_fusion_set_crf_segmentation(self.handle, None))
+            return
+        if cfg is not True:
+            self._crf = cfg
+        elif not hasattr(self, "_crf"):
+            self._crf = CrfConfig()
+        self._crf_on = True
+        check(self.ctx.lib.mmf_fusion_set_crf_segmentation(self.handle, C.byref(self._crf.to_c())))
+
+    def _crf_set(self, name, v):
+        from .segmentation import CrfConfig
+        if not hasattr(self, "_crf"):
+            self._crf = CrfConfig()
+        setattr(self._crf, name, v)
+        # (the settings reach the fusion with the CRF off too -- the spawn-offset counter runs either way -- and it stays off)
+        check(self.ctx.lib.mmf_fusion_set_crf_segmentation(self.handle, C.byref(self._crf.to_c())))
+        if not getattr(self, "_crf_on", False):
+            check(self.ctx.lib.mmf_fusion_set_crf_segmentation(self.handle, None))
+
+    def setCrfPairwiseSigmaRGB(self, v): self._crf_set("sigma_rgb", float(v))
+    def setCrfPairwiseSigmaPosition(self, v): self._crf_set("sigma_pos", float(v))
+    def setCrfPairwiseSigmaDepth(self, v): self._crf_set("sigma_depth", float(v))
+    def setCrfPairwiseWeightAppearance(self, v): self._crf_set("weight_appearance", float(v))
+    def setCrfPairwiseWeightSmoothness(self, v): self._crf_set("weight_smoothness", float(v))
+    def setCrfThresholdNew(self, v): self._crf_set("threshold_new", float(v))
+    def setCrfUnaryWeightError(self, v): self._crf_set("unary_weight_error", float(v))
+    def setCrfUnaryKError(self, v): self._crf_set("unary_k_error", float(v))
+    def setCrfIteration(self, v): self._crf_set("iterations", int(v))
+    def setNewModelMinRelativeSize(self, v): self._crf_set("min_rel_size_new", float(v))
+    def setNewModelMaxRelativeSize(self, v): self._crf_set("max_rel_size_new", float(v))
+    def setModelSpawnOffset(self, v): self._crf_set("model_spawn_offset", int(v))
+    def setSetInhibit(self, v): self._crf_set("inhibit_new", int(bool(v)))
+
+    def setSuperpixels(self, labels):
+        """the super-pixel label image (int32 [H,W] CUDA tensor) of the NEXT frame's segmentation; None: the regular grid"""
+        import torch
+        if labels is not None:
+            assert labels.dtype == torch.int32 and labels.shape == (self.height, self.width)
+            labels = labels.contiguous()
+        check(self.ctx.lib.mmf_fusion_set_superpixels(self.handle, _p(labels) if labels is not None else None))
+
+    def getLastSegmentation(self):
+        """segmentation.last() of this fusion: unaries, Q, raw and filtered maps, model data, range, B4 flag"""
+        import torch
+        from .segmentation import _last
+        return _last(self.ctx.lib.mmf_fusion_last_segmentation, self.handle, torch.device("cuda", self.ctx.device))
+
     def getConfig(self):
         cfg = mmf_fusion_config()
         check(self.ctx.lib.mmf_fusion_get_config(self.handle, C.byref(cfg)))
