@@ -212,7 +212,7 @@ int mmf_odom_download(mmf_odom *o, const char *name, int level, void *host_dst, 
 /* Timing hook for bench.py: enqueue `reps` back-to-back launches of the level-`level` ICP
  * reduction kernel on the odometry object's current maps and pose (no host work in
  * between), bracketed by HIP events on the context's stream; returns the mean time per launch.
- * variant: 0 = the shipped launch geometry, else PX * 10000 + BLOCK (tuning sweeps). */
+ * variant: must be 0 (the shipped launch geometry); any other value returns MMF_ERR_INVALID. */
 int mmf_odom_time_icp_kernel(mmf_odom *o, int level, int reps, int variant, float *mean_us_out);
 /* Measurement mode for bench.py: while on, every launch of the Gauss-Newton loop's two kernels -- the producer
  * (ICP J^T J reduction + photometric correspondence pass of one iteration) and the photometric Jacobian /

@@ -792,6 +792,7 @@ static void fusion_collect_prep(mmf_fusion* f, PrepStages& stages, FusionModel* 
 // (gridDim.y = model), the other models' streams continuing behind it; else one chain per model on the model's stream.
 static int fusion_enqueue_chains(mmf_fusion* f, FusionModel* const* fms, size_t n, bool batch, bool from_last_pose) {
     const mmf_fusion_config& g = f->cfg;
+    const TrackMode tm = track_mode(g.rgb_only, g.icp_weight, g.pyramid, g.fast_odom, g.so3);
     float pose[16];
     auto start_pose = [&](FusionModel* fm) -> const float* {
         if (from_last_pose) return fm->last_pose;
@@ -802,8 +803,7 @@ static int fusion_enqueue_chains(mmf_fusion* f, FusionModel* const* fms, size_t 
         for (size_t k = 0; k < n; ++k) {
             float trans[3], rot[9];
             pose_trans_rot(start_pose(fms[k]), trans, rot);
-            int rc = odom_enqueue_tracking(fms[k]->odom, trans, rot, g.rgb_only, g.icp_weight, g.pyramid, g.fast_odom, g.so3,
-                                           fms[k]->icp_error, fms[k]->rgb_error);
+            int rc = odom_enqueue_tracking(fms[k]->odom, trans, rot, tm, fms[k]->icp_error, fms[k]->rgb_error);
             if (rc) return rc;
         }
         return MMF_OK;
@@ -818,8 +818,7 @@ static int fusion_enqueue_chains(mmf_fusion* f, FusionModel* const* fms, size_t 
         tb.bd.d[k] = (long long)(reinterpret_cast<char*>(fms[k]->odom->slab) - reinterpret_cast<char*>(lead->odom->slab));
         pose_trans_rot(start_pose(fms[k]), tb.poses.trans[k], tb.poses.rot[k]);
     }
-    int rc = odom_enqueue_tracking(lead->odom, tb.poses.trans[0], tb.poses.rot[0], g.rgb_only, g.icp_weight, g.pyramid,
-                                   g.fast_odom, g.so3, lead->icp_error, lead->rgb_error, &tb);
+    int rc = odom_enqueue_tracking(lead->odom, tb.poses.trans[0], tb.poses.rot[0], tm, lead->icp_error, lead->rgb_error, &tb);
     if (rc) return rc;
     // the lanes continue after the chain.  With a segmentation every lane waits for ev_frame_ready before its passes anyway,
     // and that event is recorded on this very stream (the camera model's) behind the chain (the mask's upload, frame_segment):
@@ -1038,7 +1037,7 @@ static int frame_enqueue_tracking(mmf_fusion* f, FrameRun& r) {
         int rc = stages.launch(st);
         if (rc) return rc;
         r.stamp(f, 8);
-        r.batch_ok = odom_batchable(lead->odom, g.rgb_only, g.icp_weight, g.pyramid, g.fast_odom);
+        r.batch_ok = odom_batchable(lead->odom, track_mode(g.rgb_only, g.icp_weight, g.pyramid, g.fast_odom, g.so3));
         if (r.batch_ok) {
             lead->odom->exclusive_chain = true;  // one chain for all of them
             return fusion_enqueue_chains(f, tracked.data(), tracked.size(), true, false);
@@ -1509,7 +1508,8 @@ static int frame_prepare_next(mmf_fusion* f, const FrameRun& r) {
             const OdomState* stage = (g.so3 && f->so3_stage_ready >= 0) ? f->so3_stage[f->so3_stage_ready] : nullptr;
             if (!g.so3 || stage != nullptr) {
                 if (stage) MMF_HIP_TRY(fusion_wait_unless_done(st, f->ev_prefetch2_done));  // (the staged pre-alignment is complete)
-                ride = odom_begin_rider(only->odom, only->spec_pose, g.rgb_only, g.icp_weight, g.pyramid, g.fast_odom, g.so3, stage, &rider);
+                ride = odom_begin_rider(only->odom, only->spec_pose, track_mode(g.rgb_only, g.icp_weight, g.pyramid, g.fast_odom, g.so3),
+                                        stage, &rider);
             }
         }
         if (!ride) only->odom->begin_spec_valid = false;

@@ -21,7 +21,7 @@
 //     a sharded 64-bit counter (integer atomics: exact, order independent), polls until every workgroup of the launch has
 //     arrived, decides sigma and lays out the pass's 256 possible weights in LDS, while the pixel waves compute their ICP
 //     rows and reduce them.  The grid is at most kGnMaxGroups workgroups per model, all co-resident (the host checks the
-//     occupancy: odom_fused_chain_ok);
+//     occupancy: odom_plan_chain);
 //   * rgbStep's Jacobian rows (reduce.cu:504-535) from the registers, both 29-sum sets reduced over the workgroup in float
 //     and added to the launch's sums as fixed-point integers by atomics (exact, order independent): the next
 //     launch -- or gn_final_kernel -- reads 7.4 KB of totals instead of a 256-byte record per workgroup (round 3: 61 KB
@@ -1104,8 +1104,8 @@ struct GnBatchGeom {
     const unsigned long long* sensor;  // the extent words that hold the sensor frame's smallest depth (the leader's: shared, not shifted)
     unsigned sensor_gen;               // ... the number it was noted under (0: unknown)
     float sensor_cutoff;               // ... and the cut-off no sensor depth reaches (createVMap)
-    int rotate;  // the grid's first workgroup is number `rotate` of the list start[] describes (tunables: gn_obj_first: the object
-                 // models' workgroups, which have the longer way to go, are dispatched before the camera model's)
+    int rotate;  // the grid's first workgroup is number `rotate` of the list start[] describes (the host dispatches the object
+                 // models' workgroups, which have the longer way to go, before the camera model's)
 };
 constexpr int kGnFaultExtent = 3;  // OdomState::gn_fault: an object model's extent does not fit its workgroups (the host walks it densely from then on)
 

@@ -21,7 +21,9 @@
 #include <thread>
 #include <new>
 #include <string>
+#include <tuple>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "map_kernels.hpp"
@@ -38,6 +40,10 @@ using namespace mmf;
 // arguments of the nodes that changed replaced.  With one model a graph launch reaches the GPU ~10 us later than the first
 // kernel of a launch-by-launch chain; with eight models it takes the call's start from 330 to 80 us of the calling thread's
 // time and the frame is no shorter: LABNOTES.md.)
+// A timed launch (measurement mode 2, mmf_odom_enable_timing) records its dispatch's own start and end into `start` / `stop`.
+struct TimedSlot {
+    hipEvent_t start = nullptr, stop = nullptr;
+};
 struct Enqueuer {
     hipStream_t stream = nullptr;
     hipError_t err = hipSuccess;
@@ -46,7 +52,14 @@ struct Enqueuer {
 
     template <typename... KArgs, typename... Args>
     void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, Args&&... args) {
-        hipLaunchKernelGGL(kernel, grid, block, 0, stream, static_cast<KArgs>(args)...);
+        launch(TimedSlot{}, kernel, grid, block, std::forward<Args>(args)...);
+    }
+    template <typename... KArgs, typename... Args>
+    void launch(const TimedSlot& t, void (*kernel)(KArgs...), dim3 grid, dim3 block, Args&&... args) {
+        if (t.start)
+            hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, t.start, t.stop, 0, static_cast<KArgs>(args)...);
+        else
+            hipLaunchKernelGGL(kernel, grid, block, 0, stream, static_cast<KArgs>(args)...);
         const hipError_t e = hipGetLastError();
         if (err == hipSuccess) err = e;
     }
@@ -233,25 +246,6 @@ static inline LevelIntr level_intr(float fx, float fy, float cx, float cy, int l
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// ICP reduction launch.  `variant` = GEN * 1000000 + PX * 10000 + BLOCK picks the kernel (0 = the
-// tuned default): GEN 2 = icp_kernel2 gathering from a.prev_packed when it is set, GEN 1 = icp_kernel2
-// with planar gathers, PX pixels per lane (1, 2 or 4; the vector forms need cols % PX == 0 and
-// aligned rows), BLOCK threads per workgroup.  tools/sweep_icp.py on MI355X: every geometry of
-// icp_kernel2 lands within 0.2 us at 640x480 (the launch is bound by its two memory round trips
-// and the dispatch floor, no longer by instruction issue), so one default serves all levels.
-static int icp_default_variant(int /*npix*/) {
-    const int forced = tunables().icp_variant;  // tuning aid: MMF_ICP_VARIANT=<GEN*1000000 + PX*10000 + BLOCK>
-    return forced > 0 ? forced : 2020256;
-}
-
-template <int W, int NV, int BLOCK, bool PACKED, int MODE>
-static int launch_icp2_variant(mmf_ctx* c, OdomState* st, const IcpArgs& a, float* partials) {
-    const int grid = (a.cols * a.rows + BLOCK * W * NV - 1) / (BLOCK * W * NV);  // <= kMaxIcpGrid, checked by the caller
-    hipLaunchKernelGGL((icp_kernel2<W, NV, BLOCK, PACKED, MODE>), dim3(grid), dim3(BLOCK), 0, c->stream, st, a,
-                       partials);
-    return grid;
-}
-
 // largest float x with sqrtf(x) <= t, and smallest x with sqrtf(x) >= t: sqrtf is monotonic and
 // correctly rounded, so comparing squares against these is EXACTLY the reference's comparison of
 // the norms (reduce.cu:301-306) -- see icp_rows_v
@@ -291,43 +285,29 @@ static bool icp2_fits(const IcpArgs& a, int block, int px) {
     return n * a.cols < (1ll << 32) && (long long)kMaxIcpGrid * block * px >= n;
 }
 
-// launches the ICP producer; *records_out = number of partial records it writes to c->partials_icp
+// Launches the ICP producer (icp_kernel2, gathering from a.prev_packed when it is set) on q and returns the number of partial
+// records it writes.  Two pixels per lane where the maps allow, 256 lanes: every geometry of icp_kernel2 lands within 0.2 us
+// at 640x480 on MI355X (the launch is bound by its two memory round trips and the dispatch floor, no longer by instruction
+// issue), so one serves all levels.  Images too large for one pass of kMaxIcpGrid workgroups: those walk the image, one
+// pixel per lane and pass.
 template <int MODE>
-static hipError_t launch_icp(mmf_ctx* c, OdomState* st, IcpArgs a, int variant = 0, int* records_out = nullptr,
-                             float* partials = nullptr) {
-    if (!partials) partials = c->partials_icp;
-    if (variant == 0) variant = icp_default_variant(a.cols * a.rows);
+static int launch_icp(Enqueuer& q, OdomState* st, IcpArgs a, float* partials) {
     icp_args_derive(a);
-    const int gen = variant / 1000000;
-    const int px = icp_max_px(a, (variant / 10000) % 100);
-    int block = variant % 10000;
-    if (block != 64 && block != 128) block = 256;
-    int grid = 0;
-    if (icp2_fits(a, block, px)) {
-        const bool packed = gen != 1 && a.prev_packed != nullptr;
-#define MMF_ICP2(W, NV, B)                                                                 \
-    grid = packed ? launch_icp2_variant<W, NV, B, true, MODE>(c, st, a, partials) : launch_icp2_variant<W, NV, B, false, MODE>(c, st, a, partials)
-        switch (px * 10000 + block) {
-            case 40256: MMF_ICP2(2, 2, 256); break;
-            case 40128: MMF_ICP2(2, 2, 128); break;
-            case 20128: MMF_ICP2(2, 1, 128); break;
-            case 20064: MMF_ICP2(2, 1, 64); break;
-            case 10128: MMF_ICP2(1, 1, 128); break;
-            case 10064: MMF_ICP2(1, 1, 64); break;
-            case 10256: MMF_ICP2(1, 1, 256); break;
-            default: MMF_ICP2(2, 1, 256);
-        }
-#undef MMF_ICP2
-    } else {  // very large images: kMaxIcpGrid workgroups walk the image, one pixel per lane and pass
-        grid = kMaxIcpGrid;
-        const bool packed = gen != 1 && a.prev_packed != nullptr;
-        if (packed)
-            hipLaunchKernelGGL((icp_kernel2<1, 1, 256, true, MODE, true>), dim3(grid), dim3(256), 0, c->stream, st, a, partials);
-        else
-            hipLaunchKernelGGL((icp_kernel2<1, 1, 256, false, MODE, true>), dim3(grid), dim3(256), 0, c->stream, st, a, partials);
+    const int px = icp_max_px(a, 2);
+    const bool packed = a.prev_packed != nullptr;
+    if (!icp2_fits(a, 256, px)) {
+        q.launch(packed ? icp_kernel2<1, 1, 256, true, MODE, true> : icp_kernel2<1, 1, 256, false, MODE, true>,
+                 dim3(kMaxIcpGrid), dim3(256), st, a, partials);
+        return kMaxIcpGrid;
     }
-    if (records_out) *records_out = grid;
-    return hipGetLastError();
+    const int grid = (a.cols * a.rows + 256 * px - 1) / (256 * px);
+    if (px == 2)
+        q.launch(packed ? icp_kernel2<2, 1, 256, true, MODE> : icp_kernel2<2, 1, 256, false, MODE>, dim3(grid), dim3(256), st, a,
+                 partials);
+    else
+        q.launch(packed ? icp_kernel2<1, 1, 256, true, MODE> : icp_kernel2<1, 1, 256, false, MODE>, dim3(grid), dim3(256), st, a,
+                 partials);
+    return grid;
 }
 
 static void unpack_se3_host(const float* tot, float* A, float* b) {  // reduce.cu:458-472
@@ -377,11 +357,10 @@ extern "C" int mmf_icp_step(mmf_ctx* c, const float Rcurr[9], const float tcurr[
     a.prev_packed = nullptr;
     a.err_map = err_map_dev;
     a.err_stride = stride_elems(err_map_step, cols, 4);
-    int records = 0;
-    MMF_HIP_TRY(launch_icp<FINISH_RAW>(c, c->scratch_state, a, 0, &records));
-    hipLaunchKernelGGL((icp_finish_kernel<FINISH_RAW>), dim3(1), dim3(256), 0, c->stream, c->scratch_state,
-                       c->partials_icp, (unsigned)records, a.intr);
-    MMF_HIP_TRY(hipGetLastError());
+    Enqueuer q(c->stream);
+    const int records = launch_icp<FINISH_RAW>(q, c->scratch_state, a, c->partials_icp);
+    q.launch(icp_finish_kernel<FINISH_RAW>, dim3(1), dim3(256), c->scratch_state, c->partials_icp, (unsigned)records, a.intr);
+    MMF_HIP_TRY(q.flush());
     float tot[32];
     MMF_HIP_TRY(hipMemcpyAsync(tot, c->scratch_state->out_f, sizeof(float) * 32, hipMemcpyDeviceToHost, c->stream));
     MMF_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1277,8 +1256,8 @@ static void odom_prepare_collect(PrepStages& stages, mmf_odom* o, const float* d
     const bool merge_first = tunables().prep_merge >= 2;
     // The model maps in the global frame go out as the packed records (and {X, Y, Z, 1/Z} point records) the chains gather
     // from; the planar copies and the AoS cloud of the first-generation kernels (25 -> 14 MB written per frame at level 0)
-    // only for the first-generation ICP kernel (MMF_ICP_VARIANT 1xxxxxx) or on request: MMF_PREP_PLANAR=1.
-    const bool planar = tunables().prep_planar || icp_default_variant(0) / 1000000 == 1;
+    // only on request: MMF_PREP_PLANAR=1.
+    const bool planar = tunables().prep_planar;
     // The sensor frame's normal map of a level is computed in the same job as its vertex map, from the depth image
     // (PREP_VMAP_NMAP): the depth side is three dependent launches instead of four.  MMF_PREP_VN=0: apart (A/B aid).
     const bool merge_vn = tunables().prep_vn;
@@ -1545,7 +1524,48 @@ struct TrackBatch {
     BeginPoses poses;
 };
 
-static bool odom_batchable(mmf_odom* o, int rgb_only, float icp_weight, int pyramid, int fast_odom);
+// The tracking mode of one call, worked out once from the reference's five settings.
+struct TrackMode {
+    bool icp, rgb, rgb_only, so3;
+    float icp_weight;
+    int iterations[MMF_NUM_PYRS];  // Gauss-Newton iterations per level
+    int first_iter_level;          // the coarsest level that runs iterations (the ones below it all do)
+};
+static TrackMode track_mode(int rgb_only, float icp_weight, int pyramid, int fast_odom, int so3) {
+    TrackMode m;
+    m.icp = !rgb_only && icp_weight > 0;  // :221-222
+    m.rgb = rgb_only || icp_weight < 100;
+    m.rgb_only = rgb_only != 0;
+    m.so3 = so3 != 0;
+    m.icp_weight = icp_weight;
+    const int iterations[MMF_NUM_PYRS] = {fast_odom ? 3 : 10, pyramid ? 5 : 0, pyramid ? 4 : 0};  // :312-314
+    std::copy(iterations, iterations + MMF_NUM_PYRS, m.iterations);
+    m.first_iter_level = MMF_NUM_PYRS - 1;
+    while (m.first_iter_level > 0 && !m.iterations[m.first_iter_level]) --m.first_iter_level;
+    return m;
+}
+
+// The launch arguments of one pyramid level: the correspondence pass's and the ICP reduction's.  The error images are the
+// caller's (the chains write them in the last level-0 iteration only, the planner checks the odometry's own).
+struct LevelArgs {
+    int cols, rows;
+    LevelIntr in;
+    RgbResidualArgs ra;
+    IcpArgs ia;
+};
+static LevelArgs odom_level_args(mmf_odom* o, int i, float* rgb_err, float* icp_err) {
+    LevelArgs l;
+    l.cols = o->width >> i, l.rows = o->height >> i;
+    l.in = level_intr(o->fx, o->fy, o->cx, o->cy, i);
+    const float min_scale = (float)(std::pow((double)o->min_grad[i], 2.0) / std::pow((double)o->sobel_scale, 2.0));
+    l.ra = make_residual_args(min_scale, o->dIdx[i], 0, o->dIdy[i], 0, o->last_depth[i], 0,
+                              o->prep_batched ? o->last_depth[i] : o->next_depth[i], 0, o->last_image[i], 0, o->next_image[i],
+                              0, o->corres[i], o->max_depth_delta_rgb, l.cols, l.rows, rgb_err, 0);
+    l.ra.intr = l.in;
+    l.ia = odom_icp_args(o, i, icp_err);
+    return l;
+}
+
 // Launch geometry of gn_iter_kernel at a level of cols x rows pixels: a workgroup = the solver wave + the pixel waves.  The
 // launch is a chain of latencies -- records, solve, two memory round trips, the count barrier -- and every workgroup waits at
 // that barrier for the slowest one, so (measured on MI355X, tools/ab_libs.sh): at most one workgroup per CU (two on a CU
@@ -1560,15 +1580,18 @@ struct GnGeometry {
 // mixed: a launch that also carries object models walked by their extents (gn_iter_mixed_kernel).  Its register count allows
 // three waves per SIMD, and the GPU places a second 5-wave workgroup on a CU only with four (measured: tools/gn_mixed_probe.py
 // -- the object models' workgroups started when the camera model's had finished); workgroups of FOUR waves (the solver wave
-// + three pixel waves, 192 pixel lanes) take one wave slot per SIMD and three of them share a CU.
+// + three pixel waves, 192 pixel lanes) take one wave slot per SIMD and three of them share a CU.  (256 lanes measured slower
+// at 2, 4 and 8 models: LABNOTES.md.)
+constexpr int kGnMixedLanes = 192;
+static_assert(kGnMixedLanes % 64 == 0 && kGnMixedLanes <= kGnSparseLanes,
+              "the sparse walk keeps a workgroup's correspondences in LDS, sized for kGnSparseLanes lanes");
 static bool gn_geometry(int level, int cols, int rows, GnGeometry* out, bool mixed = false) {
-    if (mixed && tunables().gn_mixed_lanes > 0 && tunables().gn_mixed_lanes < kBlock) {
+    if (mixed) {
         GnGeometry base;
         if (!gn_geometry(level, cols, rows, &base, false) || base.lanes != kBlock) return false;
-        const int lanes = std::max(32, tunables().gn_mixed_lanes);
-        const int groups = (cols * rows / base.px + lanes - 1) / lanes;
+        const int groups = (cols * rows / base.px + kGnMixedLanes - 1) / kGnMixedLanes;
         if (groups > kGnMaxGroups) return false;
-        *out = GnGeometry{base.px, lanes, (lanes + 63) / 64 * 64 + 64, groups};
+        *out = GnGeometry{base.px, kGnMixedLanes, kGnMixedLanes + 64, groups};
         return true;
     }
     const int* forced = tunables().gn_px;
@@ -1597,13 +1620,25 @@ static bool gn_geometry(int level, int cols, int rows, GnGeometry* out, bool mix
     }
     return false;
 }
-struct GnChainPlan {  // how the one-launch chain walks the models of a batch (gn_fused.hpp: GnBatchGeom)
+// calls f(std::integral_constant<int, PX>) for the pixels per lane of a Gauss-Newton launch (1, 2, 4 or 5: gn_geometry)
+template <typename F>
+static auto with_gn_px(int px, F&& f) {
+    switch (px) {
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        default: return f(std::integral_constant<int, 1>{});
+    }
+}
+// How the chain of one call runs: one launch per iteration (gn_iter_kernel) or two (producer + rgb_step), and how the one-launch
+// chain walks the models of a batch (gn_fused.hpp: GnBatchGeom).  Made by odom_plan_chain, the only place that decides it.
+struct GnChainPlan {
+    bool one_launch = false;
+    bool mixed = false;  // object models walked by their extents ride the launch (gn_iter_mixed_kernel)
     unsigned sparse_mask = 0, ext_gen = 0;
-    int groups[MMF_NUM_PYRS][kMaxBatch];  // workgroups of model m at level l
+    GnGeometry geo[MMF_NUM_PYRS] = {};
+    int groups[MMF_NUM_PYRS][kMaxBatch] = {};  // workgroups of model m at level l
 };
-static bool odom_fused_chain_ok(mmf_odom* o, int rgb_only, float icp_weight, int pyramid, int fast_odom, const TrackBatch* batch = nullptr,
-                                bool sparse_on = false, GnChainPlan* plan = nullptr);
-static unsigned fused_max_models();
 // workgroups of an OBJECT model per launch of the one-launch chain at pyramid level l (a property of the model, batched or
 // alone: its float sums keep their order): its photometric box must fit them in ONE pass (32 x 1280 pixels at 640x480 level 0,
 // a box of 200 x 200), its ICP rectangle takes as many passes as it needs
@@ -1655,410 +1690,33 @@ static int gn_retry_twice() { return fail(MMF_ERR_STATE, "odometry: tracking gav
 static bool odom_sparse_on() { return (g_track_cull.load() < 0 ? tunables().track_cull : g_track_cull.load()) != 0; }
 static void odom_begin_rider_used();
 // what odom_begin_kernel is told (RGBDOdometry.cpp:221-228, 237, 252-255, 316-328); every byte defined (the blocks are compared)
-static BeginArgs odom_begin_args(const mmf_odom* o, const float trans[3], const float rot[9], int rgb_only, float icp_weight, int pyramid,
-                                 int fast_odom, int so3, bool so3_prefetched, const OdomState* so3_stage, bool fused_chain) {
-    const bool icp = !rgb_only && icp_weight > 0;  // :221-222
-    const bool rgb = rgb_only || icp_weight < 100;
-    const int iterations[MMF_NUM_PYRS] = {fast_odom ? 3 : 10, pyramid ? 5 : 0, pyramid ? 4 : 0};  // :312-314
-    int first_iter_level = MMF_NUM_PYRS - 1;  // the coarsest level that runs iterations
-    while (first_iter_level > 0 && !iterations[first_iter_level]) --first_iter_level;
+static BeginArgs odom_begin_args(const mmf_odom* o, const float trans[3], const float rot[9], const TrackMode& tm,
+                                 bool so3_prefetched, const OdomState* so3_stage, bool one_launch) {
     BeginArgs b;
     std::memset(&b, 0, sizeof(b));
     std::memcpy(b.trans, trans, sizeof(b.trans));
     std::memcpy(b.rot, rot, sizeof(b.rot));
-    b.rgb_only = rgb_only ? 1 : 0;
-    b.icp = icp ? 1 : 0;
-    b.rgb = rgb ? 1 : 0;
-    b.so3 = so3 ? 1 : 0;
-    b.icp_weight = icp_weight;
+    b.rgb_only = tm.rgb_only ? 1 : 0;
+    b.icp = tm.icp ? 1 : 0;
+    b.rgb = tm.rgb ? 1 : 0;
+    b.so3 = tm.so3 ? 1 : 0;
+    b.icp_weight = tm.icp_weight;
     b.so3_intr = level_intr(o->fx, o->fy, o->cx, o->cy, 2);
-    b.so3_prefetched = (so3 && so3_prefetched) ? 1 : 0;
+    b.so3_prefetched = (tm.so3 && so3_prefetched) ? 1 : 0;
     b.so3_stage = b.so3_prefetched ? so3_stage : nullptr;
     // nothing runs between the beginning and the first level's begin unless the SO3 loop does: one launch
-    b.fold_level_begin = (!so3 || so3_prefetched) ? 1 : 0;
+    b.fold_level_begin = (!tm.so3 || so3_prefetched) ? 1 : 0;
     // the one-launch chain has no per-level begin: its first launch reads what this one prepares
-    b.first_intr = level_intr(o->fx, o->fy, o->cx, o->cy, fused_chain ? first_iter_level : MMF_NUM_PYRS - 1);
+    b.first_intr = level_intr(o->fx, o->fy, o->cx, o->cy, one_launch ? tm.first_iter_level : MMF_NUM_PYRS - 1);
     return b;
 }
-static int odom_enqueue_tracking(mmf_odom* o, const float trans[3], const float rot[9], int rgb_only, float icp_weight,
-                                 int pyramid, int fast_odom, int so3, float* icp_err_dev, float* rgb_err_dev,
-                                 const TrackBatch* batch = nullptr) {
-    mmf_ctx* c = o->ctx;
-    MMF_HIP_TRY(hipSetDevice(c->device));
-#ifdef MMF_STAMPS  // (diagnostic builds: MMF_DBG_NO_ERR=1 leaves the error images out, so that a chain's last launch is an ordinary one)
-    if (std::getenv("MMF_DBG_NO_ERR")) icp_err_dev = rgb_err_dev = nullptr;
-#endif
-    const bool icp = !rgb_only && icp_weight > 0;  // :221-222
-    const bool rgb = rgb_only || icp_weight < 100;
-    const unsigned ny = batch ? (unsigned)batch->n : 1u;
-    BatchDelta bd;
-    BeginPoses poses;
-    std::memset(&bd, 0, sizeof(bd));
-    std::memset(&poses, 0, sizeof(poses));
-    if (batch) bd = batch->bd, poses = batch->poses;
-    MMF_REQUIRE(ny == 1 || odom_batchable(o, rgb_only, icp_weight, pyramid, fast_odom), "odom_enqueue_tracking: not batchable");
 
-    if (rgb && !o->prep_batched)
-        for (int i = 0; i < MMF_NUM_PYRS; ++i) {  // :230-235
-            int rc = launch_derivative(c, o->next_image[i], o->width >> i, o->width >> i, o->height >> i, o->dIdx[i],
-                                       o->width >> i, o->dIdy[i], o->width >> i);
-            if (rc) return rc;
-        }
-
-    const int iterations[MMF_NUM_PYRS] = {fast_odom ? 3 : 10, pyramid ? 5 : 0, pyramid ? 4 : 0};  // :312-314
-    // both terms on and every level fits: ONE launch per iteration (gn_fused.hpp) instead of producer + step
-    // (more than three models: the batched two-launch chain is as fast (four) or faster -- 8 models 1.40 ms against 1.60 --
-    // because a model's workgroups hold their CUs at the count barrier while the next models' wait for a place)
-    // Object models (extent.hpp): in the two-launch chain (track_kernels.hpp: ChainGeom) their passes skip what lies outside
-    // the model's own depth when the preparation noted its extents for this frame, and they walk their images with a
-    // quarter of the workgroups; in the one-launch chain (gn_fused.hpp: gn_iter_mixed_kernel) they walk their extents with a
-    // fraction of the workgroups, which is what lets ALL models of a frame be resident in one launch.
-    // MMF_TRACK_CULL=0 / mmf_debug_set_track_cull(0): every model like the first.
-    const bool sparse_on = odom_sparse_on();
-    bool two_launch_once = false;  // (odom_retrack_prepare: this frame is being tracked again)
-    for (unsigned m = 0; m < ny; ++m) {
-        mmf_odom* om = batch ? batch->o[m] : o;
-        two_launch_once = two_launch_once || om->two_launch_once;
-        om->two_launch_once = false;
-    }
-    GnChainPlan plan;
-    for (unsigned m = 0; m < ny; ++m) (batch ? batch->o[m] : o)->walked_by_extent = false;
-    const bool fused_chain = !two_launch_once && odom_fused_chain_ok(o, rgb_only, icp_weight, pyramid, fast_odom, batch, sparse_on, &plan) &&
-                             (ny == 1 || (ny <= fused_max_models() && odom_batchable(o, rgb_only, icp_weight, pyramid, fast_odom)));
-    const bool lead_sparse = sparse_on && o->sparse;
-    bool foll_sparse = sparse_on && batch && ny > 1;
-    unsigned foll_gen = foll_sparse ? batch->o[1]->extent_gen : 0u;
-    for (unsigned m = 1; m < ny && foll_sparse; ++m) {
-        foll_sparse = batch->o[m]->sparse;
-        if (batch->o[m]->extent_gen != foll_gen) foll_gen = 0u;
-    }
-    if (!foll_sparse) foll_gen = 0u;
-    // (the kernels drop the first model's extent in a batch; a sparse model tracked alone keeps its own)
-    const unsigned cull_gen = ny > 1 ? foll_gen : (lead_sparse ? o->extent_gen : 0u);
-    auto quarter = [](int full) { return std::max(std::min(full, 32), (full + 3) / 4); };
-    int first_iter_level = MMF_NUM_PYRS - 1;  // the coarsest level that runs iterations
-    while (first_iter_level > 0 && !iterations[first_iter_level]) --first_iter_level;
-
-    const BeginArgs b = odom_begin_args(o, trans, rot, rgb_only, icp_weight, pyramid, fast_odom, so3, o->so3_prefetched, o->so3_stage, fused_chain);
-    // nothing runs between the beginning and the first level's begin unless the SO3 loop does: one launch
-    const bool fold_first_level = b.fold_level_begin != 0;
-    o->n_timed = 0;
-    if (o->timing) MMF_HIP_TRY(hipEventRecord(o->ev_chain[0], c->stream));
-    // from here to the last step: kernels only, enqueued one by one in call order (Enqueuer keeps the first error)
-    Enqueuer q(c->stream);
-    // (the beginning may have run already, on the last launch of the preparation enqueued ahead of this frame: odom_begin_rider)
-    const bool begun = o->begin_spec_valid && o->begin_spec_ok && !batch && std::memcmp(&b, &o->begin_spec, sizeof(b)) == 0;
-    o->begin_spec_valid = o->begin_spec_ok = false;
-    if (!begun)
-        q.launch(odom_begin_kernel, dim3(ny), dim3(64), o->state, b, bd, poses);
-    else
-        odom_begin_rider_used();
-
-    o->retry_so3_prefetched = o->so3_prefetched, o->retry_so3_stage = o->so3_stage;  // (odom_retrack_prepare)
-    const bool so3_ran_here = so3 && !o->so3_prefetched;  // in the leader's state: shared with the others at the first level begin
-    if (so3 && !o->so3_prefetched) {  // :239-310
-        int rc = odom_enqueue_so3(o, q);
-        if (rc) return rc;
-    }
-    o->so3_prefetched = false;
-    o->so3_stage = nullptr;
-
-    GnIterArgs final_args;
-    bool final_pending = false;
-    std::memset(&final_args, 0, sizeof(final_args));
-    if (fused_chain) {
-        for (unsigned m = 0; m < ny; ++m) (batch ? batch->o[m] : o)->walked_by_extent = ((plan.sparse_mask >> m) & 1u) != 0;
-        int it = 0;
-        bool first = true;
-        GnIterArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.poll_sleep = tunables().gn_sleep;
-        a.max_polls = kGnMaxPolls;
-        a.check_sparse = g_sparse_check.load();
-        bool force_fault = false;
-        for (int n = g_gn_force_fault.load(); n > 0 && !force_fault;) force_fault = g_gn_force_fault.compare_exchange_weak(n, n - 1);
-        for (int i = MMF_NUM_PYRS - 1; i >= 0; --i) {
-            if (!iterations[i]) continue;
-            const int cols = o->width >> i, rows = o->height >> i;
-            const LevelIntr in = level_intr(o->fx, o->fy, o->cx, o->cy, i);
-            if (!o->prep_batched) {  // :332-334
-                MMF_HIP_TRY(q.flush());
-                int rc = launch_project(c, o->last_depth[i], cols, cols, rows, in, o->cloud[i], o->cloud4[i]);
-                if (rc) return rc;
-            }
-            if (first && !fold_first_level)  // the SO3 loop ran in between: seed resultRt from its result now
-                q.launch(gn_level_begin_kernel, dim3(ny), dim3(64), o->state, 1, in, bd, so3_ran_here ? 1 : 0);
-            first = false;
-            const float min_scale = (float)(std::pow((double)o->min_grad[i], 2.0) / std::pow((double)o->sobel_scale, 2.0));
-            GnGeometry geo;
-            MMF_REQUIRE(gn_geometry(i, cols, rows, &geo, plan.sparse_mask != 0), "odom_enqueue_tracking: no launch geometry for this level");
-            const int px = geo.px, groups = geo.groups;
-            a.lanes = geo.lanes;
-            // object models walked by their extents: one one-dimensional grid, a geometry per model (GnBatchGeom)
-            GnBatchGeom gg;
-            std::memset(&gg, 0, sizeof(gg));
-            const bool mixed = plan.sparse_mask != 0;
-            if (mixed) {
-                for (unsigned m = 0; m < (unsigned)kMaxBatch; ++m) gg.start[m + 1] = gg.start[m] + (m < ny ? plan.groups[i][m] : 0);
-                gg.sparse_mask = plan.sparse_mask, gg.ext_gen = plan.ext_gen, gg.level = i, gg.extent = o->extent;
-                gg.sensor = o->extent, gg.sensor_gen = o->sensor_gen, gg.sensor_cutoff = o->sensor_cutoff;
-                gg.rotate = tunables().gn_obj_first ? gg.start[1] : 0;  // (the first model of a batch is the camera model)
-            }
-            for (int j = 0; j < iterations[i]; ++j) {
-                const bool last_l0 = (i == 0 && j == iterations[i] - 1);
-                a.ra = make_residual_args(min_scale, o->dIdx[i], 0, o->dIdy[i], 0, o->last_depth[i], 0,
-                                          o->prep_batched ? o->last_depth[i] : o->next_depth[i], 0, o->last_image[i], 0,
-                                          o->next_image[i], 0, o->corres[i], o->max_depth_delta_rgb, cols, rows,
-                                          last_l0 ? rgb_err_dev : nullptr, 0);
-                a.ra.intr = in;
-                a.ia = odom_icp_args(o, i, last_l0 ? icp_err_dev : nullptr);
-                a.cloud4 = reinterpret_cast<const float4*>(o->cloud4[i]);
-                a.fx = in.fx, a.fy = in.fy, a.sobel_scale = o->sobel_scale;
-                a.intr = in;
-                a.ifx = 1.0 / (double)in.fx, a.ify = 1.0 / (double)in.fy;
-                a.it = it;
-                a.max_polls = (it == 2 && force_fault) ? 0 : kGnMaxPolls;
-                const bool err = last_l0 && (icp_err_dev || rgb_err_dev);
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                if (o->timing >= 2 && o->n_timed < kMaxTimedLaunches) {
-                    e0 = o->ev_kernel[2 * o->n_timed], e1 = o->ev_kernel[2 * o->n_timed + 1];
-                    o->timed_kind[o->n_timed++] = i * 2;
-                }
-#define MMF_GN_LAUNCH(PXV, ERRV)                                                                                              \
-    do {                                                                                                                      \
-        if (mixed && e0)                                                                                                      \
-            hipExtLaunchKernelGGL((gn_iter_mixed_kernel<PXV, ERRV>), dim3(gg.start[kMaxBatch]), dim3(geo.threads), 0, c->stream, \
-                                  e0, e1, 0, o->state, a, bd, gg);                                                            \
-        else if (mixed)                                                                                                       \
-            q.launch((gn_iter_mixed_kernel<PXV, ERRV>), dim3(gg.start[kMaxBatch]), dim3(geo.threads), o->state, a, bd, gg);     \
-        else if (e0)                                                                                                          \
-            hipExtLaunchKernelGGL((gn_iter_kernel<PXV, ERRV>), dim3(groups, ny), dim3(geo.threads), 0, c->stream, e0, e1, 0,      \
-                                  o->state, a, bd);                                                                           \
-        else                                                                                                                  \
-            q.launch((gn_iter_kernel<PXV, ERRV>), dim3(groups, ny), dim3(geo.threads), o->state, a, bd);                       \
-    } while (0)
-                switch (px * 2 + (err ? 1 : 0)) {
-                    case 11: MMF_GN_LAUNCH(5, true); break;
-                    case 10: MMF_GN_LAUNCH(5, false); break;
-                    case 9: MMF_GN_LAUNCH(4, true); break;
-                    case 8: MMF_GN_LAUNCH(4, false); break;
-                    case 5: MMF_GN_LAUNCH(2, true); break;
-                    case 4: MMF_GN_LAUNCH(2, false); break;
-                    case 3: MMF_GN_LAUNCH(1, true); break;
-                    default: MMF_GN_LAUNCH(1, false); break;
-                }
-#undef MMF_GN_LAUNCH
-                MMF_HIP_TRY(hipGetLastError());
-                ++it;
-            }
-        }
-        // the last solve + RGBDOdometry.cpp:464-467: one workgroup per model
-        a.it = it;
-        a.intr = level_intr(o->fx, o->fy, o->cx, o->cy, 0);
-        a.ifx = 1.0 / (double)a.intr.fx, a.ify = 1.0 / (double)a.intr.fy;
-        final_args = a;
-        // the chain's last solve shares a launch with the hand-over of the result to the host (below), unless the chain is
-        // being timed as such (its closing event lies between the two)
-        if (o->timing)
-            q.launch(gn_final_kernel, dim3(ny), dim3(kBlock), o->state, a, bd);
-        else
-            final_pending = true;
-    }
-    bool first_level = true;
-    bool end_folded = fused_chain;  // odom_end ran in the finishing lane of the frame's last rgb_step (or in gn_final_kernel)
-    bool begin_folded = fold_first_level;  // this level's gn_level_begin already ran (in odom_begin_kernel, or in the
-                                           // last rgb_step of the level before)
-    for (int i = MMF_NUM_PYRS - 1; i >= 0 && !fused_chain; --i) {
-        const int cols = o->width >> i, rows = o->height >> i;
-        const LevelIntr in = level_intr(o->fx, o->fy, o->cx, o->cy, i);
-        if (rgb && !o->prep_batched) {  // :332-334
-            MMF_HIP_TRY(q.flush());
-            int rc = launch_project(c, o->last_depth[i], cols, cols, rows, in, o->cloud[i], o->cloud4[i]);
-            if (rc) return rc;
-        }
-        if (!begin_folded)
-            q.launch(gn_level_begin_kernel, dim3(ny), dim3(64), o->state, first_level ? 1 : 0, in, bd,
-                     (first_level && so3_ran_here) ? 1 : 0);
-        first_level = false;
-        begin_folded = false;
-
-        for (int j = 0; j < iterations[i]; ++j) {
-            const bool last_l0 = (i == 0 && j == iterations[i] - 1);
-            int res_records = 0, icp_records = 0;
-            RgbResidualArgs ra;
-            bool res_vec4 = false;
-            if (rgb) {  // :363-371
-                const float min_scale = (float)(std::pow((double)o->min_grad[i], 2.0) / std::pow((double)o->sobel_scale, 2.0));
-                ra = make_residual_args(min_scale, o->dIdx[i], 0, o->dIdy[i], 0, o->last_depth[i], 0,
-                                        o->prep_batched ? o->last_depth[i] : o->next_depth[i], 0,
-                                        o->last_image[i], 0, o->next_image[i], 0, o->corres[i], o->max_depth_delta_rgb,
-                                        cols, rows, last_l0 ? rgb_err_dev : nullptr, 0);
-                ra.intr = in;
-                ra.extent = cull_gen ? o->extent : nullptr, ra.extent_gen = cull_gen, ra.extent_level = i;
-                res_vec4 = residual_vec4_ok(ra);
-                res_records = reduce_grid(cols * rows, res_vec4 ? kBlock * 4 : kBlock);
-            }
-            ChainGeom geom;
-            std::memset(&geom, 0, sizeof(geom));
-            IcpArgs ia;
-            int ipx = 1;
-            if (icp) {
-                ia = odom_icp_args(o, i, last_l0 ? icp_err_dev : nullptr);
-                ipx = std::min(2, icp_max_px(ia, 2));
-            }
-            const bool fuse_producers = rgb && icp && res_vec4 && icp2_fits(ia, kBlock, ipx) &&
-                                        icp_default_variant(cols * rows) / 1000000 != 1;
-            if (fuse_producers) {  // ICP reduction + correspondence pass side by side in one launch
-                icp_records = (cols * rows + kBlock * ipx - 1) / (kBlock * ipx);
-                if (lead_sparse)  // (every model of this launch, then)
-                    res_records = quarter(res_records);
-                else if (foll_sparse)
-                    geom.res_f = (unsigned)quarter(res_records);
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                if (o->timing >= 2 && o->n_timed < kMaxTimedLaunches) {
-                    e0 = o->ev_kernel[2 * o->n_timed], e1 = o->ev_kernel[2 * o->n_timed + 1];
-                    o->timed_kind[o->n_timed++] = i * 2;
-                }
-                if (!e0 && ipx == 2)
-                    q.launch((track_producer_kernel<2, true>), dim3(icp_records + res_records, ny), dim3(kBlock), o->state, ia,
-                             (unsigned)icp_records, ra, o->gn_partials_icp, o->gn_partials_res, bd, geom);
-                else if (!e0)
-                    q.launch((track_producer_kernel<1, true>), dim3(icp_records + res_records, ny), dim3(kBlock), o->state, ia,
-                             (unsigned)icp_records, ra, o->gn_partials_icp, o->gn_partials_res, bd, geom);
-                else if (ipx == 2)
-                    hipExtLaunchKernelGGL((track_producer_kernel<2, true>), dim3(icp_records + res_records, ny), dim3(kBlock), 0,
-                                          c->stream, e0, e1, 0, o->state, ia, (unsigned)icp_records, ra, o->gn_partials_icp,
-                                          o->gn_partials_res, bd, geom);
-                else
-                    hipExtLaunchKernelGGL((track_producer_kernel<1, true>), dim3(icp_records + res_records, ny), dim3(kBlock), 0,
-                                          c->stream, e0, e1, 0, o->state, ia, (unsigned)icp_records, ra, o->gn_partials_icp,
-                                          o->gn_partials_res, bd, geom);
-                MMF_HIP_TRY(hipGetLastError());
-            } else {
-                MMF_REQUIRE(ny == 1, "odom_enqueue_tracking: this level cannot be batched");
-                MMF_HIP_TRY(q.flush());
-                if (rgb) {
-                    if (res_vec4)
-                        hipLaunchKernelGGL((rgb_residual_kernel<FINISH_GN, 4>), dim3(res_records), dim3(kBlock), 0,
-                                           c->stream, o->state, ra, o->gn_partials_res);
-                    else
-                        hipLaunchKernelGGL((rgb_residual_kernel<FINISH_GN, 1>), dim3(res_records), dim3(kBlock), 0,
-                                           c->stream, o->state, ra, o->gn_partials_res);
-                    MMF_HIP_TRY(hipGetLastError());
-                }
-                if (icp) {  // :403-410
-                    MMF_HIP_TRY(launch_icp<FINISH_GN>(c, o->state, ia, 0, &icp_records, o->gn_partials_icp));
-                    if (!rgb) {  // ICP-only tracking: one workgroup sums the records, solves, updates the pose
-                        hipLaunchKernelGGL((icp_finish_kernel<FINISH_GN>), dim3(1), dim3(256), 0, c->stream, o->state,
-                                           o->gn_partials_icp, (unsigned)icp_records, in);
-                        MMF_HIP_TRY(hipGetLastError());
-                    }
-                }
-            }
-            if (rgb) {  // :418-423, then :425-460 in the finishing workgroup
-                RgbStepArgs a;
-                a.residual_partials = o->gn_partials_res;
-                a.residual_records = (unsigned)res_records;
-                a.icp_partials = o->gn_partials_icp;
-                a.icp_records = (unsigned)icp_records;
-                a.corres = o->corres[i];
-                a.cloud = nullptr, a.cloud4 = reinterpret_cast<const float4*>(o->cloud4[i]);
-                a.fx = in.fx;
-                a.fy = in.fy;
-                a.dIdx = o->dIdx[i];
-                a.dIdy = o->dIdy[i];
-                a.d_stride = cols;
-                a.sobel_scale = o->sobel_scale;
-                a.cols = cols;
-                a.rows = rows;
-                a.cols_magic = ra.cols_magic;
-                a.intr = in;
-                a.extent = ra.extent, a.extent_gen = ra.extent_gen, a.extent_level = ra.extent_level;
-                // the last step of a level also does the next level's gn_level_begin (one launch less per
-                // level).  Not with rgbOnly: its divergence `break` skips the finishing lane.
-                a.next_level = 0;
-                a.final_step = (last_l0 && !rgb_only) ? 1 : 0;  // odom_end in the finishing lane (which rgbOnly's `break` skips)
-                end_folded = a.final_step != 0;
-                if (j == iterations[i] - 1 && i > 0 && iterations[i - 1] > 0 && !rgb_only) {
-                    a.next_level = 1;
-                    a.intr = level_intr(o->fx, o->fy, o->cx, o->cy, i - 1);  // only read by the finishing lane's rgb_prepare
-                    begin_folded = true;
-                }
-                int grid = reduce_grid(cols * rows, kBlock * 4);  // width, height are multiples of 4
-                if (fuse_producers && lead_sparse)
-                    grid = quarter(grid);
-                else if (fuse_producers && foll_sparse)
-                    geom.step_f = (unsigned)quarter(grid);
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                if (o->timing >= 2 && o->n_timed < kMaxTimedLaunches) {
-                    e0 = o->ev_kernel[2 * o->n_timed], e1 = o->ev_kernel[2 * o->n_timed + 1];
-                    o->timed_kind[o->n_timed++] = i * 2 + 1;
-                }
-                if (!e0 && res_vec4)  // the 4-pixel correspondence pass wrote compact records
-                    q.launch((rgb_step_kernel<FINISH_GN, 4, true>), dim3(grid, ny), dim3(kBlock), o->state, a, o->gn_partials_f,
-                             o->gn_ticket, bd, geom);
-                else if (!e0)
-                    q.launch((rgb_step_kernel<FINISH_GN, 4, false>), dim3(grid, ny), dim3(kBlock), o->state, a, o->gn_partials_f,
-                             o->gn_ticket, bd, geom);
-                else if (res_vec4)
-                    hipExtLaunchKernelGGL((rgb_step_kernel<FINISH_GN, 4, true>), dim3(grid, ny), dim3(kBlock), 0, c->stream, e0, e1,
-                                          0, o->state, a, o->gn_partials_f, o->gn_ticket, bd, geom);
-                else
-                    hipExtLaunchKernelGGL((rgb_step_kernel<FINISH_GN, 4, false>), dim3(grid, ny), dim3(kBlock), 0, c->stream, e0,
-                                          e1, 0, o->state, a, o->gn_partials_f, o->gn_ticket, bd, geom);
-                MMF_HIP_TRY(hipGetLastError());
-            }
-        }
-    }
-
-    if (!end_folded) q.launch(odom_end_kernel, dim3(ny), dim3(64), o->state, bd);
-    MMF_HIP_TRY(q.flush());
-    if (o->timing) MMF_HIP_TRY(hipEventRecord(o->ev_chain[1], c->stream));
-    PublishTargets to;
-    std::memset(&to, 0, sizeof(to));
-    const unsigned seq = ++o->publish_seq;
-    for (unsigned m = 0; m < ny; ++m) {  // every model's result towards the host, on the chain's stream
-        mmf_odom* om = batch ? batch->o[m] : o;
-        to.host[m] = om->host_result_dev;
-        om->publish_seq = seq;
-        // a follower of a batch takes the LEADER's counter: whatever its own earlier chains left in the pinned flag, it is not
-        // this chain's number before this chain has written it
-        om->host_result->publish_seq = ~seq;
-        om->pending_icp = icp, om->pending_so3 = so3 != 0;
-        om->track_stream = c->stream;
-        om->result_of = o;
-        if (om != o) om->so3_prefetched = false;
-        // the image ring (:469-473).  Host bookkeeping only -- the launches above hold their pointers by value -- and
-        // done here rather than when the result is picked up, so that the next frame's sensor-side preparation can be
-        // enqueued while this chain runs
-        if (so3)
-            for (int i = 0; i < MMF_NUM_PYRS; ++i) std::swap(om->last_next_image[i], om->next_image[i]);
-    }
-    o->rider = FrameRider();
-    if (final_pending && o->defer_publish && ny == 1) {
-        hipLaunchKernelGGL(gn_final_kernel, dim3(ny), dim3(kBlock), 0, c->stream, o->state, final_args, bd);
-        o->rider.st = o->state, o->rider.host = o->host_result_dev, o->rider.seq = seq;
-    } else if (final_pending)
-        hipLaunchKernelGGL(gn_final_publish_kernel, dim3(ny), dim3(kBlock), 0, c->stream, o->state, final_args, bd, to, seq);
-    else
-        hipLaunchKernelGGL(odom_publish_kernel, dim3(ny), dim3(128), 0, c->stream, o->state, to, seq, bd);
-    MMF_HIP_TRY(hipGetLastError());
-    return MMF_OK;
-}
-
-// can several models ride one chain (every level on the fused producer path)?  Same tests as the loop above.
-static bool odom_batchable(mmf_odom* o, int rgb_only, float icp_weight, int pyramid, int fast_odom) {
-    const bool icp = !rgb_only && icp_weight > 0, rgb = rgb_only || icp_weight < 100;
-    if (!icp || !rgb || rgb_only || !o->prep_batched || icp_default_variant(0) / 1000000 == 1) return false;
-    const int iterations[MMF_NUM_PYRS] = {fast_odom ? 3 : 10, pyramid ? 5 : 0, pyramid ? 4 : 0};
-    for (int i = 0; i < MMF_NUM_PYRS; ++i) {
-        if (!iterations[i]) continue;
-        const int cols = o->width >> i, rows = o->height >> i;
-        RgbResidualArgs ra = make_residual_args(1.f, o->dIdx[i], 0, o->dIdy[i], 0, o->last_depth[i], 0, o->last_depth[i], 0,
-                                                o->last_image[i], 0, o->next_image[i], 0, o->corres[i], o->max_depth_delta_rgb,
-                                                cols, rows, nullptr, 0);
-        IcpArgs ia = odom_icp_args(o, i, nullptr);
-        if (!residual_vec4_ok(ra) || !icp2_fits(ia, kBlock, std::min(2, icp_max_px(ia, 2)))) return false;
+// can several models ride one chain (every level on the fused producer path)?  Same tests as the two-launch chain.
+static bool odom_batchable(mmf_odom* o, const TrackMode& tm) {
+    if (!tm.icp || !tm.rgb || tm.rgb_only || !o->prep_batched) return false;
+    for (int i = 0; i <= tm.first_iter_level; ++i) {
+        const LevelArgs l = odom_level_args(o, i, nullptr, nullptr);
+        if (!residual_vec4_ok(l.ra) || !icp2_fits(l.ia, kBlock, std::min(2, icp_max_px(l.ia, 2)))) return false;
     }
     return true;
 }
@@ -2086,47 +1744,42 @@ extern "C" int mmf_gn_chain_status(int* recoveries, int* one_launch_chain_in_use
     if (one_launch_chain_in_use) *one_launch_chain_in_use = g_gn_latched_off.load() ? 0 : 1;
     return MMF_OK;
 }
-static unsigned fused_max_models() {  // MMF_GN_FUSED_MAX: up to how many models one one-launch chain carries
-    return (unsigned)tunables().gn_fused_max;
+// the smaller occupancy of a launch shape's two variants (with and without the error images) bounds the chain
+template <typename K>
+static int gn_occupancy(K with_err, K without_err, int threads) {
+    int nb = 0, nb2 = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, with_err, threads, 0);
+    const hipError_t e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb2, without_err, threads, 0);
+    if (e != hipSuccess || e2 != hipSuccess) return (void)hipGetLastError(), 0;
+    return std::min(nb, nb2);
 }
-// How many workgroups of gn_iter_kernel<px, .> with `threads` threads the device holds at once: the occupancy the runtime
-// reports for the kernel (registers, LDS) x the compute units.  The launch spins on its own workgroups (count barrier), so a
-// grid beyond this could only time out; such sizes, partitioned or smaller devices take the two-launch chain.
-static long long gn_resident_groups(mmf_ctx* c, int px, int threads, bool mixed = false) {
+// How many workgroups of gn_iter_kernel<px, .> (mixed: gn_iter_mixed_kernel) with `threads` threads the device holds at once:
+// the occupancy the runtime reports for the kernel (registers, LDS) x the compute units.  The launch spins on its own
+// workgroups (count barrier), so a grid beyond this could only time out; such sizes, partitioned or smaller devices take the
+// two-launch chain.
+static long long gn_resident_groups(mmf_ctx* c, int px, bool mixed, int threads) {
     static std::mutex mu;
-    static std::map<std::pair<int, int>, int> per_cu;
+    static std::map<std::tuple<int, bool, int>, int> per_cu;
     std::lock_guard<std::mutex> lock(mu);
-    const auto key = std::make_pair(px + (mixed ? 100 : 0), threads);
+    const auto key = std::make_tuple(px, mixed, threads);
     auto it = per_cu.find(key);
     if (it == per_cu.end()) {
-        int nb = 0, nb2 = 0;
-        hipError_t e = hipErrorInvalidValue, e2 = hipSuccess;
-        switch (px + (mixed ? 100 : 0)) {  // (both variants of a launch shape: the smaller occupancy bounds the chain)
-#define MMF_OCC(PXV, KERNEL)                                                                                  \
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, KERNEL<PXV, true>, threads, 0);                  \
-    e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb2, KERNEL<PXV, false>, threads, 0);               \
-    break
-            case 5: MMF_OCC(5, gn_iter_kernel);
-            case 4: MMF_OCC(4, gn_iter_kernel);
-            case 2: MMF_OCC(2, gn_iter_kernel);
-            case 1: MMF_OCC(1, gn_iter_kernel);
-            case 105: MMF_OCC(5, gn_iter_mixed_kernel);
-            case 104: MMF_OCC(4, gn_iter_mixed_kernel);
-            case 102: MMF_OCC(2, gn_iter_mixed_kernel);
-            case 101: MMF_OCC(1, gn_iter_mixed_kernel);
-#undef MMF_OCC
-            default: break;
-        }
-        if (e2 != hipSuccess) e = e2;
-        nb = std::min(nb, nb2);
-        if (e != hipSuccess) nb = 0, (void)hipGetLastError();
+        const int nb = with_gn_px(px, [&](auto PX) {
+            constexpr int P = decltype(PX)::value;
+            return mixed ? gn_occupancy(gn_iter_mixed_kernel<P, true>, gn_iter_mixed_kernel<P, false>, threads)
+                         : gn_occupancy(gn_iter_kernel<P, true>, gn_iter_kernel<P, false>, threads);
+        });
         it = per_cu.emplace(key, nb).first;
     }
     return (long long)it->second * c->cu_count;
 }
-static bool odom_fused_chain_ok(mmf_odom* o, int rgb_only, float icp_weight, int pyramid, int fast_odom, const TrackBatch* batch,
-                                bool sparse_on, GnChainPlan* plan) {
+// The chain's plan for o (batch: the models riding with it, o first).  sparse_on: object models may be walked by their extents.
+static GnChainPlan odom_plan_chain(mmf_odom* o, const TrackMode& tm, const TrackBatch* batch, bool sparse_on) {
     const int models = batch ? batch->n : 1;
+    const int forced = g_gn_fused.load();
+    const bool enabled = (forced < 0 ? tunables().gn_fused : forced != 0) && o->exclusive_chain && !g_gn_latched_off.load();
+    // (more than MMF_GN_FUSED_MAX models: the batched two-launch chain)
+    if (!enabled || !tm.icp || !tm.rgb || tm.rgb_only || models > tunables().gn_fused_max) return GnChainPlan();
     // the models walked by their extents: object models whose preparation noted extents for THIS frame (one number for all)
     GnChainPlan pl;
     for (int m = 0; m < models && sparse_on; ++m) {
@@ -2135,34 +1788,349 @@ static bool odom_fused_chain_ok(mmf_odom* o, int rgb_only, float icp_weight, int
         if (pl.ext_gen == 0) pl.ext_gen = om->extent_gen;
         if (om->extent_gen == pl.ext_gen) pl.sparse_mask |= 1u << m;
     }
-    const bool env_enabled = tunables().gn_fused;
-    const int forced = g_gn_fused.load();
-    const bool enabled = (forced < 0 ? env_enabled : forced != 0) && o->exclusive_chain && !g_gn_latched_off.load();
-    const bool icp = !rgb_only && icp_weight > 0, rgb = rgb_only || icp_weight < 100;
-    if (!enabled || !icp || !rgb || rgb_only) return false;
-    const int iterations[MMF_NUM_PYRS] = {fast_odom ? 3 : 10, pyramid ? 5 : 0, pyramid ? 4 : 0};
-    for (int i = 0; i < MMF_NUM_PYRS; ++i) {
-        if (!iterations[i]) continue;
-        const int cols = o->width >> i, rows = o->height >> i;
-        RgbResidualArgs ra = make_residual_args(1.f, o->dIdx[i], 0, o->dIdy[i], 0, o->last_depth[i], 0,
-                                                o->prep_batched ? o->last_depth[i] : o->next_depth[i], 0, o->last_image[i], 0,
-                                                o->next_image[i], 0, o->corres[i], o->max_depth_delta_rgb, cols, rows, o->rgb_err, 0);
-        IcpArgs ia = odom_icp_args(o, i, o->icp_err);
-        if (!residual_vec4_ok(ra) || icp_max_px(ia, 4) != 4 || !ia.prev_packed) return false;
-        GnGeometry geo;
-        if (!gn_geometry(i, cols, rows, &geo, pl.sparse_mask != 0)) return false;
+    pl.mixed = pl.sparse_mask != 0;
+    for (int i = 0; i <= tm.first_iter_level; ++i) {
+        const LevelArgs l = odom_level_args(o, i, o->rgb_err, o->icp_err);
+        if (!residual_vec4_ok(l.ra) || icp_max_px(l.ia, 4) != 4 || !l.ia.prev_packed) return GnChainPlan();
+        GnGeometry& geo = pl.geo[i];
+        if (!gn_geometry(i, l.cols, l.rows, &geo, pl.mixed)) return GnChainPlan();
         // the count barrier inside the launch needs every workgroup of it resident at once
-        if (geo.lanes > kGnSparseLanes) pl.sparse_mask = 0;  // (the sparse walk keeps a workgroup's correspondences in LDS: sized for 256 lanes)
         long long total = 0;
         for (int m = 0; m < models; ++m) {
             const mmf_odom* om = batch ? batch->o[m] : o;
             pl.groups[i][m] = ((pl.sparse_mask >> m) & 1u) ? gn_sparse_groups(i, geo.groups, om->gn_need[i], geo.lanes) : geo.groups;
             total += pl.groups[i][m];
         }
-        if (total > gn_resident_groups(o->ctx, geo.px, geo.threads, pl.sparse_mask != 0)) return false;
+        if (total > gn_resident_groups(o->ctx, geo.px, pl.mixed, geo.threads)) return GnChainPlan();
     }
-    if (plan) *plan = pl;
-    return true;
+    pl.one_launch = true;
+    return pl;
+}
+
+// The models one call tracks and what both forms of the chain need to know about them, worked out once.
+// Object models (extent.hpp): in the two-launch chain (track_kernels.hpp: ChainGeom) their passes skip what lies outside
+// the model's own depth when the preparation noted its extents for this frame, and they walk their images with a
+// quarter of the workgroups; in the one-launch chain (gn_fused.hpp: gn_iter_mixed_kernel) they walk their extents with a
+// fraction of the workgroups, which is what lets ALL models of a frame be resident in one launch.
+// MMF_TRACK_CULL=0 / mmf_debug_set_track_cull(0): every model like the first.
+struct ChainCall {
+    mmf_odom* o;  // the leader
+    const TrackBatch* batch;
+    TrackMode tm;
+    unsigned ny;  // models
+    BatchDelta bd;
+    BeginPoses poses;
+    float *icp_err, *rgb_err;  // the error images the last level-0 iteration writes (null: none)
+    bool sparse_on, lead_sparse, foll_sparse;
+    unsigned cull_gen;     // the extents the two-launch chain's passes skip by (0: none)
+    bool two_launch_once;  // (odom_retrack_prepare: this frame is being tracked again)
+    bool so3_ran_here;     // the SO3 loop runs in the chain, in the leader's state: shared with the others at the first level begin
+
+    mmf_odom* model(unsigned m) const { return batch ? batch->o[m] : o; }
+};
+static ChainCall odom_chain_call(mmf_odom* o, const TrackMode& tm, const TrackBatch* batch, float* icp_err, float* rgb_err) {
+    ChainCall x;
+    x.o = o, x.batch = batch, x.tm = tm;
+    x.ny = batch ? (unsigned)batch->n : 1u;
+    std::memset(&x.bd, 0, sizeof(x.bd));
+    std::memset(&x.poses, 0, sizeof(x.poses));
+    if (batch) x.bd = batch->bd, x.poses = batch->poses;
+    x.icp_err = icp_err, x.rgb_err = rgb_err;
+    x.two_launch_once = false;
+    for (unsigned m = 0; m < x.ny; ++m) {
+        x.two_launch_once = x.two_launch_once || x.model(m)->two_launch_once;
+        x.model(m)->two_launch_once = false;
+    }
+    x.sparse_on = odom_sparse_on();
+    x.lead_sparse = x.sparse_on && o->sparse;
+    x.foll_sparse = x.sparse_on && batch && x.ny > 1;
+    unsigned foll_gen = x.foll_sparse ? batch->o[1]->extent_gen : 0u;
+    for (unsigned m = 1; m < x.ny && x.foll_sparse; ++m) {
+        x.foll_sparse = batch->o[m]->sparse;
+        if (batch->o[m]->extent_gen != foll_gen) foll_gen = 0u;
+    }
+    if (!x.foll_sparse) foll_gen = 0u;
+    // (the kernels drop the first model's extent in a batch; a sparse model tracked alone keeps its own)
+    x.cull_gen = x.ny > 1 ? foll_gen : (x.lead_sparse ? o->extent_gen : 0u);
+    x.so3_ran_here = tm.so3 && !o->so3_prefetched;
+    return x;
+}
+
+// measurement mode 2: the next event pair of o's chain for a launch of `kind` (level * 2 + 0 producer | 1 rgb_step)
+static TimedSlot odom_timed_slot(mmf_odom* o, int kind) {
+    if (o->timing < 2 || o->n_timed >= kMaxTimedLaunches) return TimedSlot{};
+    const int k = o->n_timed++;
+    o->timed_kind[k] = kind;
+    return TimedSlot{o->ev_kernel[2 * k], o->ev_kernel[2 * k + 1]};
+}
+
+// What a chain leaves to odom_chain_publish.
+struct ChainTail {
+    bool end_folded = false;     // odom_end ran in the finishing lane of the frame's last rgb_step (or in gn_final_kernel)
+    bool final_pending = false;  // the one-launch chain's last solve (final_args) shares a launch with the hand-over
+    GnIterArgs final_args;
+};
+
+// begin: the derivatives (unless the batched preparation wrote them), odom_begin_kernel (unless it rode the preparation:
+// odom_begin_rider), the SO3 loop (:239-310)
+static int odom_chain_begin(const ChainCall& x, const float trans[3], const float rot[9], bool one_launch, Enqueuer& q) {
+    mmf_odom* o = x.o;
+    mmf_ctx* c = o->ctx;
+    if (x.tm.rgb && !o->prep_batched)
+        for (int i = 0; i < MMF_NUM_PYRS; ++i) {  // :230-235
+            int rc = launch_derivative(c, o->next_image[i], o->width >> i, o->width >> i, o->height >> i, o->dIdx[i],
+                                       o->width >> i, o->dIdy[i], o->width >> i);
+            if (rc) return rc;
+        }
+    const BeginArgs b = odom_begin_args(o, trans, rot, x.tm, o->so3_prefetched, o->so3_stage, one_launch);
+    o->n_timed = 0;
+    if (o->timing) MMF_HIP_TRY(hipEventRecord(o->ev_chain[0], c->stream));
+    // from here to the last step: kernels only, enqueued one by one in call order (Enqueuer keeps the first error)
+    // (the beginning may have run already, on the last launch of the preparation enqueued ahead of this frame: odom_begin_rider)
+    const bool begun = o->begin_spec_valid && o->begin_spec_ok && !x.batch && std::memcmp(&b, &o->begin_spec, sizeof(b)) == 0;
+    o->begin_spec_valid = o->begin_spec_ok = false;
+    if (!begun)
+        q.launch(odom_begin_kernel, dim3(x.ny), dim3(64), o->state, b, x.bd, x.poses);
+    else
+        odom_begin_rider_used();
+    o->retry_so3_prefetched = o->so3_prefetched, o->retry_so3_stage = o->so3_stage;  // (odom_retrack_prepare)
+    if (x.so3_ran_here) {
+        int rc = odom_enqueue_so3(o, q);
+        if (rc) return rc;
+    }
+    o->so3_prefetched = false;
+    o->so3_stage = nullptr;
+    return MMF_OK;
+}
+
+// both terms on and every level fits: ONE launch per iteration (gn_fused.hpp) instead of producer + step, at the plan's
+// geometry.  (More than three models: the batched two-launch chain is as fast (four) or faster -- 8 models 1.40 ms against
+// 1.60 -- because a model's workgroups hold their CUs at the count barrier while the next models' wait for a place.)
+static int odom_one_launch_chain(const ChainCall& x, const GnChainPlan& plan, Enqueuer& q, ChainTail* tail) {
+    mmf_odom* o = x.o;
+    GnIterArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.poll_sleep = tunables().gn_sleep;
+    a.max_polls = kGnMaxPolls;
+    a.check_sparse = g_sparse_check.load();
+    bool force_fault = false;
+    for (int n = g_gn_force_fault.load(); n > 0 && !force_fault;) force_fault = g_gn_force_fault.compare_exchange_weak(n, n - 1);
+    int it = 0;
+    for (int i = x.tm.first_iter_level; i >= 0; --i) {
+        const LevelArgs l = odom_level_args(o, i, nullptr, nullptr);
+        LevelArgs last = l;  // the last level-0 iteration also writes the error images
+        last.ra.err_map = x.rgb_err, last.ia.err_map = x.icp_err;
+        if (!o->prep_batched) {  // :332-334
+            MMF_HIP_TRY(q.flush());
+            int rc = launch_project(o->ctx, o->last_depth[i], l.cols, l.cols, l.rows, l.in, o->cloud[i], o->cloud4[i]);
+            if (rc) return rc;
+        }
+        if (i == x.tm.first_iter_level && x.so3_ran_here)  // the SO3 loop ran in between: seed resultRt from its result now
+            q.launch(gn_level_begin_kernel, dim3(x.ny), dim3(64), o->state, 1, l.in, x.bd, 1);
+        const GnGeometry& geo = plan.geo[i];
+        a.lanes = geo.lanes;
+        a.cloud4 = reinterpret_cast<const float4*>(o->cloud4[i]);
+        a.fx = l.in.fx, a.fy = l.in.fy, a.sobel_scale = o->sobel_scale;
+        a.intr = l.in;
+        a.ifx = 1.0 / (double)l.in.fx, a.ify = 1.0 / (double)l.in.fy;
+        // object models walked by their extents: one one-dimensional grid, a geometry per model (GnBatchGeom)
+        GnBatchGeom gg;
+        std::memset(&gg, 0, sizeof(gg));
+        if (plan.mixed) {
+            for (unsigned m = 0; m < (unsigned)kMaxBatch; ++m) gg.start[m + 1] = gg.start[m] + (m < x.ny ? plan.groups[i][m] : 0);
+            gg.sparse_mask = plan.sparse_mask, gg.ext_gen = plan.ext_gen, gg.level = i, gg.extent = o->extent;
+            gg.sensor = o->extent, gg.sensor_gen = o->sensor_gen, gg.sensor_cutoff = o->sensor_cutoff;
+            gg.rotate = gg.start[1];  // the object models' workgroups first (the first model of a batch is the camera model)
+        }
+        for (int j = 0; j < x.tm.iterations[i]; ++j) {
+            const bool last_l0 = (i == 0 && j == x.tm.iterations[i] - 1);
+            a.ra = last_l0 ? last.ra : l.ra;
+            a.ia = last_l0 ? last.ia : l.ia;
+            a.it = it;
+            a.max_polls = (it == 2 && force_fault) ? 0 : kGnMaxPolls;
+            const bool err = last_l0 && (x.icp_err || x.rgb_err);
+            const TimedSlot slot = odom_timed_slot(o, i * 2);
+            with_gn_px(geo.px, [&](auto PX) {
+                constexpr int P = decltype(PX)::value;
+                if (plan.mixed)
+                    q.launch(slot, err ? gn_iter_mixed_kernel<P, true> : gn_iter_mixed_kernel<P, false>, dim3(gg.start[kMaxBatch]),
+                             dim3(geo.threads), o->state, a, x.bd, gg);
+                else
+                    q.launch(slot, err ? gn_iter_kernel<P, true> : gn_iter_kernel<P, false>, dim3(geo.groups, x.ny), dim3(geo.threads),
+                             o->state, a, x.bd);
+            });
+            ++it;
+        }
+    }
+    // the last solve + RGBDOdometry.cpp:464-467: one workgroup per model
+    a.it = it;
+    a.intr = level_intr(o->fx, o->fy, o->cx, o->cy, 0);
+    a.ifx = 1.0 / (double)a.intr.fx, a.ify = 1.0 / (double)a.intr.fy;
+    tail->end_folded = true;
+    // the chain's last solve shares a launch with the hand-over of the result to the host (odom_chain_publish), unless the
+    // chain is being timed as such (its closing event lies between the two)
+    if (o->timing)
+        q.launch(gn_final_kernel, dim3(x.ny), dim3(kBlock), o->state, a, x.bd);
+    else
+        tail->final_pending = true, tail->final_args = a;
+    return MMF_OK;
+}
+
+// producer (ICP reduction + correspondence pass, or the two apart) + rgb_step per iteration
+static int odom_two_launch_chain(const ChainCall& x, Enqueuer& q, ChainTail* tail) {
+    mmf_odom* o = x.o;
+    const TrackMode& tm = x.tm;
+    auto quarter = [](int full) { return std::max(std::min(full, 32), (full + 3) / 4); };
+    bool begin_folded = !x.so3_ran_here;  // this level's gn_level_begin already ran (in odom_begin_kernel, or in the
+                                          // last rgb_step of the level before)
+    for (int i = MMF_NUM_PYRS - 1; i >= 0; --i) {
+        const bool first_level = i == MMF_NUM_PYRS - 1;
+        const int cols = o->width >> i, rows = o->height >> i;
+        const LevelIntr in = level_intr(o->fx, o->fy, o->cx, o->cy, i);
+        if (tm.rgb && !o->prep_batched) {  // :332-334
+            MMF_HIP_TRY(q.flush());
+            int rc = launch_project(o->ctx, o->last_depth[i], cols, cols, rows, in, o->cloud[i], o->cloud4[i]);
+            if (rc) return rc;
+        }
+        if (!begin_folded)
+            q.launch(gn_level_begin_kernel, dim3(x.ny), dim3(64), o->state, first_level ? 1 : 0, in, x.bd,
+                     (first_level && x.so3_ran_here) ? 1 : 0);
+        begin_folded = false;
+        if (!tm.iterations[i]) continue;
+
+        LevelArgs l = odom_level_args(o, i, nullptr, nullptr);
+        l.ra.extent = x.cull_gen ? o->extent : nullptr, l.ra.extent_gen = x.cull_gen, l.ra.extent_level = i;
+        LevelArgs last = l;  // the last level-0 iteration also writes the error images
+        last.ra.err_map = x.rgb_err, last.ia.err_map = x.icp_err;
+        RgbStepArgs step;  // :418-423, then :425-460 in the finishing workgroup
+        step.residual_partials = o->gn_partials_res;
+        step.icp_partials = o->gn_partials_icp;
+        step.corres = o->corres[i];
+        step.cloud = nullptr, step.cloud4 = reinterpret_cast<const float4*>(o->cloud4[i]);
+        step.fx = in.fx;
+        step.fy = in.fy;
+        step.dIdx = o->dIdx[i];
+        step.dIdy = o->dIdy[i];
+        step.d_stride = cols;
+        step.sobel_scale = o->sobel_scale;
+        step.cols = cols;
+        step.rows = rows;
+        step.cols_magic = l.ra.cols_magic;
+        step.extent = l.ra.extent, step.extent_gen = l.ra.extent_gen, step.extent_level = l.ra.extent_level;
+
+        for (int j = 0; j < tm.iterations[i]; ++j) {
+            const bool last_l0 = (i == 0 && j == tm.iterations[i] - 1);
+            const RgbResidualArgs& ra = last_l0 ? last.ra : l.ra;
+            const IcpArgs& ia = last_l0 ? last.ia : l.ia;
+            const bool res_vec4 = tm.rgb && residual_vec4_ok(ra);
+            int res_records = tm.rgb ? reduce_grid(cols * rows, res_vec4 ? kBlock * 4 : kBlock) : 0, icp_records = 0;
+            const int ipx = tm.icp ? std::min(2, icp_max_px(ia, 2)) : 1;
+            ChainGeom geom;
+            std::memset(&geom, 0, sizeof(geom));
+            const bool fuse_producers = tm.rgb && tm.icp && res_vec4 && icp2_fits(ia, kBlock, ipx);
+            if (fuse_producers) {  // ICP reduction + correspondence pass side by side in one launch
+                icp_records = (cols * rows + kBlock * ipx - 1) / (kBlock * ipx);
+                if (x.lead_sparse)  // (every model of this launch, then)
+                    res_records = quarter(res_records);
+                else if (x.foll_sparse)
+                    geom.res_f = (unsigned)quarter(res_records);
+                q.launch(odom_timed_slot(o, i * 2), ipx == 2 ? track_producer_kernel<2, true> : track_producer_kernel<1, true>,
+                         dim3(icp_records + res_records, x.ny), dim3(kBlock), o->state, ia, (unsigned)icp_records, ra,
+                         o->gn_partials_icp, o->gn_partials_res, x.bd, geom);
+            } else {
+                MMF_REQUIRE(x.ny == 1, "odom_enqueue_tracking: this level cannot be batched");
+                if (tm.rgb)
+                    q.launch(res_vec4 ? rgb_residual_kernel<FINISH_GN, 4> : rgb_residual_kernel<FINISH_GN, 1>, dim3(res_records),
+                             dim3(kBlock), o->state, ra, o->gn_partials_res);
+                if (tm.icp) {  // :403-410
+                    icp_records = launch_icp<FINISH_GN>(q, o->state, ia, o->gn_partials_icp);
+                    if (!tm.rgb)  // ICP-only tracking: one workgroup sums the records, solves, updates the pose
+                        q.launch(icp_finish_kernel<FINISH_GN>, dim3(1), dim3(256), o->state, o->gn_partials_icp,
+                                 (unsigned)icp_records, in);
+                }
+            }
+            if (!tm.rgb) continue;
+            RgbStepArgs a = step;
+            a.residual_records = (unsigned)res_records;
+            a.icp_records = (unsigned)icp_records;
+            a.intr = in;
+            // the last step of a level also does the next level's gn_level_begin (one launch less per
+            // level).  Not with rgbOnly: its divergence `break` skips the finishing lane.
+            a.next_level = 0;
+            a.final_step = (last_l0 && !tm.rgb_only) ? 1 : 0;  // odom_end in the finishing lane (which rgbOnly's `break` skips)
+            tail->end_folded = a.final_step != 0;
+            if (j == tm.iterations[i] - 1 && i > 0 && tm.iterations[i - 1] > 0 && !tm.rgb_only) {
+                a.next_level = 1;
+                a.intr = level_intr(o->fx, o->fy, o->cx, o->cy, i - 1);  // only read by the finishing lane's rgb_prepare
+                begin_folded = true;
+            }
+            int grid = reduce_grid(cols * rows, kBlock * 4);  // width, height are multiples of 4
+            if (fuse_producers && x.lead_sparse)
+                grid = quarter(grid);
+            else if (fuse_producers && x.foll_sparse)
+                geom.step_f = (unsigned)quarter(grid);
+            // (the 4-pixel correspondence pass wrote compact records)
+            q.launch(odom_timed_slot(o, i * 2 + 1), res_vec4 ? rgb_step_kernel<FINISH_GN, 4, true> : rgb_step_kernel<FINISH_GN, 4, false>,
+                     dim3(grid, x.ny), dim3(kBlock), o->state, a, o->gn_partials_f, o->gn_ticket, x.bd, geom);
+        }
+    }
+    return MMF_OK;
+}
+
+// publish: the end kernel, every model's result towards the host on the chain's stream, the image ring
+static int odom_chain_publish(const ChainCall& x, Enqueuer& q, const ChainTail& tail) {
+    mmf_odom* o = x.o;
+    if (!tail.end_folded) q.launch(odom_end_kernel, dim3(x.ny), dim3(64), o->state, x.bd);
+    MMF_HIP_TRY(q.flush());
+    if (o->timing) MMF_HIP_TRY(hipEventRecord(o->ev_chain[1], o->ctx->stream));
+    PublishTargets to;
+    std::memset(&to, 0, sizeof(to));
+    const unsigned seq = ++o->publish_seq;
+    for (unsigned m = 0; m < x.ny; ++m) {
+        mmf_odom* om = x.model(m);
+        to.host[m] = om->host_result_dev;
+        om->publish_seq = seq;
+        // a follower of a batch takes the LEADER's counter: whatever its own earlier chains left in the pinned flag, it is not
+        // this chain's number before this chain has written it
+        om->host_result->publish_seq = ~seq;
+        om->pending_icp = x.tm.icp, om->pending_so3 = x.tm.so3;
+        om->track_stream = o->ctx->stream;
+        om->result_of = o;
+        if (om != o) om->so3_prefetched = false;
+        // the image ring (:469-473).  Host bookkeeping only -- the launches above hold their pointers by value -- and
+        // done here rather than when the result is picked up, so that the next frame's sensor-side preparation can be
+        // enqueued while this chain runs
+        if (x.tm.so3)
+            for (int i = 0; i < MMF_NUM_PYRS; ++i) std::swap(om->last_next_image[i], om->next_image[i]);
+    }
+    o->rider = FrameRider();
+    if (tail.final_pending && o->defer_publish && x.ny == 1) {
+        q.launch(gn_final_kernel, dim3(x.ny), dim3(kBlock), o->state, tail.final_args, x.bd);
+        o->rider.st = o->state, o->rider.host = o->host_result_dev, o->rider.seq = seq;
+    } else if (tail.final_pending) {
+        q.launch(gn_final_publish_kernel, dim3(x.ny), dim3(kBlock), o->state, tail.final_args, x.bd, to, seq);
+    } else {
+        q.launch(odom_publish_kernel, dim3(x.ny), dim3(128), o->state, to, seq, x.bd);
+    }
+    MMF_HIP_TRY(q.flush());
+    return MMF_OK;
+}
+
+static int odom_enqueue_tracking(mmf_odom* o, const float trans[3], const float rot[9], const TrackMode& tm, float* icp_err_dev,
+                                 float* rgb_err_dev, const TrackBatch* batch = nullptr) {
+    MMF_HIP_TRY(hipSetDevice(o->ctx->device));
+#ifdef MMF_STAMPS  // (diagnostic builds: MMF_DBG_NO_ERR=1 leaves the error images out, so that a chain's last launch is an ordinary one)
+    if (std::getenv("MMF_DBG_NO_ERR")) icp_err_dev = rgb_err_dev = nullptr;
+#endif
+    MMF_REQUIRE(!batch || batch->n == 1 || odom_batchable(o, tm), "odom_enqueue_tracking: not batchable");
+    const ChainCall x = odom_chain_call(o, tm, batch, icp_err_dev, rgb_err_dev);
+    const GnChainPlan plan = x.two_launch_once ? GnChainPlan() : odom_plan_chain(o, tm, batch, x.sparse_on);
+    for (unsigned m = 0; m < x.ny; ++m) x.model(m)->walked_by_extent = plan.one_launch && ((plan.sparse_mask >> m) & 1u) != 0;
+    Enqueuer q(o->ctx->stream);
+    ChainTail tail;
+    int rc = odom_chain_begin(x, trans, rot, plan.one_launch, q);
+    if (rc == MMF_OK) rc = plan.one_launch ? odom_one_launch_chain(x, plan, q, &tail) : odom_two_launch_chain(x, q, &tail);
+    return rc == MMF_OK ? odom_chain_publish(x, q, tail) : rc;
 }
 
 // The beginning of the NEXT tracking of one model, to ride the last launch of the preparation that is being enqueued ahead of
@@ -2177,17 +2145,16 @@ extern "C" int mmf_debug_set_begin_rider(int on) {
 }
 extern "C" int mmf_debug_begin_rider_count(void) { return g_begin_riders_used.load(); }
 static void odom_begin_rider_used() { g_begin_riders_used.fetch_add(1); }
-static bool odom_begin_rider(mmf_odom* o, const float pose[16], int rgb_only, float icp_weight, int pyramid, int fast_odom, int so3,
-                             const OdomState* so3_stage, BeginRider* out) {
+static bool odom_begin_rider(mmf_odom* o, const float pose[16], const TrackMode& tm, const OdomState* so3_stage, BeginRider* out) {
     o->begin_spec_valid = o->begin_spec_ok = false;
     const int forced = g_begin_rider.load();
     if (!(forced < 0 ? tunables().begin_rider : forced != 0) || o->two_launch_once) return false;
-    const bool fused = odom_fused_chain_ok(o, rgb_only, icp_weight, pyramid, fast_odom, nullptr, odom_sparse_on(), nullptr);
+    const bool one_launch = odom_plan_chain(o, tm, nullptr, odom_sparse_on()).one_launch;
     const float trans[3] = {pose[3], pose[7], pose[11]};
     const float rot[9] = {pose[0], pose[1], pose[2], pose[4], pose[5], pose[6], pose[8], pose[9], pose[10]};
     std::memset(out, 0, sizeof(*out));
     out->st = o->state;
-    out->a = odom_begin_args(o, trans, rot, rgb_only, icp_weight, pyramid, fast_odom, so3, so3_stage != nullptr, so3_stage, fused);
+    out->a = odom_begin_args(o, trans, rot, tm, so3_stage != nullptr, so3_stage, one_launch);
     o->begin_spec = out->a;
     o->begin_spec_valid = true;
     return true;
@@ -2296,12 +2263,13 @@ extern "C" int mmf_odom_get_incremental_transformation(mmf_odom* o, float trans[
     const float trans0[3] = {trans[0], trans[1], trans[2]};
     float rot0[9];
     std::memcpy(rot0, rot, sizeof(rot0));
-    int rc = odom_enqueue_tracking(o, trans, rot, rgb_only, icp_weight, pyramid, fast_odom, so3, icp_err_dev, rgb_err_dev);
+    const TrackMode tm = track_mode(rgb_only, icp_weight, pyramid, fast_odom, so3);
+    int rc = odom_enqueue_tracking(o, trans, rot, tm, icp_err_dev, rgb_err_dev);
     if (rc) return rc;
     rc = odom_finish_tracking(o, trans, rot);
     if (rc != kGnRetry) return rc;
     odom_retrack_prepare(&o, 1, so3);
-    rc = odom_enqueue_tracking(o, trans0, rot0, rgb_only, icp_weight, pyramid, fast_odom, so3, icp_err_dev, rgb_err_dev);
+    rc = odom_enqueue_tracking(o, trans0, rot0, tm, icp_err_dev, rgb_err_dev);
     if (rc) return rc;
     rc = odom_finish_tracking(o, trans, rot);
     return rc == kGnRetry ? gn_retry_twice() : rc;
@@ -2404,14 +2372,18 @@ extern "C" int mmf_odom_download(mmf_odom* o, const char* name, int level, void*
 
 extern "C" int mmf_odom_time_icp_kernel(mmf_odom* o, int level, int reps, int variant, float* mean_us_out) {
     MMF_REQUIRE(o && mean_us_out && level >= 0 && level < MMF_NUM_PYRS && reps > 0, "mmf_odom_time_icp_kernel: bad argument");
+    MMF_REQUIRE(variant == 0, "mmf_odom_time_icp_kernel: variant must be 0 (the shipped launch geometry)");
     mmf_ctx* c = o->ctx;
     MMF_HIP_TRY(hipSetDevice(c->device));
-    IcpArgs a = odom_icp_args(o, level, nullptr);
+    const IcpArgs a = odom_icp_args(o, level, nullptr);
+    Enqueuer q(c->stream);
     // the state's pose fields are whatever the last getIncrementalTransformation left (or zero);
     // FINISH_RAW only writes out_f
-    for (int w = 0; w < 3; ++w) MMF_HIP_TRY(launch_icp<FINISH_RAW>(c, o->state, a, variant));
+    for (int w = 0; w < 3; ++w) launch_icp<FINISH_RAW>(q, o->state, a, c->partials_icp);
+    MMF_HIP_TRY(q.flush());
     MMF_HIP_TRY(hipEventRecord(c->ev0, c->stream));
-    for (int r = 0; r < reps; ++r) MMF_HIP_TRY(launch_icp<FINISH_RAW>(c, o->state, a, variant));
+    for (int r = 0; r < reps; ++r) launch_icp<FINISH_RAW>(q, o->state, a, c->partials_icp);
+    MMF_HIP_TRY(q.flush());
     MMF_HIP_TRY(hipEventRecord(c->ev1, c->stream));
     MMF_HIP_TRY(hipEventSynchronize(c->ev1));
     float ms = 0.f;

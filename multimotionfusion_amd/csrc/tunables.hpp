@@ -9,15 +9,12 @@
 namespace mmf {
 
 struct Tunables {
-    // ---- Gauss-Newton chain (gn_fused.hpp, mmf_hip.hip: gn_geometry, odom_fused_chain_ok) ----
+    // ---- Gauss-Newton chain (gn_fused.hpp, mmf_hip.hip: gn_geometry, odom_plan_chain) ----
     bool gn_fused = true;     // MMF_GN_FUSED=0: always the two-launch chain (producer + step)
     int gn_fused_max = 8;     // MMF_GN_FUSED_MAX: models one one-launch chain carries at most (the residency check decides below that)
     int gn_px[3] = {0, 0, 0}; // MMF_GN_PX="p0,p1,p2": pixels per lane of a level (0 = by geometry)
     int gn_groups = 256;      // MMF_GN_GROUPS: workgroups per model per launch at most
-    int gn_mixed_lanes = 192; // MMF_GN_MIXED_LANES: pixel lanes of a workgroup in a launch that carries object models (256: as the others)
     int gn_sleep = 1;         // MMF_GN_SLEEP: s_sleep(1) repetitions between two polls of the count barrier
-    bool gn_obj_first = true; // MMF_GN_OBJ_FIRST=0: a shared launch dispatches the camera model's workgroups first
-    int icp_variant = -1;     // MMF_ICP_VARIANT: shape of the stand-alone ICP kernel (-1 = by size)
     // ---- preparation jobs (prep_batch.hpp) ----
     int prep_merge = 2;       // MMF_PREP_MERGE=0|1|2: four / three / two model-side preparation stages
     bool prep_vn = true;      // MMF_PREP_VN=0: a level's vertex and normal maps as two jobs
@@ -60,10 +57,7 @@ inline const Tunables& tunables() {
         if (v.gn_fused_max < 1) v.gn_fused_max = 1;
         if (const char* e = std::getenv("MMF_GN_PX")) std::sscanf(e, "%d,%d,%d", &v.gn_px[0], &v.gn_px[1], &v.gn_px[2]);
         v.gn_groups = (int)num("MMF_GN_GROUPS", 256);
-        v.gn_mixed_lanes = (int)num("MMF_GN_MIXED_LANES", 192);
         v.gn_sleep = (int)num("MMF_GN_SLEEP", 1);
-        v.gn_obj_first = flag("MMF_GN_OBJ_FIRST", true);
-        v.icp_variant = (int)num("MMF_ICP_VARIANT", -1);
         v.prep_merge = (int)num("MMF_PREP_MERGE", 2);
         v.prep_vn = flag("MMF_PREP_VN", true);
         v.prep_l0_late = flag("MMF_PREP_L0_LATE", true);

@@ -108,22 +108,26 @@ def test_incremental_transformation_matches_oracle(gpu_ctx, orc, w, h, mode):
     g.close()
 
 
-@pytest.mark.parametrize("mode", [MODES[0], MODES[3]], ids=["icp+rgb+so3", "fast"])
 # (sizes whose coarsest level is a few hundred pixels are left out: the Gauss-Newton iterations there are chaotic -- 11 ICP
 # inliers at 16x12 -- and any two summation orders part ways)
-@pytest.mark.parametrize("w,h", [(640, 480), (320, 240), (160, 120)])
-def test_one_launch_chain_equals_two_launch_chain(gpu_ctx, w, h, mode):
+@pytest.mark.parametrize("w,h,mode,timing", [
+    pytest.param(w, h, mode, timing, id=f"{w}-{h}-{name}" + ("-timed" if timing else ""))
+    for timing in (0, 2) for name, mode in (("icp+rgb+so3", MODES[0]), ("fast", MODES[3])) for w, h in ((640, 480), (320, 240), (160, 120))])
+def test_one_launch_chain_equals_two_launch_chain(gpu_ctx, w, h, mode, timing):
     """gn_iter_kernel (one launch per Gauss-Newton iteration, csrc/gn_fused.hpp) against the producer + step chain it
     replaces: same per-pixel arithmetic, so the correspondence counts, the inlier counts and both error images are
-    bit-identical; the float sums differ in summation order only."""
+    bit-identical; the float sums differ in summation order only.  timing=2: each chain under the measurement mode that
+    times every kernel (mmf_odom_enable_timing) computes the very bits of its untimed run and counts every launch."""
     lib = gpu_ctx.lib
-    out = []
-    for fused in (1, 0):
+    from multimotionfusion_amd.odometry import RGBDOdometry
+
+    def run(fused, timing):
         assert lib.mmf_debug_set_gn_fused(fused) == 0
         try:
-            from multimotionfusion_amd.odometry import RGBDOdometry
             K, prev, cur, fp, fc = frame_pair(w, h, seed=3)
             g = RGBDOdometry(gpu_ctx, w, h, K["cx"], K["cy"], K["fx"], K["fy"])
+            if timing:
+                g.enableTiming(timing)
             pose = prev.astype(np.float32)
             g.initFirstRGB(dev(fp["rgb"]))
             g.initICPModel(dev(fp["vertex"]), dev(fp["normal"]), 15.0, pose)
@@ -135,12 +139,28 @@ def test_one_launch_chain_equals_two_launch_chain(gpu_ctx, w, h, mode):
             rgb_err = torch.zeros(h, w, device="cuda")
             t, R = g.getIncrementalTransformation(prev[:3, 3], prev[:3, :3], icpErrorSurface=icp_err, rgbErrorSurface=rgb_err,
                                                   **mode)
-            out.append(dict(t=t, R=R, iters=g.iterations_run, icp_count=g.lastICPCount, rgb_count=g.lastRGBCount,
-                            icp_error=g.lastICPError, rgb_error=g.lastRGBError, A=g.lastA.copy(),
-                            icp_err=icp_err.cpu().numpy(), rgb_err=rgb_err.cpu().numpy()))
+            r = dict(t=t, R=R, iters=g.iterations_run, icp_count=g.lastICPCount, rgb_count=g.lastRGBCount,
+                     icp_error=g.lastICPError, rgb_error=g.lastRGBError, A=g.lastA.copy(),
+                     icp_err=icp_err.cpu().numpy(), rgb_err=rgb_err.cpu().numpy())
+            r["timing"] = g.getTiming() if timing else None
             g.close()
+            return r
         finally:
             lib.mmf_debug_set_gn_fused(-1)
+
+    out = []
+    for fused in (1, 0):
+        r = run(fused, timing)
+        if timing:
+            base = run(fused, 0)
+            for k in ("t", "R", "iters", "icp_count", "rgb_count", "icp_error", "rgb_error", "A", "icp_err", "rgb_err"):
+                assert_bit_equal(np.asarray(r[k]), np.asarray(base[k]), f"{'one' if fused else 'two'}-launch chain, timed: {k}")
+            iterations = [3, 0, 0] if mode["fastOdom"] else [10, 5, 4]
+            tm = r["timing"]
+            assert tm["chains"] == 1
+            assert [tm[f"producer_l{lvl}"]["launches"] for lvl in range(3)] == iterations
+            assert [tm[f"rgb_step_l{lvl}"]["launches"] for lvl in range(3)] == ([0, 0, 0] if fused else iterations)
+        out.append(r)
     a, b = out
     assert a["iters"] == b["iters"] == (3 if mode["fastOdom"] else 19)
     if np.isnan(b["t"]).any():

@@ -57,9 +57,8 @@ s = s[:nb]
 t0 = s[:, 0][s[:, 0] > 0].min()  # the first "state loaded" of the launch
 q = lambda v: " ".join(f"{np.percentile(v, p):6.2f}" for p in (0, 50, 90, 100))  # noqa: E731
 cam = -(-(W * H // 5) // 192)  # the camera model's workgroups in a launch that carries object models: 192 pixel lanes x 5 pixels
-obj_first = os.environ.get("MMF_GN_OBJ_FIRST", "1") != "0"  # (tunables.hpp: the object models' workgroups are dispatched first)
-cam_wgs, obj_wgs = (s[nb - cam:], s[:nb - cam]) if obj_first else (s[:cam], s[cam:])
-for name, sel in ((f"camera model ({cam} workgroups, dispatched {'last' if obj_first else 'first'})", cam_wgs), ("object models", obj_wgs)):
+cam_wgs, obj_wgs = s[nb - cam:], s[:nb - cam]  # (the object models' workgroups are dispatched first: GnBatchGeom::rotate)
+for name, sel in ((f"camera model ({cam} workgroups, dispatched last)", cam_wgs), ("object models", obj_wgs)):
     if len(sel) == 0:
         continue
     print(f"  {name}: us after the launch's first 'state loaded':                     min    p50    p90    max")
