@@ -643,6 +643,22 @@ int mmf_slic_downsample_rgb(mmf_ctx *ctx, const int *labels, int width, int heig
 int mmf_slic_upsample_u8(mmf_ctx *ctx, const int *labels, int width, int height, const uint8_t *map, int nspix,
                          uint8_t *out);
 
+/* ---- the super-pixel engine (csrc/slic_engine_kernels.hpp) -------------------------------------------
+ * The label image the calls above take, computed on the device: SLIC as the reference configures gSLICr
+ * (Core/Segmentation/Slic.cpp:33-43: RGB colour space, GIVEN_SIZE, coh_weight 0.6, 5 iterations, no connectivity
+ * enforcement).  rgb = DEVICE u8 [height][width][3] (the channels take part symmetrically, in memory order);
+ * spixel_size S in (10, 256) and it must DIVIDE width and height (MMF_ERR_INVALID otherwise: gSLICr's map is
+ * ceil(W/S) x ceil(H/S), Slic.h sizes its arrays by (W/S)(H/S)); n = (width / S) * (height / S).
+ * initialise; iterations x (associate, update); associate -- iterations = 5 is the reference's, 0 = one association.
+ *   centres_in   optional DEVICE [n][5] float32 {x, y, c0, c1, c2}: replaces the initialisation
+ *   labels_out   DEVICE int32 [height][width], values in [0, n)
+ *   centres_out  optional DEVICE [n][5] float32: the centres the last association used
+ *   counts_out   optional DEVICE [n] int32: the pixels per centre at the last update (zeros when iterations == 0)
+ * Asynchronous on the context's stream; 2 + 2 * iterations launches (+ 1 with centres_out).  Integer sums, float32 in
+ * a fixed order: the results do not depend on the order the pixels are visited in. */
+int mmf_slic_segment(mmf_ctx *ctx, const uint8_t *rgb, int width, int height, int spixel_size, int iterations,
+                     const float *centres_in, int *labels_out, float *centres_out, int *counts_out);
+
 /* ---- dense-CRF motion segmentation (Core/Segmentation/Segmentation.cpp:159-740, performSegmentationCRF) ----------
  * The segmentation that spawns object models, on the device (csrc/crf_kernels.hpp): super-pixel
  * means of the raw depth and of every model's ICP-error image and splat confidence, unaries from the ICP error, a
@@ -702,9 +718,18 @@ int mmf_crf_last(mmf_ctx *ctx, mmf_crf_info *info, mmf_segmentation_model *model
  * mmf_crf_segment in their callback).  spawnOffset (:148, :410, :484) counts the multi-model tracked frames up to
  * cfg->model_spawn_offset and restarts at every spawn; a new label is proposed only once it has reached it.
  * mmf_fusion_set_superpixels: DEVICE int32 label image (width x height) for the NEXT frame only (copied); NULL: grid.
- * mmf_fusion_last_segmentation: mmf_crf_last of the fusion's context. */
+ * mmf_fusion_last_segmentation: mmf_crf_last of the fusion's context.
+ * mmf_fusion_set_superpixel_engine: mode 0 = off (default), 1 = the label image of every frame the built-in segmentation
+ *   handles is computed from that frame's RGB by mmf_slic_segment's engine (5 iterations, spixel_size of the CRF
+ *   configuration), on a stream of its own beside the tracking.  Precedence per frame: labels handed in through
+ *   mmf_fusion_set_superpixels, then the engine, then the grid.  MMF_ERR_INVALID when spixel_size does not divide the frame
+ *   size -- here, and at the frame when the CRF configuration changed since; never a silent fall back to the grid.
+ * mmf_fusion_last_superpixels: the label image the last segmentation used, whichever of the three it was, copied to the
+ *   DEVICE int32 [height][width] labels_out.  Synchronous.  MMF_ERR_STATE before the first segmentation. */
 int mmf_fusion_set_crf_segmentation(mmf_fusion *f, const mmf_crf_config *cfg);
 int mmf_fusion_set_superpixels(mmf_fusion *f, const int *labels);
+int mmf_fusion_set_superpixel_engine(mmf_fusion *f, int mode);
+int mmf_fusion_last_superpixels(mmf_fusion *f, int *labels_out);
 int mmf_fusion_last_segmentation(mmf_fusion *f, mmf_crf_info *info, mmf_segmentation_model *models, int capacity,
                                  float *unaries, float *q, uint8_t *raw_map, uint8_t *map);
 

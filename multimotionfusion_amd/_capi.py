@@ -152,6 +152,7 @@ SIGNATURES = {
     "mmf_slic_downsample": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp]),
     "mmf_slic_downsample_rgb": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "mmf_slic_upsample_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp]),
+    "mmf_slic_segment": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mmf_rigid_fit": (_i, [_vp, _vp, _i, _vp, _vp]),
     "mmf_rigid_apply": (_i, [_vp, _vp, _vp, _i, _vp]),
     "mmf_ransac_create": (_i, [_i, _f, _f, _vp]),
@@ -204,6 +205,8 @@ SIGNATURES = {
     "mmf_fusion_set_segmentation_callback": (_i, [_vp, _vp, _vp]),
     "mmf_fusion_set_crf_segmentation": (_i, [_vp, C.POINTER(mmf_crf_config)]),
     "mmf_fusion_set_superpixels": (_i, [_vp, _vp]),
+    "mmf_fusion_set_superpixel_engine": (_i, [_vp, _i]),
+    "mmf_fusion_last_superpixels": (_i, [_vp, _vp]),
     "mmf_fusion_last_segmentation": (_i, [_vp, C.POINTER(mmf_crf_info), C.POINTER(mmf_segmentation_model), _i, _vp, _vp, _vp, _vp]),
     "mmf_crf_default_config": (_i, [C.POINTER(mmf_crf_config)]),
     "mmf_crf_segment": (_i, [_vp, C.POINTER(mmf_crf_config), _vp, _i, _i, _vp, _vp, _vp, C.POINTER(C.c_uint), _i, C.c_uint, _i,

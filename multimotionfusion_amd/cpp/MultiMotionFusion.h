@@ -567,6 +567,9 @@ class MultiMotionFusion {
     void setCrfUnaryKError(const float& v) { other_["crfUnaryKError"] = v, crf_.unary_k_error = v, pushCrf(); }
     void setNewModelMinRelativeSize(const float& v) { other_["newModelMinRelativeSize"] = v, crf_.min_rel_size_new = v, pushCrf(); }
     void setNewModelMaxRelativeSize(const float& v) { other_["newModelMaxRelativeSize"] = v, crf_.max_rel_size_new = v, pushCrf(); }
+    // the built-in segmentation's super-pixels from the frame's RGB on the device (the engine that replaces gSLICr,
+    // cpp/Slic.h) instead of the regular grid; sp_size must divide the frame size
+    void setSuperpixelEngine(bool v) { other_["superpixelEngine"] = v, mmf::check(mmf_fusion_set_superpixel_engine(f_, v ? 1 : 0), "mmf_fusion_set_superpixel_engine"); }
     void setEnableRedetection(bool v) { other_["enableRedetection"] = v; }
     void setSetInhibit(bool v) { other_["inhibitModels"] = v, crf_.inhibit_new = v ? 1 : 0, pushCrf(); }
     void setEnableSmartModelDelete(bool v) { other_["enableSmartModelDelete"] = v; }

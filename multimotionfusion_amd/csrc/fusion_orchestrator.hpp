@@ -85,6 +85,15 @@ struct mmf_fusion {
     unsigned spawn_offset = 0;       // MultiMotionFusion::spawnOffset (MultiMotionFusion.h:433)
     int* sp_labels = nullptr;        // mmf_fusion_set_superpixels: the next frame's label image (a copy)
     bool sp_next = false;
+    // the super-pixel engine (mmf_fusion_set_superpixel_engine): the frame's label image from its RGB, on a stream of its
+    // own beside the tracking chains; nothing below exists until the engine is switched on
+    int sp_engine = 0;
+    SlicEngineWs sp_ws;
+    hipStream_t sp_stream = nullptr;
+    hipEvent_t ev_sp_begin = nullptr;  // fusion stream: the frame's RGB is there, the last segmentation has read the labels
+    hipEvent_t ev_sp_done = nullptr;   // engine stream: this frame's labels are complete
+    bool sp_enqueued = false;          // ev_sp_done is recorded and nothing has waited for it yet
+    const int* sp_last = nullptr;      // the label image the last segmentation used (handed in, the engine's, or the grid)
     std::vector<mmf_segmentation_model> crf_models;
     hipEvent_t ev_frame_ready = nullptr;  // fusion stream: the frame's shared inputs are complete
     // next-frame prefetch (mmf_fusion_prefetch_frame): the filter and the input-side preparation of frame t+1 run
@@ -335,6 +344,11 @@ extern "C" void mmf_fusion_destroy(mmf_fusion* f) {
     (void)hipFree(f->filtered[1]);
     (void)hipFree(f->mask);
     (void)hipFree(f->sp_labels);
+    if (f->sp_stream) (void)hipStreamSynchronize(f->sp_stream);
+    (void)hipFree(f->sp_ws.mem);
+    if (f->ev_sp_begin) (void)hipEventDestroy(f->ev_sp_begin);
+    if (f->ev_sp_done) (void)hipEventDestroy(f->ev_sp_done);
+    if (f->sp_stream) (void)hipStreamDestroy(f->sp_stream);
     (void)hipFree(f->mask_boxes);
     (void)hipFree(f->side_partials);
     (void)hipFree(f->side_ticket);
@@ -517,9 +531,47 @@ extern "C" int mmf_fusion_set_superpixels(mmf_fusion* f, const int* labels) {
     f->sp_next = false;
     if (!labels) return MMF_OK;
     MMF_HIP_TRY(hipSetDevice(f->ctx->device));
+    if (f->sp_last == f->sp_labels) f->sp_last = nullptr;  // (the copy the last segmentation used is about to be replaced)
     if (!f->sp_labels) MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&f->sp_labels), (size_t)f->width * f->height * sizeof(int)));
     MMF_HIP_TRY(hipMemcpyAsync(f->sp_labels, labels, (size_t)f->width * f->height * sizeof(int), hipMemcpyDeviceToDevice, f->ctx->stream));
     f->sp_next = true;
+    return MMF_OK;
+}
+// the engine's streams and label image for the fusion's frame size and the CRF configuration's super-pixel size
+static int fusion_sp_engine_prepare(mmf_fusion* f, const char* who) {
+    if (int rc = slic_engine_check(f->width, f->height, f->crf_cfg.spixel_size, who)) return rc;
+    const int S = f->crf_cfg.spixel_size;
+    const size_t cells = (size_t)(f->width / S) * (f->height / S), pixels = (size_t)f->width * f->height;
+    if (!f->sp_stream) {
+        MMF_HIP_TRY(hipStreamCreateWithFlags(&f->sp_stream, hipStreamNonBlocking));
+        MMF_HIP_TRY(hipEventCreateWithFlags(&f->ev_sp_begin, hipEventDisableTiming));
+        MMF_HIP_TRY(hipEventCreateWithFlags(&f->ev_sp_done, hipEventDisableTiming));
+    }
+    if (cells > f->sp_ws.cells || pixels > f->sp_ws.pixels) {  // (the setter, or a CRF configuration with a smaller S since)
+        MMF_HIP_TRY(hipStreamSynchronize(f->sp_stream));
+        if (f->sp_ws.mem && f->sp_last == f->sp_ws.labels()) f->sp_last = nullptr;
+        if (int rc = slic_engine_workspace(&f->sp_ws, cells, pixels, f->ctx->stream)) return rc;
+    }
+    return MMF_OK;
+}
+extern "C" int mmf_fusion_set_superpixel_engine(mmf_fusion* f, int mode) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_set_superpixel_engine: null fusion object");
+    MMF_REQUIRE(mode == 0 || mode == 1, "mmf_fusion_set_superpixel_engine: mode is 0 (off) or 1 (SLIC from the frame's RGB)");
+    if (mode == 0) {
+        f->sp_engine = 0;
+        return MMF_OK;
+    }
+    MMF_HIP_TRY(hipSetDevice(f->ctx->device));
+    if (int rc = fusion_sp_engine_prepare(f, "mmf_fusion_set_superpixel_engine")) return rc;
+    f->sp_engine = 1;
+    return MMF_OK;
+}
+extern "C" int mmf_fusion_last_superpixels(mmf_fusion* f, int* labels_out) {
+    MMF_REQUIRE(f && labels_out, "mmf_fusion_last_superpixels: null argument");
+    if (!f->sp_last) return fail(MMF_ERR_STATE, "mmf_fusion_last_superpixels: no segmentation has run on this fusion (or its labels were replaced)");
+    MMF_HIP_TRY(hipSetDevice(f->ctx->device));
+    MMF_HIP_TRY(hipMemcpyAsync(labels_out, f->sp_last, (size_t)f->width * f->height * sizeof(int), hipMemcpyDeviceToDevice, f->ctx->stream));
+    MMF_HIP_TRY(hipStreamSynchronize(f->ctx->stream));
     return MMF_OK;
 }
 extern "C" int mmf_fusion_last_segmentation(mmf_fusion* f, mmf_crf_info* info, mmf_segmentation_model* models, int capacity,
@@ -754,6 +806,7 @@ struct FrameRun {
     mmf_model early_snapshot;  // the model's host bookkeeping before the passes enqueued ahead of the pose (fusion_retrack)
     bool early_snapshot_valid = false;
     int pass_mode = 0;  // fusion_batch_mode, once the frame's model list is final
+    bool superpixels = false;  // the super-pixel engine runs for this frame (ev_sp_begin is recorded)
 
     // MMF_HOST_TRACE=1: where the calling thread is, in us after the call began (averages over 100 calls)
     void stamp(mmf_fusion* f, int i) const {
@@ -1172,6 +1225,33 @@ static int frame_pick_up_poses(mmf_fusion* f, FrameRun& r) {
     return MMF_OK;
 }
 
+// The engine's label image of this frame.  It depends on the frame's RGB only, so it runs on a stream of its own beside the
+// tracking chains and fusion_crf_segment joins it in front of stage 1.  Two halves: ev_sp_begin is recorded on the fusion's
+// stream when the frame begins (the RGB is there; the last segmentation that read the label image ended in a host wait),
+// the twelve launches are enqueued once the chains are, while the host would only wait for the poses -- in front of the
+// chains their enqueue is host time the whole frame waits for.  Only when this frame's segmentation will be the built-in
+// one on the engine's labels.
+static int frame_superpixels_begin(mmf_fusion* f, FrameRun& r) {
+    mmf_ctx* c = f->ctx;
+    if (f->sp_enqueued) {  // a frame that failed between the engine and its segmentation
+        MMF_HIP_TRY(hipStreamWaitEvent(c->stream, f->ev_sp_done, 0));
+        f->sp_enqueued = false;
+    }
+    if (int rc = fusion_sp_engine_prepare(f, "mmf_fusion_process_frame (super-pixel engine)")) return rc;
+    MMF_HIP_TRY(hipEventRecord(f->ev_sp_begin, c->stream));
+    r.superpixels = true;
+    return MMF_OK;
+}
+static int frame_superpixels_enqueue(mmf_fusion* f, const FrameRun& r) {
+    MMF_HIP_TRY(hipStreamWaitEvent(f->sp_stream, f->ev_sp_begin, 0));
+    if (int rc = slic_engine_enqueue(f->sp_ws, f->sp_stream, r.fr->rgb, f->width, f->height, f->crf_cfg.spixel_size, 5, nullptr, nullptr,
+                                     nullptr, nullptr))
+        return rc;
+    MMF_HIP_TRY(hipEventRecord(f->ev_sp_done, f->sp_stream));
+    f->sp_enqueued = true;
+    return MMF_OK;
+}
+
 // :299-400: every model's tracking, enqueued before the first result is awaited, then the bootstrap
 static int frame_track(mmf_fusion* f, FrameRun& r) {
     const mmf_frame* fr = r.fr;
@@ -1197,6 +1277,10 @@ static int frame_track(mmf_fusion* f, FrameRun& r) {
         for (int i = 0; i < MMF_NUM_PYRS; ++i) std::swap(global->odom->last_next_image[i], global->odom->next_image[i]);
     if (r.early_image == 1 && r.image_early_ok && !r.tracked.empty()) {  // (see frame_track_sensor_side)
         rc = fusion_prefetch_image(f, fr->next_rgb, f->tick + 1, true);
+        if (rc) return rc;
+    }
+    if (r.superpixels) {  // the super-pixel engine, beside the chains
+        rc = frame_superpixels_enqueue(f, r);
         if (rc) return rc;
     }
     r.stamp(f, 0);
@@ -1247,9 +1331,17 @@ static int fusion_crf_segment(mmf_fusion* f, mmf_segmentation* out) {
     const int allow_new = f->spawn_offset >= (unsigned)cfg.model_spawn_offset ? 1 : 0;  // (:148)
     CrfWs* w = nullptr;
     const int* labels = nullptr;
-    int rc = crf_begin(c, &cfg, f->sp_next ? f->sp_labels : nullptr, W, H, ids.data(), M, next_id, allow_new,
-                       "mmf_fusion_process_frame (segmentation)", &w, &labels);
+    // labels handed in for this frame, then the engine's, then the grid (B3)
+    const bool engine = !f->sp_next && f->sp_engine;
+    if (engine && !f->sp_enqueued) return fail(MMF_ERR_STATE, "mmf_fusion_process_frame: the super-pixel engine did not run for this frame");
+    int rc = crf_begin(c, &cfg, f->sp_next ? f->sp_labels : (engine ? f->sp_ws.labels() : nullptr), W, H, ids.data(), M, next_id,
+                       allow_new, "mmf_fusion_process_frame (segmentation)", &w, &labels);
     if (rc) return rc;
+    f->sp_last = labels;
+    if (engine) {
+        MMF_HIP_TRY(hipStreamWaitEvent(c->stream, f->ev_sp_done, 0));
+        f->sp_enqueued = false;
+    }
     // behind every model's tracking chain: the chains write the ICP-error images on the models' streams
     for (FusionModel* fm : f->models) {
         hipStream_t ls = fm->lane->stream;
@@ -1584,6 +1676,10 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
         if (rc) return rc;
     } else {
         f->tracking_ok = 1;
+        if (f->sp_engine && r.track && f->cfg.enable_multiple_models && !fr->segmentation && !f->seg_fn && f->crf_on && !f->sp_next) {
+            rc = frame_superpixels_begin(f, r);
+            if (rc) return rc;
+        }
         rc = r.track ? frame_track(f, r) : frame_dictated_pose(f, r);
         if (rc) return rc;
         if (r.track && f->cfg.enable_multiple_models) {

@@ -126,6 +126,8 @@ struct mmf_ctx {
     size_t match_ws_rows = 0;
     void* slic_ws = nullptr;  // super-pixel resampling workspace (boxes, counts, sums), grown on demand
     size_t slic_ws_n = 0;
+    void* slic_engine_ws = nullptr;  // super-pixel engine workspace (centres, counts, labels), grown on demand
+    size_t slic_engine_cells = 0;
     struct CrfWs* crf_ws = nullptr;  // dense-CRF segmentation workspace (crf_kernels.hpp), grown on demand
     char arch[64] = {0};
     int cu_count = 0;  // compute units of the device (the one-launch Gauss-Newton chain needs its grid resident at once)
@@ -201,6 +203,7 @@ extern "C" void mmf_ctx_destroy(mmf_ctx* c) {
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     (void)hipFree(c->match_ws);
     (void)hipFree(c->slic_ws);
+    (void)hipFree(c->slic_engine_ws);
     crf_ws_free(c->crf_ws);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -3406,6 +3409,82 @@ extern "C" int mmf_slic_upsample_u8(mmf_ctx* c, const int* labels, int width, in
     hipLaunchKernelGGL(mmf::slic_upsample_u8_kernel, grid1d(npix), dim3(256), 0, c->stream, labels, npix, nspix, map, out);
     MMF_HIP_TRY(hipGetLastError());
     return MMF_OK;
+}
+
+// ---- the super-pixel engine (slic_engine_kernels.hpp) -----------------------------------------------------
+#include "slic_engine_kernels.hpp"
+
+// centres [cells][8] float, counts [cells] int, labels [pixels] int in one allocation (a context's, or a fusion's own:
+// the fusion runs the engine on a stream of its own)
+struct SlicEngineWs {
+    void* mem = nullptr;
+    size_t cells = 0, pixels = 0;
+    float* centres() const { return static_cast<float*>(mem); }
+    int* counts() const { return reinterpret_cast<int*>(centres() + cells * mmf::kSlicCentreStride); }
+    int* labels() const { return counts() + ((cells + 3) & ~(size_t)3); }  // (16-byte aligned: one store per four labels)
+};
+
+// `quiet`: the stream whose enqueued work may still use the old allocation
+static int slic_engine_workspace(SlicEngineWs* ws, size_t cells, size_t pixels, hipStream_t quiet) {
+    if (cells <= ws->cells && pixels <= ws->pixels) return MMF_OK;
+    cells = std::max(cells, ws->cells), pixels = std::max(pixels, ws->pixels);
+    MMF_HIP_TRY(hipStreamSynchronize(quiet));
+    (void)hipFree(ws->mem);
+    ws->mem = nullptr, ws->cells = ws->pixels = 0;
+    const size_t bytes = cells * mmf::kSlicCentreStride * sizeof(float) + ((cells + 3) & ~(size_t)3) * sizeof(int) + pixels * sizeof(int);
+    MMF_HIP_TRY(hipMalloc(&ws->mem, bytes));
+    ws->cells = cells, ws->pixels = pixels;
+    return MMF_OK;
+}
+
+// S in (10, 256) and dividing both sides: gSLICr's map is ceil(W/S) x ceil(H/S) while Slic.h sizes everything by
+// (W/S) (H/S) -- on a ragged image the reference indexes past its own arrays
+static int slic_engine_check(int width, int height, int spixel_size, const char* who) {
+    if (width <= 0 || height <= 0 || !(spixel_size > 10 && spixel_size < 256))
+        return fail(MMF_ERR_INVALID, std::string(who) + ": super-pixel size must be in (10, 256)");
+    if (width % spixel_size != 0 || height % spixel_size != 0 || (long long)width * height > (long long)INT_MAX / 4)
+        return fail(MMF_ERR_INVALID, std::string(who) + ": the super-pixel size must divide the image's width and height (" +
+                                         std::to_string(width) + " x " + std::to_string(height) + ", S = " + std::to_string(spixel_size) + ")");
+    return MMF_OK;
+}
+
+// initialise; iterations x (associate, update); associate -- 2 + 2 * iterations launches on `st` (+ 1 for centres_out);
+// labels_out == nullptr: the workspace's label image (the fusion's)
+static int slic_engine_enqueue(const SlicEngineWs& ws, hipStream_t st, const uint8_t* rgb, int W, int H, int S, int iterations,
+                               const float* centres_in, int* labels_out, float* centres_out, int* counts_out) {
+    using namespace mmf;
+    SlicEngineGeom g;
+    g.W = W, g.H = H, g.S = S, g.mx = W / S, g.my = H / S;
+    const float t = 1.0f / (1.4242f * (float)S), u = 5.0f / (1.7321f * 128.0f);
+    g.nxy = t * t, g.nc = u * u;
+    const int n = g.mx * g.my;
+    int* labels = labels_out ? labels_out : ws.labels();
+    const int vec = (reinterpret_cast<uintptr_t>(rgb) % 4 == 0 && reinterpret_cast<uintptr_t>(labels) % 16 == 0) ? 1 : 0;
+    const dim3 agrid = grid1d(((size_t)W * H + 3) / 4);
+    hipLaunchKernelGGL(slic_engine_init_kernel, grid1d(n), dim3(256), 0, st, g, rgb, centres_in, ws.centres(), ws.counts());
+    for (int it = 0; it < iterations; ++it) {
+        hipLaunchKernelGGL(slic_engine_associate_kernel, agrid, dim3(256), 0, st, g, rgb, (const float*)ws.centres(), labels, vec);
+        hipLaunchKernelGGL(slic_engine_update_kernel, dim3(n), dim3(256), 0, st, g, rgb, (const int*)labels, ws.centres(), ws.counts());
+    }
+    hipLaunchKernelGGL(slic_engine_associate_kernel, agrid, dim3(256), 0, st, g, rgb, (const float*)ws.centres(), labels, vec);
+    if (centres_out) hipLaunchKernelGGL(slic_engine_export_kernel, grid1d(n), dim3(256), 0, st, n, (const float*)ws.centres(), centres_out);
+    MMF_HIP_TRY(hipGetLastError());
+    if (counts_out) MMF_HIP_TRY(hipMemcpyAsync(counts_out, ws.counts(), (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, st));
+    return MMF_OK;
+}
+
+extern "C" int mmf_slic_segment(mmf_ctx* c, const uint8_t* rgb, int width, int height, int spixel_size, int iterations,
+                                const float* centres_in, int* labels_out, float* centres_out, int* counts_out) {
+    MMF_REQUIRE(c && rgb && labels_out, "mmf_slic_segment: null argument");
+    MMF_REQUIRE(iterations >= 0 && iterations <= 1000, "mmf_slic_segment: iterations must be in [0, 1000]");
+    if (int rc = slic_engine_check(width, height, spixel_size, "mmf_slic_segment")) return rc;
+    MMF_HIP_TRY(hipSetDevice(c->device));
+    SlicEngineWs ws;
+    ws.mem = c->slic_engine_ws, ws.cells = c->slic_engine_cells, ws.pixels = 0;
+    const int rc = slic_engine_workspace(&ws, (size_t)(width / spixel_size) * (height / spixel_size), 0, c->stream);
+    c->slic_engine_ws = ws.mem, c->slic_engine_cells = ws.cells;
+    if (rc) return rc;
+    return slic_engine_enqueue(ws, c->stream, rgb, width, height, spixel_size, iterations, centres_in, labels_out, centres_out, counts_out);
 }
 
 // ---- dense-CRF motion segmentation (crf_kernels.hpp; Segmentation.cpp:159-740) ---------------------------------------

@@ -257,6 +257,18 @@ class MultiMotionFusion:
             labels = labels.contiguous()
         check(self.ctx.lib.mmf_fusion_set_superpixels(self.handle, _p(labels) if labels is not None else None))
 
+    def setSuperpixelEngine(self, on):
+        """the built-in segmentation computes every frame's super-pixels from its RGB on the device (SLIC, DESIGN.md B5);
+        labels handed in through setSuperpixels still win for their frame; off (default): the regular grid"""
+        check(self.ctx.lib.mmf_fusion_set_superpixel_engine(self.handle, 1 if on else 0))
+
+    def getLastSuperpixels(self):
+        """the label image (int32 [H,W] CUDA tensor) the last segmentation used: handed in, the engine's, or the grid"""
+        import torch
+        out = torch.empty((self.height, self.width), dtype=torch.int32, device=torch.device("cuda", self.ctx.device))
+        check(self.ctx.lib.mmf_fusion_last_superpixels(self.handle, _p(out)))
+        return out
+
     def getLastSegmentation(self):
         """segmentation.last() of this fusion: unaries, Q, raw and filtered maps, model data, range, B4 flag"""
         import torch

@@ -1,6 +1,7 @@
 """Super-pixel resampling on the device: the host-side mirror of Slic::downsample / downsampleThresholded /
 upsample (Core/Segmentation/Slic.h:48-146, Slic.cpp:82-112) as Segmentation.cpp:177-178,218-221,683 uses them,
-over the C ABI -- no fallback.  The label image is gSLICr's segmentation mask (an input)."""
+over the C ABI -- no fallback.  The label image is gSLICr's segmentation mask: an input, or `segment`'s output (the
+on-device SLIC engine)."""
 import torch
 
 from .cudafuncs import Context, _p, check
@@ -46,3 +47,22 @@ def upsample_u8(ctx: Context, labels, small):
     out = torch.empty((H, W), dtype=torch.uint8, device=labels.device)
     check(ctx.lib.mmf_slic_upsample_u8(ctx.handle, _p(labels), W, H, _p(small), small.numel(), _p(out)))
     return out
+
+
+def segment(ctx: Context, rgb, spixelSize, iterations=5, centres=None, with_centres=False):
+    """The super-pixel engine (Slic::processFrame with the reference's gSLICr settings, DESIGN.md B5): rgb [H,W,3] u8 CUDA
+    -> labels [H,W] int32 in [0, (W/S)(H/S)).  spixelSize must divide W and H.  centres [n,5] float32 {x, y, c0, c1, c2}
+    replaces the initialisation; iterations=0 is one association.  with_centres: (labels, centres [n,5], counts [n])."""
+    assert rgb.dtype == torch.uint8 and rgb.is_cuda and rgb.dim() == 3 and rgb.shape[2] == 3
+    rgb = rgb.contiguous()
+    H, W = rgb.shape[:2]
+    S = int(spixelSize)
+    n = (W // S) * (H // S) if S > 0 else 0
+    if centres is not None:
+        assert centres.dtype == torch.float32 and centres.is_cuda and tuple(centres.shape) == (n, 5)
+        centres = centres.contiguous()
+    labels = torch.empty((H, W), dtype=torch.int32, device=rgb.device)
+    c_out = torch.empty((n, 5), dtype=torch.float32, device=rgb.device) if with_centres else None
+    k_out = torch.empty((n,), dtype=torch.int32, device=rgb.device) if with_centres else None
+    check(ctx.lib.mmf_slic_segment(ctx.handle, _p(rgb), W, H, S, int(iterations), _p(centres), _p(labels), _p(c_out), _p(k_out)))
+    return (labels, c_out, k_out) if with_centres else labels
