@@ -733,6 +733,73 @@ int mmf_fusion_last_superpixels(mmf_fusion *f, int *labels_out);
 int mmf_fusion_last_segmentation(mmf_fusion *f, mmf_crf_info *info, mmf_segmentation_model *models, int capacity,
                                  float *unaries, float *q, uint8_t *raw_map, uint8_t *map);
 
+/* ---- keypoint redetection of inactive models (Core/MultiMotionFusion.cpp:425-436, 489-559; Model::getBestMatch,
+ * Core/Model/Model.cpp:781-874; Model::store / activate, :1617-1656) -------------------------------------------------
+ * A VIEW is what one time index of a model's stored local tracks holds (tracks_local = the result of
+ * computeTrackProjectionFirstFrame, Model.cpp:508-522): n valid keypoints -- null and non-finite ones dropped, :806-811 --
+ * with descriptor [n][256] float32 and coordinate [n][3] in the model's local frame.  The view store keeps the views of
+ * all models in one device buffer; a query set (the keypoints of one segment) is matched against EVERY view of the store
+ * in three launches, whatever the number of views (csrc/redetect_kernels.hpp): per view what
+ * cv::BFMatcher(NORM_L2, true).match(query, view) returns, no distance gate, distances the fmaf chains of
+ * mmf_match_descriptors.  Views are processed in ascending index and one RigidRANSAC{10, 0.03, 0.8} is constructed per
+ * best-match call.
+ *   mmf_viewstore_store       HOST arrays: counts[n_views] valid keypoints per view (0 allowed), the views' descriptors and
+ *                         coordinates one after the other.  Like Model::store (:1618-1621) a model that has stored views
+ *                         ignores a second store: *stored = 0.  Synchronous.  The store only grows; growing never frees a
+ *                         buffer before mmf_viewstore_destroy.
+ *   mmf_viewstore_forget      the model is gone: its views stay in place, belong to nobody and match nothing of interest
+ *   mmf_viewstore_num_views / _view   the views in store order (models in the order they were stored, a model's views ascending)
+ *   mmf_viewstore_match       query = DEVICE [nq][256] (16-byte aligned); HOST train_idx / distance [views][nq]: the row of the
+ *                         view that query row matched or -1, and the distance (0 when unmatched).  Synchronous.
+ *   mmf_viewstore_best_match  Model::getBestMatch for one model: coordinate = HOST [nq][3] of the query keypoints; views with at
+ *                         least 3 matches (:839), estimate(query, train) per view, estimates without inliers dropped (:859), the
+ *                         smallest error wins, the first of equals (:870-873).  *found = 0: no estimate (T identity, error +inf).
+ *                         T = Result::transformation (query ~ T train), *view = index of the winning view inside the model,
+ *                         *n_matches its matches, inlier (optional, capacity nq) = Result::inlier over the hash-sorted matches.
+ *   mmf_viewstore_last_launches   kernel launches the last match enqueued (3 per query set; 0 with an empty store)
+ * Inside processFrame (off by default; MMF_ERR_STATE with world > 1):
+ *   mmf_fusion_set_redetection   setEnableRedetection.  With it on, a frame that has keypoints, inactive models and stored views
+ *                         labels the keypoints by the id image, and per label other than 0 / 255 with at least 3 finite
+ *                         keypoints (labels ascending) and per inactive model (list order) accepts the best match when
+ *                         error < 0.01 and inliers > 5 (:516): a pending new label is cancelled (no model is spawned, no id
+ *                         consumed), an active model carrying the label is dropped and freed unless it is older (smaller id)
+ *                         than the inactive one -- then nothing happens for the pair --, and the inactive model joins the active
+ *                         list with pose = transformation^-1 (Model::activate), its map and its id.  Two host waits per such
+ *                         frame (labels, matches); otherwise nothing is enqueued and nothing awaited.
+ *   mmf_fusion_set_keypoints     the last keypoint of every currently visible track (track->back(), :428-436) for the NEXT
+ *                         processFrame only: HOST xy [n][2] int pixels (outside the image: dropped, :432), coordinate [n][3]
+ *                         camera frame (non-finite allowed), descriptor [n][256].  Copied.
+ *   mmf_fusion_viewstore         the fusion's store (owned by the fusion): store a model's views there when it turns up in the
+ *                         inactive list
+ *   mmf_fusion_last_redetections what the last frame did, accepted matches in order (also the refused older / newer pairs:
+ *                         activated = 0) */
+typedef struct mmf_viewstore mmf_viewstore;
+typedef struct {
+    int label;      /* the segment's label in the id image */
+    int model_id;   /* the inactive model whose view matched */
+    int removed_id; /* the active model that carried the label and was dropped, or -1 */
+    int activated;  /* 0: refused, an older active model carries the label (:536-541) */
+    float error;    /* RigidRANSAC::Result::error of the best view */
+    int inliers, view;
+    float transformation[16]; /* Result::transformation; the model's new pose is its inverse */
+} mmf_redetection;
+int mmf_viewstore_create(mmf_ctx *ctx, mmf_viewstore **out);
+void mmf_viewstore_destroy(mmf_viewstore *vs);
+int mmf_viewstore_store(mmf_viewstore *vs, int model_id, int n_views, const int *counts, const float *descriptor,
+                        const float *coordinate, int *stored);
+int mmf_viewstore_forget(mmf_viewstore *vs, int model_id);
+int mmf_viewstore_num_views(mmf_viewstore *vs);
+int mmf_viewstore_view(mmf_viewstore *vs, int view, int *model_id, int *index, int *rows);
+int mmf_viewstore_match(mmf_viewstore *vs, const float *query, int nq, int *train_idx, float *distance);
+int mmf_viewstore_best_match(mmf_viewstore *vs, int model_id, const float *query, const float *coordinate, int nq,
+                             float T[16], float *error, int *inliers, int *view, int *n_matches, unsigned char *inlier,
+                             int *found);
+int mmf_viewstore_last_launches(mmf_viewstore *vs);
+int mmf_fusion_set_redetection(mmf_fusion *f, int on);
+int mmf_fusion_set_keypoints(mmf_fusion *f, int n, const int *xy, const float *coordinate, const float *descriptor);
+mmf_viewstore *mmf_fusion_viewstore(mmf_fusion *f);
+int mmf_fusion_last_redetections(mmf_fusion *f, mmf_redetection *out, int capacity, int *n_out);
+
 /* ---- keypoint-based pose initialisation: RigidRANSAC (Core/Utils/RigidRANSAC.h:6-32, .cpp:73-180) ----
  * Host code, like the reference's (a few dozen keypoint tracks): p0, p1 are HOST arrays of n 3-D points
  * (row-major n x 3), mask an optional n-byte selection; T receives the row-major 4x4 of T_01 with

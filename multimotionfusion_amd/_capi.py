@@ -82,6 +82,11 @@ class mmf_crf_info(C.Structure):
                 ("n_components", C.c_int), ("range", C.c_float)]
 
 
+class mmf_redetection(C.Structure):
+    _fields_ = [("label", C.c_int), ("model_id", C.c_int), ("removed_id", C.c_int), ("activated", C.c_int),
+                ("error", C.c_float), ("inliers", C.c_int), ("view", C.c_int), ("transformation", C.c_float * 16)]
+
+
 SEGMENTATION_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(mmf_frame), C.POINTER(mmf_segmentation))
 
 
@@ -255,6 +260,19 @@ SIGNATURES = {
     "mmf_model_set_confidence_threshold": (_i, [_vp, _f]),
     "mmf_model_confidence_threshold": (_f, [_vp]),
     "mmf_model_id": (_i, [_vp]),
+    "mmf_viewstore_create": (_i, [_vp, C.POINTER(_vp)]),
+    "mmf_viewstore_destroy": (None, [_vp]),
+    "mmf_viewstore_store": (_i, [_vp, _i, _i, _vp, _vp, _vp, _ip]),
+    "mmf_viewstore_forget": (_i, [_vp, _i]),
+    "mmf_viewstore_num_views": (_i, [_vp]),
+    "mmf_viewstore_view": (_i, [_vp, _i, _ip, _ip, _ip]),
+    "mmf_viewstore_match": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "mmf_viewstore_best_match": (_i, [_vp, _i, _vp, _vp, _i, _vp, _fp, _ip, _ip, _ip, _vp, _ip]),
+    "mmf_viewstore_last_launches": (_i, [_vp]),
+    "mmf_fusion_set_redetection": (_i, [_vp, _i]),
+    "mmf_fusion_set_keypoints": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "mmf_fusion_viewstore": (_vp, [_vp]),
+    "mmf_fusion_last_redetections": (_i, [_vp, C.POINTER(mmf_redetection), _i, _ip]),
 }
 
 _lib = None

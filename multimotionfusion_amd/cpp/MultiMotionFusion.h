@@ -21,6 +21,7 @@
 
 #include "GPUTexture.h"
 #include "RGBDOdometry.h"
+#include "RigidRANSAC.h"
 
 // FrameData (Core/FrameData.h:25-43) without OpenCV: one frame in HOST memory, as the log readers deliver it
 struct FrameData {
@@ -330,6 +331,48 @@ class Model {
     GPUTexture getSparseVertConfTex() const { return GPUTexture(texture("vertConf"), width_, height_, GPUTexture::RGBA32F, "vertConf"); }
     GPUTexture getSparseColorTimeTex() const { return GPUTexture(texture("colorTime"), width_, height_, GPUTexture::RGBA32F, "colorTime"); }
     GPUTexture getSparseNormalRadTex() const { return GPUTexture(texture("normRad"), width_, height_, GPUTexture::RGBA32F, "normRad"); }
+    // ----- keypoint redetection (Model.cpp:781-874, 1617-1656).  tracker::KeypointPtr lists become host arrays: n keypoints with
+    // descriptor [n][256] and coordinate [n][3].  The views live in a view store (mmf_viewstore: the fusion's for a model of a
+    // MultiMotionFusion object, set by getModels / getInactiveModels; setViewStore for a stand-alone model).
+    void setViewStore(mmf_viewstore* vs) { views_ = vs; }
+    // Model::store(model_db_path, pose, clear) without the files: the views of tracks_local = computeTrackProjectionFirstFrame(),
+    // n_views time indices with counts[v] valid keypoints each, rows one after the other, coordinates in the model's frame.
+    // false: stored before, skipped (:1618-1621)
+    bool store(int n_views, const int* counts, const float* descriptor, const float* coordinate) {
+        int stored = 0;
+        mmf::check(mmf_viewstore_store(need_views(), (int)getID(), n_views, counts, descriptor, coordinate, &stored), "mmf_viewstore_store");
+        return stored != 0;
+    }
+    struct BestMatch : RigidRANSAC::Result {
+        int view = -1;  // the time index of the winning view (-1: no estimate; transformation identity, error +inf)
+    };
+    // Model::getBestMatch(keypoints, config): the config must be the one the reference passes, {10, 0.03, 0.8}
+    // (MultiMotionFusion.cpp:513): the library constructs that RigidRANSAC itself
+    BestMatch getBestMatch(const float* descriptor, const float* coordinate, int n, const RigidRANSAC::Config& config) const {
+        if (config.iterations != 10 || config.inlier_threshold != 0.03f || config.inlier_fraction != 0.8f)
+            mmf::check(MMF_ERR_INVALID, "Model::getBestMatch: only RigidRANSAC::Config{10, 0.03, 0.8}");
+        float* dev = nullptr;
+        if (n > 0 && (hipMalloc(reinterpret_cast<void**>(&dev), (size_t)n * 256 * sizeof(float)) != hipSuccess ||
+                      hipMemcpy(dev, descriptor, (size_t)n * 256 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)) {
+            (void)hipFree(dev);
+            mmf::check(MMF_ERR_HIP, "Model::getBestMatch: upload of the descriptors");
+        }
+        BestMatch best;
+        best.inlier.assign((size_t)(n > 0 ? n : 1), 0);
+        int inliers = 0, n_matches = 0, found = 0;
+        const int rc = mmf_viewstore_best_match(need_views(), (int)getID(), dev, coordinate, n, best.transformation, &best.error, &inliers,
+                                                &best.view, &n_matches, best.inlier.data(), &found);
+        (void)hipFree(dev);
+        mmf::check(rc, "mmf_viewstore_best_match");
+        best.inlier.resize(found ? (size_t)n_matches : 0);
+        return best;
+    }
+    // Model::activate(pose, timestamp): overridePose and a pose list of one entry.  (Inside processFrame the library activates a
+    // re-detected model itself: mmf_fusion_set_redetection.)
+    void activate(const float pose[16], const int64_t& timestamp) {
+        overridePose(pose);
+        timestamp_ns_.assign(1, timestamp);
+    }
     mmf_model* handle() const { return m_; }
     mmf_odom* odometryHandle() const { return o_; }
 
@@ -356,6 +399,11 @@ class Model {
         if (hipMemcpy(host.data(), dev, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) host.clear();
         return host;
     }
+    mmf_viewstore* need_views() const {
+        if (!views_) mmf::check(MMF_ERR_STATE, "Model: no view store (setViewStore)");
+        return views_;
+    }
+    mmf_viewstore* views_ = nullptr;
     mmf_model* m_ = nullptr;
     mmf_odom* o_ = nullptr;
     bool owned_ = false;
@@ -508,8 +556,17 @@ class MultiMotionFusion {
             for (int k = 0; k < n; ++k)
                 models_.push_back(std::make_shared<Model>(mmf_fusion_model_at(f_, k), mmf_fusion_odometry_at(f_, k), width_, height_,
                                                           k == 0 && cfg_.fill_in));
+            for (auto& m : models_) m->setViewStore(mmf_fusion_viewstore(f_));
         }
         return models_;
+    }
+    ModelList& getInactiveModels() {  // inactiveModels (MultiMotionFusion.h:351): rebuilt from the native list
+        inactive_.clear();
+        for (int k = 0; k < mmf_fusion_num_inactive_models(f_); ++k) {
+            inactive_.push_back(std::make_shared<Model>(mmf_fusion_inactive_model_at(f_, k), nullptr, width_, height_, false));
+            inactive_.back()->setViewStore(mmf_fusion_viewstore(f_));
+        }
+        return inactive_;
     }
     // getTextures() (:124): the raw input images of the current frame
     std::map<std::string, GPUTexture*>& getTextures() {
@@ -570,7 +627,20 @@ class MultiMotionFusion {
     // the built-in segmentation's super-pixels from the frame's RGB on the device (the engine that replaces gSLICr,
     // cpp/Slic.h) instead of the regular grid; sp_size must divide the frame size
     void setSuperpixelEngine(bool v) { other_["superpixelEngine"] = v, mmf::check(mmf_fusion_set_superpixel_engine(f_, v ? 1 : 0), "mmf_fusion_set_superpixel_engine"); }
-    void setEnableRedetection(bool v) { other_["enableRedetection"] = v; }
+    // redetection of inactive models by their stored keypoint views (:489-559), inside processFrame; off until switched on
+    void setEnableRedetection(bool v) { other_["enableRedetection"] = v, mmf::check(mmf_fusion_set_redetection(f_, v ? 1 : 0), "mmf_fusion_set_redetection"); }
+    // the last keypoint of every visible track (track->back(), :428-436) for the next processFrame: xy [n][2] pixels,
+    // coordinate [n][3] camera frame, descriptor [n][256]
+    void setKeypoints(int n, const int* xy, const float* coordinate, const float* descriptor) {
+        mmf::check(mmf_fusion_set_keypoints(f_, n, xy, coordinate, descriptor), "mmf_fusion_set_keypoints");
+    }
+    std::vector<mmf_redetection> getLastRedetections() {
+        int n = 0;
+        mmf::check(mmf_fusion_last_redetections(f_, nullptr, 0, &n), "mmf_fusion_last_redetections");
+        std::vector<mmf_redetection> out((size_t)n);
+        if (n) mmf::check(mmf_fusion_last_redetections(f_, out.data(), n, &n), "mmf_fusion_last_redetections");
+        return out;
+    }
     void setSetInhibit(bool v) { other_["inhibitModels"] = v, crf_.inhibit_new = v ? 1 : 0, pushCrf(); }
     void setEnableSmartModelDelete(bool v) { other_["enableSmartModelDelete"] = v; }
     const std::map<std::string, float>& frontEndSettings() const { return other_; }
@@ -609,7 +679,7 @@ class MultiMotionFusion {
     OdometryConfig odom_cfg_;
     SegmentationConfiguration segm_cfg_;
     std::string exportDirectory_;
-    ModelList models_;
+    ModelList models_, inactive_;
     std::map<std::string, GPUTexture*> textures_;
     std::map<std::string, float> other_;
     mmf_crf_config crf_;

@@ -95,6 +95,15 @@ struct mmf_fusion {
     bool sp_enqueued = false;          // ev_sp_done is recorded and nothing has waited for it yet
     const int* sp_last = nullptr;      // the label image the last segmentation used (handed in, the engine's, or the grid)
     std::vector<mmf_segmentation_model> crf_models;
+    // keypoint redetection of inactive models (MultiMotionFusion.cpp:489-559; redetect_host.hpp): off unless switched on
+    bool redetect_on = false;
+    mmf_viewstore* views = nullptr;  // the stored keypoint views of the inactive models (created on first use)
+    bool kp_next = false;            // mmf_fusion_set_keypoints: the NEXT frame's keypoints
+    std::vector<int> kp_xy;
+    std::vector<float> kp_coord, kp_desc;
+    int *kp_xy_pin = nullptr, *kp_label_pin = nullptr;  // host memory the gather kernel reads / writes
+    size_t kp_cap = 0;
+    std::vector<mmf_redetection> redetections;  // what the last frame's redetection did
     hipEvent_t ev_frame_ready = nullptr;  // fusion stream: the frame's shared inputs are complete
     // next-frame prefetch (mmf_fusion_prefetch_frame): the filter and the input-side preparation of frame t+1 run
     // on `side` while frame t is fused on the context's stream.  Two filtered-depth buffers: frame t's fuse /
@@ -349,6 +358,9 @@ extern "C" void mmf_fusion_destroy(mmf_fusion* f) {
     if (f->ev_sp_begin) (void)hipEventDestroy(f->ev_sp_begin);
     if (f->ev_sp_done) (void)hipEventDestroy(f->ev_sp_done);
     if (f->sp_stream) (void)hipStreamDestroy(f->sp_stream);
+    mmf_viewstore_destroy(f->views);
+    if (f->kp_xy_pin) (void)hipHostFree(f->kp_xy_pin);
+    if (f->kp_label_pin) (void)hipHostFree(f->kp_label_pin);
     (void)hipFree(f->mask_boxes);
     (void)hipFree(f->side_partials);
     (void)hipFree(f->side_ticket);
@@ -415,6 +427,7 @@ static inline bool fusion_owns(const mmf_fusion* f, size_t index) { return index
 extern "C" int mmf_fusion_set_shard(mmf_fusion* f, int rank, int world) {
     MMF_REQUIRE(f && world >= 1 && rank >= 0 && rank < world, "mmf_fusion_set_shard: bad argument");
     MMF_REQUIRE(f->models.size() == 1 && f->inactive.empty(), "mmf_fusion_set_shard: call it before the first object model is spawned");
+    if (world > 1 && f->redetect_on) return fail(MMF_ERR_STATE, "mmf_fusion_set_shard: redetection is on (sharded redetection is not supported)");
     f->shard_rank = rank, f->shard_world = world;
     // models created ahead of their use (preallocateModels): the ones this rank will not own shrink to bookkeeping
     for (FusionModel*& fm : f->preallocated) {
@@ -1373,6 +1386,178 @@ static int fusion_crf_segment(mmf_fusion* f, mmf_segmentation* out) {
     return MMF_OK;
 }
 
+// ---- keypoint redetection (MultiMotionFusion.cpp:425-436, 489-559) ----------------------------------------------------------
+static int fusion_viewstore(mmf_fusion* f) {
+    if (f->views) return MMF_OK;
+    return mmf_viewstore_create(f->ctx, &f->views);
+}
+extern "C" mmf_viewstore* mmf_fusion_viewstore(mmf_fusion* f) {
+    if (!f || fusion_viewstore(f) != MMF_OK) return nullptr;
+    return f->views;
+}
+// setEnableRedetection (MultiMotionFusion.h:414 defaults to true; here OFF by default: every call behaves as before)
+extern "C" int mmf_fusion_set_redetection(mmf_fusion* f, int on) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_set_redetection: null fusion object");
+    if (on && f->shard_world > 1) return fail(MMF_ERR_STATE, "mmf_fusion_set_redetection: sharded redetection is not supported (world > 1)");
+    if (on) {
+        int rc = fusion_viewstore(f);
+        if (rc) return rc;
+    }
+    f->redetect_on = on != 0;
+    return MMF_OK;
+}
+// the last keypoint of every currently visible track (track->back(), :428-436) for the NEXT processFrame only: HOST arrays
+// xy [n][2] integer pixels, coordinate [n][3] camera frame (non-finite allowed), descriptor [n][256].  Copied.
+extern "C" int mmf_fusion_set_keypoints(mmf_fusion* f, int n, const int* xy, const float* coordinate, const float* descriptor) {
+    MMF_REQUIRE(f && n >= 0 && ((xy && coordinate && descriptor) || n == 0), "mmf_fusion_set_keypoints: bad argument");
+    f->kp_xy.assign(xy, xy + 2 * (size_t)n);
+    f->kp_coord.assign(coordinate, coordinate + 3 * (size_t)n);
+    f->kp_desc.assign(descriptor, descriptor + (size_t)kRdDim * (size_t)n);
+    f->kp_next = true;
+    return MMF_OK;
+}
+extern "C" int mmf_fusion_last_redetections(mmf_fusion* f, mmf_redetection* out, int capacity, int* n_out) {
+    MMF_REQUIRE(f && n_out && capacity >= 0 && (out || capacity == 0), "mmf_fusion_last_redetections: bad argument");
+    *n_out = (int)f->redetections.size();
+    for (int i = 0; i < *n_out && i < capacity; ++i) out[i] = f->redetections[(size_t)i];
+    return MMF_OK;
+}
+
+// Isometry3f::inverse(): [R^T | -(R^T t)], float, sums left to right
+static void redetect_inverse_pose(const mmf::Isometry3f& T, float pose[16]) {
+    identity16(pose);
+    for (int r = 0; r < 3; ++r) {
+        for (int q = 0; q < 3; ++q) pose[r * 4 + q] = T.R[q * 3 + r];
+        float s = T.R[0 * 3 + r] * T.t[0];
+        s = s + T.R[1 * 3 + r] * T.t[1];
+        s = s + T.R[2 * 3 + r] * T.t[2];
+        pose[r * 4 + 3] = -s;
+    }
+}
+
+// models.remove(model_act_rm) (:542): the reference drops the model; freed once nothing enqueued uses it
+static int redetect_drop_active(mmf_fusion* f, FusionModel* fm) {
+    f->models.erase(std::find(f->models.begin(), f->models.end(), fm));
+    MMF_HIP_TRY(hipStreamSynchronize(fm->lane->stream));
+    MMF_HIP_TRY(hipStreamSynchronize(f->ctx->stream));  // (batched passes and the segmentation read it from there)
+    for (FusionModel* m : f->models)
+        if (m->lane->stream != f->ctx->stream) MMF_HIP_TRY(hipStreamSynchronize(m->lane->stream));  // (a batch led by another object)
+    if (f->views) mmf_viewstore_forget(f->views, (int)fm->model->id);
+    fusion_model_destroy(fm);
+    return MMF_OK;
+}
+
+// Model::activate(pose, timestamp) (Model.cpp:1646-1656) + models.push_back (:544): the model is in the state
+// overridePose leaves (pose == lastPose), nothing prepared ahead is valid, and its stream -- idle since it left the list --
+// continues behind this frame's inputs.  Its extents (extent.hpp) need nothing: they are stamped with the frame that noted them.
+static int redetect_activate(mmf_fusion* f, FusionModel* fm, const float pose[16]) {
+    mmf_model_set_pose(fm->model, pose);
+    std::memcpy(fm->last_pose, pose, sizeof(float) * 16);
+    fm->unseen = 0;
+    fm->tracking = false, fm->early_done = false, fm->early_fused = false;
+    fm->spec_valid = false, fm->spec_hit = false;
+    fm->odom->so3_prefetched = false, fm->odom->so3_stage = nullptr;
+    f->inactive.erase(std::find(f->inactive.begin(), f->inactive.end(), fm));
+    f->models.push_back(fm);
+    if (fm->lane->stream != f->ctx->stream) return lane_wait(fm, f->ev_frame_ready);
+    return MMF_OK;
+}
+
+// :425-436 + :489-559.  Waits on the host twice: for the keypoints' labels, then for the matches of all segments.
+// *has_new: segmentationResult.hasNewLabel, cancelled by an accepted match (:522-524).
+static int frame_redetect(mmf_fusion* f, bool* has_new) {
+    const bool have_kp = f->kp_next;
+    f->kp_next = false;  // (for this frame only)
+    if (!f->redetect_on || !have_kp || f->inactive.empty() || !f->views || f->views->views.empty()) return MMF_OK;
+    mmf_ctx* c = f->ctx;
+    mmf_viewstore* vs = f->views;
+    const size_t n = f->kp_xy.size() / 2;
+    if (n == 0) return MMF_OK;
+    if (n > f->kp_cap) {
+        if (f->kp_xy_pin) (void)hipHostFree(f->kp_xy_pin);
+        if (f->kp_label_pin) (void)hipHostFree(f->kp_label_pin);
+        f->kp_xy_pin = f->kp_label_pin = nullptr, f->kp_cap = 0;
+        const size_t cap = n + n / 2 + 64;
+        MMF_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&f->kp_xy_pin), cap * 2 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+        MMF_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&f->kp_label_pin), cap * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+        f->kp_cap = cap;
+    }
+    std::memcpy(f->kp_xy_pin, f->kp_xy.data(), n * 2 * sizeof(int));
+    hipLaunchKernelGGL(mmf::rd_gather_labels_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t*)f->mask,
+                       f->width, f->height, (const int*)f->kp_xy_pin, (int)n, f->kp_label_pin);
+    MMF_HIP_TRY(hipGetLastError());
+    MMF_HIP_TRY(wait_stream(c->stream));  // wait 1: the labels
+    // per label other than 0 and 255 the keypoints with finite coordinates (:494-507), labels ascending
+    std::vector<std::vector<int>> by_label(256);
+    for (size_t i = 0; i < n; ++i) {
+        const int l = f->kp_label_pin[i];
+        const float* p = f->kp_coord.data() + 3 * i;
+        if (l <= 0 || l >= 255) continue;
+        if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]))) continue;
+        by_label[(size_t)l].push_back((int)i);
+    }
+    std::vector<RdSet> sets;
+    std::vector<int> set_label;
+    size_t total_q = 0;
+    for (int l = 1; l < 255; ++l) {
+        if (by_label[(size_t)l].size() < 3) continue;  // min_tracks (:493, :507)
+        sets.push_back(RdSet{nullptr, (int)by_label[(size_t)l].size(), total_q});
+        set_label.push_back(l);
+        total_q += by_label[(size_t)l].size();
+    }
+    if (sets.empty()) return MMF_OK;
+    int rc = viewstore_stage(vs, total_q);
+    if (rc) return rc;
+    std::vector<float> coords(total_q * 3);
+    for (size_t s = 0; s < sets.size(); ++s) {
+        sets[s].q = vs->q_dev + sets[s].q0 * kRdDim;
+        const std::vector<int>& idx = by_label[(size_t)set_label[s]];
+        for (size_t k = 0; k < idx.size(); ++k) {
+            std::memcpy(vs->q_pin + (sets[s].q0 + k) * kRdDim, f->kp_desc.data() + (size_t)idx[k] * kRdDim, kRdDim * sizeof(float));
+            std::memcpy(coords.data() + (sets[s].q0 + k) * 3, f->kp_coord.data() + (size_t)idx[k] * 3, 3 * sizeof(float));
+        }
+    }
+    MMF_HIP_TRY(hipMemcpyAsync(vs->q_dev, vs->q_pin, total_q * kRdDim * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    rc = viewstore_enqueue(vs, c->stream, sets.data(), (int)sets.size());
+    if (rc) return rc;
+    MMF_HIP_TRY(wait_stream(c->stream));  // wait 2: the matches of every segment against every view
+    for (size_t s = 0; s < sets.size(); ++s) {
+        const int label = set_label[s];
+        for (size_t mi = 0; mi < f->inactive.size();) {
+            FusionModel* im = f->inactive[mi];
+            const RdBest best = viewstore_best(vs, (int)im->model->id, sets[s], coords.data() + sets[s].q0 * 3, kRedetectRansac);
+            if (!(best.found && (double)best.error < 0.01 && best.inliers > 5)) {  // :516
+                ++mi;
+                continue;
+            }
+            *has_new = false;  // :522-524
+            mmf_redetection rd;
+            std::memset(&rd, 0, sizeof(rd));
+            rd.label = label, rd.model_id = (int)im->model->id, rd.removed_id = -1, rd.activated = 0;
+            rd.error = best.error, rd.inliers = best.inliers, rd.view = best.view;
+            isometry_to_4x4(best.transformation, rd.transformation);
+            FusionModel* act = fusion_find(f, label);
+            if (act && act->model->id < im->model->id) {  // an older model is not replaced by a newer one (:537-541)
+                f->redetections.push_back(rd);
+                ++mi;
+                continue;
+            }
+            if (act) {
+                rd.removed_id = (int)act->model->id;
+                rc = redetect_drop_active(f, act);
+                if (rc) return rc;
+            }
+            float pose[16];
+            redetect_inverse_pose(best.transformation, pose);  // activate(best.transformation.inverse(), ...) (:545)
+            rc = redetect_activate(f, im, pose);  // (leaves the inactive list: inactive[mi] is the next one)
+            if (rc) return rc;
+            rd.activated = 1;
+            f->redetections.push_back(rd);
+        }
+    }
+    return MMF_OK;
+}
+
 // :407-622: the segmentation's mask, a new model's first surfels, models that leave the list, confidence thresholds
 static int frame_segment(mmf_fusion* f, const FrameRun& r) {
     const mmf_frame* fr = r.fr;
@@ -1398,8 +1583,16 @@ static int frame_segment(mmf_fusion* f, const FrameRun& r) {
     f->mask_is_zero = false;
     MMF_HIP_TRY(hipEventRecord(f->ev_frame_ready, c->stream));
     const int n_data = seg->model_data ? seg->n_models : 0;
+    // redetection via keypoints (:489-559) runs BEFORE a model is spawned: a label it cancels (:522-524) consumes neither an id
+    // nor a preallocated model (the reference spawns first and abandons newModel, :468-487, :565)
+    bool has_new = seg->has_new_label != 0;
+    {
+        int rc = frame_redetect(f, &has_new);
+        if (rc) return rc;
+    }
+    if (seg->has_new_label && !has_new) f->spawn_offset = 0;  // (the reference had spawned already: :484)
     FusionModel* fresh = nullptr;
-    if (seg->has_new_label) {  // :469-487
+    if (has_new) {  // :469-487
         int rc = fusion_spawn(f, &fresh);
         if (rc) return rc;
         f->spawn_offset = 0;  // (:484)
@@ -1668,6 +1861,7 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
     r.have_init = fr->init_transforms != nullptr && fr->n_init_transforms > 0;
     r.track = f->tick > 1 && (fr->bootstrap || !fr->in_pose);
     f->t_tracking_s = 0;
+    f->redetections.clear();  // (mmf_fusion_last_redetections speaks of this call)
     int rc = frame_begin(f, r);
     if (rc) return rc;
     const bool first = f->tick == 1;
@@ -1689,6 +1883,7 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
         r.stamp(f, 2);
     }
     f->sp_next = false;  // (mmf_fusion_set_superpixels: this call's labels only, whichever segmentation ran)
+    f->kp_next = false;  // (mmf_fusion_set_keypoints: this call's keypoints only, whether or not a segmentation ran)
     r.pass_mode = fusion_batch_mode(f);  // (the model list stays as it is from here to the end of the call)
     if (!first) {
         rc = frame_fuse_clean(f, r);
@@ -2052,6 +2247,10 @@ extern "C" int mmf_fusion_reset(mmf_fusion* f) {
     f->models.resize(1);
     f->inactive.clear();
     f->scheduled_deactivation.clear();
+    if (f->views)  // the stored views belonged to the models of the map that ends here
+        for (RdView& v : f->views->views) v.model = -1;
+    f->kp_next = false;
+    f->redetections.clear();
     std::vector<FusionModel*> all(f->preallocated);
     all.push_back(f->models[0]);
     for (FusionModel* fm : all) {

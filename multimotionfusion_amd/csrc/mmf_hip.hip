@@ -3318,6 +3318,11 @@ extern "C" int mmf_ransac_estimate(mmf_ransac* r, const float* p0, const float* 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Keypoint redetection: the view store and Model::getBestMatch (Core/Model/Model.cpp:781-874)
+// ---------------------------------------------------------------------------------------------
+#include "redetect_host.hpp"
+
+// ---------------------------------------------------------------------------------------------
 // SuperPoint keypoint network (Core/MultiMotionFusion.cpp:78,233)
 // ---------------------------------------------------------------------------------------------
 #include "superpoint_host.hpp"

@@ -275,6 +275,36 @@ class MultiMotionFusion:
         from .segmentation import _last
         return _last(self.ctx.lib.mmf_fusion_last_segmentation, self.handle, torch.device("cuda", self.ctx.device))
 
+    # ----- keypoint redetection of inactive models (MultiMotionFusion.cpp:489-559; redetection.py)
+    def setEnableRedetection(self, on):
+        """off by default; with it on, processFrame re-activates an inactive model whose stored keypoint views match the
+        keypoints (setKeypoints) of a segment of the frame"""
+        check(self.ctx.lib.mmf_fusion_set_redetection(self.handle, 1 if on else 0))
+
+    def setKeypoints(self, xy, coordinate, descriptor):
+        """the last keypoint of every currently visible track, for the NEXT processFrame only: xy [n,2] integer pixels,
+        coordinate [n,3] camera frame (non-finite allowed), descriptor [n,256]"""
+        xy = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
+        n = xy.shape[0]
+        co = np.ascontiguousarray(coordinate, np.float32).reshape(n, 3)
+        de = np.ascontiguousarray(descriptor, np.float32).reshape(n, 256)
+        check(self.ctx.lib.mmf_fusion_set_keypoints(self.handle, n, xy.ctypes.data, co.ctypes.data, de.ctypes.data))
+
+    def getViewStore(self):
+        from .redetection import ViewStore
+        h = self.ctx.lib.mmf_fusion_viewstore(self.handle)
+        if not h:
+            check(-1)
+        return ViewStore(self.ctx, C.c_void_p(h), owner=self)
+
+    def storeViews(self, model_id, views):
+        """Model::store of an inactive model's keypoint views (redetection.ViewStore.store)"""
+        return self.getViewStore().store(model_id, views)
+
+    def getLastRedetections(self):
+        from .redetection import last_redetections
+        return last_redetections(self.ctx, self.handle)
+
     def getConfig(self):
         cfg = mmf_fusion_config()
         check(self.ctx.lib.mmf_fusion_get_config(self.handle, C.byref(cfg)))

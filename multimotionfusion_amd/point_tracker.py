@@ -128,6 +128,93 @@ def getLastTrackTransform(tracks, config=(10, 0.03, 0.6)):
     return T, inlier
 
 
+def project_kp(kp, T):
+    """project_kp (Model.cpp:130-141): the keypoint in the frame T maps the camera frame to (double, like the reference)"""
+    if kp is None:
+        return None
+    T = np.asarray(T, np.float32).astype(np.float64)
+    return Keypoint(kp.timestamp, kp.xy, T[:3, :3] @ np.asarray(kp.coordinate, np.float64) + T[:3, 3], kp.descriptor)
+
+
+class ModelTracks:
+    """The keypoint bookkeeping of one Model the stored views come from: `tracks` (camera-frame tracks associated with the
+    model, Model.h), the per-frame pose list `poses` / `timestamp_ns`, `tracks_local` (the stored views)."""
+
+    def __init__(self, model_id):
+        self.id = int(model_id)
+        self.tracks = {}  # id(track) -> track: the reference's std::set of shared pointers, here in insertion order
+        self.poses, self.timestamp_ns, self.tracks_local = [], [], []
+
+    def initGlobalTracks(self, tracks, initial_pose, time):
+        """Model.cpp:620-628"""
+        assert not self.poses and not self.tracks
+        self.tracks = {id(t): t for t in tracks}
+        self.timestamp_ns.append(int(time))
+        self.poses.append(np.asarray(initial_pose, np.float32).reshape(4, 4).copy())
+
+    def addPose(self, pose, time):
+        """one entry of the per-frame pose list (camera frame -> model frame at that frame)"""
+        self.timestamp_ns.append(int(time))
+        self.poses.append(np.asarray(pose, np.float32).reshape(4, 4).copy())
+
+    def updateTracks(self, tracks_add, tracks_remove):
+        """Model.cpp:630-640"""
+        assert self.poses
+        for t in tracks_add:
+            self.tracks[id(t)] = t
+        for t in tracks_remove:
+            self.tracks.pop(id(t), None)
+
+    def computeTrackProjectionFirstFrame(self):
+        """Model.cpp:508-522: every track's last len(poses) keypoints in the model's frame"""
+        assert len(self.poses) == len(self.timestamp_ns)
+        local = []
+        for track in self.tracks.values():
+            if not track:
+                continue
+            assert len(track) >= len(self.poses)
+            offset = len(track) - len(self.poses)
+            local.append([project_kp(track[offset + ip], self.poses[ip]) for ip in range(len(self.poses))])
+        return local
+
+    def store(self, clear=False):
+        """Model::store (Model.cpp:1617-1644) without the files: False when stored before (nothing changes)"""
+        if self.tracks_local:
+            return False
+        self.tracks_local = self.computeTrackProjectionFirstFrame()
+        if clear:
+            self.tracks = {}
+        return True
+
+    def views(self):
+        """the stored views as Model::getBestMatch builds them (Model.cpp:798-816): per time index the descriptors and
+        coordinates (float32) of the keypoints that exist and are finite"""
+        out = []
+        if not self.tracks_local:
+            return out
+        for i in range(len(self.tracks_local[0])):
+            kps = [t[i] for t in self.tracks_local if t[i] is not None and np.all(np.isfinite(t[i].coordinate))]
+            desc = np.stack([k.descriptor for k in kps]).astype(np.float32) if kps else np.zeros((0, 256), np.float32)
+            coord = np.stack([k.coordinate for k in kps]).astype(np.float32) if kps else np.zeros((0, 3), np.float32)
+            out.append((desc, coord))
+        return out
+
+    def activate(self, pose, timestamp):
+        """Model::activate (Model.cpp:1646-1656): the stored tracks become the model's tracks, one pose"""
+        self.tracks = {id(t): t for t in self.tracks_local}
+        self.poses = [np.asarray(pose, np.float32).reshape(4, 4).copy()]
+        self.timestamp_ns = [int(timestamp)]
+
+
+def visibleKeypoints(tracks):
+    """track->back() of every track that has one (MultiMotionFusion.cpp:428-431) -> (tracks, xy, coordinate, descriptor)"""
+    vis = [t for t in tracks if t and t[-1] is not None]
+    xy = np.array([t[-1].xy for t in vis], np.int32).reshape(-1, 2)
+    co = np.array([t[-1].coordinate for t in vis], np.float32).reshape(-1, 3)
+    de = np.array([t[-1].descriptor for t in vis], np.float32).reshape(len(vis), -1)
+    return vis, xy, co, de
+
+
 class KeypointFrontEnd:
     """The keypoint half of processFrame for one pyramid level (MultiMotionFusion.cpp:223-248, 286-296, 322-337):
     SuperPoint features -> PointTracker -> getLastTrackTransform -> processFrame(initTransform=...)."""
@@ -136,14 +223,61 @@ class KeypointFrontEnd:
         self.ctx, self.fusion, self.kp, self.icp_refine = ctx, fusion, kp_predictor, icp_refine
         self.tracker = PointTracker(ctx, intrinsics)
         self.last_inlier = None
+        self.model_tracks = {}  # model id -> ModelTracks (redetection)
+        self.redetection = False
+
+    def setEnableRedetection(self, on):
+        """hand the frame's keypoints to processFrame and store the views of models that turn up in the inactive list"""
+        self.redetection = bool(on)
+        self.fusion.setEnableRedetection(on)
+
+    def _before_frame(self):
+        if not self.redetection:
+            return None
+        vis, xy, co, de = visibleKeypoints(self.tracker.getTracks())
+        self.fusion.setKeypoints(xy, co, de)
+        return vis, xy
+
+    def _after_frame(self, handed, timestamp):
+        """:584-604 updateTracks per visible model from the frame's id image; Model::store for new inactive models;
+        Model::activate for re-detected ones"""
+        if handed is None or not self.fusion.getConfig().enable_multiple_models:
+            return
+        vis, xy = handed
+        mask = self.fusion.getTexture("MASK").cpu().numpy()
+        h, w = mask.shape
+        by_label = {}
+        for t, (x, y) in zip(vis, xy):
+            if 0 <= x < w and 0 <= y < h:
+                by_label.setdefault(int(mask[y, x]), []).append(t)
+        models = self.fusion.getModels()
+        poses = {m.id: m.getPose() for m in models[1:]}  # an object model's pose maps the camera frame to the model's frame
+        activated = set()
+        for rd in self.fusion.getLastRedetections():
+            if rd["activated"] and rd["model_id"] in self.model_tracks and rd["model_id"] in poses:
+                self.model_tracks[rd["model_id"]].activate(poses[rd["model_id"]], timestamp)  # = transformation^-1
+                activated.add(rd["model_id"])
+        for m in models[1:]:
+            mt = self.model_tracks.setdefault(m.id, ModelTracks(m.id))
+            if m.id not in activated:
+                mt.addPose(poses[m.id], timestamp)
+            if m.id in by_label:
+                remove = [t for l, ts in by_label.items() if l != m.id for t in ts]
+                mt.updateTracks(by_label[m.id], remove)
+        for m in self.fusion.getInactiveModels():
+            mt = self.model_tracks.get(m.id)
+            if mt is not None and mt.store():
+                self.fusion.storeViews(m.id, mt.views())
 
     def processFrame(self, rgb, depth, timestamp, weightMultiplier=1.0):
         coordinates, descriptors = self.kp.getFeatures(rgb)
         self.tracker.addKeypoints(coordinates, descriptors, timestamp, depth.cpu().numpy(), 0.7, 30)
         self.tracker.prune(30, max(int(timestamp) - int(1e9), 0))  # :246
+        handed = self._before_frame()
         if self.fusion.getTick() == 1:
             self.fusion.processFrame(rgb, depth, timestamp=timestamp, weightMultiplier=weightMultiplier)
             return
         T, self.last_inlier = getLastTrackTransform(self.tracker.getTracks())
         self.fusion.processFrame(rgb, depth, timestamp=timestamp, weightMultiplier=weightMultiplier, initTransform=T,
                                  icpRefine=self.icp_refine)
+        self._after_frame(handed, timestamp)

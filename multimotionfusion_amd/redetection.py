@@ -1,0 +1,102 @@
+"""Keypoint redetection of inactive models through the C ABI: the view store (all stored keypoint views of all models in
+one device buffer, csrc/redetect_kernels.hpp) and Model::getBestMatch (Core/Model/Model.cpp:781-874) -- no fallback."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from ._capi import check, fptr, mmf_redetection
+from .cudafuncs import Context, _p
+
+DIM = 256
+
+
+class ViewStore:
+    """views of a model = list of (descriptor [n,256] float32, coordinate [n,3] float32 in the model's frame), one entry per
+    time index of the stored tracks, valid keypoints only (n may be 0)."""
+
+    def __init__(self, ctx: Context, handle=None, owner=None):
+        self.ctx, self._owner = ctx, owner  # (a borrowed store lives as long as the fusion that owns it)
+        self._own = handle is None
+        if handle is None:
+            handle = C.c_void_p()
+            check(ctx.lib.mmf_viewstore_create(ctx.handle, C.byref(handle)))
+        self.handle = handle
+
+    def store(self, model_id, views):
+        """Model::store: False when the model has stored views already (nothing changes, Model.cpp:1618-1621)"""
+        counts = np.array([len(d) for d, _ in views], np.int32)
+        total = int(counts.sum())
+        desc = np.zeros((total, DIM), np.float32)
+        coord = np.zeros((total, 3), np.float32)
+        o = 0
+        for d, c in views:
+            n = len(d)
+            if n:
+                desc[o:o + n], coord[o:o + n] = np.asarray(d, np.float32).reshape(n, DIM), np.asarray(c, np.float32).reshape(n, 3)
+            o += n
+        stored = C.c_int()
+        check(self.ctx.lib.mmf_viewstore_store(self.handle, int(model_id), len(views), counts.ctypes.data, desc.ctypes.data,
+                                               coord.ctypes.data, C.byref(stored)))
+        return bool(stored.value)
+
+    def forget(self, model_id):
+        check(self.ctx.lib.mmf_viewstore_forget(self.handle, int(model_id)))
+
+    def views(self):
+        """[(model id, view index inside the model, valid keypoints)] in store order"""
+        out = []
+        m, i, r = C.c_int(), C.c_int(), C.c_int()
+        for v in range(self.ctx.lib.mmf_viewstore_num_views(self.handle)):
+            check(self.ctx.lib.mmf_viewstore_view(self.handle, v, C.byref(m), C.byref(i), C.byref(r)))
+            out.append((m.value, i.value, r.value))
+        return out
+
+    def match(self, query: torch.Tensor):
+        """query [nq,256] float32 CUDA tensor against every view -> (trainIdx [views,nq] int32, -1 = unmatched; distance)"""
+        assert query.dtype == torch.float32 and query.is_cuda and (query.shape[0] == 0 or query.shape[1] == DIM)
+        query = query.contiguous()
+        nq, nv = query.shape[0], self.ctx.lib.mmf_viewstore_num_views(self.handle)
+        idx, dist = np.full((nv, nq), -1, np.int32), np.zeros((nv, nq), np.float32)
+        check(self.ctx.lib.mmf_viewstore_match(self.handle, _p(query) if nq else None, nq, idx.ctypes.data, dist.ctypes.data))
+        return idx, dist
+
+    def lastLaunches(self):
+        return self.ctx.lib.mmf_viewstore_last_launches(self.handle)
+
+    def bestMatch(self, model_id, query: torch.Tensor, coordinate):
+        """Model::getBestMatch(keypoints, {10, 0.03, 0.8}) -> dict(found, transformation 4x4, error, inliers, view,
+        n_matches, inlier [n_matches] bool over the hash-sorted matches)"""
+        assert query.dtype == torch.float32 and query.is_cuda
+        query = query.contiguous()
+        nq = query.shape[0]
+        coord = np.ascontiguousarray(coordinate, np.float32).reshape(nq, 3)
+        T = np.zeros((4, 4), np.float32)
+        err, inl, view, nm, found = C.c_float(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        mask = np.zeros(max(nq, 1), np.uint8)
+        check(self.ctx.lib.mmf_viewstore_best_match(self.handle, int(model_id), _p(query) if nq else None, coord.ctypes.data, nq,
+                                                    T.ctypes.data, C.byref(err), C.byref(inl), C.byref(view), C.byref(nm),
+                                                    mask.ctypes.data, C.byref(found)))
+        return dict(found=bool(found.value), transformation=T, error=err.value, inliers=inl.value, view=view.value,
+                    n_matches=nm.value, inlier=mask[:nm.value].astype(bool))
+
+    def close(self):
+        if self._own and self.handle and self.ctx.handle:
+            self.ctx.lib.mmf_viewstore_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def last_redetections(ctx, fusion_handle):
+    n = C.c_int()
+    check(ctx.lib.mmf_fusion_last_redetections(fusion_handle, None, 0, C.byref(n)))
+    arr = (mmf_redetection * max(n.value, 1))()
+    check(ctx.lib.mmf_fusion_last_redetections(fusion_handle, arr, n.value, C.byref(n)))
+    return [dict(label=r.label, model_id=r.model_id, removed_id=r.removed_id, activated=bool(r.activated), error=r.error,
+                 inliers=r.inliers, view=r.view, transformation=np.array(r.transformation, np.float32).reshape(4, 4))
+            for r in arr[:n.value]]
