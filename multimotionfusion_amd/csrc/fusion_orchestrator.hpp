@@ -653,9 +653,9 @@ static void odom_alias_sensor_side(mmf_odom* o, const mmf_odom* primary) {
 
 // where an OBJECT model's latest prediction is non-zero (device, PassBoxes::spl_nz of its last resolve), for a model-side
 // preparation that may then leave the rest of the frame alone; null: unknown, or not such a model
-static const int* fusion_pred_box(const FusionModel* fm, int side) {
+static const int* fusion_pred_box(const FusionModel* fm) {
     const mmf_model* m = fm->model;
-    if (side != PREP_MODEL_SIDE || fm->fill_in || !fm->odom->sparse || !m->boxes || !m->spl_nz_known) return nullptr;
+    if (fm->fill_in || !fm->odom->sparse || !m->boxes || !m->spl_nz_known) return nullptr;
     return m->boxes->spl_nz[m->sgen & 1u];
 }
 // the covered thumbnail samples of a model's latest prediction (thumbnail_count_px)
@@ -845,12 +845,25 @@ static void fusion_collect_prep(mmf_fusion* f, PrepStages& stages, FusionModel* 
                                 unsigned ext_gen) {
     const mmf_fusion_config& g = f->cfg;
     const mmf_model* m = fm->model;
-    const uint8_t* pi = (const uint8_t*)((g.frame_to_frame_rgb && fm->fill_in) ? m->fill_image : m->image);
-    odom_prepare_collect(stages, fm->odom, f->depth_filtered, g.max_depth_processed, f->frame_rgb, 3, (const float*)m->vertexConf,
-                         (const float*)m->normalRadius, pi, 4, pose, fm->fill_in ? fusion_thumb_count(m) : nullptr,
-                         (const float*)m->fill_vertex, (const float*)m->fill_normal, (const uint8_t*)m->fill_image, side,
-                         (m->width / 20) * (m->height / 20), 0.75f, boxed && fm->odom->sparse ? ext_gen : 0u,
-                         boxed ? fusion_pred_box(fm, side) : nullptr);
+    PrepPrediction p;
+    p.vertex = (const float*)m->vertexConf, p.normal = (const float*)m->normalRadius;
+    p.image = (const uint8_t*)((g.frame_to_frame_rgb && fm->fill_in) ? m->fill_image : m->image);
+    p.channels = 4;
+    p.pose = pose;
+    p.depth_l0 = f->depth_filtered;
+    p.sel = fm->fill_in ? fusion_thumb_count(m) : nullptr;
+    p.alt_vertex = (const float*)m->fill_vertex, p.alt_normal = (const float*)m->fill_normal, p.alt_image = (const uint8_t*)m->fill_image;
+    p.sel_total = (m->width / 20) * (m->height / 20), p.sel_ratio = 0.75f;
+    p.ext_gen = boxed && fm->odom->sparse ? ext_gen : 0u;
+    if (side == PREP_ALL) {
+        PrepSensorFrame fr;
+        fr.depth_filtered = f->depth_filtered, fr.depth_cutoff = g.max_depth_processed;
+        fr.rgb = f->frame_rgb, fr.channels = 3;
+        prep_collect_all(stages, fm->odom, fr, p);
+    } else {
+        p.pred_box = boxed ? fusion_pred_box(fm) : nullptr;
+        prep_collect_model(stages, fm->odom, p);
+    }
 }
 
 // The Gauss-Newton chains (Model::performTracking, Model.cpp:409-433) of n tracked models, from their poses or, on a retrack,
@@ -970,10 +983,10 @@ static int frame_track_sensor_side(mmf_fusion* f, FrameRun& r) {
     }
     r.one_pass = n_models == 1 && !r.have_init && fusion_owns(f, 0) && !global->spec_hit;
     if (!r.prefetched && !r.one_pass) {
-        float identity[16];
-        identity16(identity);
-        int rc = odom_prepare_batched(global->odom, f->depth_filtered, g.max_depth_processed, fr->rgb, 3, nullptr, nullptr, nullptr, 4,
-                                      identity, nullptr, nullptr, nullptr, nullptr, PREP_INPUT_IMAGE | PREP_INPUT_DEPTH);
+        PrepSensorFrame sf;
+        sf.depth_filtered = f->depth_filtered, sf.depth_cutoff = g.max_depth_processed;
+        sf.rgb = fr->rgb, sf.channels = 3;
+        int rc = odom_prepare_sensor(global->odom, sf, PREP_INPUT_IMAGE | PREP_INPUT_DEPTH);
         if (rc) return rc;
         odom_adopt_gradients(global->odom);
     }
@@ -2150,13 +2163,12 @@ static int fusion_prefetch_init(mmf_fusion* f) {
 static int fusion_prefetch_image(mmf_fusion* f, const uint8_t* rgb, int tick_at_use, bool ahead) {
     const mmf_fusion_config& g = f->cfg;
     mmf_odom* odom = f->models[0]->odom;
-    float identity[16];
-    identity16(identity);
     hipStream_t img_stream = f->side2;
     if (!ahead && f->inputs_free_recorded) MMF_HIP_TRY(hipStreamWaitEvent(img_stream, f->ev_inputs_free, 0));
     Enqueuer qi(img_stream);
-    int rc = odom_prepare_batched(odom, nullptr, g.max_depth_processed, rgb, 3, nullptr, nullptr, nullptr, 4, identity, nullptr,
-                                  nullptr, nullptr, nullptr, PREP_INPUT_IMAGE, img_stream, &qi);
+    PrepSensorFrame sf;
+    sf.rgb = rgb, sf.channels = 3;
+    int rc = odom_prepare_sensor(odom, sf, PREP_INPUT_IMAGE, &qi);
     if (rc) return rc;
     f->so3_stage_ready = -1;
     if (g.so3 && tick_at_use > 1) {  // a model exists: the frame will be tracked, SO3 first
@@ -2188,8 +2200,6 @@ static int fusion_prefetch_impl(mmf_fusion* f, const uint8_t* rgb, const float* 
     }
     if (f->inputs_free_recorded) MMF_HIP_TRY(hipStreamWaitEvent(f->side, f->ev_inputs_free, 0));
     const mmf_fusion_config& g = f->cfg;
-    float identity[16];
-    identity16(identity);
     // depth chain (first side stream): filter, depth pyramid, vertex and normal maps -- what the chains' ICP term reads,
     // hence behind ev_inputs_free.  Enqueued before the image chain when that is still to come: it is five launches that
     // start with the 40 us filter, the image chain fifteen short ones.
@@ -2197,8 +2207,9 @@ static int fusion_prefetch_impl(mmf_fusion* f, const uint8_t* rgb, const float* 
     Enqueuer qd(f->side);
     int rc = filter_depth_on(c, qd, depth, f->width, f->height, g.depth_cutoff, target);
     if (rc) return rc;
-    rc = odom_prepare_batched(odom, target, g.max_depth_processed, rgb, 3, nullptr, nullptr, nullptr, 4, identity, nullptr,
-                              nullptr, nullptr, nullptr, PREP_INPUT_DEPTH, f->side, &qd);
+    PrepSensorFrame sf;
+    sf.depth_filtered = target, sf.depth_cutoff = g.max_depth_processed;
+    rc = odom_prepare_sensor(odom, sf, PREP_INPUT_DEPTH, &qd);
     if (rc) return rc;
     MMF_HIP_TRY(qd.flush());
     if (f->image_pre_rgb != rgb) {  // (else: enqueued at the start of the frame)

@@ -817,7 +817,7 @@ struct mmf_odom {
     bool alias_inputs = false;
     const float *vtmp = nullptr, *ntmp = nullptr;  // what populateRGBDData / copyMaps read: own copy or alias
     const float* depth_l0 = nullptr;               // level 0 of the depth pyramid: own copy or alias
-    // set by odom_prepare_batched: gradients and point clouds are already built, and next_depth is
+    // set by the batched model-side preparation (prep_collect_model): gradients and point clouds are already built, and next_depth is
     // last_depth (both come from the same prediction, RGBDOdometry.cpp:179 -- see odom_populate_rgbd)
     bool prep_batched = false;
     bool so3_prefetched = false;  // this frame's SO3 pre-alignment already ran (odom_prefetch_so3)
@@ -1219,231 +1219,209 @@ struct PrepStages {  // the four dependent launches of a frame's preparation
 // Everything initICPModel + initRGBModel + generateCUDATextures/initICP + initRGB + the gradient and
 // point-cloud passes of getIncrementalTransformation compute (RGBDOdometry.cpp:108-235, 332-334;
 // Model.cpp:359-407), for inputs that stay untouched until tracking returns (the native orchestrator).
-// `sel` (device, may be null): when *sel != 0 the prediction is read from the alt_* images instead.
-// `side`: the jobs split into those that depend only on the NEW sensor frame (filtered depth, RGB: vertex / normal
-// maps, depth and intensity pyramids, gradients) and those that depend on the model's prediction and pose.
-// The orchestrator can run the first group for frame t+1 on a second stream while frame t is still being fused
-// (mmf_fusion_prefetch_frame); PREP_ALL is both groups in the same four launches.
+// The jobs split into those that depend only on the NEW sensor frame (filtered depth, RGB: vertex / normal maps, depth
+// and intensity pyramids, gradients: prep_collect_sensor) and those that depend on the model's prediction and pose
+// (prep_collect_model).  The orchestrator can run the first group for frame t+1 on a second stream while frame t is still
+// being fused (mmf_fusion_prefetch_frame); PREP_ALL is both groups in the same four launches (prep_collect_all).
+// Which stage a job goes to, and where in it, is fixed (prep_batch.hpp: the one arrangement): a stage's list of jobs decides
+// which workgroup of the launch does what.
 enum PrepSide { PREP_INPUT_IMAGE = 1, PREP_INPUT_DEPTH = 2, PREP_MODEL_SIDE = 4, PREP_ALL = 7 };
+
+struct PrepSensorFrame {  // what the sensor side reads
+    const float* depth_filtered = nullptr;  // the depth side's input
+    float depth_cutoff = 0.f;
+    const uint8_t* rgb = nullptr;  // the image side's input: interleaved, `channels` bytes per pixel
+    int channels = 3;
+};
+struct PrepPrediction {  // what the model side reads: a model's prediction and the pose it is tracked from
+    const float *vertex = nullptr, *normal = nullptr;  // RGBA32F
+    const uint8_t* image = nullptr;
+    int channels = 4;
+    const float* pose = nullptr;      // row-major 4 x 4
+    const float* depth_l0 = nullptr;  // the frame's filtered depth, which the model's chain reads as level 0 of the depth pyramid
+    // optional device-side choice of the sources (PrepJob::sel): the alt_* images instead when *sel != 0 or, with sel_total
+    // != 0, when fewer than sel_ratio of the sel_total thumbnail samples are covered
+    const int* sel = nullptr;
+    const float *alt_vertex = nullptr, *alt_normal = nullptr;
+    const uint8_t* alt_image = nullptr;
+    int sel_total = 0;
+    float sel_ratio = 0.f;
+    unsigned ext_gen = 0;  // != 0: the jobs that write the model's depth and vertex pyramids note the extent of what is valid (extent.hpp)
+    // (device, level-0 pixels {x0, y0, x1, y1}; an OBJECT model prepared on its own only): where the prediction's images are
+    // non-zero -- the jobs then cover the hull of that box and of the one the previous preparation saw (PrepJob::rect_*)
+    const int* pred_box = nullptr;
+};
 
 static std::atomic<int> g_prep_rect{-1};  // -1: MMF_PREP_RECT decides (default on); 0 / 1: mmf_debug_set_prep_rect
 extern "C" int mmf_debug_set_prep_rect(int on) {
     g_prep_rect.store(on < 0 ? -1 : (on ? 1 : 0));
     return MMF_OK;
 }
-static void odom_prepare_collect(PrepStages& stages, mmf_odom* o, const float* depth_filtered, float depth_cutoff, const uint8_t* rgb,
-                                 int rgb_channels, const float* pred_vertex, const float* pred_normal,
-                                 const uint8_t* pred_image, int pred_channels, const float pose[16],
-                                 const int* sel = nullptr, const float* alt_vertex = nullptr,
-                                 const float* alt_normal = nullptr, const uint8_t* alt_image = nullptr,
-                                 int side = PREP_ALL, int sel_total = 0, float sel_ratio = 0.f, unsigned ext_gen = 0,
-                                 const int* pred_box = nullptr) {
-    // pred_box (device, level-0 pixels {x0, y0, x1, y1}; an OBJECT model's model side only): where the prediction's images are
-    // non-zero -- the jobs then cover the hull of that box and of the one the previous preparation saw (PrepJob::rect_*)
-    const bool in_img = (side & PREP_INPUT_IMAGE) != 0, in_depth = (side & PREP_INPUT_DEPTH) != 0;
-    const bool model_side = (side & PREP_MODEL_SIDE) != 0;
-    size_t jobs_before[4];
-    for (int k = 0; k < 4; ++k) jobs_before[k] = stages.stage[k].jobs.size();
-    const int W = o->width, H = o->height;
-    const size_t n0 = (size_t)W * H;
-    // camera-frame model pyramids (before the transform into the global frame) live in the two 4*N-float
-    // staging images, which this path does not need as copies: 3*N*(1 + 1/4 + 1/16) floats each
-    float* uv[3] = {o->vmaps_tmp, o->vmaps_tmp + 3 * n0, o->vmaps_tmp + 3 * n0 + 3 * (n0 / 4)};
-    float* un[3] = {o->nmaps_tmp, o->nmaps_tmp + 3 * n0, o->nmaps_tmp + 3 * n0 + 3 * (n0 / 4)};
-    // The coarsest level's model-side products (transformed + packed maps, point cloud) are computed in the SAME stage as
-    // its pyramid step, from the level above (PREP_RESIZE_TP, PREP_PYR_PROJECT): the model side is three dependent launches
-    // instead of four.  MMF_PREP_MERGE=0: the four-stage form (A/B aid).
-    const bool merge_last = tunables().prep_merge != 0;
-    // ... and level 0 and the first pyramid step are computed straight from the prediction's images (PREP_TEX_*): two
-    // dependent launches.  MMF_PREP_MERGE=1: only the last stage merged (A/B aid).
-    const bool merge_first = tunables().prep_merge >= 2;
-    // The model maps in the global frame go out as the packed records (and {X, Y, Z, 1/Z} point records) the chains gather
-    // from; the planar copies and the AoS cloud of the first-generation kernels (25 -> 14 MB written per frame at level 0)
-    // only on request: MMF_PREP_PLANAR=1.
-    const bool planar = tunables().prep_planar;
-    // The sensor frame's normal map of a level is computed in the same job as its vertex map, from the depth image
-    // (PREP_VMAP_NMAP): the depth side is three dependent launches instead of four.  MMF_PREP_VN=0: apart (A/B aid).
-    const bool merge_vn = tunables().prep_vn;
-    // ext_gen != 0: the jobs that write the model's depth and vertex pyramids note the extent of what is valid (extent.hpp)
-    const bool note_extent = model_side && merge_first && merge_last && ext_gen != 0;
-    auto noted = [&](PrepJob& j, int lvl) {  // (the depth jobs: extent.hpp, extent_of_level)
-        if (note_extent) j.ext = o->extent + 4 * lvl, j.ext_gen = ext_gen;
-    };
-    if (model_side) o->extent_gen = note_extent ? ext_gen : 0u;
-    auto intr_f = [&](PrepJob& j, int lvl, bool cutoff_too, float cutoff) {
-        const LevelIntr in = level_intr(o->fx, o->fy, o->cx, o->cy, lvl);
-        j.f[0] = 1.f / in.fx, j.f[1] = 1.f / in.fy, j.f[2] = in.cx, j.f[3] = in.cy;
-        if (cutoff_too) j.f[4] = cutoff;
-    };
-    auto pyr = [&](PrepBuilder& pb, int op, const void* src, void* dst, int lvl) {  // level lvl-1 -> lvl
-        PrepJob& j = pb.add(op, W >> lvl, H >> lvl);
-        j.src0 = src, j.dst0 = dst;
-        j.scols = W >> (lvl - 1), j.srows = H >> (lvl - 1);
-    };
-    auto level_jobs = [&](PrepBuilder& pb, int lvl) {  // jobs whose inputs are the level-lvl images
-        const int cols = W >> lvl, rows = H >> lvl;
-        if (model_side && merge_first && lvl == 0) {  // from the prediction's images
-            const float R[9] = {pose[0], pose[1], pose[2], pose[4], pose[5], pose[6], pose[8], pose[9], pose[10]};
-            PrepJob& t = pb.add(PREP_TEX_TP, cols, rows);
-            t.src0 = pred_vertex, t.src1 = pred_normal, t.sel = sel, t.alt0 = alt_vertex, t.alt1 = alt_normal;
-            t.dst0 = planar ? o->vmaps_g_prev[0] : nullptr, t.dst1 = planar ? o->nmaps_g_prev[0] : nullptr, t.dst2 = o->prev_packed[0];
-            for (int k = 0; k < 9; ++k) t.f[k] = R[k];
-            t.f[9] = pose[3], t.f[10] = pose[7], t.f[11] = pose[11];
-            if (note_extent) t.aabb = o->extent, t.ext_gen = ext_gen;  // (extent.hpp: the pixel box and depth range of the valid vertices)
-            PrepJob& p = pb.add(PREP_TEX_PROJECT, cols, rows);
-            p.src0 = pred_vertex, p.sel = sel, p.alt0 = alt_vertex;
-            p.dst0 = planar ? o->cloud[0] : nullptr, p.dst1 = o->cloud4[0], p.dst2 = o->last_depth[0];
-            intr_f(p, 0, false, 0.f);
-            p.f[4] = o->max_depth_rgb;
-            noted(p, 0);
-            PrepJob& il = pb.add(PREP_INTENSITY, W, H);
-            il.src0 = pred_image, il.dst0 = o->last_image[0], il.scols = W * pred_channels, il.channels = pred_channels;
-            il.sel = sel, il.alt0 = alt_image;
-        } else if (model_side && !(merge_last && lvl == MMF_NUM_PYRS - 1)) {
-            PrepJob& t = pb.add(PREP_TRANSFORM_PACK, cols, rows);
-            t.src0 = uv[lvl], t.src1 = un[lvl];
-            t.dst0 = planar ? o->vmaps_g_prev[lvl] : nullptr, t.dst1 = planar ? o->nmaps_g_prev[lvl] : nullptr, t.dst2 = o->prev_packed[lvl];
-            const float R[9] = {pose[0], pose[1], pose[2], pose[4], pose[5], pose[6], pose[8], pose[9], pose[10]};
-            for (int k = 0; k < 9; ++k) t.f[k] = R[k];
-            t.f[9] = pose[3], t.f[10] = pose[7], t.f[11] = pose[11];
-            PrepJob& p = pb.add(PREP_PROJECT, cols, rows);
-            p.src0 = o->last_depth[lvl], p.dst0 = planar ? o->cloud[lvl] : nullptr, p.dst1 = o->cloud4[lvl];
-            intr_f(p, lvl, false, 0.f);
-        }
-        if (in_img) {
-            PrepJob& d = pb.add(PREP_DERIV, cols, rows);
-            d.src0 = o->next_image[lvl], d.dst0 = o->grad_w_dx[lvl], d.dst1 = o->grad_w_dy[lvl];  // (odom_adopt_gradients)
-        }
-        if (in_depth && !merge_vn) {
-            PrepJob& nm = pb.add(PREP_NMAP, cols, rows);
-            nm.src0 = o->vmaps_curr[lvl], nm.dst0 = o->nmaps_curr[lvl];
-        }
-    };
-    auto vmap_job = [&](PrepBuilder& pb, int lvl, const float* depth) {
-        PrepJob& j = pb.add(merge_vn ? PREP_VMAP_NMAP : PREP_VMAP, W >> lvl, H >> lvl);
-        j.src0 = depth, j.dst0 = o->vmaps_curr[lvl], j.dst1 = o->nmaps_curr[lvl];
-        intr_f(j, lvl, true, depth_cutoff);
+
+static void prep_intr_f(PrepJob& j, const mmf_odom* o, int lvl) {  // f = {1/fx, 1/fy, cx, cy} of a level
+    const LevelIntr in = level_intr(o->fx, o->fy, o->cx, o->cy, lvl);
+    j.f[0] = 1.f / in.fx, j.f[1] = 1.f / in.fy, j.f[2] = in.cx, j.f[3] = in.cy;
+}
+static void prep_pose_f(PrepJob& j, const float pose[16]) {  // f = {R[9], t[3]}
+    for (int r = 0; r < 3; ++r) {
+        for (int q = 0; q < 3; ++q) j.f[3 * r + q] = pose[4 * r + q];
+        j.f[9 + r] = pose[4 * r + 3];
+    }
+}
+static PrepJob& prep_pyr_step(PrepBuilder& pb, const mmf_odom* o, int op, const void* src, void* dst, int lvl) {  // level lvl-1 -> lvl
+    PrepJob& j = pb.add(op, o->width >> lvl, o->height >> lvl);
+    j.src0 = src, j.dst0 = dst;
+    j.scols = o->width >> (lvl - 1), j.srows = o->height >> (lvl - 1);
+    return j;
+}
+// the fill-in images a model-side job reads instead of the prediction's when the device says so (PrepPrediction::sel)
+static void prep_alt(PrepJob& j, const PrepPrediction& p, const void* alt0, const void* alt1 = nullptr) {
+    j.sel = p.sel, j.alt0 = alt0, j.alt1 = alt1;
+    if (p.sel && p.sel_total) j.sel_total = p.sel_total, j.sel_ratio = p.sel_ratio;  // *sel is a count (PrepJob::sel_total)
+}
+
+// depth side: stage k makes level k's vertex and normal maps and level k+1 of the depth pyramid -- three dependent launches
+static void prep_depth_jobs(PrepStages& stages, mmf_odom* o, const PrepSensorFrame& fr) {
+    const float* depth[MMF_NUM_PYRS] = {fr.depth_filtered, o->depth_pyr[1], o->depth_pyr[2]};
+    for (int lvl = 0; lvl < MMF_NUM_PYRS; ++lvl) {
+        PrepBuilder& pb = stages.stage[lvl];
+        if (lvl + 1 < MMF_NUM_PYRS) prep_pyr_step(pb, o, PREP_PYRDOWN_F, depth[lvl], o->depth_pyr[lvl + 1], lvl + 1);
+        PrepJob& j = pb.add(PREP_VMAP_NMAP, o->width >> lvl, o->height >> lvl);
+        j.src0 = depth[lvl], j.dst0 = o->vmaps_curr[lvl], j.dst1 = o->nmaps_curr[lvl];
+        prep_intr_f(j, o, lvl);
+        j.f[4] = fr.depth_cutoff;
         if (lvl == 0) {  // (extent.hpp: the sensor frame's smallest valid depth, for the object models' error-image launches)
             j.zmin = o->extent, j.zmin_gen = ++o->sensor_gen;
-            o->sensor_cutoff = depth_cutoff;
+            o->sensor_cutoff = fr.depth_cutoff;
         }
-    };
-    auto down_jobs = [&](PrepBuilder& pb, int lvl, const float* depth_src) {  // level lvl-1 -> lvl of every pyramid
-        if (in_img) pyr(pb, PREP_PYRDOWN_U8, o->next_image[lvl - 1], o->next_image[lvl], lvl);
-        if (model_side && merge_first && lvl == 1) {  // from the prediction's images
-            const int cols = W >> 1, rows = H >> 1;
-            PrepJob& d = pb.add(PREP_TEX_PYR_F, cols, rows);
-            d.src0 = pred_vertex, d.sel = sel, d.alt0 = alt_vertex, d.scols = W, d.srows = H;
-            d.dst0 = o->last_depth[1], d.f[0] = o->max_depth_rgb;
-            noted(d, 1);
-            PrepJob& u = pb.add(PREP_TEX_PYR_U8, cols, rows);
-            u.src0 = pred_image, u.sel = sel, u.alt0 = alt_image, u.scols = W, u.srows = H, u.channels = pred_channels;
-            u.dst0 = o->last_image[1];
-            PrepJob& r = pb.add(PREP_TEX_RESIZE, cols, rows);
-            r.src0 = pred_vertex, r.src1 = pred_normal, r.sel = sel, r.alt0 = alt_vertex, r.alt1 = alt_normal, r.scols = W, r.srows = H;
-            r.dst0 = uv[1], r.dst1 = un[1];
-        } else if (model_side && merge_last && lvl == MMF_NUM_PYRS - 1) {
-            pyr(pb, PREP_PYRDOWN_U8, o->last_image[lvl - 1], o->last_image[lvl], lvl);
-            const int cols = W >> lvl, rows = H >> lvl;
-            PrepJob& t = pb.add(PREP_RESIZE_TP, cols, rows);
-            t.src0 = uv[lvl - 1], t.src1 = un[lvl - 1], t.scols = W >> (lvl - 1), t.srows = H >> (lvl - 1);
-            t.dst0 = planar ? o->vmaps_g_prev[lvl] : nullptr, t.dst1 = planar ? o->nmaps_g_prev[lvl] : nullptr, t.dst2 = o->prev_packed[lvl];
-            const float R[9] = {pose[0], pose[1], pose[2], pose[4], pose[5], pose[6], pose[8], pose[9], pose[10]};
-            for (int k = 0; k < 9; ++k) t.f[k] = R[k];
-            t.f[9] = pose[3], t.f[10] = pose[7], t.f[11] = pose[11];
-            PrepJob& p = pb.add(PREP_PYR_PROJECT, cols, rows);
-            p.src0 = o->last_depth[lvl - 1], p.scols = W >> (lvl - 1), p.srows = H >> (lvl - 1);
-            p.dst0 = planar ? o->cloud[lvl] : nullptr, p.dst1 = o->cloud4[lvl], p.dst2 = o->last_depth[lvl];
-            intr_f(p, lvl, false, 0.f);
-            noted(p, lvl);
-        } else if (model_side) {
-            pyr(pb, PREP_PYRDOWN_F, o->last_depth[lvl - 1], o->last_depth[lvl], lvl);
-            pyr(pb, PREP_PYRDOWN_U8, o->last_image[lvl - 1], o->last_image[lvl], lvl);
-            pyr(pb, PREP_RESIZE_V, uv[lvl - 1], uv[lvl], lvl);
-            pyr(pb, PREP_RESIZE_N, un[lvl - 1], un[lvl], lvl);
-        }
-        (void)depth_src;
-    };
+    }
+}
+// image side: the intensity image in stage 0, then stage k+1 makes level k's gradients and level k+1 of the pyramid -- four
+static void prep_image_jobs(PrepStages& stages, mmf_odom* o, const PrepSensorFrame& fr) {
+    PrepJob& in = stages.stage[0].add(PREP_INTENSITY, o->width, o->height);
+    in.src0 = fr.rgb, in.dst0 = o->next_image[0], in.scols = o->width * fr.channels, in.channels = fr.channels;
+    for (int lvl = 0; lvl < MMF_NUM_PYRS; ++lvl) {
+        PrepBuilder& pb = stages.stage[lvl + 1];
+        PrepJob& d = pb.add(PREP_DERIV, o->width >> lvl, o->height >> lvl);
+        d.src0 = o->next_image[lvl], d.dst0 = o->grad_w_dx[lvl], d.dst1 = o->grad_w_dy[lvl];  // (odom_adopt_gradients)
+        if (lvl + 1 < MMF_NUM_PYRS) prep_pyr_step(pb, o, PREP_PYRDOWN_U8, o->next_image[lvl], o->next_image[lvl + 1], lvl + 1);
+    }
+    o->grad_pending = true;
+}
+static void prep_collect_sensor(PrepStages& stages, mmf_odom* o, const PrepSensorFrame& fr, int sides) {
+    if (sides & PREP_INPUT_DEPTH) prep_depth_jobs(stages, o, fr);
+    if (sides & PREP_INPUT_IMAGE) prep_image_jobs(stages, o, fr);
+}
 
-    if (model_side) {
-        o->depth_l0 = depth_filtered;
-        o->vtmp = pred_vertex, o->ntmp = pred_normal;
-        o->have_tmp = true;
+// Model side, two dependent launches (stages 1 and 2).  Level 1 of the camera-frame model maps (before the transform into
+// the global frame) is the one thing a job stores for another: it lives behind level 0's place in the two 4*N-float staging
+// images, which this path does not need as copies.
+static float* prep_level1_of(float* staging, const mmf_odom* o) { return staging + 3 * (size_t)o->width * o->height; }
+// ... what is made from a level's images: the packed records and the point records of levels 0 and 1, level 0's depth and
+// intensity.  Nothing of the preparation reads level 0's, which come straight from the prediction: l0_stage is 2, beside the
+// small jobs of levels 1 and 2, so that the first launch is the three quarter-size pyramid jobs alone (1: with a sensor side
+// in the same launches)
+static void prep_model_level_jobs(PrepStages& stages, mmf_odom* o, const PrepPrediction& p, int l0_stage) {
+    const int W = o->width, H = o->height;
+    {
+        PrepBuilder& pb = stages.stage[l0_stage];
+        PrepJob& t = pb.add(PREP_TEX_TP, W, H);
+        t.src0 = p.vertex, t.src1 = p.normal, t.dst2 = o->prev_packed[0];
+        prep_alt(t, p, p.alt_vertex, p.alt_normal);
+        prep_pose_f(t, p.pose);
+        if (p.ext_gen) t.aabb = o->extent, t.ext_gen = p.ext_gen;  // (extent.hpp: the pixel box and depth range of the valid vertices)
+        PrepJob& c = pb.add(PREP_TEX_PROJECT, W, H);
+        c.src0 = p.vertex, c.dst1 = o->cloud4[0], c.dst2 = o->last_depth[0];
+        prep_alt(c, p, p.alt_vertex);
+        prep_intr_f(c, o, 0);
+        c.f[4] = o->max_depth_rgb;
+        if (p.ext_gen) c.ext = o->extent, c.ext_gen = p.ext_gen;  // (the depth jobs: extent.hpp, extent_of_level)
+        PrepJob& il = pb.add(PREP_INTENSITY, W, H);
+        il.src0 = p.image, il.dst0 = o->last_image[0], il.scols = W * p.channels, il.channels = p.channels;
+        prep_alt(il, p, p.alt_image);
     }
-
-    {   // stage 1: inputs -> level 0 (and level 1 of the depth pyramid)
-        PrepBuilder& pb = stages.stage[0];
-        if (in_depth) {
-            pyr(pb, PREP_PYRDOWN_F, depth_filtered, o->depth_pyr[1], 1);
-            vmap_job(pb, 0, depth_filtered);
-        }
-        if (in_img) {
-            PrepJob& in = pb.add(PREP_INTENSITY, W, H);
-            in.src0 = rgb, in.dst0 = o->next_image[0], in.scols = W * rgb_channels, in.channels = rgb_channels;
-        }
-        if (model_side && !merge_first) {
-            PrepJob& v = pb.add(PREP_V2D, W, H);
-            v.src0 = pred_vertex, v.dst0 = o->last_depth[0], v.f[0] = o->max_depth_rgb;
-            v.sel = sel, v.alt0 = alt_vertex;
-            PrepJob& il = pb.add(PREP_INTENSITY, W, H);
-            il.src0 = pred_image, il.dst0 = o->last_image[0], il.scols = W * pred_channels, il.channels = pred_channels;
-            il.sel = sel, il.alt0 = alt_image;
-            PrepJob& cm = pb.add(PREP_COPY_MAPS, W, H);
-            cm.src0 = pred_vertex, cm.src1 = pred_normal, cm.dst0 = uv[0], cm.dst1 = un[0];
-            cm.sel = sel, cm.alt0 = alt_vertex, cm.alt1 = alt_normal;
-        }
-    }
-    {   // stage 2: level 0 -> level 1 (and level 2 of the depth pyramid)
-        PrepBuilder& pb = stages.stage[1];
-        if (in_depth) {
-            pyr(pb, PREP_PYRDOWN_F, o->depth_pyr[1], o->depth_pyr[2], 2);
-            vmap_job(pb, 1, o->depth_pyr[1]);
-        }
-        // The model side's level-0 products come straight from the prediction's images (merge_first) and nothing of the
-        // preparation reads them: they go into the LAST of its two launches, beside the small jobs of levels 1 and 2, and the
-        // first launch is the three quarter-size pyramid jobs alone (MMF_PREP_L0_LATE=0: in the first, as before).
-        const bool l0_late = tunables().prep_l0_late;
-        level_jobs(model_side && merge_first && merge_last && l0_late && !in_img && !in_depth ? stages.stage[2] : pb, 0);
-        down_jobs(pb, 1, nullptr);
-    }
-    {   // stage 3: level 1 -> level 2
+    {
         PrepBuilder& pb = stages.stage[2];
-        if (in_depth) vmap_job(pb, 2, o->depth_pyr[2]);
-        level_jobs(pb, 1);
-        down_jobs(pb, 2, nullptr);
+        PrepJob& t = pb.add(PREP_TRANSFORM_PACK, W >> 1, H >> 1);
+        t.src0 = prep_level1_of(o->vmaps_tmp, o), t.src1 = prep_level1_of(o->nmaps_tmp, o), t.dst2 = o->prev_packed[1];
+        prep_pose_f(t, p.pose);
+        PrepJob& c = pb.add(PREP_PROJECT, W >> 1, H >> 1);
+        c.src0 = o->last_depth[1], c.dst1 = o->cloud4[1];
+        prep_intr_f(c, o, 1);
     }
-    {   // stage 4: level 2
-        PrepBuilder& pb = stages.stage[3];
-        level_jobs(pb, 2);
+}
+// ... and the pyramid steps: level 1 from the prediction's images, level 2 -- with its records, in the same job -- from level 1
+static void prep_model_pyramid_jobs(PrepStages& stages, mmf_odom* o, const PrepPrediction& p) {
+    const int W = o->width, H = o->height;
+    {
+        PrepBuilder& pb = stages.stage[1];
+        PrepJob& d = pb.add(PREP_TEX_PYR_F, W >> 1, H >> 1);
+        d.src0 = p.vertex, d.scols = W, d.srows = H, d.dst0 = o->last_depth[1], d.f[0] = o->max_depth_rgb;
+        prep_alt(d, p, p.alt_vertex);
+        if (p.ext_gen) d.ext = o->extent + 4, d.ext_gen = p.ext_gen;
+        PrepJob& u = pb.add(PREP_TEX_PYR_U8, W >> 1, H >> 1);
+        u.src0 = p.image, u.scols = W, u.srows = H, u.channels = p.channels, u.dst0 = o->last_image[1];
+        prep_alt(u, p, p.alt_image);
+        PrepJob& r = pb.add(PREP_TEX_RESIZE, W >> 1, H >> 1);
+        r.src0 = p.vertex, r.src1 = p.normal, r.scols = W, r.srows = H;
+        r.dst0 = prep_level1_of(o->vmaps_tmp, o), r.dst1 = prep_level1_of(o->nmaps_tmp, o);
+        prep_alt(r, p, p.alt_vertex, p.alt_normal);
     }
-    if (model_side) {
-        const bool rect_on = g_prep_rect.load() < 0 ? tunables().prep_rect : g_prep_rect.load() != 0;
-        const bool rect = pred_box != nullptr && side == PREP_MODEL_SIDE && sel == nullptr && rect_on && o->prep_box != nullptr;
-        if (rect) {
-            const unsigned g = ++o->prep_gen;
-            bool first = true;
-            for (int k = 0; k < 4; ++k)
-                for (size_t q = jobs_before[k]; q < stages.stage[k].jobs.size(); ++q) {
-                    PrepJob& j = stages.stage[k].jobs[q];
-                    int lvl = 0;
-                    while ((W >> lvl) > j.cols && lvl < MMF_NUM_PYRS - 1) ++lvl;
-                    j.rect_now = pred_box, j.rect_prev = o->prep_box_known ? o->prep_box + 4 * ((g + 1u) & 1u) : nullptr;
-                    j.rect_level = lvl;
-                    j.rect_groups = lvl == 0 ? 48 : (lvl == 1 ? 32 : 16);
-                    j.rect_store = first ? o->prep_box + 4 * (g & 1u) : nullptr;
-                    first = false;
-                }
-            o->prep_box_known = true;
-        } else {
-            o->prep_box_known = false;
-        }
-        o->prep_batched = true;
+    {
+        PrepBuilder& pb = stages.stage[2];
+        prep_pyr_step(pb, o, PREP_PYRDOWN_U8, o->last_image[1], o->last_image[2], 2);
+        PrepJob& t = prep_pyr_step(pb, o, PREP_RESIZE_TP, prep_level1_of(o->vmaps_tmp, o), nullptr, 2);
+        t.src1 = prep_level1_of(o->nmaps_tmp, o), t.dst2 = o->prev_packed[2];
+        prep_pose_f(t, p.pose);
+        PrepJob& c = prep_pyr_step(pb, o, PREP_PYR_PROJECT, o->last_depth[1], nullptr, 2);
+        c.dst1 = o->cloud4[2], c.dst2 = o->last_depth[2];
+        prep_intr_f(c, o, 2);
+        if (p.ext_gen) c.ext = o->extent + 8, c.ext_gen = p.ext_gen;
     }
-    if (in_img) o->grad_pending = true;
-    if (sel && sel_total)  // *sel is a count (PrepJob::sel_total)
-        for (PrepBuilder& pb : stages.stage)
-            for (PrepJob& j : pb.jobs)
-                if (j.sel == sel) j.sel_total = sel_total, j.sel_ratio = sel_ratio;
+}
+// what the odometry remembers of a model-side preparation.  from (null: not boxed): the jobs of `stages` from these counts
+// on are this preparation's, and they cover the prediction's box only (PrepPrediction::pred_box)
+static void prep_model_done(PrepStages& stages, mmf_odom* o, const PrepPrediction& p, const size_t* from) {
+    o->depth_l0 = p.depth_l0;
+    o->vtmp = p.vertex, o->ntmp = p.normal;
+    o->have_tmp = true;
+    o->extent_gen = p.ext_gen;
+    if (from) {
+        const unsigned g = ++o->prep_gen;
+        const int* prev = o->prep_box_known ? o->prep_box + 4 * ((g + 1u) & 1u) : nullptr;
+        bool first = true;
+        for (int k = 0; k < 4; ++k)
+            for (size_t q = from[k]; q < stages.stage[k].jobs.size(); ++q) {
+                PrepJob& j = stages.stage[k].jobs[q];
+                int lvl = 0;
+                while ((o->width >> lvl) > j.cols && lvl < MMF_NUM_PYRS - 1) ++lvl;
+                j.rect_now = p.pred_box, j.rect_prev = prev;
+                j.rect_level = lvl;
+                j.rect_groups = lvl == 0 ? 48 : (lvl == 1 ? 32 : 16);
+                j.rect_store = first ? o->prep_box + 4 * (g & 1u) : nullptr;
+                first = false;
+            }
+    }
+    o->prep_box_known = from != nullptr;
+    o->prep_batched = true;
+}
+static void prep_collect_model(PrepStages& stages, mmf_odom* o, const PrepPrediction& p) {
+    const bool rect_on = g_prep_rect.load() < 0 ? tunables().prep_rect : g_prep_rect.load() != 0;
+    const bool boxed = p.pred_box != nullptr && p.sel == nullptr && rect_on && o->prep_box != nullptr;
+    size_t from[4];
+    for (int k = 0; k < 4; ++k) from[k] = stages.stage[k].jobs.size();
+    prep_model_level_jobs(stages, o, p, 2);
+    prep_model_pyramid_jobs(stages, o, p);
+    prep_model_done(stages, o, p, boxed ? from : nullptr);
+}
+// One model and a sensor side not prepared ahead: both in the same four launches.  Within a stage: the depth side's jobs, what
+// the model makes from a level's images, the image side's jobs, the model's pyramid steps.
+static void prep_collect_all(PrepStages& stages, mmf_odom* o, const PrepSensorFrame& fr, const PrepPrediction& p) {
+    prep_depth_jobs(stages, o, fr);
+    prep_model_level_jobs(stages, o, p, 1);
+    prep_image_jobs(stages, o, fr);
+    prep_model_pyramid_jobs(stages, o, p);
+    prep_model_done(stages, o, p, nullptr);
 }
 // the gradients the batched preparation wrote last become the ones the chain reads
 static void odom_adopt_gradients(mmf_odom* o) {
@@ -1452,17 +1430,11 @@ static void odom_adopt_gradients(mmf_odom* o) {
     for (int i = 0; i < MMF_NUM_PYRS; ++i) std::swap(o->dIdx[i], o->grad_w_dx[i]), std::swap(o->dIdy[i], o->grad_w_dy[i]);
 }
 
-static int odom_prepare_batched(mmf_odom* o, const float* depth_filtered, float depth_cutoff, const uint8_t* rgb,
-                                int rgb_channels, const float* pred_vertex, const float* pred_normal,
-                                const uint8_t* pred_image, int pred_channels, const float pose[16],
-                                const int* sel = nullptr, const float* alt_vertex = nullptr,
-                                const float* alt_normal = nullptr, const uint8_t* alt_image = nullptr,
-                                int side = PREP_ALL, hipStream_t stream = nullptr, Enqueuer* q = nullptr) {
+// one or both halves of a sensor frame's side, as launches of their own: recorded in q (the caller flushes) or on the context's stream
+static int odom_prepare_sensor(mmf_odom* o, const PrepSensorFrame& fr, int sides, Enqueuer* q = nullptr) {
     PrepStages stages;
-    odom_prepare_collect(stages, o, depth_filtered, depth_cutoff, rgb, rgb_channels, pred_vertex, pred_normal, pred_image,
-                         pred_channels, pose, sel, alt_vertex, alt_normal, alt_image, side);
-    if (q) return stages.launch(*q);
-    return stages.launch(stream ? stream : o->ctx->stream);
+    prep_collect_sensor(stages, o, fr, sides);
+    return q ? stages.launch(*q) : stages.launch(o->ctx->stream);
 }
 
 static IcpArgs odom_icp_args(mmf_odom* o, int level, float* err_map) {

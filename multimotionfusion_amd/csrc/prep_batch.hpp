@@ -12,6 +12,10 @@
 // model side (prediction -> pyramids, global-frame maps, point clouds) is TWO dependent launches (PREP_TEX_*, PREP_RESIZE_TP,
 // PREP_PYR_PROJECT), the depth side of the sensor frame THREE (PREP_VMAP_NMAP), its image side four; a launch on the
 // model's stream costs ~4.5 us before it does anything, which is most of what a small stage takes.
+// This is the ONE arrangement of the jobs (mmf_hip.hip: prep_collect_sensor, prep_collect_model); the earlier ones -- four and
+// three model-side stages, vertex and normal maps as two jobs, planar model maps and an AoS cloud beside the records -- were
+// measured against it in LABNOTES rounds 3 to 5 and are gone.  The model maps in the global frame go out as the packed
+// records and the {X, Y, Z, 1/Z} point records the chains gather from, nothing else.
 #pragma once
 #include "extent.hpp"
 #include "icp_kernels.hpp"
@@ -20,31 +24,26 @@
 namespace mmf {
 
 enum PrepOp : int {
-    PREP_VMAP,            // src0 depth -> dst0 vmap                          f = {1/fx, 1/fy, cx, cy, cutoff}
-    PREP_NMAP,            // src0 vmap -> dst0 nmap
-    PREP_TRANSFORM_PACK,  // src0 vmap, src1 nmap -> dst0 vmap, dst1 nmap, dst2 packed records   f = {R[9], t[3]}
-    PREP_COPY_MAPS,       // src0, src1 RGBA32F prediction -> dst0, dst1 planar
-    PREP_RESIZE_V,        // src0 (scols x srows) -> dst0
-    PREP_RESIZE_N,
-    PREP_PYRDOWN_F,       // src0 (scols x srows) -> dst0
+    // (the stand-alone kernels named below are those of map_kernels.hpp: a job computes what they would, with what one of them
+    // would have written to memory for the next staying in registers.  Same per-pixel functions on the same values: same bits.)
+    PREP_VMAP_NMAP,       // create_vmap + create_nmap of a level: src0 depth -> dst0 vmap, dst1 nmap   f = {1/fx, 1/fy, cx, cy, cutoff}
+    PREP_PYRDOWN_F,       // src0 (scols x srows) -> dst0: the sensor frame's depth pyramid
     PREP_PYRDOWN_U8,
-    PREP_V2D,             // src0 RGBA32F vertices -> dst0 depth                f = {cutoff}
     PREP_INTENSITY,       // src0 interleaved u8 (stride scols bytes, `channels`) -> dst0
     PREP_DERIV,           // src0 u8 -> dst0 dIdx, dst1 dIdy
-    PREP_PROJECT,         // src0 depth -> dst0 AoS cloud, dst1 {X, Y, Z, 1/Z} records   f = {1/fx, 1/fy, cx, cy}
+    PREP_TRANSFORM_PACK,  // transform_maps + pack_prev: src0 vmap, src1 nmap -> dst2 packed records   f = {R[9], t[3]}
+    PREP_PROJECT,         // src0 depth -> dst1 {X, Y, Z, 1/Z} records   f = {1/fx, 1/fy, cx, cy}
     // The coarsest level's products straight from the level above (the pyramid step's value stays in a register), so that the
     // chain of stages ends one launch earlier:
-    PREP_RESIZE_TP,       // PREP_RESIZE_V + PREP_RESIZE_N + PREP_TRANSFORM_PACK: src0 vmap, src1 nmap (scols x srows) -> dst0, dst1, dst2   f = {R[9], t[3]}
-    PREP_PYR_PROJECT,     // PREP_PYRDOWN_F + PREP_PROJECT: src0 depth (scols x srows) -> dst2 depth, dst0 cloud, dst1 records   f = {1/fx, 1/fy, cx, cy}
-    // Level 0 and the first pyramid step straight from the prediction's RGBA32F / RGBA8 images (what PREP_V2D, PREP_INTENSITY
-    // and PREP_COPY_MAPS would have written to memory first stays in registers), so that the chain of stages STARTS one launch
-    // later: the model side is two dependent launches.  Same per-pixel functions on the same values: same bits.
-    PREP_TEX_TP,          // PREP_COPY_MAPS + PREP_TRANSFORM_PACK: src0, src1 prediction -> dst0, dst1, dst2   f = {R[9], t[3]}
-    PREP_TEX_PROJECT,     // PREP_V2D + PREP_PROJECT: src0 vertices -> dst2 depth, dst0 cloud, dst1 records   f = {1/fx, 1/fy, cx, cy, cutoff}
-    PREP_TEX_PYR_F,       // PREP_V2D + PREP_PYRDOWN_F: src0 vertices (scols x srows) -> dst0 depth   f = {cutoff}
+    PREP_RESIZE_TP,       // resize_map (vertices, normals) + PREP_TRANSFORM_PACK: src0 vmap, src1 nmap (scols x srows) -> dst2   f = {R[9], t[3]}
+    PREP_PYR_PROJECT,     // PREP_PYRDOWN_F + PREP_PROJECT: src0 depth (scols x srows) -> dst2 depth, dst1 records   f = {1/fx, 1/fy, cx, cy}
+    // Level 0 and the first pyramid step straight from the prediction's RGBA32F / RGBA8 images, so that the chain of stages
+    // STARTS one launch later: the model side is two dependent launches.
+    PREP_TEX_TP,          // copy_maps + PREP_TRANSFORM_PACK: src0, src1 prediction -> dst2   f = {R[9], t[3]}
+    PREP_TEX_PROJECT,     // vertices_to_depth + PREP_PROJECT: src0 vertices -> dst2 depth, dst1 records   f = {1/fx, 1/fy, cx, cy, cutoff}
+    PREP_TEX_PYR_F,       // vertices_to_depth + PREP_PYRDOWN_F: src0 vertices (scols x srows) -> dst0 depth   f = {cutoff}
     PREP_TEX_PYR_U8,      // PREP_INTENSITY + PREP_PYRDOWN_U8: src0 image (scols x srows pixels of `channels` bytes) -> dst0
-    PREP_VMAP_NMAP,       // PREP_VMAP + PREP_NMAP of the same level: src0 depth -> dst0 vmap, dst1 nmap   f = {1/fx, 1/fy, cx, cy, cutoff}
-    PREP_TEX_RESIZE,      // PREP_COPY_MAPS + PREP_RESIZE_V + PREP_RESIZE_N: src0, src1 prediction (scols x srows) -> dst0 vmap, dst1 nmap
+    PREP_TEX_RESIZE,      // copy_maps + resize_map (vertices, normals): src0, src1 prediction (scols x srows) -> dst0 vmap, dst1 nmap
 };
 
 struct PrepJob {
@@ -74,7 +73,7 @@ struct PrepJob {
     // non-null (PREP_TEX_TP of an object model): the job notes the pixel box and the depth range of the valid vertices it
     // reads into these extent words (extent.hpp: aabb_note), with ext_gen
     unsigned long long* aabb;
-    // non-null (the sensor side's level-0 PREP_VMAP / PREP_VMAP_NMAP): the job notes the smallest valid depth it reads into the
+    // non-null (the sensor side's level-0 PREP_VMAP_NMAP): the job notes the smallest valid depth it reads into the
     // extent words (extent.hpp: sensor_zmin_note) with zmin_gen
     unsigned long long* zmin;
     unsigned zmin_gen;
@@ -106,27 +105,12 @@ using PrepBatchWide = PrepBatchT<kMaxPrepJobsWide>;
 // transform_maps_px + pack_prev_kernel in one pass (same arithmetic; an invalid pixel's record is all NaN)
 // (v_ok / n_ok: the source vertex / normal is valid, i.e. its x is not NaN)
 // returns the global-frame vertex (NaN when the source is invalid)
-__device__ __forceinline__ f3 transform_pack_store(int x, int y, int rows, int cols, bool v_ok, f3 vs, bool n_ok, f3 ns, m33 R, f3 t,
-                                                   float* __restrict__ vdst, float* __restrict__ ndst, float* __restrict__ packed) {
-    // (vdst / ndst: the planar copies, or null -- the chains gather from the packed records only)
+__device__ __forceinline__ f3 transform_pack_store(int x, int y, int cols, bool v_ok, f3 vs, bool n_ok, f3 ns, m33 R, f3 t,
+                                                   float* __restrict__ packed) {
     f3 vd = make_f3(qnan(), qnan(), qnan());
-    if (v_ok) {
-        vd = R * vs + t;
-        if (vdst) {
-            vdst[(size_t)(y + rows) * cols + x] = vd.y;
-            vdst[(size_t)(y + 2 * rows) * cols + x] = vd.z;
-        }
-    }
-    if (vdst) vdst[(size_t)y * cols + x] = vd.x;
+    if (v_ok) vd = R * vs + t;
     f3 nd = make_f3(qnan(), qnan(), qnan());
-    if (n_ok) {
-        nd = R * ns;
-        if (ndst) {
-            ndst[(size_t)(y + rows) * cols + x] = nd.y;
-            ndst[(size_t)(y + 2 * rows) * cols + x] = nd.z;
-        }
-    }
-    if (ndst) ndst[(size_t)y * cols + x] = nd.x;
+    if (n_ok) nd = R * ns;
     float2* o = reinterpret_cast<float2*>(packed + 6 * ((size_t)y * cols + x));
     o[0] = make_float2(vd.x, vd.y);
     o[1] = make_float2(vd.z, nd.x);
@@ -138,8 +122,7 @@ struct PrepNote {
     float lo[3], hi[3];
 };
 __device__ __forceinline__ bool transform_pack_px(int x, int y, int rows, int cols, const float* __restrict__ vsrc,
-                                                  const float* __restrict__ nsrc, m33 R, f3 t, float* __restrict__ vdst,
-                                                  float* __restrict__ ndst, float* __restrict__ packed) {
+                                                  const float* __restrict__ nsrc, m33 R, f3 t, float* __restrict__ packed) {
     if (x >= cols || y >= rows) return false;
     f3 vs = make_f3(0.f, 0.f, 0.f), ns = vs;
     vs.x = vsrc[(size_t)y * cols + x];
@@ -154,7 +137,7 @@ __device__ __forceinline__ bool transform_pack_px(int x, int y, int rows, int co
         ns.y = nsrc[(size_t)(y + rows) * cols + x];
         ns.z = nsrc[(size_t)(y + 2 * rows) * cols + x];
     }
-    transform_pack_store(x, y, rows, cols, v_ok, vs, n_ok, ns, R, t, vdst, ndst, packed);
+    transform_pack_store(x, y, cols, v_ok, vs, n_ok, ns, R, t, packed);
     return v_ok;  // (the vertex is valid)
 }
 
@@ -162,43 +145,27 @@ __device__ __forceinline__ bool transform_pack_px(int x, int y, int rows, int co
 __device__ __forceinline__ void prep_job_px(const PrepJob& J, const void* src0, const void* src1, int x, int y, PrepNote& note) {
     const int cols = J.cols, rows = J.rows;
     switch (J.op) {
-        case PREP_VMAP:
-            create_vmap_px(x, y, (const float*)src0, cols, cols, rows, (float*)J.dst0, cols, J.f[0], J.f[1], J.f[2], J.f[3],
-                           J.f[4]);
+        case PREP_VMAP_NMAP:
+            create_vmap_nmap_px(x, y, (const float*)src0, cols, rows, (float*)J.dst0, (float*)J.dst1, J.f[0], J.f[1], J.f[2], J.f[3],
+                                J.f[4]);
             if (J.zmin != nullptr && x < cols && y < rows) {  // (uniform test; the depth is in the cache)
                 const float z = ((const float*)src0)[(size_t)y * cols + x];
                 if (z != 0 && z < J.f[4]) note.lo[2] = fminf(note.lo[2], z);
             }
             break;
-        case PREP_VMAP_NMAP:
-            create_vmap_nmap_px(x, y, (const float*)src0, cols, rows, (float*)J.dst0, (float*)J.dst1, J.f[0], J.f[1], J.f[2], J.f[3],
-                                J.f[4]);
-            if (J.zmin != nullptr && x < cols && y < rows) {
-                const float z = ((const float*)src0)[(size_t)y * cols + x];
-                if (z != 0 && z < J.f[4]) note.lo[2] = fminf(note.lo[2], z);
-            }
-            break;
-        case PREP_NMAP: create_nmap_px(x, y, rows, cols, (const float*)src0, cols, (float*)J.dst0, cols); break;
         case PREP_TRANSFORM_PACK: {
             m33 R;
 #pragma unroll
             for (int k = 0; k < 9; ++k) R.m[k] = J.f[k];
-            transform_pack_px(x, y, rows, cols, (const float*)src0, (const float*)src1, R, make_f3(J.f[9], J.f[10], J.f[11]),
-                              (float*)J.dst0, (float*)J.dst1, (float*)J.dst2);
+            transform_pack_px(x, y, rows, cols, (const float*)src0, (const float*)src1, R, make_f3(J.f[9], J.f[10], J.f[11]), (float*)J.dst2);
             break;
         }
-        case PREP_COPY_MAPS:
-            copy_maps_px(x, y, rows, cols, (const float4*)src0, (const float4*)src1, (float*)J.dst0, (float*)J.dst1, cols);
-            break;
-        case PREP_RESIZE_V: resize_map_px<false>(x, y, rows, cols, J.srows, (const float*)src0, J.scols, (float*)J.dst0, cols); break;
-        case PREP_RESIZE_N: resize_map_px<true>(x, y, rows, cols, J.srows, (const float*)src0, J.scols, (float*)J.dst0, cols); break;
         case PREP_PYRDOWN_F:
             pyrdown_gauss_f_px(x, y, (const float*)src0, J.scols, J.scols, J.srows, (float*)J.dst0, cols, cols, rows);
             break;
         case PREP_PYRDOWN_U8:
             pyrdown_uchar_gauss_px(x, y, (const uint8_t*)src0, J.scols, J.scols, J.srows, (uint8_t*)J.dst0, cols, cols, rows);
             break;
-        case PREP_V2D: vertices_to_depth_px(x, y, (const float4*)src0, cols, rows, (float*)J.dst0, cols, J.f[0]); break;
         case PREP_INTENSITY:
             image_to_intensity_px(x, y, (const uint8_t*)src0, J.scols, J.channels, cols, rows, (uint8_t*)J.dst0, cols);
             break;
@@ -206,7 +173,7 @@ __device__ __forceinline__ void prep_job_px(const PrepJob& J, const void* src0, 
             derivative_px(x, y, (const uint8_t*)src0, cols, cols, rows, (int16_t*)J.dst0, cols, (int16_t*)J.dst1, cols);
             break;
         case PREP_PROJECT:
-            project_points_px(x, y, (const float*)src0, cols, cols, rows, (float*)J.dst0, J.f[0], J.f[1], J.f[2], J.f[3], (float4*)J.dst1);
+            project_points_px(x, y, (const float*)src0, cols, cols, rows, nullptr, J.f[0], J.f[1], J.f[2], J.f[3], (float4*)J.dst1);
             break;
         case PREP_RESIZE_TP: {
             if (x >= cols || y >= rows) break;
@@ -216,8 +183,7 @@ __device__ __forceinline__ void prep_job_px(const PrepJob& J, const void* src0, 
             f3 vs = make_f3(0.f, 0.f, 0.f), ns = vs;
             const bool v_ok = resize_map_value<false>(x, y, J.srows, (const float*)src0, J.scols, vs);
             const bool n_ok = resize_map_value<true>(x, y, J.srows, (const float*)src1, J.scols, ns);
-            transform_pack_store(x, y, rows, cols, v_ok, vs, n_ok, ns, R, make_f3(J.f[9], J.f[10], J.f[11]), (float*)J.dst0,
-                                 (float*)J.dst1, (float*)J.dst2);
+            transform_pack_store(x, y, cols, v_ok, vs, n_ok, ns, R, make_f3(J.f[9], J.f[10], J.f[11]), (float*)J.dst2);
             break;
         }
         case PREP_TEX_TP: {
@@ -229,8 +195,7 @@ __device__ __forceinline__ void prep_job_px(const PrepJob& J, const void* src0, 
             const bool ok = !(v.z == 0);  // copy_maps_px: an empty texel is an invalid vertex AND an invalid normal
             const f3 vs = ok ? make_f3(v.x, v.y, v.z) : make_f3(qnan(), qnan(), qnan());
             const f3 ns = ok ? make_f3(n.x, n.y, n.z) : make_f3(qnan(), qnan(), qnan());
-            transform_pack_store(x, y, rows, cols, !(vs.x != vs.x), vs, !(ns.x != ns.x), ns, R, make_f3(J.f[9], J.f[10], J.f[11]),
-                                 (float*)J.dst0, (float*)J.dst1, (float*)J.dst2);
+            transform_pack_store(x, y, cols, !(vs.x != vs.x), vs, !(ns.x != ns.x), ns, R, make_f3(J.f[9], J.f[10], J.f[11]), (float*)J.dst2);
             if (ok) {  // (extent.hpp: the pixel box and the camera-frame depth range of the valid vertices)
                 note.lo[0] = fminf(note.lo[0], (float)x), note.lo[1] = fminf(note.lo[1], (float)y), note.lo[2] = fminf(note.lo[2], v.z);
                 note.hi[0] = fmaxf(note.hi[0], (float)x), note.hi[1] = fmaxf(note.hi[1], (float)y), note.hi[2] = fmaxf(note.hi[2], v.z);
@@ -241,7 +206,7 @@ __device__ __forceinline__ void prep_job_px(const PrepJob& J, const void* src0, 
             if (x >= cols || y >= rows) break;
             const float z = vertex_depth_value(((const float4*)src0)[(size_t)y * cols + x].z, J.f[4]);
             ((float*)J.dst2)[(size_t)y * cols + x] = z;
-            project_points_store(x, y, z, cols, (float*)J.dst0, J.f[0], J.f[1], J.f[2], J.f[3], (float4*)J.dst1);
+            project_points_store(x, y, z, cols, nullptr, J.f[0], J.f[1], J.f[2], J.f[3], (float4*)J.dst1);
             extent_note(J.ext, J.ext_gen, x, y, !(z != z) && (x == cols - 1 || y == rows - 1));  // (extent_of_level: level 0's last column / row)
             break;
         }
@@ -318,7 +283,7 @@ __device__ __forceinline__ void prep_job_px(const PrepJob& J, const void* src0, 
             if (x >= cols || y >= rows) break;
             const float z = pyrdown_gauss_f_value(x, y, (const float*)src0, J.scols, J.scols, J.srows);
             ((float*)J.dst2)[(size_t)y * cols + x] = z;
-            project_points_store(x, y, z, cols, (float*)J.dst0, J.f[0], J.f[1], J.f[2], J.f[3], (float4*)J.dst1);
+            project_points_store(x, y, z, cols, nullptr, J.f[0], J.f[1], J.f[2], J.f[3], (float4*)J.dst1);
             extent_note(J.ext, J.ext_gen, x, y, !(z != z));
             break;
         }

@@ -16,11 +16,7 @@ struct Tunables {
     int gn_groups = 256;      // MMF_GN_GROUPS: workgroups per model per launch at most
     int gn_sleep = 1;         // MMF_GN_SLEEP: s_sleep(1) repetitions between two polls of the count barrier
     // ---- preparation jobs (prep_batch.hpp) ----
-    int prep_merge = 2;       // MMF_PREP_MERGE=0|1|2: four / three / two model-side preparation stages
-    bool prep_vn = true;      // MMF_PREP_VN=0: a level's vertex and normal maps as two jobs
-    bool prep_l0_late = true; // MMF_PREP_L0_LATE=0: the model side's level-0 jobs in its first launch
     long prep_big = -1;       // MMF_PREP_BIG=<pixels>|0: from how many pixels a job's workgroups take four tiles each
-    bool prep_planar = false; // MMF_PREP_PLANAR=1: also write the planar model maps and the AoS point cloud
     bool begin_rider = true;  // MMF_BEGIN_RIDER=0: odom_begin_kernel always as a launch of its own (else: on the last launch of a preparation enqueued ahead of the frame)
     bool prep_rect = true;    // MMF_PREP_RECT=0: an object model's model-side preparation covers the whole frame (else: the box its prediction is non-zero in)
     // ---- orchestrator (fusion_orchestrator.hpp) ----
@@ -58,11 +54,7 @@ inline const Tunables& tunables() {
         if (const char* e = std::getenv("MMF_GN_PX")) std::sscanf(e, "%d,%d,%d", &v.gn_px[0], &v.gn_px[1], &v.gn_px[2]);
         v.gn_groups = (int)num("MMF_GN_GROUPS", 256);
         v.gn_sleep = (int)num("MMF_GN_SLEEP", 1);
-        v.prep_merge = (int)num("MMF_PREP_MERGE", 2);
-        v.prep_vn = flag("MMF_PREP_VN", true);
-        v.prep_l0_late = flag("MMF_PREP_L0_LATE", true);
         v.prep_big = num("MMF_PREP_BIG", -1);
-        v.prep_planar = flag("MMF_PREP_PLANAR", false);
         v.prep_rect = flag("MMF_PREP_RECT", true);
         v.begin_rider = flag("MMF_BEGIN_RIDER", true);
         if (const char* e = std::getenv("MMF_EARLY_IMAGE")) v.early_image = std::strcmp(e, "off") == 0 ? 0 : (std::strcmp(e, "chain") == 0 ? 1 : 2);
