@@ -517,11 +517,27 @@ int mmf_debug_set_gn_fused(int on);
  * occupancy before it uses that chain, but another process on the same GPU can still keep a launch from becoming resident as
  * a whole.  A launch that gives up marks the chain's result void; the call that waits for it tracks the frame again on the
  * two-launch chain from the pose it started with (RGBDOdometry.cpp:464-467: the call returns a pose, it never aborts) and the
- * process stops using the one-launch chain.  recoveries: how often that happened; one_launch_chain_in_use: 0 afterwards.
+ * process stops using the one-launch chain.  A launch whose sums leave the 64-bit fixed-point range its workgroups add them
+ * up in (an ICP partial beyond 2^23: a scene some hundred metres deep) gives up in the same way, with the same consequence: the
+ * next frames of such a scene would give up as well.  recoveries: how often that happened; one_launch_chain_in_use: 0 afterwards.
  * Either pointer may be NULL. */
 int mmf_gn_chain_status(int *recoveries, int *one_launch_chain_in_use);
 /* test hook: the next n one-launch chains of this process give up at their third launch */
 int mmf_debug_force_gn_fault(int n);
+/* test hook (process wide): the next one-launch chain runs n launches of its per-iteration kernel at pyramid level first_level
+ * and nothing else (n = 0 disarms).  It ends like any chain (the divergence guard, the pose handed out), after n - 1 solves.
+ * The call fails if it cannot take the one-launch chain.  mmf_debug_gn_truncated then gives, for that odometry: the 58 totals of
+ * the last launch as the next launch would have decoded them ([0, 29) ICP, [29, 58) photometric), that pass's
+ * {count, sum diff^2 mod 2^32}, and what the last solve left (n = 1: what the chain began with): the running transform's three
+ * rows and Rcurr[9], tcurr[3], K R K^-1 [9], K t [3] (at first_level's intrinsics).  Of the call's results only the pose and
+ * iterations_run (n - 1) mean anything: the other statistics stay as the odometry's last full chain left them. */
+int mmf_debug_gn_truncate(int n, int first_level);
+int mmf_debug_gn_truncated(mmf_odom *o, double totals[58], unsigned count_sumsq[2], double rt[12], float pose[24]);
+/* test hook: the one-launch chain's solve and pose update (one wave, a row per lane) on n systems in device memory:
+ * sys = n x {A[36], b[6]} and rt = n x 16 (the running transform) as doubles, prev = n x {Rprev[9], tprev[3]} floats, the level's
+ * intrinsics; rt_out = n x 12 doubles (the new running transform's three rows), pose_out = n x 24 floats (as above). */
+int mmf_debug_gn_solve(mmf_ctx *ctx, const double *sys_dev, const double *rt_dev, const float *prev_dev, float fx, float fy,
+                       float cx, float cy, int n, double *rt_out_dev, float *pose_out_dev);
 /* test hooks of the object models' walk in the one-launch chain (csrc/gn_fused.hpp: an object model's ICP term covers only the
  * rectangle of sensor pixels its prediction can reach under the iteration's pose).  Checking mode (process wide): such models
  * walk the WHOLE image and count the correspondences icpStep accepts outside that rectangle.  mmf_debug_odom_sparse_outside:

@@ -237,6 +237,9 @@ SIGNATURES = {
     "mmf_debug_set_gn_fused": (_i, [_i]),
     "mmf_debug_set_mid_predict": (_i, [_i]),
     "mmf_debug_force_gn_fault": (_i, [_i]),
+    "mmf_debug_gn_truncate": (_i, [_i, _i]),
+    "mmf_debug_gn_truncated": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "mmf_debug_gn_solve": (_i, [_vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _vp, _vp]),
     "mmf_debug_set_sparse_check": (_i, [_i]),
     "mmf_debug_set_pass_batch": (_i, [_i]),
     "mmf_debug_set_prep_rect": (_i, [_i]),

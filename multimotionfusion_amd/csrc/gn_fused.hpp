@@ -113,6 +113,10 @@ __device__ __forceinline__ int gn_rgb_exp(float sigma_val) {
     const float s = sigma_val > 1.0f ? sigma_val : 1.0f;  // (also NaN -> 1)
     return kGnSumRgbExp0 + 2 * ((int)((__builtin_bit_cast(unsigned, s) >> 23) & 0xFFu) - 127);
 }
+// the binary exponent of sum `lane` of the 58 (lane < 29: ICP; 29 + 27: the photometric residual; else photometric by sigma)
+__device__ __forceinline__ int gn_sum_exp(int lane, int rgb_exp) {
+    return lane < 29 ? kGnSumIcpExp : (lane == 29 + 27 ? kGnSumRgbResExp : rgb_exp);
+}
 struct GnSumLoads {
     long long q[kGnSumShards];    // lane k < 58: sum k of every shard
     unsigned long long cnt;  // lane t < 16: shard t of the previous launch's {arrivals, count, sum diff^2}
@@ -137,7 +141,7 @@ __device__ __forceinline__ void gn_totals_to_lds(const GnSumLoads& sl, GnLds& ld
     unsigned s2 = lane < kResShards ? (unsigned)sl.cnt : 0u;  // wraps at 2^32 like the reference's int
     c = wave_sum_to_lane63(c), s2 = wave_sum_to_lane63(s2);
     count = (unsigned)__builtin_amdgcn_readlane((int)c, 63), sumsq = (unsigned)__builtin_amdgcn_readlane((int)s2, 63);
-    const int e = lane < 29 ? kGnSumIcpExp : gn_rgb_exp(gn_sigma_val(count, sumsq));
+    const int e = gn_sum_exp(lane, gn_rgb_exp(gn_sigma_val(count, sumsq)));
     long long q = sl.q[0];
 #pragma unroll
     for (int x = 1; x < kGnSumShards; ++x) q += sl.q[x];
@@ -147,7 +151,7 @@ __device__ __forceinline__ void gn_totals_to_lds(const GnSumLoads& sl, GnLds& ld
 }
 // lane k < 58 adds sum k of this workgroup (float) to the launch's sums; false: the value does not fit the fixed-point range
 __device__ __forceinline__ bool gn_sum_add(OdomState* st, int it, int lane, float v, int rgb_exp, unsigned bid) {
-    const double d = __builtin_ldexp((double)v, lane < 29 ? kGnSumIcpExp : rgb_exp);  // exact
+    const double d = __builtin_ldexp((double)v, gn_sum_exp(lane, rgb_exp));  // exact
     const bool ok = __builtin_fabs(d) < 9007199254740992.0;  // 2^53 per workgroup: 512 of them fit 2^62 (a NaN fails too)
     const long long q = ok ? (long long)__builtin_rint(d) : 0ll;
     if (lane < 58)
@@ -1177,6 +1181,72 @@ __global__ __launch_bounds__(kBlock) void gn_final_kernel(OdomState* st, GnIterA
         st = batch_shift(st, bd.d[blockIdx.x]);
     }
     gn_final_solve(st, a, lds);
+}
+
+// Test kernel (mmf_debug_gn_truncate): the end of a one-launch chain that stops after a.it launches of gn_iter_kernel at one
+// level (a.intr: that level's).  One wave.  It leaves in `out` what the chain's next reader would have
+// started from: the pose of the chain's last launch -- for a.it >= 2 by running that launch's solve once more, with the very
+// code and inputs of its solver waves (launch a.it - 1 read gn_sum / gn_acc[(a.it + 1) % 3] and gn_rt[(a.it - 1) & 1]; no later
+// launch has touched them) -- and the last launch's totals as gn_totals_to_lds decodes them.  Then the frame ends as it does
+// after any chain: the pose goes to the state, odom_end.  No solve follows the last launch's sums.
+__global__ __launch_bounds__(64) void gn_truncated_final_kernel(OdomState* st, GnIterArgs a, GnTruncated* out) {
+    __shared__ GnLds lds;
+    if (st->gn_fault) return;  // (uniform) the chain's result is void, as in gn_final_solve
+    const int lane = threadIdx.x;
+    if (a.it >= 2) {
+        GnIterArgs p = a;
+        p.it = a.it - 1;
+        GnSumLoads sl;
+        gn_sums_issue(st, p, sl, lane);
+        unsigned pc, ps;
+        gn_totals_to_lds(sl, lds, lane, pc, ps);
+        gn_solve_wave<false>(st, p, lds, false, lane, pc, ps);
+    } else {
+        gn_first_pose(st, lds, false, lane);
+    }
+    __syncthreads();
+    if (lane < 24) out->pose[lane] = lds.pose[lane];
+    if (lane < 12) out->rt[lane] = st->gn_rt[a.it & 1][lane];
+    GnSumLoads sl;
+    gn_sums_issue(st, a, sl, lane);
+    unsigned count, sumsq;
+    gn_totals_to_lds(sl, lds, lane, count, sumsq);
+    __syncthreads();
+    if (lane < 58) out->tot[lane] = lds.dtot[lane];
+    if (lane == 0) {
+        out->cnt[0] = count, out->cnt[1] = sumsq;
+        for (int k = 0; k < 12; ++k) st->resultRt[k] = st->gn_rt[a.it & 1][k];
+        for (int k = 0; k < 9; ++k) st->Rcurr[k] = lds.pose[k], st->krkinv[k] = lds.pose[12 + k];
+        for (int k = 0; k < 3; ++k) st->tcurr[k] = lds.pose[9 + k], st->kt[k] = lds.pose[21 + k];
+        st->st.iterations_run = a.it - 1;
+        odom_end(st);
+    }
+}
+
+// Test kernel (mmf_debug_gn_solve): gn_solve_rows, the solve and pose update of every gn_iter_kernel launch, on n systems of the
+// caller's.  One wave; system s: A[36] b[6] (sys + 42 s), the running transform (rt + 16 s), Rprev[9] tprev[3] (prev + 12 s).
+// Lanes 0..2 write their own row of the new running transform (rt_out + 12 s) and the wave's pose floats go out as the
+// launch's pixel waves would read them from LDS (pose_out + 24 s).
+__global__ __launch_bounds__(64) void gn_solve_debug_kernel(const double* __restrict__ sys, const double* __restrict__ rt,
+                                                            const float* __restrict__ prev, LevelIntr in, int n,
+                                                            double* __restrict__ rt_out, float* __restrict__ pose_out) {
+    __shared__ GnLds lds;
+    const int lane = threadIdx.x;
+    const double ifx = 1.0 / (double)in.fx, ify = 1.0 / (double)in.fy;  // what the host passes in GnIterArgs
+    for (int s = 0; s < n; ++s) {
+        if (lane < 42) lds.sol[lane] = sys[42 * s + lane];
+        if (lane < 16) lds.sd[lane] = rt[16 * s + lane];
+        if (lane < 12) lds.sf[lane] = prev[12 * s + lane];
+        if (lane < 24) lds.pose[lane] = 0.f;
+        __syncthreads();
+        double nr[4];
+        gn_solve_rows(lds.sol, lds.sd, lds.sf, in, ifx, ify, lane, lds.xch, lds.pose, nr);
+        if (lane < 3)
+            for (int c = 0; c < 4; ++c) rt_out[12 * s + lane * 4 + c] = nr[c];
+        __syncthreads();
+        if (lane < 24) pose_out[24 * s + lane] = lds.pose[lane];
+        __syncthreads();
+    }
 }
 
 // the same, and the result goes to the host in the same launch (odom_publish_kernel's two waves behind the solve: the copy

@@ -801,6 +801,7 @@ struct mmf_odom {
     // many as the box of its own depth needed in its LAST chain plus a quarter (OdomState::gn_need; 0: no chain yet)
     int gn_need[MMF_NUM_PYRS] = {0, 0, 0};
     int last_gn_fault = 0;          // OdomState::gn_fault of the last result picked up (odom_finish_tracking)
+    GnTruncated* gn_truncated = nullptr;  // test hook (mmf_debug_gn_truncate): made by the first truncated chain
     bool walked_by_extent = false;  // the last chain enqueued walked this model by its extents (gn_iter_mixed_kernel)
     bool two_launch_once = false;  // the next chain this odometry leads is the two-launch chain (a frame tracked again)
     OdomState* state = nullptr;  // device
@@ -974,6 +975,7 @@ extern "C" void mmf_odom_destroy(mmf_odom* o) {
     (void)hipSetDevice(o->ctx->device);
     (void)hipStreamSynchronize(o->ctx->stream);
     (void)hipFree(o->slab);
+    if (o->gn_truncated) (void)hipFree(o->gn_truncated);
     (void)hipHostFree(o->host_result);
     for (hipEvent_t e : o->ev_kernel)
         if (e) (void)hipEventDestroy(e);
@@ -1711,6 +1713,27 @@ extern "C" int mmf_debug_force_gn_fault(int n) {
     g_gn_force_fault.store(n < 0 ? 0 : n);
     return MMF_OK;
 }
+// test hook: the next one-launch chain of this process runs n launches of gn_iter_kernel at pyramid level first_level and
+// nothing else, then ends (gn_truncated_final_kernel) and leaves its last launch's sums and the pose its last solve made in
+// a buffer of the odometry's (GnTruncated; read by mmf_debug_gn_truncated).  A call that cannot take the one-launch chain while this is armed fails.
+static std::atomic<int> g_gn_truncate{0};  // n << 8 | first_level
+extern "C" int mmf_debug_gn_truncate(int n, int first_level) {
+    if (n < 0 || n > 64 || first_level < 0 || first_level >= MMF_NUM_PYRS) return fail(MMF_ERR_INVALID, "mmf_debug_gn_truncate: bad argument");
+    g_gn_truncate.store(n ? (n << 8 | first_level) : 0);
+    return MMF_OK;
+}
+extern "C" int mmf_debug_gn_truncated(mmf_odom* o, double totals[58], unsigned count_sumsq[2], double rt[12], float pose[24]) {
+    MMF_REQUIRE(o && o->gn_truncated && totals && count_sumsq && rt && pose, "mmf_debug_gn_truncated: null argument, or no truncated chain ran");
+    MMF_HIP_TRY(hipSetDevice(o->ctx->device));
+    MMF_HIP_TRY(hipStreamSynchronize(o->ctx->stream));
+    GnTruncated h;
+    MMF_HIP_TRY(hipMemcpy(&h, o->gn_truncated, sizeof(h), hipMemcpyDeviceToHost));
+    std::memcpy(totals, h.tot, sizeof(h.tot));
+    std::memcpy(count_sumsq, h.cnt, sizeof(h.cnt));
+    std::memcpy(rt, h.rt, sizeof(h.rt));
+    std::memcpy(pose, h.pose, sizeof(h.pose));
+    return MMF_OK;
+}
 // how often a one-launch chain gave up and its frame was tracked again on the two-launch chain, and whether the one-launch
 // chain is still in use (it is latched off by the first such event: whatever kept its workgroups from being resident
 // together -- another process on this GPU -- is likely still there)
@@ -1881,7 +1904,7 @@ static int odom_chain_begin(const ChainCall& x, const float trans[3], const floa
 // both terms on and every level fits: ONE launch per iteration (gn_fused.hpp) instead of producer + step, at the plan's
 // geometry.  (More than three models: the batched two-launch chain is as fast (four) or faster -- 8 models 1.40 ms against
 // 1.60 -- because a model's workgroups hold their CUs at the count barrier while the next models' wait for a place.)
-static int odom_one_launch_chain(const ChainCall& x, const GnChainPlan& plan, Enqueuer& q, ChainTail* tail) {
+static int odom_one_launch_chain(const ChainCall& x, const GnChainPlan& plan, Enqueuer& q, ChainTail* tail, bool truncated = false) {
     mmf_odom* o = x.o;
     GnIterArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -1936,6 +1959,14 @@ static int odom_one_launch_chain(const ChainCall& x, const GnChainPlan& plan, En
             });
             ++it;
         }
+    }
+    if (truncated) {  // (mmf_debug_gn_truncate) no solve behind the last launch: its sums and the pose it ran with, then the frame's end
+        tail->end_folded = true;
+        a.it = it;
+        a.intr = level_intr(o->fx, o->fy, o->cx, o->cy, x.tm.first_iter_level);  // the level the launches ran at (the loop went on to level 0)
+        a.ifx = 1.0 / (double)a.intr.fx, a.ify = 1.0 / (double)a.intr.fy;
+        q.launch(gn_truncated_final_kernel, dim3(1), dim3(64), o->state, a, o->gn_truncated);
+        return MMF_OK;
     }
     // the last solve + RGBDOdometry.cpp:464-467: one workgroup per model
     a.it = it;
@@ -2098,13 +2129,25 @@ static int odom_enqueue_tracking(mmf_odom* o, const float trans[3], const float 
     if (std::getenv("MMF_DBG_NO_ERR")) icp_err_dev = rgb_err_dev = nullptr;
 #endif
     MMF_REQUIRE(!batch || batch->n == 1 || odom_batchable(o, tm), "odom_enqueue_tracking: not batchable");
-    const ChainCall x = odom_chain_call(o, tm, batch, icp_err_dev, rgb_err_dev);
-    const GnChainPlan plan = x.two_launch_once ? GnChainPlan() : odom_plan_chain(o, tm, batch, x.sparse_on);
+    TrackMode tmx = tm;
+    const int truncate = g_gn_truncate.exchange(0);
+    if (truncate) {  // (mmf_debug_gn_truncate) n launches at one level
+        for (int i = 0; i < MMF_NUM_PYRS; ++i) tmx.iterations[i] = 0;
+        tmx.first_iter_level = truncate & 0xFF;
+        tmx.iterations[tmx.first_iter_level] = truncate >> 8;
+    }
+    const ChainCall x = odom_chain_call(o, tmx, batch, icp_err_dev, rgb_err_dev);
+    const GnChainPlan plan = x.two_launch_once ? GnChainPlan() : odom_plan_chain(o, tmx, batch, x.sparse_on);
+    MMF_REQUIRE(!truncate || (plan.one_launch && x.ny == 1), "odom_enqueue_tracking: a truncated chain needs the one-launch chain of one model");
+    if (truncate && !o->gn_truncated) {
+        MMF_HIP_TRY(hipMalloc(&o->gn_truncated, sizeof(GnTruncated)));
+        MMF_HIP_TRY(hipMemset(o->gn_truncated, 0, sizeof(GnTruncated)));
+    }
     for (unsigned m = 0; m < x.ny; ++m) x.model(m)->walked_by_extent = plan.one_launch && ((plan.sparse_mask >> m) & 1u) != 0;
     Enqueuer q(o->ctx->stream);
     ChainTail tail;
     int rc = odom_chain_begin(x, trans, rot, plan.one_launch, q);
-    if (rc == MMF_OK) rc = plan.one_launch ? odom_one_launch_chain(x, plan, q, &tail) : odom_two_launch_chain(x, q, &tail);
+    if (rc == MMF_OK) rc = plan.one_launch ? odom_one_launch_chain(x, plan, q, &tail, truncate != 0) : odom_two_launch_chain(x, q, &tail);
     return rc == MMF_OK ? odom_chain_publish(x, q, tail) : rc;
 }
 
@@ -3723,6 +3766,19 @@ extern "C" int mmf_debug_expf(mmf_ctx* c, const float* x_dev, int n, float* out_
     MMF_REQUIRE(c && x_dev && out_mmf_dev && out_packed_dev && n > 0, "mmf_debug_expf: bad argument");
     MMF_HIP_TRY(hipSetDevice(c->device));
     hipLaunchKernelGGL(debug_expf_kernel, grid1d(((size_t)n + 1) / 2), dim3(256), 0, c->stream, x_dev, n, out_mmf_dev, out_packed_dev);
+    MMF_HIP_TRY(hipGetLastError());
+    return MMF_OK;
+}
+
+// the one-launch chain's wave-parallel solve and pose update (gn_fused.hpp: gn_solve_rows) on n caller-supplied systems, so that
+// a test can hold it against float64 outside the 19 iterations it otherwise hides in.  Device pointers: sys = n x {A[36], b[6]},
+// rt = n x 16 doubles, prev = n x {Rprev[9], tprev[3]} floats; rt_out = n x 12 doubles, pose_out = n x 24 floats.
+extern "C" int mmf_debug_gn_solve(mmf_ctx* c, const double* sys_dev, const double* rt_dev, const float* prev_dev, float fx, float fy,
+                                  float cx, float cy, int n, double* rt_out_dev, float* pose_out_dev) {
+    MMF_REQUIRE(c && sys_dev && rt_dev && prev_dev && rt_out_dev && pose_out_dev && n > 0, "mmf_debug_gn_solve: bad argument");
+    MMF_HIP_TRY(hipSetDevice(c->device));
+    const LevelIntr in{fx, fy, cx, cy};
+    hipLaunchKernelGGL(gn_solve_debug_kernel, dim3(1), dim3(64), 0, c->stream, sys_dev, rt_dev, prev_dev, in, n, rt_out_dev, pose_out_dev);
     MMF_HIP_TRY(hipGetLastError());
     return MMF_OK;
 }

@@ -97,8 +97,23 @@ struct OdomState {
     // between a buffer's writers and its readers.
     alignas(128) long long gn_sum[3][16][64];
 };
-constexpr int kGnSumIcpExp = 30;  // ICP sums: value x 2^30 (per-workgroup partials < 2^23: 1280 pixels x |v|^2)
+// What a truncated one-launch chain leaves for a test (mmf_debug_gn_truncate, gn_truncated_final_kernel): the 58 totals of its
+// last launch as the next reader decodes them, that pass's {count, sum diff^2}, the running transform (3 x 4) and the pose
+// (Rcurr, tcurr, krkinv, kt) its last solve left.  A buffer of its own, made when the hook is first used: the state keeps its
+// size, and with it the layout of everything carved behind it.
+struct GnTruncated {
+    double tot[58];
+    double rt[12];
+    float pose[24];
+    unsigned cnt[2];
+};
+constexpr int kGnSumIcpExp = 30;  // ICP sums: value x 2^30 (per-workgroup partials < 2^23: 1280 pixels x |v|^2, v in the MODEL's camera frame; beyond that -- a scene some hundred metres deep -- the launch gives up, value 2)
 constexpr int kGnSumRgbExp0 = 4;  // photometric sums: value x 2^(4 + 2 floor(log2 sigma)) -- the rows carry w = 1 / (sigma + |d|)
+// ... except the photometric residual, sum (w d)^2: |w d| < 1 whatever sigma is, so a workgroup's partial is below its pixel
+// count (< 2^12) and takes a fixed 2^40.  At the scale above its quantum (2^-22 at 1 000 correspondences) is as large as
+// the float32 bound of the sum itself once the differences are small: 1.1 x helpers.se3_sum_tolerance at level 2 of a
+// 160 x 120 pair (tests/test_gpu_gn_range.py).  Nothing in the solve reads that sum.
+constexpr int kGnSumRgbResExp = 40;
 constexpr int kGnSumShards = 16;
 constexpr int kResShards = 16;
 constexpr int kResStride = 16;  // 64-bit words between two shards (128 B)
