@@ -8,6 +8,7 @@ import torch
 
 from helpers import assert_bit_equal
 from multimotionfusion_amd import synth
+from surfel_shapes import splat_bound, surfel_cycle  # noqa: F401  (splat_bound: fixture)
 
 pytestmark = pytest.mark.gpu
 MAXD = 20.0      # maxDepthProcessed
@@ -34,94 +35,12 @@ def test_filter_depth_bit_exact(gpu_ctx, orc, w, h):
     assert_bit_equal(out.cpu().numpy(), orc.bilateral_filter(f["depth"], CUTOFF), "bilateral filter")
 
 
-@pytest.fixture
-def splat_bound(gpu_ctx, request):
-    """combinedPredict's early depth test (splat_kernel<true>: the key image is read before a fragment is evaluated): -1 = by the surfel count, 1 = always"""
-    gpu_ctx.lib.mmf_debug_set_splat_bound(request.param)
-    yield request.param
-    gpu_ctx.lib.mmf_debug_set_splat_bound(-1)
-
-
 @pytest.mark.parametrize("splat_bound", [-1, 1], indirect=True)
 @pytest.mark.parametrize("w,h", [(640, 480), (160, 120)])
 def test_surfel_cycle_bit_exact(gpu_ctx, orc, w, h, splat_bound):
-    """initialise -> (predictIndices, fuse, predictIndices, clean, combinedPredict, fill-in) x 3 frames."""
-    from multimotionfusion_amd.model import filterDepth
-    K, m = make_model(gpu_ctx, w, h)
-    poses = synth.trajectory(4, seed=5)
-    frames = [synth.render(p, w, h, seed=i) for i, p in enumerate(poses)]
-    mask = np.zeros((h, w), np.uint8)
-    d_mask = dev(mask)
-
-    f0 = frames[0]
-    fil0 = orc.bilateral_filter(f0["depth"], CUTOFF)
-    d_fil0 = filterDepth(gpu_ctx, dev(f0["depth"]), CUTOFF)
-    m.overridePose(poses[0])
-    m.initialise(dev(f0["rgb"]), dev(f0["depth"]), d_fil0, 1, MAXD)
-    s = orc.surfel_initialise(f0["rgb"], f0["depth"], fil0, K, 1, MAXD)
-    assert m.lastCount() == s.shape[0] > 0.8 * w * h
-    assert_bit_equal(m.downloadMap(), s, "initialise")
-
-    for t in range(1, 4):
-        tick = t + 1
-        f = frames[t]
-        pose = poses[t].astype(np.float32)  # ground-truth pose stands in for the tracker here
-        fil = orc.bilateral_filter(f["depth"], CUTOFF)
-        d_rgb, d_raw = dev(f["rgb"]), dev(f["depth"])
-        d_fil = filterDepth(gpu_ctx, d_raw, CUTOFF)
-        m.overridePose(pose)
-
-        m.predictIndices(tick, MAXD, TIME_DELTA)
-        index, vc, ct, nr = orc.predict_indices(s, pose, K, w, h, MAXD, tick, TIME_DELTA)
-        assert_bit_equal(m.texture("index").cpu().numpy().view(np.uint32), index, f"index map t={t}")
-        assert_bit_equal(m.texture("vertConf").cpu().numpy(), vc, f"vertConf t={t}")
-        assert_bit_equal(m.texture("colorTime").cpu().numpy(), ct, f"colorTime t={t}")
-        assert_bit_equal(m.texture("normRad").cpu().numpy(), nr, f"normRad t={t}")
-
-        m.fuse(tick, d_rgb, d_mask, d_raw, d_fil, MAXD, 1.0)
-        s_upd, new = orc.fuse(s, f["rgb"], f["depth"], fil, mask, index, vc, nr, pose, K, tick, 1.0, 0, MAXD)
-        assert_bit_equal(m.downloadMap(), s_upd, f"fused surfels t={t}")
-
-        m.predictIndices(tick, MAXD, TIME_DELTA)
-        index, vc, ct, nr = orc.predict_indices(s_upd, pose, K, w, h, MAXD, tick, TIME_DELTA)
-        assert_bit_equal(m.texture("index").cpu().numpy().view(np.uint32), index, f"index map after fuse t={t}")
-
-        m.clean(tick, TIME_DELTA, MAXD, d_fil, d_mask, 3.0)
-        s = orc.clean(s_upd, new, pose, K, w, h, tick, TIME_DELTA, CONF, 3.0, 0, index, vc, ct, fil, mask)
-        assert m.lastCount() == s.shape[0]
-        assert_bit_equal(m.downloadMap(), s, f"cleaned surfels t={t}")
-
-        # at confGlobalInit nothing is stable yet after three frames and the splat below draws nothing: a leg with the
-        # model's threshold at 0.5 draws the sprites of most of the map (same pass, same threshold on both sides)
-        m.setConfidenceThreshold(0.5)
-        m.combinedPredict(MAXD, tick, tick, TIME_DELTA)
-        m.setConfidenceThreshold(CONF)
-        image, vcp, nrp, tm = orc.combined_predict(s, pose, K, w, h, MAXD, 0.5, tick, tick, TIME_DELTA)
-        assert (vcp[..., 2] > 0).mean() > 0.5, (t, float((vcp[..., 2] > 0).mean()))
-        assert_bit_equal(m.texture("image").cpu().numpy(), image, f"splat image t={t} conf=0.5")
-        assert_bit_equal(m.texture("vertexConf").cpu().numpy(), vcp, f"splat vertexConf t={t} conf=0.5")
-        assert_bit_equal(m.texture("normalRadius").cpu().numpy(), nrp, f"splat normalRadius t={t} conf=0.5")
-        assert_bit_equal(m.texture("time").cpu().numpy().view(np.uint16), tm, f"splat time t={t} conf=0.5")
-
-        m.combinedPredict(MAXD, tick, tick, TIME_DELTA)
-        image, vcp, nrp, tm = orc.combined_predict(s, pose, K, w, h, MAXD, CONF, tick, tick, TIME_DELTA)
-        assert_bit_equal(m.texture("image").cpu().numpy(), image, f"splat image t={t}")
-        assert_bit_equal(m.texture("vertexConf").cpu().numpy(), vcp, f"splat vertexConf t={t}")
-        assert_bit_equal(m.texture("normalRadius").cpu().numpy(), nrp, f"splat normalRadius t={t}")
-        assert_bit_equal(m.texture("time").cpu().numpy().view(np.uint16), tm, f"splat time t={t}")
-        # ModelProjection::synthesizeDepth: the same sprites, depth only, explicit confidence threshold
-        for conf in (CONF, 0.5):
-            m.synthesizeDepth(MAXD, conf, tick, tick, TIME_DELTA)
-            sd = orc.synthesize_depth(s, pose, K, w, h, MAXD, conf, tick, tick, TIME_DELTA)
-            assert_bit_equal(m.texture("depth").cpu().numpy(), sd, f"synthesized depth t={t} conf={conf}")
-
-        m.performFillIn(d_rgb, d_fil, False, False)
-        vo, no, io = orc.fill_in(vcp, nrp, image, fil, f["rgb"], K, 0, 0)
-        assert_bit_equal(m.texture("fillVertex").cpu().numpy(), vo, f"fill vertex t={t}")
-        assert_bit_equal(m.texture("fillNormal").cpu().numpy(), no, f"fill normal t={t}")
-        assert_bit_equal(m.texture("fillImage").cpu().numpy(), io, f"fill image t={t}")
-        assert m.requiresFillIn(0.75) == orc.requires_fill_in(image, 0.75)
-    m.close()
+    """initialise -> (predictIndices, fuse, predictIndices, clean, combinedPredict, fill-in) x 3 frames (the loop is
+    surfel_shapes.surfel_cycle, shared with the ragged sizes of test_gpu_surfel_shapes.py)."""
+    surfel_cycle(orc, w, h, gpu_ctx)
 
 
 @pytest.mark.parametrize("w,h", [(320, 240), (640, 480)])
