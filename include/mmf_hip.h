@@ -302,9 +302,9 @@ int mmf_model_id(mmf_model *m);
  * with its own RGBDOdometry, tracked / predicted / fused / cleaned per frame.  With
  * enable_multiple_models == 0 this is the static-scene configuration (all-zero mask, :268-275).
  * The segmentation RESULT is handed in per frame (mmf_segmentation: gSLICr + dense CRF of the reference's
- * front-end, or the ground-truth id image of Segmentation.cpp:89-150), pulled through a callback at the point
- * where the reference calls performSegmentation (:412), or computed by the built-in dense CRF
- * (mmf_fusion_set_crf_segmentation, below).  Relocalisation and loop closure stay in the reference's front-end.
+ * front-end), pulled through a callback at the point where the reference calls performSegmentation (:412), computed
+ * from the frame's raw label image (Segmentation.cpp:89-147: mmf_fusion_set_mask_segmentation, below) or by the built-in
+ * dense CRF (mmf_fusion_set_crf_segmentation, below).  Relocalisation and loop closure stay in the reference's front-end.
  * Every model runs on its own stream ("lane"); every public call returns with the fusion's own
  * stream (the context's) ordered after all lanes.
  * ------------------------------------------------------------------------------------- */
@@ -342,7 +342,8 @@ typedef struct {
     const uint8_t *mask;  /* DEVICE, width*height u8: fullSegmentation = model id per pixel */
     int has_new_label;    /* hasNewLabel: spawn an object model for the id mmf_fusion_next_model_id() (:469-487) */
     int n_models;         /* entries of model_data: the active models in list order, then the new label's */
-    const mmf_segmentation_model *model_data; /* HOST; NULL: no max-depth / confidence / unseen updates */
+    const mmf_segmentation_model *model_data; /* HOST; NULL: no max-depth / confidence / unseen updates -- or, with
+                                                 mmf_fusion_set_mask_segmentation on, mask = RAW LABELS to be segmented */
 } mmf_segmentation;
 
 /* one processFrame call (MultiMotionFusion.h:78-80): FrameData + the optional arguments */
@@ -385,7 +386,8 @@ int mmf_fusion_process_frame(mmf_fusion *f, const uint8_t *rgb, const float *dep
 /* processFrame with every optional input (multiple models, pose initialisation of every model) */
 int mmf_fusion_process_frame_ex(mmf_fusion *f, const mmf_frame *frame);
 /* processFrame(const FrameData&) with the frame in HOST memory: rgb, depth and the optional id image
- * (mask_host != NULL: FrameData::mask, already mapped to model ids) are staged through pinned double buffers
+ * (mask_host != NULL: FrameData::mask, already mapped to model ids -- raw labels with
+ * mmf_fusion_set_mask_segmentation on) are staged through pinned double buffers
  * and uploaded on the fusion's stream (:221, :261, :416). */
 int mmf_fusion_process_frame_host(mmf_fusion *f, const uint8_t *rgb_host, const float *depth_host,
                                   const uint8_t *mask_host, int has_new_label, long long timestamp,
@@ -748,6 +750,54 @@ int mmf_fusion_set_superpixel_engine(mmf_fusion *f, int mode);
 int mmf_fusion_last_superpixels(mmf_fusion *f, int *labels_out);
 int mmf_fusion_last_segmentation(mmf_fusion *f, mmf_crf_info *info, mmf_segmentation_model *models, int capacity,
                                  float *unaries, float *q, uint8_t *raw_map, uint8_t *map);
+
+/* ---- segmentation from a frame's GIVEN label image (Core/Segmentation/Segmentation.cpp:89-147: the branch of
+ * performSegmentation for `frame.mask.total() != 0`, tested before the segmentation mode) -----------------------------------
+ * What a mask dataset (Mask####.png, -maskdir), ground-truth ids or an external instance segmenter hand in: arbitrary labels
+ * per pixel.  On the device (csrc/mask_kernels.hpp): labels are mapped to model ids through a 256-entry
+ * table that persists from frame to frame (label 0 is background and never reads it); with allow_new the unmapped non-zero label
+ * whose first pixel comes first in raster order becomes the new model's (table[label] = next_id); pixels of labels that stay
+ * unmapped get id 0, are NOT counted for id 0 and DO enter the depth statistics of the global model.  Model data: the active
+ * models in list order, then the new label's entry; super_pixel_count = pixels / 256 (the new entry: at least 1),
+ * avg_confidence = 0.4, depth_mean / depth_std = mean and mean absolute deviation of the raw depth over the pixels of the id,
+ * zero depth included, summed in float64 in a fixed order (B7: same input, same bits).  A label mapped to an id that is
+ * neither in `ids` nor the new label's keeps that id in the mask and enters no entry (B7).
+ *   mmf_mask_default_config  model_spawn_offset 22, inhibit_new 0.  Needs no device.
+ *   mmf_mask_segment         stand-alone, synchronous: labels (u8) / depth (f32 metres) = DEVICE width*height images; ids =
+ *                        HOST model ids in list order (ids[0] == 0, all <= 255, at most 255), next_id <= 255; mapping = HOST
+ *                        table, in / out; mask_out = DEVICE width*height u8 (must not overlap labels); models_out = HOST,
+ *                        capacity n_models + 1; *new_label = the input label that became new, or -1.  Two passes over the
+ *                        image and two one-workgroup launches.
+ * Inside processFrame (off by default; MMF_ERR_STATE with world > 1 -- a sharded front end calls mmf_mask_segment in its
+ * segmentation callback):
+ *   mmf_fusion_set_mask_segmentation   cfg == NULL switches it off.  With it on, a frame whose mmf_segmentation has
+ *                        model_data == NULL -- and the mask_host of mmf_fusion_process_frame_host[_next] -- carries RAW LABELS and
+ *                        has_new_label is ignored: the frame is segmented here, on the fusion's stream, before the callback and
+ *                        the built-in CRF are considered; allow_new = spawnOffset >= cfg->model_spawn_offset (the counter of
+ *                        mmf_fusion_set_crf_segmentation), inhibit_new clears has_new_label afterwards (the mask and the table
+ *                        entry stay, MultiMotionFusion.cpp:413-415).  One host wait for the summary.  A mmf_segmentation that
+ *                        brings model_data keeps its meaning; a frame without a mask goes to the callback / the CRF.
+ *                        The labels must not be the fusion's own "MASK" texture (mmf_fusion_texture), which the id image
+ *                        is written to: MMF_ERR_INVALID, as for any mask_out that overlaps the labels.
+ *   mmf_fusion_mask_mapping  the fusion's table (cleared by mmf_fusion_reset)
+ *   mmf_fusion_last_mask_segmentation  what the last frame this path handled computed; has_new_label as processFrame used it
+ *                        (after inhibit_new).  MMF_ERR_STATE before the first such frame. */
+typedef struct {
+    int model_spawn_offset; /* frames between spawns (22) */
+    int inhibit_new;        /* setSetInhibit (hasNewLabel forced to 0) */
+} mmf_mask_config;
+typedef struct {
+    int n_models;      /* entries of the model data */
+    int allow_new, has_new_label;
+    int new_label;     /* the input label that became new, or -1 */
+} mmf_mask_info;
+int mmf_mask_default_config(mmf_mask_config *cfg);
+int mmf_mask_segment(mmf_ctx *ctx, int width, int height, const uint8_t *labels, const float *depth, const unsigned *ids,
+                     int n_models, unsigned next_id, int allow_new, uint8_t mapping[256], uint8_t *mask_out,
+                     mmf_segmentation_model *models_out, int *n_models_out, int *has_new_label, int *new_label);
+int mmf_fusion_set_mask_segmentation(mmf_fusion *f, const mmf_mask_config *cfg);
+int mmf_fusion_mask_mapping(mmf_fusion *f, uint8_t mapping_out[256]);
+int mmf_fusion_last_mask_segmentation(mmf_fusion *f, mmf_mask_info *info, mmf_segmentation_model *models, int capacity);
 
 /* ---- keypoint redetection of inactive models (Core/MultiMotionFusion.cpp:425-436, 489-559; Model::getBestMatch,
  * Core/Model/Model.cpp:781-874; Model::store / activate, :1617-1656) -------------------------------------------------

@@ -82,6 +82,14 @@ class mmf_crf_info(C.Structure):
                 ("n_components", C.c_int), ("range", C.c_float)]
 
 
+class mmf_mask_config(C.Structure):
+    _fields_ = [("model_spawn_offset", C.c_int), ("inhibit_new", C.c_int)]
+
+
+class mmf_mask_info(C.Structure):
+    _fields_ = [("n_models", C.c_int), ("allow_new", C.c_int), ("has_new_label", C.c_int), ("new_label", C.c_int)]
+
+
 class mmf_redetection(C.Structure):
     _fields_ = [("label", C.c_int), ("model_id", C.c_int), ("removed_id", C.c_int), ("activated", C.c_int),
                 ("error", C.c_float), ("inliers", C.c_int), ("view", C.c_int), ("transformation", C.c_float * 16)]
@@ -217,6 +225,12 @@ SIGNATURES = {
     "mmf_crf_segment": (_i, [_vp, C.POINTER(mmf_crf_config), _vp, _i, _i, _vp, _vp, _vp, C.POINTER(C.c_uint), _i, C.c_uint, _i,
                              _vp, C.POINTER(mmf_segmentation_model), _ip, _ip]),
     "mmf_crf_last": (_i, [_vp, C.POINTER(mmf_crf_info), C.POINTER(mmf_segmentation_model), _i, _vp, _vp, _vp, _vp]),
+    "mmf_mask_default_config": (_i, [C.POINTER(mmf_mask_config)]),
+    "mmf_mask_segment": (_i, [_vp, _i, _i, _vp, _vp, C.POINTER(C.c_uint), _i, C.c_uint, _i, C.POINTER(C.c_uint8), _vp,
+                              C.POINTER(mmf_segmentation_model), _ip, _ip, _ip]),
+    "mmf_fusion_set_mask_segmentation": (_i, [_vp, C.POINTER(mmf_mask_config)]),
+    "mmf_fusion_mask_mapping": (_i, [_vp, C.POINTER(C.c_uint8)]),
+    "mmf_fusion_last_mask_segmentation": (_i, [_vp, C.POINTER(mmf_mask_info), C.POINTER(mmf_segmentation_model), _i]),
     "mmf_fusion_export_poses": (_i, [_vp, C.c_char_p]),
     "mmf_fusion_pose_log": (_i, [_vp, _i, C.POINTER(C.c_longlong), _fp, _i, _ip]),
     "mmf_compute_fusion_weight": (_i, [_fp, _fp, _f, _fp]),

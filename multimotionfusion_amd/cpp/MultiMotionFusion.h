@@ -28,8 +28,11 @@ struct FrameData {
     int64_t timestamp = 0;
     const uint8_t* rgb = nullptr;   // CV_8UC3, width x height
     const float* depth = nullptr;   // CV_32FC1 metres, 0 = invalid
-    const uint8_t* mask = nullptr;  // optional CV_8UC1 id image, already mapped to model ids (Segmentation.cpp:89-150)
-    bool hasNewLabel = false;       // SegmentationResult::hasNewLabel of that id image
+    // optional CV_8UC1 image.  With setMaskSegmentation(true): the frame's raw labels as the reference's log readers deliver
+    // them (Segmentation.cpp:89-147 runs inside processFrame; hasNewLabel is ignored).  Otherwise: an id image already mapped
+    // to model ids, and hasNewLabel = SegmentationResult::hasNewLabel of it.
+    const uint8_t* mask = nullptr;
+    bool hasNewLabel = false;
 };
 // the same frame already resident in HBM (no upload inside processFrame)
 struct FrameDataDevice {
@@ -465,6 +468,7 @@ class MultiMotionFusion {
         // (Farneback flow + keypoint tracks) is not part of this path and keeps the error of a missing segmentation
         mmf::check(mmf_crf_default_config(&crf_), "mmf_crf_default_config");
         crf_.model_spawn_offset = (int)modelSpawnOffset, crf_.spixel_size = segm_cfg.sp_size;
+        mask_.model_spawn_offset = (int)modelSpawnOffset;
         pushCrf();
     }
     static mmf::Context& defaultContext() {
@@ -611,7 +615,10 @@ class MultiMotionFusion {
     // recorded, not interpreted here.  The CRF and spawn settings are recorded too and forwarded to the built-in
     // segmentation (mmf_fusion_set_crf_segmentation).
     void setFernThresh(const float& v) { other_["fernThresh"] = v; }
-    void setModelSpawnOffset(const unsigned& v) { other_["modelSpawnOffset"] = (float)v, crf_.model_spawn_offset = (int)v, pushCrf(); }
+    void setModelSpawnOffset(const unsigned& v) {
+        other_["modelSpawnOffset"] = (float)v, crf_.model_spawn_offset = (int)v, mask_.model_spawn_offset = (int)v;
+        pushCrf(), pushMask();
+    }
     void setModelDeactivateCount(const unsigned& v) { other_["modelDeactivateCount"] = (float)v; }
     void setCrfPairwiseSigmaRGB(const float& v) { other_["crfPairwiseSigmaRGB"] = v, crf_.sigma_rgb = v, pushCrf(); }
     void setCrfPairwiseSigmaPosition(const float& v) { other_["crfPairwiseSigmaPosition"] = v, crf_.sigma_pos = v, pushCrf(); }
@@ -641,7 +648,20 @@ class MultiMotionFusion {
         if (n) mmf::check(mmf_fusion_last_redetections(f_, out.data(), n, &n), "mmf_fusion_last_redetections");
         return out;
     }
-    void setSetInhibit(bool v) { other_["inhibitModels"] = v, crf_.inhibit_new = v ? 1 : 0, pushCrf(); }
+    void setSetInhibit(bool v) {
+        other_["inhibitModels"] = v, crf_.inhibit_new = v ? 1 : 0, mask_.inhibit_new = v ? 1 : 0;
+        pushCrf(), pushMask();
+    }
+    // not in the reference, where a frame with a mask always takes this branch (Segmentation.cpp:89): with it on,
+    // FrameData::mask / FrameDataDevice::mask are RAW labels; processFrame maps them to model ids through a table it keeps,
+    // spawns a model for the raster-first new label (modelSpawnOffset, inhibitModels) and computes the model data
+    // (unseen counts, confidence 0.4, max depth).  Off (default): the mask is an id image mapped by the caller.
+    void setMaskSegmentation(bool v) { mask_on_ = v, other_["maskSegmentation"] = v, pushMask(true); }
+    std::vector<uint8_t> getMaskMapping() {
+        std::vector<uint8_t> out(256);
+        mmf::check(mmf_fusion_mask_mapping(f_, out.data()), "mmf_fusion_mask_mapping");
+        return out;
+    }
     void setEnableSmartModelDelete(bool v) { other_["enableSmartModelDelete"] = v; }
     const std::map<std::string, float>& frontEndSettings() const { return other_; }
 
@@ -669,6 +689,9 @@ class MultiMotionFusion {
     void pushCrf() {
         mmf::check(mmf_fusion_set_crf_segmentation(f_, segm_cfg_.mode.empty() ? &crf_ : nullptr), "mmf_fusion_set_crf_segmentation");
     }
+    void pushMask(bool always = false) {  // (the settings are pushed while the mode is on)
+        if (mask_on_ || always) mmf::check(mmf_fusion_set_mask_segmentation(f_, mask_on_ ? &mask_ : nullptr), "mmf_fusion_set_mask_segmentation");
+    }
     const mmf_fusion_config& refresh() {
         mmf::check(mmf_fusion_get_config(f_, &cfg_), "mmf_fusion_get_config");
         return cfg_;
@@ -683,6 +706,8 @@ class MultiMotionFusion {
     std::map<std::string, GPUTexture*> textures_;
     std::map<std::string, float> other_;
     mmf_crf_config crf_;
+    mmf_mask_config mask_ = {22, 0};  // (mmf_mask_default_config)
+    bool mask_on_ = false;
     bool lost_ = false;
     FrameData next_;
 };

@@ -2,10 +2,11 @@
 // 863-875) for a list of rigid-body models: the global (camera) model plus the object models the segmentation
 // spawns.  Textually included at the end of mmf_hip.hip (it uses that file's static helpers).
 //
-// The segmentation is handed in per frame (mmf_segmentation: the reference's gSLICr + dense CRF, or a ground-truth id
-// image), pulled through a callback at the point where the reference calls performSegmentation (:412), or computed by the
-// built-in dense CRF (crf_kernels.hpp, mmf_fusion_set_crf_segmentation).  What stays with the caller: relocalisation,
-// ferns, deformation (closeLoops / reloc off).
+// The segmentation is handed in per frame (mmf_segmentation: the reference's gSLICr + dense CRF), pulled through a
+// callback at the point where the reference calls performSegmentation (:412), computed from the frame's raw label image
+// (mask_kernels.hpp, mmf_fusion_set_mask_segmentation: the `frame.mask` branch of Segmentation.cpp:89-147, which comes
+// first as it does there) or by the built-in dense CRF (crf_kernels.hpp, mmf_fusion_set_crf_segmentation).  What stays
+// with the caller: relocalisation, ferns, deformation (closeLoops / reloc off).
 //
 // MI355X mapping: every model owns a LANE (a child context: its own stream + reduction scratch), so the
 // latency-bound Gauss-Newton chains of different models (19 x two small launches each) overlap on the device;
@@ -95,6 +96,13 @@ struct mmf_fusion {
     bool sp_enqueued = false;          // ev_sp_done is recorded and nothing has waited for it yet
     const int* sp_last = nullptr;      // the label image the last segmentation used (handed in, the engine's, or the grid)
     std::vector<mmf_segmentation_model> crf_models;
+    // the segmentation from the frame's raw label image (mmf_fusion_set_mask_segmentation): off unless configured
+    bool mask_on = false;
+    mmf_mask_config mask_cfg;
+    uint8_t mask_map[256] = {0};     // Segmentation.cpp:92: input label -> model id, from frame to frame
+    bool mask_valid = false;         // a frame went through this path (mmf_fusion_last_mask_segmentation)
+    mmf_mask_info mask_info;
+    std::vector<mmf_segmentation_model> mask_models;
     // keypoint redetection of inactive models (MultiMotionFusion.cpp:489-559; redetect_host.hpp): off unless switched on
     bool redetect_on = false;
     mmf_viewstore* views = nullptr;  // the stored keypoint views of the inactive models (created on first use)
@@ -290,6 +298,7 @@ extern "C" int mmf_fusion_create(mmf_ctx* c, int width, int height, float cx, fl
     else
         mmf_fusion_default_config(&f->cfg);
     mmf_crf_default_config(&f->crf_cfg);
+    mmf_mask_default_config(&f->mask_cfg);
     f->width = width, f->height = height;
     f->cx = cx, f->cy = cy, f->fx = fx, f->fy = fy;
     FusionModel* global = nullptr;
@@ -537,6 +546,32 @@ extern "C" int mmf_fusion_set_crf_segmentation(mmf_fusion* f, const mmf_crf_conf
     }
     if (int rc = crf_check_config(cfg, "mmf_fusion_set_crf_segmentation")) return rc;
     f->crf_cfg = *cfg, f->crf_on = true;
+    return MMF_OK;
+}
+extern "C" int mmf_fusion_set_mask_segmentation(mmf_fusion* f, const mmf_mask_config* cfg) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_set_mask_segmentation: null fusion object");
+    if (!cfg) {
+        f->mask_on = false;
+        return MMF_OK;
+    }
+    MMF_REQUIRE(cfg->model_spawn_offset >= 0, "mmf_fusion_set_mask_segmentation: model_spawn_offset must not be negative");
+    if (f->shard_world != 1)
+        return fail(MMF_ERR_STATE, "mmf_fusion_set_mask_segmentation: needs world == 1 (a sharded front end calls mmf_mask_segment "
+                                   "in its segmentation callback)");
+    f->mask_cfg = *cfg, f->mask_on = true;
+    return MMF_OK;
+}
+extern "C" int mmf_fusion_mask_mapping(mmf_fusion* f, uint8_t mapping_out[256]) {
+    MMF_REQUIRE(f && mapping_out, "mmf_fusion_mask_mapping: null argument");
+    std::memcpy(mapping_out, f->mask_map, 256);
+    return MMF_OK;
+}
+extern "C" int mmf_fusion_last_mask_segmentation(mmf_fusion* f, mmf_mask_info* info, mmf_segmentation_model* models, int capacity) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_last_mask_segmentation: null fusion object");
+    if (!f->mask_valid) return fail(MMF_ERR_STATE, "mmf_fusion_last_mask_segmentation: no frame has been segmented from its labels yet");
+    if (info) *info = f->mask_info;
+    if (models)
+        for (int i = 0; i < (int)f->mask_models.size() && i < capacity; ++i) models[i] = f->mask_models[(size_t)i];
     return MMF_OK;
 }
 extern "C" int mmf_fusion_set_superpixels(mmf_fusion* f, const int* labels) {
@@ -1399,6 +1434,38 @@ static int fusion_crf_segment(mmf_fusion* f, mmf_segmentation* out) {
     return MMF_OK;
 }
 
+// The `frame.mask` branch of performSegmentation (Segmentation.cpp:89-147) on the fusion's stream: `labels` (the frame's raw
+// label image, uploaded on this stream or handed in as a device image) into textures[MASK], one pinned read of the summary.
+// `out` points at f->mask and f->mask_models.
+static int fusion_mask_segment(mmf_fusion* f, const uint8_t* labels, mmf_segmentation* out) {
+    if (f->shard_world != 1)
+        return fail(MMF_ERR_STATE, "mmf_fusion_process_frame: the segmentation from the frame's labels needs world == 1 (a sharded "
+                                   "front end calls mmf_mask_segment in its segmentation callback)");
+    mmf_ctx* c = f->ctx;
+    const int M = (int)f->models.size();
+    std::vector<unsigned> ids((size_t)M);
+    for (int i = 0; i < M; ++i) ids[(size_t)i] = (unsigned)f->models[(size_t)i]->model->id;
+    const unsigned next_id = (unsigned)mmf_fusion_next_model_id(f);
+    const int allow_new = f->spawn_offset >= (unsigned)f->mask_cfg.model_spawn_offset ? 1 : 0;  // (:148)
+    MaskWs* w = nullptr;
+    int rc = mask_enqueue(c, f->width, f->height, labels, f->frame_depth, ids.data(), M, next_id, allow_new, f->mask_map, f->mask,
+                          "mmf_fusion_process_frame (segmentation from labels)", &w);
+    if (rc) return rc;
+    MMF_HIP_TRY(wait_stream(c->stream));
+    const mmf::MaskSummary& s = *w->sum_host;
+    std::memcpy(f->mask_map, s.mapping, 256);
+    f->mask_models.assign(s.models, s.models + s.n_models_out);
+    std::memset(out, 0, sizeof(*out));
+    out->mask = f->mask;
+    out->has_new_label = s.has_new_label && !f->mask_cfg.inhibit_new;  // inhibitModels (:413-415): the mask and the entry stay
+    out->n_models = s.n_models_out;
+    out->model_data = f->mask_models.data();
+    f->mask_info.n_models = s.n_models_out, f->mask_info.allow_new = allow_new;
+    f->mask_info.has_new_label = out->has_new_label, f->mask_info.new_label = s.new_label;
+    f->mask_valid = true;
+    return MMF_OK;
+}
+
 // ---- keypoint redetection (MultiMotionFusion.cpp:425-436, 489-559) ----------------------------------------------------------
 static int fusion_viewstore(mmf_fusion* f) {
     if (f->views) return MMF_OK;
@@ -1578,8 +1645,15 @@ static int frame_segment(mmf_fusion* f, const FrameRun& r) {
     mmf_ctx* c = f->ctx;
     mmf_segmentation seg_cb;
     const mmf_segmentation* seg = fr->segmentation;
-    if (f->spawn_offset < (unsigned)f->crf_cfg.model_spawn_offset) f->spawn_offset++;  // (:410)
-    if (!seg && f->seg_fn) {  // performSegmentation(frame) (:412)
+    // a frame that brings raw labels (Segmentation.cpp:89: `frame.mask.total()` is tested before anything else)
+    const bool from_labels = f->mask_on && seg && seg->mask && !seg->model_data;
+    const int spawn_after = from_labels ? f->mask_cfg.model_spawn_offset : f->crf_cfg.model_spawn_offset;
+    if (f->spawn_offset < (unsigned)spawn_after) f->spawn_offset++;  // (:410)
+    if (from_labels) {
+        int rc = fusion_mask_segment(f, seg->mask, &seg_cb);
+        if (rc) return rc;
+        seg = &seg_cb;
+    } else if (!seg && f->seg_fn) {  // performSegmentation(frame) (:412)
         std::memset(&seg_cb, 0, sizeof(seg_cb));
         if (f->seg_fn(f->seg_user, f, fr, &seg_cb)) return fail(MMF_ERR_STATE, "mmf_fusion_process_frame: the segmentation callback failed");
         seg = &seg_cb;
@@ -1589,7 +1663,8 @@ static int frame_segment(mmf_fusion* f, const FrameRun& r) {
         seg = &seg_cb;
     }
     MMF_REQUIRE(seg && seg->mask, "mmf_fusion_process_frame: enableMultipleModels needs a segmentation "
-                                  "(mmf_frame::segmentation, mmf_fusion_set_segmentation_callback or mmf_fusion_set_crf_segmentation)");
+                                  "(mmf_frame::segmentation, mmf_fusion_set_segmentation_callback, mmf_fusion_set_crf_segmentation "
+                                  "or, for a frame that brings its labels, mmf_fusion_set_mask_segmentation)");
     // textures[MASK]->Upload(fullSegmentation) (:416)
     if (seg->mask != f->mask)
         MMF_HIP_TRY(hipMemcpyAsync(f->mask, seg->mask, (size_t)f->width * f->height, hipMemcpyDeviceToDevice, c->stream));
@@ -2262,6 +2337,8 @@ extern "C" int mmf_fusion_reset(mmf_fusion* f) {
         for (RdView& v : f->views->views) v.model = -1;
     f->kp_next = false;
     f->redetections.clear();
+    std::memset(f->mask_map, 0, sizeof(f->mask_map));  // (the table speaks of the models of the map that ends here)
+    f->mask_valid = false;
     std::vector<FusionModel*> all(f->preallocated);
     all.push_back(f->models[0]);
     for (FusionModel* fm : all) {

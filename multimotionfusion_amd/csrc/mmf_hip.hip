@@ -110,6 +110,8 @@ constexpr int kMaxIcpGrid = 8192;  // the single-pass ICP producer needs one wor
 
 struct CrfWs;
 static void crf_ws_free(CrfWs* w);
+struct MaskWs;
+static void mask_ws_free(MaskWs* w);
 
 struct mmf_ctx {
     int device = 0;
@@ -129,6 +131,7 @@ struct mmf_ctx {
     void* slic_engine_ws = nullptr;  // super-pixel engine workspace (centres, counts, labels), grown on demand
     size_t slic_engine_cells = 0;
     struct CrfWs* crf_ws = nullptr;  // dense-CRF segmentation workspace (crf_kernels.hpp), grown on demand
+    struct MaskWs* mask_ws = nullptr;  // label-image segmentation workspace (mask_kernels.hpp), created on first use
     char arch[64] = {0};
     int cu_count = 0;  // compute units of the device (the one-launch Gauss-Newton chain needs its grid resident at once)
 };
@@ -205,6 +208,7 @@ extern "C" void mmf_ctx_destroy(mmf_ctx* c) {
     (void)hipFree(c->slic_ws);
     (void)hipFree(c->slic_engine_ws);
     crf_ws_free(c->crf_ws);
+    mask_ws_free(c->mask_ws);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -3743,6 +3747,133 @@ extern "C" int mmf_crf_last(mmf_ctx* c, mmf_crf_info* info, mmf_segmentation_mod
     if (raw_map) MMF_HIP_TRY(hipMemcpyAsync(raw_map, w->raw_map, N, hipMemcpyDeviceToDevice, c->stream));
     if (map) MMF_HIP_TRY(hipMemcpyAsync(map, w->map, N, hipMemcpyDeviceToDevice, c->stream));
     MMF_HIP_TRY(hipStreamSynchronize(c->stream));
+    return MMF_OK;
+}
+
+// ---- segmentation from a frame's given label image (mask_kernels.hpp; Segmentation.cpp:89-147) ----------------------------
+#include "mask_kernels.hpp"
+
+struct MaskWs {
+    double* slab = nullptr;  // [2][rows][256]: the workgroups' float64 partial sums of pass 1 and pass 2
+    size_t rows = 0;
+    unsigned *cnt = nullptr, *first = nullptr;  // [256] pixels / smallest pixel index per label (zero / ~0 between calls)
+    mmf::MaskPlan* plan = nullptr;
+    mmf::MaskSummary* sum_dev = nullptr;
+    mmf::MaskSummary* sum_host = nullptr;  // pinned
+};
+
+static void mask_ws_free(MaskWs* w) {
+    if (!w) return;
+    for (void* p : {(void*)w->slab, (void*)w->cnt, (void*)w->first, (void*)w->plan, (void*)w->sum_dev}) (void)hipFree(p);
+    (void)hipHostFree(w->sum_host);
+    delete w;
+}
+
+static int mask_workspace(mmf_ctx* c, size_t rows, MaskWs** out) {
+    if (!c->mask_ws) {
+        c->mask_ws = new (std::nothrow) MaskWs();
+        MMF_REQUIRE(c->mask_ws != nullptr, "mmf_mask: out of host memory");
+        MaskWs* w = c->mask_ws;
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->cnt), 256 * sizeof(unsigned)));
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->first), 256 * sizeof(unsigned)));
+        MMF_HIP_TRY(hipMemsetAsync(w->cnt, 0, 256 * sizeof(unsigned), c->stream));
+        MMF_HIP_TRY(hipMemsetAsync(w->first, 0xff, 256 * sizeof(unsigned), c->stream));
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->plan), sizeof(mmf::MaskPlan)));
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->sum_dev), sizeof(mmf::MaskSummary)));
+        MMF_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&w->sum_host), sizeof(mmf::MaskSummary), hipHostMallocDefault));
+    }
+    MaskWs* w = c->mask_ws;
+    if (rows > w->rows) {
+        MMF_HIP_TRY(hipStreamSynchronize(c->stream));
+        (void)hipFree(w->slab);
+        w->slab = nullptr, w->rows = 0;
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->slab), 2 * rows * 256 * sizeof(double)));
+        w->rows = rows;
+    }
+    *out = w;
+    return MMF_OK;
+}
+
+// checks shared by the stand-alone call and the fusion, then the four launches and the summary's copy on the context's stream.
+// labels / depth / mask_out: DEVICE; ids / mapping: HOST.  The result is in ws->sum_host once the stream has drained.
+static int mask_enqueue(mmf_ctx* c, int W, int H, const uint8_t* labels, const float* depth, const unsigned* ids, int M,
+                        unsigned next_id, int allow_new, const uint8_t* mapping, uint8_t* mask_out, const char* who, MaskWs** ws) {
+    using namespace mmf;
+    MMF_REQUIRE(W > 0 && H > 0 && (long long)W * H < (1ll << 31), std::string(who) + ": bad image size");
+    MMF_REQUIRE(M >= 1 && M <= 255, std::string(who) + ": 1 to 255 models");
+    MMF_REQUIRE(ids[0] == 0u, std::string(who) + ": the first model of the list is the global one (id 0)");
+    MMF_REQUIRE(next_id <= 255u, std::string(who) + ": the new label's id must fit the id image (<= 255)");
+    for (int i = 0; i < M; ++i) {
+        MMF_REQUIRE(ids[i] <= 255u, std::string(who) + ": model ids must fit the id image (<= 255)");
+        for (int j = 0; j < i; ++j) MMF_REQUIRE(ids[i] != ids[j], std::string(who) + ": duplicate model id");
+        MMF_REQUIRE(!allow_new || ids[i] != next_id, std::string(who) + ": the new label's id is a model's");
+    }
+    const size_t n = (size_t)W * H;
+    MMF_REQUIRE(labels + n <= mask_out || mask_out + n <= labels, std::string(who) + ": mask_out overlaps the label image");
+    const size_t rows = (n + kMaskTile - 1) / kMaskTile;
+    MaskWs* w = nullptr;
+    if (int rc = mask_workspace(c, rows, &w)) return rc;
+    MaskArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.n = (int)n, a.n_models = M, a.allow_new = allow_new ? 1 : 0, a.next_id = next_id;
+    for (int i = 0; i < M; ++i) a.ids[i] = (uint8_t)ids[i];
+    std::memcpy(a.mapping, mapping, 256);
+    hipStream_t st = c->stream;
+    double *slab1 = w->slab, *slab2 = w->slab + rows * 256;
+    const bool vec = reinterpret_cast<uintptr_t>(labels) % 4 == 0 && reinterpret_cast<uintptr_t>(mask_out) % 4 == 0 &&
+                     reinterpret_cast<uintptr_t>(depth) % 16 == 0;
+    const dim3 grid((unsigned)rows), block(kMaskThreads);
+    if (vec)
+        hipLaunchKernelGGL((mask_bins_kernel<1, true>), grid, block, 0, st, labels, depth, a.n, (const MaskPlan*)nullptr, (uint8_t*)nullptr,
+                           slab1, w->cnt, w->first);
+    else
+        hipLaunchKernelGGL((mask_bins_kernel<1, false>), grid, block, 0, st, labels, depth, a.n, (const MaskPlan*)nullptr, (uint8_t*)nullptr,
+                           slab1, w->cnt, w->first);
+    hipLaunchKernelGGL(mask_decide_kernel, dim3(1), dim3(256), 0, st, a, (const double*)slab1, (int)rows, (const unsigned*)w->cnt,
+                       (const unsigned*)w->first, w->plan);
+    if (vec)
+        hipLaunchKernelGGL((mask_bins_kernel<2, true>), grid, block, 0, st, labels, depth, a.n, (const MaskPlan*)w->plan, mask_out, slab2,
+                           (unsigned*)nullptr, (unsigned*)nullptr);
+    else
+        hipLaunchKernelGGL((mask_bins_kernel<2, false>), grid, block, 0, st, labels, depth, a.n, (const MaskPlan*)w->plan, mask_out, slab2,
+                           (unsigned*)nullptr, (unsigned*)nullptr);
+    hipLaunchKernelGGL(mask_finish_kernel, dim3(1), dim3(256), 0, st, a, (const double*)slab2, (int)rows, (const MaskPlan*)w->plan, w->cnt,
+                       w->first, w->sum_dev);
+    if (const hipError_t e = hipGetLastError()) {
+        // a launch was refused: whatever went out before it may have left counts in the integer bins that only the finish
+        // launch clears, so they are re-armed here, behind that work, for the next call on this context
+        (void)hipMemsetAsync(w->cnt, 0, 256 * sizeof(unsigned), st);
+        (void)hipMemsetAsync(w->first, 0xff, 256 * sizeof(unsigned), st);
+        return fail(MMF_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    MMF_HIP_TRY(hipMemcpyAsync(w->sum_host, w->sum_dev, sizeof(MaskSummary), hipMemcpyDeviceToHost, st));
+    *ws = w;
+    return MMF_OK;
+}
+
+extern "C" int mmf_mask_default_config(mmf_mask_config* cfg) {
+    MMF_REQUIRE(cfg != nullptr, "mmf_mask_default_config: cfg is null");
+    cfg->model_spawn_offset = 22;  // (as mmf_crf_default_config: what the GUI pushes into setModelSpawnOffset)
+    cfg->inhibit_new = 0;
+    return MMF_OK;
+}
+
+extern "C" int mmf_mask_segment(mmf_ctx* c, int width, int height, const uint8_t* labels, const float* depth, const unsigned* ids,
+                                int n_models, unsigned next_id, int allow_new, uint8_t mapping[256], uint8_t* mask_out,
+                                mmf_segmentation_model* models_out, int* n_models_out, int* has_new_label, int* new_label) {
+    MMF_REQUIRE(c && labels && depth && ids && mapping && mask_out, "mmf_mask_segment: null argument");
+    MMF_HIP_TRY(hipSetDevice(c->device));
+    MaskWs* w = nullptr;
+    if (int rc = mask_enqueue(c, width, height, labels, depth, ids, n_models, next_id, allow_new, mapping, mask_out, "mmf_mask_segment", &w))
+        return rc;
+    MMF_HIP_TRY(hipStreamSynchronize(c->stream));
+    const mmf::MaskSummary& s = *w->sum_host;
+    std::memcpy(mapping, s.mapping, 256);
+    if (models_out)
+        for (int i = 0; i < s.n_models_out; ++i) models_out[i] = s.models[i];
+    if (n_models_out) *n_models_out = s.n_models_out;
+    if (has_new_label) *has_new_label = s.has_new_label;
+    if (new_label) *new_label = s.new_label;
     return MMF_OK;
 }
 

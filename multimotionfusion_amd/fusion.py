@@ -6,7 +6,7 @@ import weakref
 
 import numpy as np
 
-from ._capi import check, fptr, mmf_frame, mmf_fusion_config, mmf_segmentation, mmf_segmentation_model
+from ._capi import check, fptr, mmf_frame, mmf_fusion_config, mmf_mask_info, mmf_segmentation, mmf_segmentation_model
 from .cudafuncs import Context, _p
 from .model import Model
 from .odometry import RGBDOdometry
@@ -46,6 +46,8 @@ class MultiMotionFusion:
         # borrowed views of the objects the fusion owns
         self._model = self._borrow_model(ctx.lib.mmf_fusion_model(h))
         self._odom = self._borrow_odom(ctx.lib.mmf_fusion_odometry(h))
+        from .segmentation import MaskConfig
+        self._mask, self._mask_on = MaskConfig(), False  # (setMaskSegmentation)
 
     def _borrow_model(self, handle):
         m = Model.__new__(Model)
@@ -69,7 +71,8 @@ class MultiMotionFusion:
         to the pose before the dense tracker (which then refines it when icpRefine, `-icp_refine`).
         mask / hasNewLabel / modelData: the SegmentationResult of this frame when enable_multiple_models is set
         (fullSegmentation as a CUDA uint8 [H,W] tensor of model ids; modelData: dicts with id, super_pixel_count,
-        avg_confidence, depth_mean, depth_std in list order).  initTransforms: one 4x4 per active model.
+        avg_confidence, depth_mean, depth_std in list order).  With setMaskSegmentation on, a mask without modelData is the
+        frame's RAW label image and hasNewLabel is ignored.  initTransforms: one 4x4 per active model.
         next: (rgb, depth) the NEXT call will be given -- prefetchFrame folded into this call: the next frame's
         sensor-side preparation is enqueued while this one waits for its pose (mmf_frame::next_rgb / next_depth)."""
         if mask is not None or initTransforms is not None or next is not None:
@@ -246,8 +249,50 @@ class MultiMotionFusion:
     def setCrfIteration(self, v): self._crf_set("iterations", int(v))
     def setNewModelMinRelativeSize(self, v): self._crf_set("min_rel_size_new", float(v))
     def setNewModelMaxRelativeSize(self, v): self._crf_set("max_rel_size_new", float(v))
-    def setModelSpawnOffset(self, v): self._crf_set("model_spawn_offset", int(v))
-    def setSetInhibit(self, v): self._crf_set("inhibit_new", int(bool(v)))
+    def setModelSpawnOffset(self, v):
+        self._crf_set("model_spawn_offset", int(v))
+        self._mask_set("model_spawn_offset", int(v))
+
+    def setSetInhibit(self, v):
+        self._crf_set("inhibit_new", int(bool(v)))
+        self._mask_set("inhibit_new", int(bool(v)))
+
+    # ----- the segmentation from a frame's own label image (Segmentation.cpp:89-147; segmentation.mask_segment)
+    def setMaskSegmentation(self, cfg=True):
+        """cfg: a segmentation.MaskConfig (True: the current settings); None / False: off (the default).  With it on, a
+        mask handed to processFrame / processFrameHost WITHOUT modelData is the frame's raw label image (Mask####.png,
+        ground-truth ids, an instance segmenter's output): processFrame maps it to model ids through its persistent table,
+        spawns a model for the raster-first new label and computes the model data itself; hasNewLabel is ignored."""
+        if cfg is None or cfg is False:
+            self._mask_on = False
+            check(self.ctx.lib.mmf_fusion_set_mask_segmentation(self.handle, None))
+            return
+        if cfg is not True:
+            self._mask = cfg
+        self._mask_on = True
+        check(self.ctx.lib.mmf_fusion_set_mask_segmentation(self.handle, C.byref(self._mask.to_c())))
+
+    def _mask_set(self, name, v):
+        setattr(self._mask, name, v)
+        if self._mask_on:  # (pushed while the mode is on; kept for when it is switched on otherwise)
+            check(self.ctx.lib.mmf_fusion_set_mask_segmentation(self.handle, C.byref(self._mask.to_c())))
+
+    def maskMapping(self):
+        """the persistent input label -> model id table (numpy uint8 [256]); reset() clears it"""
+        out = np.zeros(256, np.uint8)
+        check(self.ctx.lib.mmf_fusion_mask_mapping(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def lastMaskSegmentation(self):
+        """what the last frame segmented from its labels computed: model data (list order, then the new label's entry),
+        allow_new, has_new_label as processFrame used it, new_label (the input label that became new, or -1)"""
+        from .segmentation import model_data_dicts
+        info = mmf_mask_info()
+        check(self.ctx.lib.mmf_fusion_last_mask_segmentation(self.handle, C.byref(info), None, 0))
+        md = (mmf_segmentation_model * max(info.n_models, 1))()
+        check(self.ctx.lib.mmf_fusion_last_mask_segmentation(self.handle, C.byref(info), md, info.n_models))
+        return dict(model_data=model_data_dicts(md, info.n_models), allow_new=bool(info.allow_new),
+                    has_new_label=bool(info.has_new_label), new_label=info.new_label)
 
     def setSuperpixels(self, labels):
         """the super-pixel label image (int32 [H,W] CUDA tensor) of the NEXT frame's segmentation; None: the regular grid"""

@@ -1,5 +1,6 @@
-"""The dense-CRF motion segmentation on the device (Segmentation::performSegmentationCRF, Core/Segmentation/
-Segmentation.cpp:159-740; csrc/crf_kernels.hpp) over the C ABI -- no fallback.
+"""The segmentations of Segmentation::performSegmentation on the device, over the C ABI -- no fallback: the dense CRF
+(performSegmentationCRF, Core/Segmentation/Segmentation.cpp:159-740; csrc/crf_kernels.hpp) and the branch for a frame that
+brings its own label image (:89-147; csrc/mask_kernels.hpp, `mask_segment`).
 
 `segment` is the stand-alone call (per-super-pixel maps in, mask and model data out): what a sharded front end runs in
 its segmentation callback on the maps of mmf_shard_gather_maps.  MultiMotionFusion.setCrfSegmentation runs the same
@@ -9,7 +10,7 @@ from dataclasses import dataclass, fields
 
 import torch
 
-from ._capi import check, mmf_crf_config, mmf_crf_info, mmf_segmentation_model
+from ._capi import check, mmf_crf_config, mmf_crf_info, mmf_mask_config, mmf_segmentation_model
 from .cudafuncs import Context, _p
 
 
@@ -65,6 +66,40 @@ def segment(ctx: Context, rgb, depth, low_maps, ids, next_id, allow_new, cfg: Cr
                                   _p(depth), _p(low_maps), c_ids, M, int(next_id), int(bool(allow_new)), _p(mask), out,
                                   C.byref(n_out), C.byref(has_new)))
     return mask, model_data_dicts(out, n_out.value), bool(has_new.value)
+
+
+@dataclass
+class MaskConfig:
+    """The settings the label-image segmentation reads inside processFrame (MultiMotionFusion.setMaskSegmentation)."""
+    model_spawn_offset: int = 22
+    inhibit_new: int = 0
+
+    def to_c(self):
+        c = mmf_mask_config()
+        c.model_spawn_offset, c.inhibit_new = int(self.model_spawn_offset), int(self.inhibit_new)
+        return c
+
+
+def mask_segment(ctx: Context, labels, depth, ids, next_id, allow_new, mapping):
+    """Segmentation.cpp:89-147 for one frame.  labels [H,W] u8 (arbitrary input labels, 0 = background), depth [H,W] float32
+    metres (CUDA tensors); ids = the model ids in list order (ids[0] == 0); mapping = the 256-entry label -> id table as the
+    frame finds it (any sequence of 256 values; not modified).
+    Returns (mask [H,W] u8 CUDA tensor, model data list of dicts, has_new_label, new_label or -1, the updated table as a
+    numpy uint8 array)."""
+    import numpy as np
+    H, W = depth.shape
+    assert labels.dtype == torch.uint8 and labels.shape == (H, W) and depth.dtype == torch.float32
+    labels, depth = labels.contiguous(), depth.contiguous()
+    table = np.ascontiguousarray(np.asarray(mapping, np.uint8).reshape(256).copy())
+    mask = torch.empty((H, W), dtype=torch.uint8, device=depth.device)
+    M = len(ids)
+    c_ids = (C.c_uint * max(M, 1))(*[int(i) for i in ids])
+    out = (mmf_segmentation_model * (M + 1))()
+    n_out, has_new, new_label = C.c_int(), C.c_int(), C.c_int()
+    check(ctx.lib.mmf_mask_segment(ctx.handle, W, H, _p(labels), _p(depth), c_ids, M, int(next_id), int(bool(allow_new)),
+                                   table.ctypes.data_as(C.POINTER(C.c_uint8)), _p(mask), out, C.byref(n_out), C.byref(has_new),
+                                   C.byref(new_label)))
+    return mask, model_data_dicts(out, n_out.value), bool(has_new.value), new_label.value, table
 
 
 def _last(fn, handle, device):
