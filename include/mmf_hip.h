@@ -882,6 +882,86 @@ void mmf_ransac_destroy(mmf_ransac *r);
 int mmf_ransac_estimate(mmf_ransac *r, const float *p0, const float *p1, int n, const unsigned char *mask,
                         float T[16], float *error, unsigned char *inlier, int *has_inlier);
 
+/* ---- keypoint tracks on the device: tracker::PointTracker (Core/Utils/PointTracker.cpp:27-226), the per-model track sets
+ * (Model::tracks, Model::updateTracks, Core/Model/Model.cpp:630-640; MultiMotionFusion.cpp:425-436, 584-604, 622-627) and
+ * Model::getLastTrackTransform (Model.cpp:739-775) -------------------------------------------------------------------------
+ * A TRACKER is a table of at most `capacity` tracks in the order of the reference's `tracks` vector (csrc/tracker_kernels.hpp).
+ * Per track it keeps what the reference's consumers read, not the history: the descriptor of the last non-null keypoint, the
+ * last two slots `cur` = end()[-1] and `prev` = end()[-2] (xy, coordinate, timestamp, non-null flag; a null slot holds zeros),
+ * age (frames since the last non-null keypoint, 0 = this frame), nvalid (non-null keypoints so far), last_stamp, a uid that is
+ * never reused, this frame's label and `member`, a 256-bit set of model ids: bit m = the track is in Model m's `tracks`.
+ * `length` is the common length of the reference's tracks: frames since the table was last empty (0 when empty).
+ * Pyramid level 0 only.  Every call enqueues a fixed number of launches on the context's stream, whatever the number of
+ * keypoints and tracks, and returns; the calls marked "waits" wait for the stream once.  Differences from the reference:
+ * a track that does not fit is dropped and counted (the reference's vector grows without bound), and a keypoint outside
+ * the image gets NaN coordinates (the reference reads the depth image out of bounds there).
+ *   mmf_tracker_create      intrinsics of level 0; max_keypoints bounds n of an add
+ *   mmf_tracker_add_keypoints   addKeypoints (:27-131): DEVICE xy [n][2] int pixels (cvRound(normalised * (cols, rows)), :38),
+ *                       DEVICE descriptor [n][256] (16-byte aligned), DEVICE depth [height][width] f32; all three are read
+ *                       by the enqueued work.  coordinate = z * (x - cx) / fx, ... in float, NaN where z <= 0.  The active
+ *                       tracks (age < history before this frame; history 0: all) are matched with the kernels of
+ *                       mmf_match_descriptors (cross check, distance <= min_feature_distance unless that is < epsilon); every
+ *                       track is extended by a null keypoint, matched tracks get theirs, unmatched keypoints start tracks in
+ *                       ascending index.  An empty table adds without matching and restarts `length` at 1 (:61-66).
+ *   mmf_tracker_prune       prune (:170-203): tracks with nvalid < min_kps AND last_stamp < min_time go, the rest close up in order
+ *   mmf_tracker_associate   mask = DEVICE u8 id image [height][width].  label = mask at cur.xy for tracks whose cur is non-null
+ *                       and inside the image, else -1.  For every listed model m that is some track's label: bit m of every
+ *                       LABELLED track becomes (label == m); unlabelled tracks keep their sets (updateTracks(segm_tracks[m],
+ *                       the other segments' tracks), :584-604)
+ *   mmf_tracker_associate_all   every track joins every listed model (:622-627; initGlobalTracks at the first frame)
+ *   mmf_tracker_forget_model    the model is gone: its bit is cleared everywhere
+ *   mmf_tracker_last_pairs  waits.  For every listed model, in ONE launch: the tracks of the model, in table order, whose prev and
+ *                       cur are non-null with finite coordinates (Model.cpp:747-761).  *p0 (prev) / *p1 (cur) = pinned HOST
+ *                       [n_models][*stride][3], *counts = pinned HOST [n_models]; valid until the tracker's next call
+ *   mmf_tracker_last_track_transform   waits.  getLastTrackTransform of one model: a fresh RigidRANSAC(cfg; NULL = {10, 0.03, 0.6})
+ *                       on its pairs, p0 ~ T p1; fewer than 3 pairs: identity, error +inf, *has_inlier = 0.  inlier (optional)
+ *                       holds at least `capacity` bytes: Result::inlier over the hash-sorted pairs
+ *   mmf_tracker_visible     waits.  The tracks with a non-null cur, in order (track->back(), MultiMotionFusion.cpp:428-431): HOST xy
+ *                       [*n][2], coordinate [*n][3], descriptor [*n][256], uid [*n]; arrays of `capacity` rows, any may be NULL
+ *   mmf_tracker_status      waits.  Tracks, length, and the appends dropped since creation / reset
+ *   mmf_tracker_download    waits.  The whole table into HOST arrays of `capacity` rows (tests and tools): the two-slot arrays
+ *                       hold cur at row 0 and prev at row `capacity`; any array may be NULL
+ *   mmf_tracker_last_launches   kernel launches of the tracker's last call
+ *   mmf_tracker_reset       empty table, uid and counters from 0
+ * Inside processFrame (off by default; MMF_ERR_STATE with world > 1; the fusion does not own the tracker, which must share
+ * its context and image size):
+ *   mmf_fusion_set_tracker      tracker = NULL detaches.  The caller adds and prunes a frame's keypoints BEFORE processFrame
+ *                       (MultiMotionFusion.cpp:223-248).  First frame: every track joins model 0.  Later tracked frames with
+ *                       odom_init_kp: one pairs call for all active models, one transformation per model in list order,
+ *                       handed to the init_transforms path with the setter's icp_refine (a frame that brings init_transforms
+ *                       of its own: MMF_ERR_INVALID).  After the frame's segmentation, redetection and spawn: associate against
+ *                       textures[MASK] with the active ids (associate_all without enable_multiple_models); a model that left
+ *                       the active list is forgotten.  With redetection on, a frame without mmf_fusion_set_keypoints takes
+ *                       the tracker's visible set as its keypoints.
+ *   mmf_fusion_last_track_transforms   the transformations the last frame's models were initialised with (list order) */
+typedef struct mmf_tracker mmf_tracker;
+typedef struct {
+    int iterations;
+    float inlier_threshold, inlier_fraction;
+} mmf_ransac_config;
+int mmf_tracker_create(mmf_ctx *ctx, int width, int height, float fx, float fy, float cx, float cy, int capacity,
+                       int max_keypoints, mmf_tracker **out);
+void mmf_tracker_destroy(mmf_tracker *t);
+int mmf_tracker_add_keypoints(mmf_tracker *t, int n, const int *xy, const float *descriptor, const float *depth,
+                              long long timestamp, float min_feature_distance, int history);
+int mmf_tracker_prune(mmf_tracker *t, int min_kps, long long min_time);
+int mmf_tracker_associate(mmf_tracker *t, const uint8_t *mask, const int *model_ids, int n_models);
+int mmf_tracker_associate_all(mmf_tracker *t, const int *model_ids, int n_models);
+int mmf_tracker_forget_model(mmf_tracker *t, int model_id);
+int mmf_tracker_last_pairs(mmf_tracker *t, const int *model_ids, int n_models, const float **p0, const float **p1,
+                           const int **counts, int *stride);
+int mmf_tracker_last_track_transform(mmf_tracker *t, int model_id, const mmf_ransac_config *cfg, float T[16], float *error,
+                                     unsigned char *inlier, int *has_inlier);
+int mmf_tracker_visible(mmf_tracker *t, int capacity, int *n, int *xy, float *coordinate, float *descriptor, long long *uid);
+int mmf_tracker_status(mmf_tracker *t, int *n_tracks, int *length, int *dropped);
+int mmf_tracker_download(mmf_tracker *t, int capacity, int *n_tracks, float *descriptor, int *age, int *nvalid,
+                         long long *last_stamp, long long *uid, int *xy, float *coordinate, long long *timestamp, int *nonnull,
+                         unsigned *member, int *label);
+int mmf_tracker_last_launches(mmf_tracker *t);
+int mmf_tracker_reset(mmf_tracker *t);
+int mmf_fusion_set_tracker(mmf_fusion *f, mmf_tracker *tracker, int odom_init_kp, int icp_refine);
+int mmf_fusion_last_track_transforms(mmf_fusion *f, float *T, int capacity, int *n_out);
+
 #ifdef __cplusplus
 }
 #endif

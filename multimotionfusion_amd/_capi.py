@@ -95,7 +95,11 @@ class mmf_redetection(C.Structure):
                 ("error", C.c_float), ("inliers", C.c_int), ("view", C.c_int), ("transformation", C.c_float * 16)]
 
 
-SEGMENTATION_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(mmf_frame), C.POINTER(mmf_segmentation))
+class mmf_ransac_config(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("inlier_threshold", C.c_float), ("inlier_fraction", C.c_float)]
+
+
+SEGMENTATION_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(mmf_frame), C.POINTER(mmf_segmentation))
 
 
 _vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
@@ -290,6 +294,22 @@ SIGNATURES = {
     "mmf_fusion_set_keypoints": (_i, [_vp, _i, _vp, _vp, _vp]),
     "mmf_fusion_viewstore": (_vp, [_vp]),
     "mmf_fusion_last_redetections": (_i, [_vp, C.POINTER(mmf_redetection), _i, _ip]),
+    "mmf_tracker_create": (_i, [_vp, _i, _i, _f, _f, _f, _f, _i, _i, C.POINTER(_vp)]),
+    "mmf_tracker_destroy": (None, [_vp]),
+    "mmf_tracker_add_keypoints": (_i, [_vp, _i, _vp, _vp, _vp, C.c_longlong, _f, _i]),
+    "mmf_tracker_prune": (_i, [_vp, _i, C.c_longlong]),
+    "mmf_tracker_associate": (_i, [_vp, _vp, _ip, _i]),
+    "mmf_tracker_associate_all": (_i, [_vp, _ip, _i]),
+    "mmf_tracker_forget_model": (_i, [_vp, _i]),
+    "mmf_tracker_last_pairs": (_i, [_vp, _ip, _i, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_ip), _ip]),
+    "mmf_tracker_last_track_transform": (_i, [_vp, _i, C.POINTER(mmf_ransac_config), _vp, _fp, _vp, _ip]),
+    "mmf_tracker_visible": (_i, [_vp, _i, _ip, _vp, _vp, _vp, _vp]),
+    "mmf_tracker_status": (_i, [_vp, _ip, _ip, _ip]),
+    "mmf_tracker_download": (_i, [_vp, _i, _ip] + [_vp] * 11),
+    "mmf_tracker_last_launches": (_i, [_vp]),
+    "mmf_tracker_reset": (_i, [_vp]),
+    "mmf_fusion_set_tracker": (_i, [_vp, _vp, _i, _i]),
+    "mmf_fusion_last_track_transforms": (_i, [_vp, _vp, _i, _ip]),
 }
 
 _lib = None

@@ -22,6 +22,8 @@
 #include "GPUTexture.h"
 #include "RGBDOdometry.h"
 #include "RigidRANSAC.h"
+#include "PointTracker.h"
+#include "SuperPoint.h"
 
 // FrameData (Core/FrameData.h:25-43) without OpenCV: one frame in HOST memory, as the log readers deliver it
 struct FrameData {
@@ -427,7 +429,7 @@ class MultiMotionFusion {
     // GUI defaults of GUI/MainController.cpp:333-345, 514-517
     MultiMotionFusion(mmf::Context& ctx, int width, int height, float cx, float cy, float fx, float fy,
                       const mmf_fusion_config* cfg = nullptr)
-        : width_(width), height_(height) {
+        : width_(width), height_(height), ctx_(ctx.get()), fx_(fx), fy_(fy), cx_(cx), cy_(cy) {
         mmf::check(mmf_fusion_create(ctx.get(), width, height, cx, cy, fx, fy, cfg, &f_), "mmf_fusion_create");
         mmf::check(mmf_fusion_get_config(f_, &cfg_), "mmf_fusion_get_config");
         mmf::check(mmf_crf_default_config(&crf_), "mmf_crf_default_config");
@@ -462,6 +464,7 @@ class MultiMotionFusion {
         other_["modelSpawnOffset"] = (float)modelSpawnOffset, other_["exportSegmentationResults"] = exportSegmentationResults;
         other_["hasKeypointPredictor"] = !keypoint_predictor_path.empty();
         const Intrinsics& K = Intrinsics::getInstance();
+        ctx_ = defaultContext().get(), fx_ = K.fx(), fy_ = K.fy(), cx_ = K.cx(), cy_ = K.cy();
         mmf::check(mmf_fusion_create(defaultContext().get(), width_, height_, K.cx(), K.cy(), K.fx(), K.fy(), &cfg, &f_), "mmf_fusion_create");
         mmf::check(mmf_fusion_get_config(f_, &cfg_), "mmf_fusion_get_config");
         // the segmentation of a maskless multi-model frame: the built-in dense CRF in the default mode (""); "flow_crf"
@@ -482,6 +485,9 @@ class MultiMotionFusion {
         for (auto& kv : textures_) delete kv.second;
         models_.clear();
         mmf_fusion_destroy(f_);
+        tracker_.reset();  // (after the fusion, which holds its handle)
+        (void)hipFree(kp_rgb_);
+        (void)hipFree(kp_depth_);
     }
     MultiMotionFusion(const MultiMotionFusion&) = delete;
     MultiMotionFusion& operator=(const MultiMotionFusion&) = delete;
@@ -496,6 +502,7 @@ class MultiMotionFusion {
                       void* /*GroundTruthOdometryInterface*/ = nullptr, const bool bootstrap = false) {
         const FrameData next = next_;  // announced by announceNextFrame (one call only)
         next_ = FrameData();
+        if (kp_predictor_ && frame.rgb && frame.depth && frame.timestamp >= 0 && !addFrameKeypoints(frame)) return false;
         return finish(mmf_fusion_process_frame_host_next(f_, frame.rgb, frame.depth, frame.mask, frame.hasNewLabel, frame.timestamp, inPose,
                                                          weightMultiplier, bootstrap, next.rgb, next.depth),
                       "mmf_fusion_process_frame_host");
@@ -648,6 +655,27 @@ class MultiMotionFusion {
         if (n) mmf::check(mmf_fusion_last_redetections(f_, out.data(), n, &n), "mmf_fusion_last_redetections");
         return out;
     }
+    // ----- keypoint tracks (MultiMotionFusion.h:307-309, 366; .cpp:223-248, 312-335): with a predictor set, processFrame(FrameData)
+    // runs getFeatures on the frame, adds its keypoints to the tracker (0.7, 30) and prunes it (30, 1 s) before the library
+    // call, which initialises every model from its own tracks when odom_cfg.init == "kp" and keeps the models' track sets
+    void setOdomInit(const std::string& init) { odom_cfg_.init = init, pushTracker(); }  // "kp" or ""
+    void setOdomRefine(bool icp_refine) { odom_cfg_.icp_refine = icp_refine, pushTracker(); }
+    // not owned; nullptr detaches the tracker.  max_tracks bounds the table (dropped appends are counted: getTracker()->dropped())
+    void setKeypointPredictor(SuperPoint* predictor, int max_tracks = 4096, int max_keypoints = 4096) {
+        kp_predictor_ = predictor;
+        if (predictor && !tracker_)
+            tracker_.reset(new tracker::PointTracker(ctx_, width_, height_, fx_, fy_, cx_, cy_, max_tracks, max_keypoints));
+        pushTracker();
+    }
+    tracker::PointTracker* getTracker() { return tracker_.get(); }
+    // the transformations the last frame's models were initialised with, list order (row-major 4x4 each)
+    std::vector<float> getLastTrackTransforms() {
+        int n = 0;
+        mmf::check(mmf_fusion_last_track_transforms(f_, nullptr, 0, &n), "mmf_fusion_last_track_transforms");
+        std::vector<float> out((size_t)n * 16);
+        if (n) mmf::check(mmf_fusion_last_track_transforms(f_, out.data(), n, &n), "mmf_fusion_last_track_transforms");
+        return out;
+    }
     void setSetInhibit(bool v) {
         other_["inhibitModels"] = v, crf_.inhibit_new = v ? 1 : 0, mask_.inhibit_new = v ? 1 : 0;
         pushCrf(), pushMask();
@@ -689,6 +717,33 @@ class MultiMotionFusion {
     void pushCrf() {
         mmf::check(mmf_fusion_set_crf_segmentation(f_, segm_cfg_.mode.empty() ? &crf_ : nullptr), "mmf_fusion_set_crf_segmentation");
     }
+    void pushTracker() {
+        other_["odomInitKp"] = odom_cfg_.init == "kp", other_["hasKeypointPredictor"] = kp_predictor_ != nullptr;
+        mmf::check(mmf_fusion_set_tracker(f_, kp_predictor_ && tracker_ ? tracker_->handle() : nullptr, odom_cfg_.init == "kp" ? 1 : 0,
+                                          odom_cfg_.icp_refine ? 1 : 0),
+                   "mmf_fusion_set_tracker");
+    }
+    // MultiMotionFusion.cpp:223-248 at level 0: the frame's features into the tracker (device copies of rgb and depth of its own)
+    bool addFrameKeypoints(const FrameData& frame) {
+        const size_t npix = (size_t)width_ * height_;
+        if (!kp_rgb_ && (hipMalloc(reinterpret_cast<void**>(&kp_rgb_), npix * 3) != hipSuccess ||
+                         hipMalloc(reinterpret_cast<void**>(&kp_depth_), npix * sizeof(float)) != hipSuccess)) {
+            std::fprintf(stderr, "MultiMotionFusion: hipMalloc of the keypoint images failed\n");
+            return false;
+        }
+        mmf::check(mmf_ctx_synchronize(ctx_), "mmf_ctx_synchronize");  // (the last frame's add has read the depth copy)
+        if (hipMemcpy(kp_rgb_, frame.rgb, npix * 3, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(kp_depth_, frame.depth, npix * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+            std::fprintf(stderr, "MultiMotionFusion: upload of the keypoint images failed\n");
+            return false;
+        }
+        std::vector<double> coordinates, descriptors;
+        std::tie(coordinates, descriptors) = kp_predictor_->getFeatures(kp_rgb_, width_, height_, 3);
+        tracker_->addKeypoints(coordinates, descriptors, frame.timestamp, kp_depth_, 0.7f, 30);
+        const int64_t old = (int64_t)frame.timestamp - 1000000000LL;
+        tracker_->prune(30, (uint64_t)(old > 0 ? old : 0));  // tracks older than 1 s with fewer than 30 keypoints (:246)
+        return true;
+    }
     void pushMask(bool always = false) {  // (the settings are pushed while the mode is on)
         if (mask_on_ || always) mmf::check(mmf_fusion_set_mask_segmentation(f_, mask_on_ ? &mask_ : nullptr), "mmf_fusion_set_mask_segmentation");
     }
@@ -699,6 +754,12 @@ class MultiMotionFusion {
     mmf_fusion* f_ = nullptr;
     mmf_fusion_config cfg_;
     int width_, height_;
+    mmf_ctx* ctx_ = nullptr;
+    float fx_ = 0, fy_ = 0, cx_ = 0, cy_ = 0;
+    SuperPoint* kp_predictor_ = nullptr;
+    std::unique_ptr<tracker::PointTracker> tracker_;
+    unsigned char* kp_rgb_ = nullptr;
+    float* kp_depth_ = nullptr;
     OdometryConfig odom_cfg_;
     SegmentationConfiguration segm_cfg_;
     std::string exportDirectory_;

@@ -112,6 +112,11 @@ struct mmf_fusion {
     int *kp_xy_pin = nullptr, *kp_label_pin = nullptr;  // host memory the gather kernel reads / writes
     size_t kp_cap = 0;
     std::vector<mmf_redetection> redetections;  // what the last frame's redetection did
+    // keypoint tracks (tracker_host.hpp; mmf_fusion_set_tracker): not owned, off unless attached
+    mmf_tracker* tracker = nullptr;
+    bool trk_init_kp = false, trk_icp_refine = true;
+    std::vector<int> trk_ids;      // the active models' ids at the last association
+    std::vector<float> trk_T;      // the transformations the last frame's models were initialised with, list order
     hipEvent_t ev_frame_ready = nullptr;  // fusion stream: the frame's shared inputs are complete
     // next-frame prefetch (mmf_fusion_prefetch_frame): the filter and the input-side preparation of frame t+1 run
     // on `side` while frame t is fused on the context's stream.  Two filtered-depth buffers: frame t's fuse /
@@ -1466,6 +1471,57 @@ static int fusion_mask_segment(mmf_fusion* f, const uint8_t* labels, mmf_segment
     return MMF_OK;
 }
 
+// ---- keypoint tracks (MultiMotionFusion.cpp:312-335, 425-436, 584-604, 622-627; tracker_host.hpp) ------------------------------
+extern "C" int mmf_fusion_set_tracker(mmf_fusion* f, mmf_tracker* tracker, int odom_init_kp, int icp_refine) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_set_tracker: null fusion object");
+    if (tracker && f->shard_world > 1) return fail(MMF_ERR_STATE, "mmf_fusion_set_tracker: sharded use is not supported (world > 1)");
+    MMF_REQUIRE(!tracker || (tracker->ctx == f->ctx && tracker->width == f->width && tracker->height == f->height),
+                "mmf_fusion_set_tracker: the tracker must share the fusion's context and image size");
+    f->tracker = tracker;
+    f->trk_init_kp = tracker && odom_init_kp != 0, f->trk_icp_refine = icp_refine != 0;
+    f->trk_ids.clear(), f->trk_T.clear();
+    return MMF_OK;
+}
+extern "C" int mmf_fusion_last_track_transforms(mmf_fusion* f, float* T, int capacity, int* n_out) {
+    MMF_REQUIRE(f && n_out && capacity >= 0 && (T || capacity == 0), "mmf_fusion_last_track_transforms: bad argument");
+    *n_out = (int)(f->trk_T.size() / 16);
+    for (int i = 0; i < *n_out && i < capacity; ++i) std::memcpy(T + 16 * i, f->trk_T.data() + 16 * (size_t)i, 16 * sizeof(float));
+    return MMF_OK;
+}
+
+// model->getLastTrackTransform() of every active model (:322), list order: one pairs launch, one wait, RANSAC on the host
+static int frame_track_transforms(mmf_fusion* f) {
+    std::vector<int> ids;
+    for (FusionModel* fm : f->models) ids.push_back((int)fm->model->id);
+    const float *p0 = nullptr, *p1 = nullptr;
+    const int* counts = nullptr;
+    int stride = 0;
+    int rc = mmf_tracker_last_pairs(f->tracker, ids.data(), (int)ids.size(), &p0, &p1, &counts, &stride);
+    if (rc) return rc;
+    f->trk_T.resize(16 * ids.size());
+    for (size_t k = 0; k < ids.size(); ++k) {
+        const mmf::RigidRANSAC::Result res = tracker_transform(p0 + k * (size_t)stride * 3, p1 + k * (size_t)stride * 3, counts[k], kTrackRansac);
+        isometry_to_4x4(res.transformation, f->trk_T.data() + 16 * k);
+    }
+    return MMF_OK;
+}
+
+// the models' track sets after the frame's segmentation, spawn and redetection (:584-604; one model: :622-627; the first
+// frame: initGlobalTracks); a model that left the active list since the last association is forgotten
+static int frame_associate_tracks(mmf_fusion* f, bool all, bool by_mask) {
+    std::vector<int> ids;
+    for (FusionModel* fm : f->models) ids.push_back((int)fm->model->id);
+    for (int old : f->trk_ids)
+        if (std::find(ids.begin(), ids.end(), old) == ids.end()) {
+            int rc = mmf_tracker_forget_model(f->tracker, old);
+            if (rc) return rc;
+        }
+    f->trk_ids = ids;
+    if (all) return mmf_tracker_associate_all(f->tracker, ids.data(), (int)ids.size());
+    if (by_mask) return mmf_tracker_associate(f->tracker, f->mask, ids.data(), (int)ids.size());
+    return MMF_OK;  // (a frame with a dictated pose has no segmentation)
+}
+
 // ---- keypoint redetection (MultiMotionFusion.cpp:425-436, 489-559) ----------------------------------------------------------
 static int fusion_viewstore(mmf_fusion* f) {
     if (f->views) return MMF_OK;
@@ -1548,7 +1604,18 @@ static int redetect_activate(mmf_fusion* f, FusionModel* fm, const float pose[16
 static int frame_redetect(mmf_fusion* f, bool* has_new) {
     const bool have_kp = f->kp_next;
     f->kp_next = false;  // (for this frame only)
-    if (!f->redetect_on || !have_kp || f->inactive.empty() || !f->views || f->views->views.empty()) return MMF_OK;
+    if (!f->redetect_on || !(have_kp || f->tracker) || f->inactive.empty() || !f->views || f->views->views.empty()) return MMF_OK;
+    if (!have_kp) {  // no mmf_fusion_set_keypoints for this frame: the attached tracker's visible set (:428-431)
+        int nv = 0;
+        int rc = tracker_visible_device(f->tracker, &nv);
+        if (rc) return rc;
+        f->kp_xy.resize(2 * (size_t)nv), f->kp_coord.resize(3 * (size_t)nv), f->kp_desc.resize((size_t)kRdDim * (size_t)nv);
+        if (nv > 0) {
+            MMF_HIP_TRY(hipMemcpy(f->kp_xy.data(), f->tracker->vis_xy, f->kp_xy.size() * sizeof(int), hipMemcpyDeviceToHost));
+            MMF_HIP_TRY(hipMemcpy(f->kp_coord.data(), f->tracker->vis_co, f->kp_coord.size() * sizeof(float), hipMemcpyDeviceToHost));
+            MMF_HIP_TRY(hipMemcpy(f->kp_desc.data(), f->tracker->vis_desc, f->kp_desc.size() * sizeof(float), hipMemcpyDeviceToHost));
+        }
+    }
     mmf_ctx* c = f->ctx;
     mmf_viewstore* vs = f->views;
     const size_t n = f->kp_xy.size() / 2;
@@ -1948,6 +2015,19 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
     r.host_trace = tunables().host_trace;
     r.have_init = fr->init_transforms != nullptr && fr->n_init_transforms > 0;
     r.track = f->tick > 1 && (fr->bootstrap || !fr->in_pose);
+    mmf_frame fr_kp;  // the frame with the transformations of the attached tracker (odom_cfg.init == "kp")
+    if (f->tracker) {
+        MMF_REQUIRE(!r.have_init, "mmf_fusion_process_frame: a tracker is attached (mmf_fusion_set_tracker): the frame cannot bring init_transforms");
+        f->trk_T.clear();
+        if (f->trk_init_kp && r.track) {
+            int rc = frame_track_transforms(f);
+            if (rc) return rc;
+            fr_kp = *fr;
+            fr_kp.init_transforms = f->trk_T.data(), fr_kp.n_init_transforms = (int)(f->trk_T.size() / 16);
+            fr_kp.icp_refine = f->trk_icp_refine ? 1 : 0;
+            fr = &fr_kp, r.fr = fr, r.have_init = true;
+        }
+    }
     f->t_tracking_s = 0;
     f->redetections.clear();  // (mmf_fusion_last_redetections speaks of this call)
     int rc = frame_begin(f, r);
@@ -1969,6 +2049,10 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
             if (rc) return rc;
         }
         r.stamp(f, 2);
+    }
+    if (f->tracker) {
+        rc = frame_associate_tracks(f, first || !f->cfg.enable_multiple_models, r.track);
+        if (rc) return rc;
     }
     f->sp_next = false;  // (mmf_fusion_set_superpixels: this call's labels only, whichever segmentation ran)
     f->kp_next = false;  // (mmf_fusion_set_keypoints: this call's keypoints only, whether or not a segmentation ran)
@@ -2337,6 +2421,7 @@ extern "C" int mmf_fusion_reset(mmf_fusion* f) {
         for (RdView& v : f->views->views) v.model = -1;
     f->kp_next = false;
     f->redetections.clear();
+    f->trk_ids.clear(), f->trk_T.clear();
     std::memset(f->mask_map, 0, sizeof(f->mask_map));  // (the table speaks of the models of the map that ends here)
     f->mask_valid = false;
     std::vector<FusionModel*> all(f->preallocated);

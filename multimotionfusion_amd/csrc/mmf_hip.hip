@@ -3342,6 +3342,12 @@ extern "C" int mmf_ransac_estimate(mmf_ransac* r, const float* p0, const float* 
 #include "redetect_host.hpp"
 
 // ---------------------------------------------------------------------------------------------
+// Keypoint tracks on the device: tracker::PointTracker and the per-model track sets
+// (Core/Utils/PointTracker.cpp:27-226; Core/Model/Model.cpp:630-640, 739-775)
+// ---------------------------------------------------------------------------------------------
+#include "tracker_host.hpp"
+
+// ---------------------------------------------------------------------------------------------
 // SuperPoint keypoint network (Core/MultiMotionFusion.cpp:78,233)
 // ---------------------------------------------------------------------------------------------
 #include "superpoint_host.hpp"

@@ -1,0 +1,387 @@
+// tracker_kernels.hpp -- the keypoint track table on the device (gfx950): tracker::PointTracker
+// (Core/Utils/PointTracker.cpp:27-226), the per-model track sets (Model::tracks, Model::updateTracks,
+// Core/Model/Model.cpp:630-640) and the pair lists of Model::getLastTrackTransform (:739-775).
+//
+// The table is a structure of arrays over `capacity` tracks in the order of the reference's `tracks` vector.  It keeps
+// what the reference's consumers read and not the history: the descriptor of the last non-null keypoint, the last two
+// slots (end()[-1] = slot 0 `cur`, end()[-2] = slot 1 `prev`), the age (frames since the last non-null keypoint), the
+// number of non-null keypoints and the stamp of the last one (prune), a 256-bit set of model ids per track (every
+// Model::tracks at once) and a uid that is never reused.  A null slot holds zeros.
+//
+// Every operation is a fixed number of launches on the context's stream, whatever the number of keypoints and tracks,
+// and none reads anything back: counts the next kernel needs stay in the table's head record on the device.  The
+// bookkeeping kernels are ONE workgroup of 1024 lanes (a table is a few thousand tracks: this is latency, not
+// bandwidth): ordered compactions from 64-bit ballots and a scan over the 16 wave totals.  Descriptor rows (1 KB) move
+// in grid kernels, one wave of 64 lanes x 16 B per row.  The counters the host reads go to a pinned record with
+// ordinary stores at the end of the kernel that changes them.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace mmf {
+
+constexpr int kTrkDim = 256;     // SuperPoint descriptors
+constexpr int kTrkWords = 8;     // 256 model ids
+constexpr int kTrkBlock = 1024;  // lanes of the bookkeeping workgroup
+constexpr int kTrkMaxModels = 256;
+constexpr float kTrkFiller = 1e30f;  // a padding row of the gathered train set: its distance to anything is +inf
+
+struct TrkHead {  // on the device
+    int n_tracks, length, dropped, n_active;
+    long long next_uid;
+};
+
+struct TrkRecord {  // pinned host memory the kernels write
+    int n_tracks, length, dropped, dropped_last, n_visible, pad_;
+    int pair_count[kTrkMaxModels];
+};
+
+struct TrkTable {
+    int capacity;
+    TrkHead* head;
+    int *age, *nvalid, *label;
+    long long *last_stamp, *uid;
+    int* xy[2];         // [capacity][2]
+    float* co[2];       // [capacity][3]
+    long long* ts[2];   // [capacity]
+    int* ok[2];         // [capacity] non-null flag
+    unsigned* member;   // [capacity][8]
+};
+
+struct TrkModelSet {
+    unsigned w[kTrkWords];
+};
+struct TrkModelList {
+    int n;
+    unsigned char id[kTrkMaxModels];
+};
+
+// exclusive rank of this lane among the lanes of the workgroup with `flag`, in lane order; *total = their number.
+// Every lane of the (kTrkBlock wide) workgroup calls it.
+__device__ __forceinline__ int trk_block_rank(bool flag, int* total) {
+    __shared__ int wave_sum[kTrkBlock / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const unsigned long long b = __ballot(flag);
+    const int in_wave = __popcll(b & ((1ull << lane) - 1ull));
+    __syncthreads();  // the previous call's totals have been read
+    if (lane == 0) wave_sum[w] = __popcll(b);
+    __syncthreads();
+    int base = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < kTrkBlock / 64; ++k) {
+        const int s = wave_sum[k];
+        base += k < w ? s : 0;
+        tot += s;
+    }
+    *total = tot;
+    return base + in_wave;
+}
+
+__device__ __forceinline__ float trk_nan() { return __uint_as_float(0x7fc00000u); }
+__device__ __forceinline__ bool trk_finite3(const float* p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
+
+// add, step 1: the keypoints of the frame (PointTracker.cpp:35-56, float operation for float operation: the build has
+// -ffp-contract=off), the ordered compaction of the active tracks (getLastActiveKeypoints, :205-224) and the shift of
+// every track by one null keypoint (:71-73).  An empty table is not shifted: its length restarts at 1 (:61-66).
+__global__ __launch_bounds__(kTrkBlock) void trk_begin_kernel(TrkTable T, int n, const int* __restrict__ q_xy,
+                                                              const float* __restrict__ depth, int width, int height, float fx,
+                                                              float fy, float cx, float cy, int history,
+                                                              float* __restrict__ q_co, int* __restrict__ active_idx) {
+    const int tid = threadIdx.x;
+    const int nt = min(T.head->n_tracks, T.capacity);
+    for (int q = tid; q < n; q += kTrkBlock) {
+        const int x = q_xy[2 * q], y = q_xy[2 * q + 1];
+        float X = trk_nan(), Y = trk_nan(), Z = trk_nan();
+        if (x >= 0 && x < width && y >= 0 && y < height) {
+            const float z = depth[(size_t)y * width + x];
+            if (z > 0.f) {
+                X = (z * ((float)x - cx)) / fx;
+                Y = (z * ((float)y - cy)) / fy;
+                Z = z;
+            }
+        }
+        q_co[3 * q] = X, q_co[3 * q + 1] = Y, q_co[3 * q + 2] = Z;
+    }
+    int base = 0;
+    for (int i0 = 0; i0 < nt; i0 += kTrkBlock) {
+        const int i = i0 + tid;
+        const bool in = i < nt;
+        const bool active = in && (history == 0 || T.age[i] < history);
+        int tot;
+        const int rank = trk_block_rank(active, &tot);
+        if (active) active_idx[base + rank] = i;
+        base += tot;
+        if (in) {
+            T.xy[1][2 * i] = T.xy[0][2 * i], T.xy[1][2 * i + 1] = T.xy[0][2 * i + 1];
+            T.xy[0][2 * i] = 0, T.xy[0][2 * i + 1] = 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) T.co[1][3 * i + k] = T.co[0][3 * i + k], T.co[0][3 * i + k] = 0.f;
+            T.ts[1][i] = T.ts[0][i], T.ts[0][i] = 0;
+            T.ok[1][i] = T.ok[0][i], T.ok[0][i] = 0;
+            T.age[i] += 1;
+        }
+    }
+    if (tid == 0) {
+        T.head->n_active = base;
+        T.head->length = nt ? T.head->length + 1 : 1;
+    }
+}
+
+// add, step 2: the descriptors of the active tracks, in order, as the train set of the search; the rows from n_active
+// to nt_pad (what the host knows to be no less than the number of tracks) are padding that nothing matches
+__global__ __launch_bounds__(256) void trk_gather_kernel(TrkTable T, const float* __restrict__ desc,
+                                                         const int* __restrict__ active_idx, float* __restrict__ train, int nt_pad) {
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), waves = gridDim.x * 4;
+    const int na = min(T.head->n_active, T.capacity);
+    for (int r = wave; r < nt_pad; r += waves) {
+        float4 v = make_float4(kTrkFiller, kTrkFiller, kTrkFiller, kTrkFiller);
+        if (r < na) {
+            const int i = min(max(active_idx[r], 0), T.capacity - 1);
+            v = reinterpret_cast<const float4*>(desc + (size_t)i * kTrkDim)[lane];
+        }
+        reinterpret_cast<float4*>(train + (size_t)r * kTrkDim)[lane] = v;
+    }
+}
+
+// add, step 3 (after the search): matched tracks get their keypoint (:107-112), unmatched keypoints start tracks in
+// ascending query index (:116-121); appends past the capacity are dropped and counted.  dest_row[q] = the row the
+// descriptor of keypoint q goes to, or -1.
+__global__ __launch_bounds__(kTrkBlock) void trk_finish_kernel(TrkTable T, TrkRecord* __restrict__ rec, int n,
+                                                               const int* __restrict__ q_xy, const float* __restrict__ q_co,
+                                                               const int* __restrict__ train_idx,
+                                                               const int* __restrict__ active_idx, long long timestamp,
+                                                               int* __restrict__ dest_row) {
+    const int tid = threadIdx.x;
+    const int nt = min(T.head->n_tracks, T.capacity), na = min(T.head->n_active, T.capacity);
+    const long long uid0 = T.head->next_uid;
+    int base = 0;
+    for (int q0 = 0; q0 < n; q0 += kTrkBlock) {
+        const int q = q0 + tid;
+        const bool in = q < n;
+        int t = in ? train_idx[q] : 0;
+        if (t >= na) t = -1;  // (a padding row never matches)
+        const bool fresh = in && t < 0;
+        int tot;
+        const int rank = trk_block_rank(fresh, &tot);
+        int dst = -1;
+        if (in && !fresh) {
+            dst = active_idx[t];
+            if (dst < 0 || dst >= nt) dst = -1;
+        } else if (fresh && nt + base + rank < T.capacity) {
+            dst = nt + base + rank;
+        }
+        if (in) dest_row[q] = dst;
+        if (dst >= 0) {
+            const size_t i = (size_t)dst;
+            T.xy[0][2 * i] = q_xy[2 * q], T.xy[0][2 * i + 1] = q_xy[2 * q + 1];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) T.co[0][3 * i + k] = q_co[3 * q + k];
+            T.ts[0][i] = timestamp, T.ok[0][i] = 1;
+            T.age[i] = 0, T.last_stamp[i] = timestamp;
+            if (fresh) {
+                T.nvalid[i] = 1, T.uid[i] = uid0 + base + rank, T.label[i] = -1;
+                T.xy[1][2 * i] = 0, T.xy[1][2 * i + 1] = 0;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) T.co[1][3 * i + k] = 0.f;
+                T.ts[1][i] = 0, T.ok[1][i] = 0;
+#pragma unroll
+                for (int w = 0; w < kTrkWords; ++w) T.member[kTrkWords * i + w] = 0u;
+            } else {
+                T.nvalid[i] += 1;
+            }
+        }
+        base += tot;
+    }
+    if (tid == 0) {
+        const int appended = min(base, T.capacity - nt), lost = base - appended;
+        T.head->n_tracks = nt + appended;
+        T.head->next_uid = uid0 + appended;
+        T.head->dropped += lost;
+        if (nt + appended == 0) T.head->length = 0;
+        rec->n_tracks = nt + appended, rec->length = T.head->length, rec->dropped = T.head->dropped, rec->dropped_last = lost;
+    }
+}
+
+// descriptor rows of a set of keypoints to their rows of the table (dest_row < 0: nowhere)
+__global__ __launch_bounds__(256) void trk_scatter_rows_kernel(const float* __restrict__ q_desc, int n,
+                                                               const int* __restrict__ dest_row, float* __restrict__ desc,
+                                                               int capacity) {
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), waves = gridDim.x * 4;
+    for (int q = wave; q < n; q += waves) {
+        const int d = dest_row[q];
+        if (d < 0 || d >= capacity) continue;
+        reinterpret_cast<float4*>(desc + (size_t)d * kTrkDim)[lane] = reinterpret_cast<const float4*>(q_desc + (size_t)q * kTrkDim)[lane];
+    }
+}
+
+// prune (:170-203): tracks with fewer than min_kps keypoints whose last keypoint is older than min_time go; the others
+// close up in order.  A chunk of 1024 tracks is read into registers before any of it is written, and what it writes lies
+// below the next chunk.  map[dst] = src for the descriptor rows, which move into the table's second buffer.
+__global__ __launch_bounds__(kTrkBlock) void trk_prune_kernel(TrkTable T, TrkRecord* __restrict__ rec, int min_kps,
+                                                              long long min_time, int* __restrict__ map) {
+    const int tid = threadIdx.x;
+    const int nt = min(T.head->n_tracks, T.capacity);
+    int base = 0;
+    for (int i0 = 0; i0 < nt; i0 += kTrkBlock) {
+        const int i = i0 + tid;
+        const bool in = i < nt;
+        int age = 0, nvalid = 0, label = 0, xy[2][2] = {}, ok[2] = {};
+        long long last = 0, uid = 0, ts[2] = {};
+        float co[2][3] = {};
+        unsigned mem[kTrkWords] = {};
+        if (in) {
+            age = T.age[i], nvalid = T.nvalid[i], label = T.label[i], last = T.last_stamp[i], uid = T.uid[i];
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                xy[s][0] = T.xy[s][2 * i], xy[s][1] = T.xy[s][2 * i + 1];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) co[s][k] = T.co[s][3 * i + k];
+                ts[s] = T.ts[s][i], ok[s] = T.ok[s][i];
+            }
+#pragma unroll
+            for (int w = 0; w < kTrkWords; ++w) mem[w] = T.member[kTrkWords * (size_t)i + w];
+        }
+        const bool keep = in && !(nvalid < min_kps && last < min_time);
+        int tot;
+        const int rank = trk_block_rank(keep, &tot);  // (its barriers order the reads above before the writes below)
+        if (keep) {
+            const size_t d = (size_t)(base + rank);
+            map[d] = i;
+            T.age[d] = age, T.nvalid[d] = nvalid, T.label[d] = label, T.last_stamp[d] = last, T.uid[d] = uid;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                T.xy[s][2 * d] = xy[s][0], T.xy[s][2 * d + 1] = xy[s][1];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) T.co[s][3 * d + k] = co[s][k];
+                T.ts[s][d] = ts[s], T.ok[s][d] = ok[s];
+            }
+#pragma unroll
+            for (int w = 0; w < kTrkWords; ++w) T.member[kTrkWords * d + w] = mem[w];
+        }
+        base += tot;
+    }
+    if (tid == 0) {
+        T.head->n_tracks = base;
+        if (base == 0) T.head->length = 0;
+        rec->n_tracks = base, rec->length = T.head->length;
+    }
+}
+
+// rows map[0 .. n) of `from` to rows 0 .. n of `to`; n = *count (on the device), a different buffer: no row is
+// overwritten before another wave has read it
+__global__ __launch_bounds__(256) void trk_gather_rows_kernel(const float* __restrict__ from, const int* __restrict__ map,
+                                                              const int* __restrict__ count, float* __restrict__ to, int capacity) {
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), waves = gridDim.x * 4;
+    const int n = min(*count, capacity);
+    for (int r = wave; r < n; r += waves) {
+        const int s = min(max(map[r], 0), capacity - 1);
+        reinterpret_cast<float4*>(to + (size_t)r * kTrkDim)[lane] = reinterpret_cast<const float4*>(from + (size_t)s * kTrkDim)[lane];
+    }
+}
+
+// associate (MultiMotionFusion.cpp:425-436, 584-604): label = the id image at the last keypoint of every visible track
+// inside the image; for every listed model whose label some track carries, a labelled track belongs to it exactly when
+// it carries its label (updateTracks(segm_tracks[id], all other segments' tracks)).  Unlabelled tracks keep their sets.
+__global__ __launch_bounds__(kTrkBlock) void trk_associate_kernel(TrkTable T, const unsigned char* __restrict__ mask, int width,
+                                                                  int height, TrkModelSet listed) {
+    __shared__ unsigned present[kTrkWords];
+    const int tid = threadIdx.x;
+    const int nt = min(T.head->n_tracks, T.capacity);
+    if (tid < kTrkWords) present[tid] = 0u;
+    __syncthreads();
+    for (int i = tid; i < nt; i += kTrkBlock) {
+        int l = -1;
+        if (T.ok[0][i]) {
+            const int x = T.xy[0][2 * i], y = T.xy[0][2 * i + 1];
+            if (x >= 0 && x < width && y >= 0 && y < height) l = mask[(size_t)y * width + x];
+        }
+        T.label[i] = l;
+        if (l >= 0) atomicOr(&present[l >> 5], 1u << (l & 31));
+    }
+    __syncthreads();
+    for (int i = tid; i < nt; i += kTrkBlock) {
+        const int l = T.label[i];
+        if (l < 0) continue;
+#pragma unroll
+        for (int w = 0; w < kTrkWords; ++w) {
+            const unsigned upd = listed.w[w] & present[w];
+            unsigned m = T.member[kTrkWords * (size_t)i + w] & ~upd;
+            if ((l >> 5) == w) m |= upd & (1u << (l & 31));
+            T.member[kTrkWords * (size_t)i + w] = m;
+        }
+    }
+}
+
+// every track joins (clear = 0: updateTracks(tracks, {}), initGlobalTracks) or leaves (clear = 1) the models of `set`
+__global__ __launch_bounds__(256) void trk_member_kernel(TrkTable T, TrkModelSet set, int clear) {
+    const int nt = min(T.head->n_tracks, T.capacity);
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < nt * kTrkWords; e += gridDim.x * 256) {
+        const unsigned s = set.w[e & (kTrkWords - 1)];
+        T.member[e] = clear ? (T.member[e] & ~s) : (T.member[e] | s);
+    }
+}
+
+// pairs (Model::getLastTrackTransform, :747-761): workgroup j = model list.id[j]; the ordered compaction of its tracks
+// whose last two keypoints exist and are finite -> p0 (prev) / p1 (cur) [j][stride][3] and the count, in pinned memory
+__global__ __launch_bounds__(kTrkBlock) void trk_pairs_kernel(TrkTable T, TrkRecord* __restrict__ rec, TrkModelList list,
+                                                              float* __restrict__ p0, float* __restrict__ p1, int stride) {
+    const int tid = threadIdx.x, j = blockIdx.x;
+    const int nt = min(T.head->n_tracks, T.capacity);
+    const int m = list.id[j];
+    int base = 0;
+    for (int i0 = 0; i0 < nt; i0 += kTrkBlock) {
+        const int i = i0 + tid;
+        bool take = false;
+        float a[3] = {}, b[3] = {};
+        if (i < nt && ((T.member[kTrkWords * (size_t)i + (m >> 5)] >> (m & 31)) & 1u) && T.ok[0][i] && T.ok[1][i]) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) a[k] = T.co[1][3 * i + k], b[k] = T.co[0][3 * i + k];
+            take = trk_finite3(a) && trk_finite3(b);
+        }
+        int tot;
+        const int rank = trk_block_rank(take, &tot);
+        if (take && base + rank < stride) {
+            const size_t d = ((size_t)j * stride + base + rank) * 3;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) p0[d + k] = a[k], p1[d + k] = b[k];
+        }
+        base += tot;
+    }
+    if (tid == 0) {
+        rec->pair_count[j] = min(base, stride);
+        if (j == 0) rec->n_tracks = nt, rec->length = T.head->length, rec->dropped = T.head->dropped;
+    }
+}
+
+// visible (track->back() of every track that has one, MultiMotionFusion.cpp:428-431): ordered compaction -> rows
+__global__ __launch_bounds__(kTrkBlock) void trk_visible_kernel(TrkTable T, TrkRecord* __restrict__ rec, int* __restrict__ map,
+                                                                int* __restrict__ count, int* __restrict__ xy,
+                                                                float* __restrict__ co, long long* __restrict__ uid) {
+    const int tid = threadIdx.x;
+    const int nt = min(T.head->n_tracks, T.capacity);
+    int base = 0;
+    for (int i0 = 0; i0 < nt; i0 += kTrkBlock) {
+        const int i = i0 + tid;
+        const bool vis = i < nt && T.ok[0][i];
+        int tot;
+        const int rank = trk_block_rank(vis, &tot);
+        if (vis) {
+            const size_t d = (size_t)(base + rank);
+            map[d] = i;
+            xy[2 * d] = T.xy[0][2 * i], xy[2 * d + 1] = T.xy[0][2 * i + 1];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) co[3 * d + k] = T.co[0][3 * i + k];
+            uid[d] = T.uid[i];
+        }
+        base += tot;
+    }
+    if (tid == 0) {
+        *count = base;
+        rec->n_visible = base, rec->n_tracks = nt, rec->length = T.head->length, rec->dropped = T.head->dropped;
+    }
+}
+
+}  // namespace mmf

@@ -350,6 +350,24 @@ class MultiMotionFusion:
         from .redetection import last_redetections
         return last_redetections(self.ctx, self.handle)
 
+    # ----- keypoint tracks on the device (tracker.py): `-init kp` for every model, the models' track sets
+    def setTracker(self, tracker, odom_init_kp=True, icp_refine=True):
+        """attach a tracker.DevicePointTracker (None: detach; the default).  The caller adds and prunes a frame's keypoints
+        before processFrame; processFrame then initialises every active model from its own tracks (odom_init_kp; the dense
+        tracker refines when icp_refine), associates the tracks with the models by the frame's id image and, with
+        redetection on and no setKeypoints for the frame, takes the tracker's visible keypoints."""
+        check(self.ctx.lib.mmf_fusion_set_tracker(self.handle, tracker.handle if tracker is not None else None,
+                                                  int(bool(odom_init_kp)), int(bool(icp_refine))))
+        self._tracker = tracker  # (the fusion does not own it: kept alive here)
+
+    def getLastTrackTransforms(self):
+        """the transformations the last frame's models were initialised with, [n,4,4] in list order (n = 0: none)"""
+        n = C.c_int()
+        check(self.ctx.lib.mmf_fusion_last_track_transforms(self.handle, None, 0, C.byref(n)))
+        T = np.zeros((max(n.value, 1), 4, 4), np.float32)
+        check(self.ctx.lib.mmf_fusion_last_track_transforms(self.handle, T.ctypes.data, n.value, C.byref(n)))
+        return T[:n.value]
+
     def getConfig(self):
         cfg = mmf_fusion_config()
         check(self.ctx.lib.mmf_fusion_get_config(self.handle, C.byref(cfg)))

@@ -1,0 +1,175 @@
+"""The keypoint track table on the device (mmf_tracker_*, csrc/tracker_kernels.hpp): tracker::PointTracker
+(Core/Utils/PointTracker.cpp:27-226), the per-model track sets and Model::getLastTrackTransform (Core/Model/Model.cpp:739-775)
+without host bookkeeping, and the `-init kp` front end on top of it -- no fallback.
+
+point_tracker.py keeps the host-side mirror of the same classes (lists like the reference's); the two agree bit for bit
+where the table's capacity is not reached."""
+import ctypes as C
+import weakref
+
+import numpy as np
+import torch
+
+from ._capi import check, mmf_ransac_config
+from .cudafuncs import Context, _p
+
+
+class DevicePointTracker:
+    """tracker::PointTracker for pyramid level 0 with the tracks on the device.  Differences from the reference: at most
+    `capacity` tracks (appends that do not fit are dropped and counted), NaN coordinates for a keypoint outside the image."""
+
+    def __init__(self, ctx: Context, width, height, intrinsics, capacity=4096, max_keypoints=1024):
+        """intrinsics: (fx, fy, cx, cy) of level 0"""
+        self.ctx, self.width, self.height = ctx, int(width), int(height)
+        self.capacity, self.max_keypoints = int(capacity), int(max_keypoints)
+        fx, fy, cx, cy = (float(v) for v in intrinsics)
+        h = C.c_void_p()
+        check(ctx.lib.mmf_tracker_create(ctx.handle, self.width, self.height, fx, fy, cx, cy, self.capacity, self.max_keypoints,
+                                         C.byref(h)))
+        self.handle = h
+        self._dev = torch.device("cuda", ctx.device)
+        ctx._children.append(weakref.ref(self))
+
+    # ----- PointTracker
+    def pixels(self, coordinates):
+        """normalised keypoint coordinates [n,2] -> integer pixels, cv::Point(cv::Vec2d): round half to even (:38)"""
+        c = np.asarray(coordinates, np.float64).reshape(-1, 2)
+        return np.rint(c * np.array([self.width, self.height], np.float64)).astype(np.int32)
+
+    def addKeypoints(self, coordinates, descriptors, timestamp, depth, min_feature_distance=0.7, history=30):
+        """coordinates [n,2] normalised to [0,1) (host), descriptors [n,256] (host or CUDA tensor), depth [rows,cols] float32
+        CUDA tensor"""
+        self.addKeypointsPixels(self.pixels(coordinates), descriptors, timestamp, depth, min_feature_distance, history)
+
+    def addKeypointsPixels(self, xy, descriptors, timestamp, depth, min_feature_distance=0.7, history=30):
+        """xy [n,2] integer pixels (host array or int32 CUDA tensor)"""
+        if not torch.is_tensor(xy):
+            xy = torch.from_numpy(np.ascontiguousarray(xy, np.int32).reshape(-1, 2))
+        if not torch.is_tensor(descriptors):
+            descriptors = torch.from_numpy(np.ascontiguousarray(descriptors, np.float32))
+        xy = xy.to(self._dev, torch.int32).contiguous()
+        n = xy.shape[0]
+        de = descriptors.to(self._dev, torch.float32).reshape(n, 256).contiguous()
+        assert depth.is_cuda and depth.dtype == torch.float32 and depth.shape == (self.height, self.width)
+        depth = depth.contiguous()
+        check(self.ctx.lib.mmf_tracker_add_keypoints(self.handle, n, _p(xy) if n else None, _p(de) if n else None, _p(depth),
+                                                     int(timestamp), float(min_feature_distance), int(history)))
+
+    def prune(self, min_kps, min_time):
+        check(self.ctx.lib.mmf_tracker_prune(self.handle, int(min_kps), int(min_time)))
+
+    def status(self):
+        """(tracks, length, dropped appends); waits for the stream"""
+        n, length, dropped = C.c_int(), C.c_int(), C.c_int()
+        check(self.ctx.lib.mmf_tracker_status(self.handle, C.byref(n), C.byref(length), C.byref(dropped)))
+        return n.value, length.value, dropped.value
+
+    def numTracks(self):
+        return self.status()[0]
+
+    def lastLaunches(self):
+        return self.ctx.lib.mmf_tracker_last_launches(self.handle)
+
+    def reset(self):
+        check(self.ctx.lib.mmf_tracker_reset(self.handle))
+
+    # ----- the models' track sets
+    @staticmethod
+    def _ids(model_ids):
+        ids = np.ascontiguousarray(np.atleast_1d(np.asarray(model_ids, np.int32)))
+        return ids, ids.ctypes.data_as(C.POINTER(C.c_int))
+
+    def associate(self, mask, model_ids):
+        """mask: uint8 [rows,cols] CUDA tensor of model ids (textures[MASK]); model_ids: the active models"""
+        assert mask.is_cuda and mask.dtype == torch.uint8 and mask.shape == (self.height, self.width)
+        ids, p = self._ids(model_ids)
+        check(self.ctx.lib.mmf_tracker_associate(self.handle, _p(mask.contiguous()), p, ids.size))
+
+    def associateAll(self, model_ids):
+        ids, p = self._ids(model_ids)
+        check(self.ctx.lib.mmf_tracker_associate_all(self.handle, p, ids.size))
+
+    def forgetModel(self, model_id):
+        check(self.ctx.lib.mmf_tracker_forget_model(self.handle, int(model_id)))
+
+    def lastPairs(self, model_ids):
+        """[(p0 [k,3], p1 [k,3])] per listed model: the last two keypoints of its tracks where both exist and are finite"""
+        ids, p = self._ids(model_ids)
+        p0, p1, cnt, stride = C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.POINTER(C.c_int)(), C.c_int()
+        check(self.ctx.lib.mmf_tracker_last_pairs(self.handle, p, ids.size, C.byref(p0), C.byref(p1), C.byref(cnt), C.byref(stride)))
+        out = []
+        for j in range(ids.size):
+            k, off = cnt[j], j * stride.value * 3
+            a = np.ctypeslib.as_array(p0, (ids.size * stride.value * 3,))[off:off + 3 * k].reshape(k, 3).copy() if k else np.zeros((0, 3), np.float32)
+            b = np.ctypeslib.as_array(p1, (ids.size * stride.value * 3,))[off:off + 3 * k].reshape(k, 3).copy() if k else np.zeros((0, 3), np.float32)
+            out.append((a, b))
+        return out
+
+    def getLastTrackTransform(self, model_id=0, config=(10, 0.03, 0.6)):
+        """Model::getLastTrackTransform -> (T 4x4 float32, error, inlier mask or None)"""
+        cfg = mmf_ransac_config(int(config[0]), float(config[1]), float(config[2]))
+        T = np.zeros((4, 4), np.float32)
+        err, has = C.c_float(), C.c_int()
+        inl = np.zeros(self.capacity, np.uint8)
+        check(self.ctx.lib.mmf_tracker_last_track_transform(self.handle, int(model_id), C.byref(cfg), T.ctypes.data,
+                                                            C.byref(err), inl.ctypes.data, C.byref(has)))
+        return T, err.value, (inl.astype(bool) if has.value else None)
+
+    def visible(self):
+        """the last keypoint of every visible track -> (xy [n,2], coordinate [n,3], descriptor [n,256], uid [n])"""
+        n = C.c_int()
+        xy = np.zeros((self.capacity, 2), np.int32)
+        co = np.zeros((self.capacity, 3), np.float32)
+        de = np.zeros((self.capacity, 256), np.float32)
+        uid = np.zeros(self.capacity, np.int64)
+        check(self.ctx.lib.mmf_tracker_visible(self.handle, self.capacity, C.byref(n), xy.ctypes.data, co.ctypes.data,
+                                               de.ctypes.data, uid.ctypes.data))
+        k = n.value
+        return xy[:k], co[:k], de[:k], uid[:k]
+
+    def download(self):
+        """the whole table as a dict of host arrays (tests and tools)"""
+        c = self.capacity
+        a = dict(desc=np.zeros((c, 256), np.float32), age=np.zeros(c, np.int32), nvalid=np.zeros(c, np.int32),
+                 last_stamp=np.zeros(c, np.int64), uid=np.zeros(c, np.int64), xy=np.zeros((2, c, 2), np.int32),
+                 coordinate=np.zeros((2, c, 3), np.float32), timestamp=np.zeros((2, c), np.int64),
+                 nonnull=np.zeros((2, c), np.int32), member=np.zeros((c, 8), np.uint32), label=np.zeros(c, np.int32))
+        n = C.c_int()
+        check(self.ctx.lib.mmf_tracker_download(self.handle, c, C.byref(n), *[a[k].ctypes.data for k in (
+            "desc", "age", "nvalid", "last_stamp", "uid", "xy", "coordinate", "timestamp", "nonnull", "member", "label")]))
+        k = n.value
+        out = {key: (v[:, :k].copy() if key in ("xy", "coordinate", "timestamp", "nonnull") else v[:k].copy()) for key, v in a.items()}
+        out["n_tracks"], out["length"], out["dropped"] = self.status()
+        return out
+
+    def close(self):
+        if self.handle and self.ctx.handle:
+            self.ctx.lib.mmf_tracker_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NativeKeypointFrontEnd:
+    """The keypoint half of processFrame (MultiMotionFusion.cpp:223-248, 312-335) with the tracks on the device: SuperPoint
+    features -> DevicePointTracker -> processFrame, which initialises EVERY active model from its own tracks and keeps the
+    models' track sets up to date from the frame's segmentation (fusion.setTracker)."""
+
+    def __init__(self, ctx: Context, fusion, kp_predictor, intrinsics, icp_refine=True, capacity=4096, max_keypoints=1024):
+        self.ctx, self.fusion, self.kp = ctx, fusion, kp_predictor
+        self.tracker = DevicePointTracker(ctx, fusion.width, fusion.height, intrinsics, capacity, max_keypoints)
+        fusion.setTracker(self.tracker, odom_init_kp=True, icp_refine=icp_refine)
+
+    def processFrame(self, rgb, depth, timestamp, weightMultiplier=1.0, **frame):
+        coordinates, descriptors = self.kp.getFeatures(rgb)
+        self.tracker.addKeypoints(coordinates, descriptors, timestamp, depth, 0.7, 30)
+        self.tracker.prune(30, max(int(timestamp) - int(1e9), 0))  # :246
+        self.fusion.processFrame(rgb, depth, timestamp=timestamp, weightMultiplier=weightMultiplier, **frame)
+
+    def close(self):
+        self.fusion.setTracker(None)
+        self.tracker.close()
