@@ -813,6 +813,10 @@ int mmf_fusion_last_mask_segmentation(mmf_fusion *f, mmf_mask_info *info, mmf_se
  *                         coordinates one after the other.  Like Model::store (:1618-1621) a model that has stored views
  *                         ignores a second store: *stored = 0.  Synchronous.  The store only grows; growing never frees a
  *                         buffer before mmf_viewstore_destroy.
+ *   mmf_viewstore_store_device   the same with the rows on the DEVICE (what mmf_tracker_model_views returns): counts = HOST,
+ *                         descriptor (16-byte aligned) / coordinate = DEVICE, the views' rows one after the other.  A kernel
+ *                         scatters the rows to their padded places; the coordinates come back through pinned memory.  One
+ *                         wait.  The store is then what mmf_viewstore_store leaves with the same views downloaded.
  *   mmf_viewstore_forget      the model is gone: its views stay in place, belong to nobody and match nothing of interest
  *   mmf_viewstore_num_views / _view   the views in store order (models in the order they were stored, a model's views ascending)
  *   mmf_viewstore_match       query = DEVICE [nq][256] (16-byte aligned); HOST train_idx / distance [views][nq]: the row of the
@@ -853,6 +857,8 @@ int mmf_viewstore_create(mmf_ctx *ctx, mmf_viewstore **out);
 void mmf_viewstore_destroy(mmf_viewstore *vs);
 int mmf_viewstore_store(mmf_viewstore *vs, int model_id, int n_views, const int *counts, const float *descriptor,
                         const float *coordinate, int *stored);
+int mmf_viewstore_store_device(mmf_viewstore *vs, int model_id, int n_views, const int *counts, const float *descriptor,
+                               const float *coordinate, int *stored);
 int mmf_viewstore_forget(mmf_viewstore *vs, int model_id);
 int mmf_viewstore_num_views(mmf_viewstore *vs);
 int mmf_viewstore_view(mmf_viewstore *vs, int view, int *model_id, int *index, int *rows);
@@ -922,7 +928,27 @@ int mmf_ransac_estimate(mmf_ransac *r, const float *p0, const float *p1, int n, 
  *   mmf_tracker_download    waits.  The whole table into HOST arrays of `capacity` rows (tests and tools): the two-slot arrays
  *                       hold cur at row 0 and prev at row `capacity`; any array may be NULL
  *   mmf_tracker_last_launches   kernel launches of the tracker's last call
- *   mmf_tracker_reset       empty table, uid and counters from 0
+ *   mmf_tracker_reset       empty table, uid and counters from 0; the view log is emptied and its stamps restart
+ * The VIEW LOG (off by default) is what Model::store's views are built from without a history kept by the caller:
+ *   mmf_tracker_set_view_log    frames = 0: off, the ring is freed and an add stays 7 launches.  Otherwise a ring of `frames`
+ *                       slots is allocated here, behind a wait for the stream, and starts empty.  With it on every add also
+ *                       writes the frame's visible set -- count, uid, camera-frame coordinate and the descriptor of THAT
+ *                       frame's keypoint, in table order -- into slot stamp % frames: two more launches, nothing read back.
+ *   mmf_tracker_frame       adds since creation / reset = the stamp of the newest frame (host-known, no wait)
+ *   mmf_tracker_model_views waits once.  View v = the logged keypoints of frame frames[v], in log order (uid ascending), whose
+ *                       uid is in the table NOW (a pruned track has left), whose track has bit model_id NOW (a track that
+ *                       joined later brings its earlier keypoints, one that left brings none) and whose coordinate in the
+ *                       frame of poses[v] (HOST [n_views][16], row-major, camera -> model) is finite: project_kp
+ *                       (Model.cpp:130-141), floats widened to double, ((r0 x + r1 y) + r2 z) + t per row with every product
+ *                       and sum rounded on its own, rounded to float.  A frame that is not in the ring (older than `frames`
+ *                       adds, newer than the newest, before the last reset or the switching on) gives an empty view and
+ *                       counts in *missing.  *counts = pinned HOST [n_views]; *descriptor / *coordinate = DEVICE, the views'
+ *                       rows one after the other ([rows][256], [rows][3]); they belong to the tracker and stay valid until
+ *                       its next call.  Two launches whatever n_views is (0 allowed).
+ * Differences from the reference: the history is bounded by the log (Model::store has poses.size() views, this the last
+ * `frames` of them), and a caller pairs poses with frames BY STAMP (the reference pairs from the end of the lists, which
+ * shifts every keypoint against its pose by one frame when a deactivation is scheduled).  refineTrackSubset and the on-disk
+ * files are out of scope.
  * Inside processFrame (off by default; MMF_ERR_STATE with world > 1; the fusion does not own the tracker, which must share
  * its context and image size):
  *   mmf_fusion_set_tracker      tracker = NULL detaches.  The caller adds and prunes a frame's keypoints BEFORE processFrame
@@ -932,7 +958,13 @@ int mmf_ransac_estimate(mmf_ransac *r, const float *p0, const float *p1, int n, 
  *                       of its own: MMF_ERR_INVALID).  After the frame's segmentation, redetection and spawn: associate against
  *                       textures[MASK] with the active ids (associate_all without enable_multiple_models); a model that left
  *                       the active list is forgotten.  With redetection on, a frame without mmf_fusion_set_keypoints takes
- *                       the tracker's visible set as its keypoints.
+ *                       the tracker's visible set as its keypoints.  With redetection on AND a view log, every active
+ *                       object model gets one (stamp, pose after tracking) entry per tracked frame (a spawned model at the end
+ *                       of its first frame; a re-activated one restarts with the activation pose, Model::activate), trimmed
+ *                       to the log's length, and a model that leaves the active list -- lost or scheduled -- stores its
+ *                       views from the log (mmf_tracker_model_views -> mmf_viewstore_store_device), entries paired with frames
+ *                       by stamp, before the tracker forgets it, once.  Otherwise nothing is recorded, enqueued or awaited.
+ *   mmf_fusion_last_stored_views    what the last frame stored: per model its id, its views and their rows in all
  *   mmf_fusion_last_track_transforms   the transformations the last frame's models were initialised with (list order) */
 typedef struct mmf_tracker mmf_tracker;
 typedef struct {
@@ -959,8 +991,13 @@ int mmf_tracker_download(mmf_tracker *t, int capacity, int *n_tracks, float *des
                          unsigned *member, int *label);
 int mmf_tracker_last_launches(mmf_tracker *t);
 int mmf_tracker_reset(mmf_tracker *t);
+int mmf_tracker_set_view_log(mmf_tracker *t, int frames);
+int mmf_tracker_frame(mmf_tracker *t);
+int mmf_tracker_model_views(mmf_tracker *t, int model_id, int n_views, const int *frames, const float *poses,
+                            const int **counts, const float **descriptor, const float **coordinate, int *missing);
 int mmf_fusion_set_tracker(mmf_fusion *f, mmf_tracker *tracker, int odom_init_kp, int icp_refine);
 int mmf_fusion_last_track_transforms(mmf_fusion *f, float *T, int capacity, int *n_out);
+int mmf_fusion_last_stored_views(mmf_fusion *f, int *model_ids, int *n_views, int *rows, int capacity, int *n_out);
 
 #ifdef __cplusplus
 }

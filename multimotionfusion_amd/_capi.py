@@ -284,6 +284,7 @@ SIGNATURES = {
     "mmf_viewstore_create": (_i, [_vp, C.POINTER(_vp)]),
     "mmf_viewstore_destroy": (None, [_vp]),
     "mmf_viewstore_store": (_i, [_vp, _i, _i, _vp, _vp, _vp, _ip]),
+    "mmf_viewstore_store_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _ip]),
     "mmf_viewstore_forget": (_i, [_vp, _i]),
     "mmf_viewstore_num_views": (_i, [_vp]),
     "mmf_viewstore_view": (_i, [_vp, _i, _ip, _ip, _ip]),
@@ -308,7 +309,11 @@ SIGNATURES = {
     "mmf_tracker_download": (_i, [_vp, _i, _ip] + [_vp] * 11),
     "mmf_tracker_last_launches": (_i, [_vp]),
     "mmf_tracker_reset": (_i, [_vp]),
+    "mmf_tracker_set_view_log": (_i, [_vp, _i]),
+    "mmf_tracker_frame": (_i, [_vp]),
+    "mmf_tracker_model_views": (_i, [_vp, _i, _i, _vp, _vp, C.POINTER(_ip), C.POINTER(_fp), C.POINTER(_fp), _ip]),
     "mmf_fusion_set_tracker": (_i, [_vp, _vp, _i, _i]),
+    "mmf_fusion_last_stored_views": (_i, [_vp, _vp, _vp, _vp, _i, _ip]),
     "mmf_fusion_last_track_transforms": (_i, [_vp, _vp, _i, _ip]),
 }
 

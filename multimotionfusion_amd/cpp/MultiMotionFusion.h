@@ -348,6 +348,13 @@ class Model {
         mmf::check(mmf_viewstore_store(need_views(), (int)getID(), n_views, counts, descriptor, coordinate, &stored), "mmf_viewstore_store");
         return stored != 0;
     }
+    // the same with the rows on the DEVICE (tracker::PointTracker::modelViews): nothing passes through the host
+    bool storeDevice(int n_views, const int* counts, const float* descriptor_dev, const float* coordinate_dev) {
+        int stored = 0;
+        mmf::check(mmf_viewstore_store_device(need_views(), (int)getID(), n_views, counts, descriptor_dev, coordinate_dev, &stored),
+                   "mmf_viewstore_store_device");
+        return stored != 0;
+    }
     struct BestMatch : RigidRANSAC::Result {
         int view = -1;  // the time index of the winning view (-1: no estimate; transformation identity, error +inf)
     };
@@ -653,6 +660,19 @@ class MultiMotionFusion {
         mmf::check(mmf_fusion_last_redetections(f_, nullptr, 0, &n), "mmf_fusion_last_redetections");
         std::vector<mmf_redetection> out((size_t)n);
         if (n) mmf::check(mmf_fusion_last_redetections(f_, out.data(), n, &n), "mmf_fusion_last_redetections");
+        return out;
+    }
+    // what the last processFrame stored when a model left the active list (a tracker with a view log, redetection on)
+    struct StoredViews {
+        int model_id, n_views, rows;
+    };
+    std::vector<StoredViews> getLastStoredViews() {
+        int n = 0;
+        mmf::check(mmf_fusion_last_stored_views(f_, nullptr, nullptr, nullptr, 0, &n), "mmf_fusion_last_stored_views");
+        std::vector<int> ids((size_t)n), views((size_t)n), rows((size_t)n);
+        if (n) mmf::check(mmf_fusion_last_stored_views(f_, ids.data(), views.data(), rows.data(), n, &n), "mmf_fusion_last_stored_views");
+        std::vector<StoredViews> out;
+        for (int k = 0; k < n; ++k) out.push_back(StoredViews{ids[(size_t)k], views[(size_t)k], rows[(size_t)k]});
         return out;
     }
     // ----- keypoint tracks (MultiMotionFusion.h:307-309, 366; .cpp:223-248, 312-335): with a predictor set, processFrame(FrameData)

@@ -98,6 +98,33 @@ class PointTracker {
         xy.resize((size_t)n * 2), coordinate.resize((size_t)n * 3), descriptor.resize((size_t)n * 256);
         return n;
     }
+    // the models' track sets (Model::updateTracks with every track: :622-627, initGlobalTracks); inside processFrame the
+    // library associates by the frame's id image itself
+    void associateAll(const std::vector<int>& modelIds) {
+        mmf::check(mmf_tracker_associate_all(t_, modelIds.data(), (int)modelIds.size()), "mmf_tracker_associate_all");
+    }
+    // ----- the view log: the visible sets of the last `frames` adds stay on the device (0: off, the default), and
+    // Model::store's views (Model.cpp:1617-1644, 508-522) are built from it -- no history kept by the caller
+    void setViewLog(int frames) { mmf::check(mmf_tracker_set_view_log(t_, frames), "mmf_tracker_set_view_log"); }
+    int frame() const { return mmf_tracker_frame(t_); }  // adds so far = the stamp of the newest frame
+    struct ModelViews {
+        std::vector<int> counts;             // keypoints per view
+        const float* descriptor = nullptr;   // DEVICE [rows][256], the views one after the other; the tracker's, valid until
+        const float* coordinate = nullptr;   // DEVICE [rows][3]                                  its next call
+        int missing = 0;                     // views whose frame is not in the log (they are empty)
+    };
+    // view v = the logged keypoints of frame frames[v] that belong to the model now, in the frame poses[16 v ..] (row-major
+    // 4 x 4, camera -> model at that frame) maps to; Model::storeDevice takes the result
+    ModelViews modelViews(int modelId, const std::vector<int>& frames, const std::vector<float>& poses) {
+        if (poses.size() != frames.size() * 16) mmf::check(MMF_ERR_INVALID, "PointTracker::modelViews: one pose per frame");
+        ModelViews out;
+        const int* counts = nullptr;
+        mmf::check(mmf_tracker_model_views(t_, modelId, (int)frames.size(), frames.data(), poses.data(), &counts, &out.descriptor,
+                                           &out.coordinate, &out.missing),
+                   "mmf_tracker_model_views");
+        out.counts.assign(counts, counts + frames.size());
+        return out;
+    }
     mmf_tracker* handle() const { return t_; }
 
    private:

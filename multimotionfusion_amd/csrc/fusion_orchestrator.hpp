@@ -117,6 +117,15 @@ struct mmf_fusion {
     bool trk_init_kp = false, trk_icp_refine = true;
     std::vector<int> trk_ids;      // the active models' ids at the last association
     std::vector<float> trk_T;      // the transformations the last frame's models were initialised with, list order
+    // the models' keypoint views on deactivation (Model::store, Model.cpp:1617-1644): active only with redetection on and an
+    // attached tracker that keeps a view log.  Per object model the list of (tracker stamp, pose after that frame's tracking)
+    // -- Model::poses, host memory, trimmed to the log's length -- and what the last frame stored
+    struct ViewPose {
+        int stamp;
+        float pose[16];
+    };
+    std::map<int, std::vector<ViewPose>> view_poses;
+    std::vector<int> stored_ids, stored_views, stored_rows;
     hipEvent_t ev_frame_ready = nullptr;  // fusion stream: the frame's shared inputs are complete
     // next-frame prefetch (mmf_fusion_prefetch_frame): the filter and the input-side preparation of frame t+1 run
     // on `side` while frame t is fused on the context's stream.  Two filtered-depth buffers: frame t's fuse /
@@ -800,10 +809,69 @@ static int lane_wait(FusionModel* fm, hipEvent_t ev) {
     return MMF_OK;
 }
 
-// inactivateModel (:962-981) without the on-disk model database: the model leaves the active list and keeps its map
-static void fusion_inactivate(mmf_fusion* f, FusionModel* fm) {
+static bool fusion_view_log_on(const mmf_fusion* f) { return f->redetect_on && f->views && f->tracker && f->tracker->log.frames > 0; }
+
+// Model::appendPoses: one (stamp, pose) entry per object model and tracked frame.  after_tracking: every active object model
+// gets this frame's entry; otherwise (the end of the frame) only the models that have none yet -- the one spawned in it.
+// Stamps that do not ascend mean the tracker was reset: the list restarts.
+static void fusion_note_view_poses(mmf_fusion* f, bool after_tracking) {
+    if (!fusion_view_log_on(f)) return;
+    const int stamp = (int)f->tracker->frame;
+    for (size_t k = 1; k < f->models.size(); ++k) {
+        std::vector<mmf_fusion::ViewPose>& list = f->view_poses[(int)f->models[k]->model->id];
+        if (!list.empty() && list.back().stamp > stamp) list.clear();
+        if (!list.empty() && list.back().stamp == stamp) {
+            if (after_tracking) mmf_model_get_pose(f->models[k]->model, list.back().pose);
+            continue;
+        }
+        mmf_fusion::ViewPose e;
+        e.stamp = stamp;
+        mmf_model_get_pose(f->models[k]->model, e.pose);
+        list.push_back(e);
+        if ((int)list.size() > f->tracker->log.frames) list.erase(list.begin(), list.end() - f->tracker->log.frames);
+    }
+}
+
+// Model::store (Model.cpp:1617-1644) without the files: the model's views from the tracker's log (mmf_tracker_model_views),
+// its pose entries paired with the log's frames BY STAMP, into the view store without passing through the host
+// (mmf_viewstore_store_device).  One host wait in each.  A model that has stored views stores nothing (:1618-1621).
+static int fusion_store_views(mmf_fusion* f, FusionModel* fm) {
+    const int id = (int)fm->model->id;
+    if (!fusion_view_log_on(f) || id <= 0 || id >= mmf::kTrkMaxModels || viewstore_has_model(f->views, id)) return MMF_OK;
+    std::vector<int> frames;
+    std::vector<float> poses;
+    auto it = f->view_poses.find(id);
+    if (it != f->view_poses.end())
+        for (const mmf_fusion::ViewPose& e : it->second) {
+            frames.push_back(e.stamp);
+            poses.insert(poses.end(), e.pose, e.pose + 16);
+        }
+    const int n = (int)frames.size();
+    if (n == 0) return MMF_OK;  // (no tracked frame since the log is kept: nothing is known of the model)
+    const int* counts = nullptr;
+    const float *desc = nullptr, *coord = nullptr;
+    int rc = mmf_tracker_model_views(f->tracker, id, n, frames.data(), poses.data(), &counts, &desc, &coord, nullptr);
+    if (rc) return rc;
+    int stored = 0;
+    rc = mmf_viewstore_store_device(f->views, id, n, counts, desc, coord, &stored);
+    if (rc) return rc;
+    if (stored) {
+        int rows = 0;
+        for (int v = 0; v < n; ++v) rows += counts[v];
+        f->stored_ids.push_back(id), f->stored_views.push_back(n), f->stored_rows.push_back(rows);
+    }
+    f->view_poses.erase(id);
+    return MMF_OK;
+}
+
+// inactivateModel (:962-981) without the on-disk model database: the model stores its keypoint views (when a view log is
+// kept), leaves the active list and keeps its map
+static int fusion_inactivate(mmf_fusion* f, FusionModel* fm) {
+    int rc = fusion_store_views(f, fm);
+    if (rc) return rc;
     f->models.erase(std::find(f->models.begin(), f->models.end(), fm));
     f->inactive.push_back(fm);
+    return MMF_OK;
 }
 
 // spawnObjectModel (:938-947)
@@ -981,7 +1049,10 @@ static int frame_begin(mmf_fusion* f, FrameRun& r) {
         f->mask_is_zero = true;
     }
     for (int id : f->scheduled_deactivation)  // :279-283
-        if (FusionModel* fm = fusion_find(f, id)) fusion_inactivate(f, fm);
+        if (FusionModel* fm = fusion_find(f, id)) {
+            int rc = fusion_inactivate(f, fm);
+            if (rc) return rc;
+        }
     f->scheduled_deactivation.clear();
     return MMF_OK;
 }
@@ -1480,6 +1551,18 @@ extern "C" int mmf_fusion_set_tracker(mmf_fusion* f, mmf_tracker* tracker, int o
     f->tracker = tracker;
     f->trk_init_kp = tracker && odom_init_kp != 0, f->trk_icp_refine = icp_refine != 0;
     f->trk_ids.clear(), f->trk_T.clear();
+    f->view_poses.clear();  // (the entries carry the stamps of the tracker that leaves)
+    return MMF_OK;
+}
+// what the last frame stored on deactivation: per model its id, the number of views and their rows in all
+extern "C" int mmf_fusion_last_stored_views(mmf_fusion* f, int* model_ids, int* n_views, int* rows, int capacity, int* n_out) {
+    MMF_REQUIRE(f && n_out && capacity >= 0, "mmf_fusion_last_stored_views: bad argument");
+    *n_out = (int)f->stored_ids.size();
+    for (int i = 0; i < *n_out && i < capacity; ++i) {
+        if (model_ids) model_ids[i] = f->stored_ids[(size_t)i];
+        if (n_views) n_views[i] = f->stored_views[(size_t)i];
+        if (rows) rows[i] = f->stored_rows[(size_t)i];
+    }
     return MMF_OK;
 }
 extern "C" int mmf_fusion_last_track_transforms(mmf_fusion* f, float* T, int capacity, int* n_out) {
@@ -1595,6 +1678,12 @@ static int redetect_activate(mmf_fusion* f, FusionModel* fm, const float pose[16
     fm->odom->so3_prefetched = false, fm->odom->so3_stage = nullptr;
     f->inactive.erase(std::find(f->inactive.begin(), f->inactive.end(), fm));
     f->models.push_back(fm);
+    if (fusion_view_log_on(f)) {  // Model::activate (:1646-1656): one pose, the activation's
+        mmf_fusion::ViewPose e;
+        e.stamp = (int)f->tracker->frame;
+        std::memcpy(e.pose, pose, sizeof(e.pose));
+        f->view_poses[(int)fm->model->id].assign(1, e);
+    }
     if (fm->lane->stream != f->ctx->stream) return lane_wait(fm, f->ev_frame_ready);
     return MMF_OK;
 }
@@ -1780,7 +1869,10 @@ static int frame_segment(mmf_fusion* f, const FrameRun& r) {
         if (!fm || fm == fresh) continue;
         if (seg->model_data[i].super_pixel_count <= 0 && ++fm->unseen > 0 && fm->model->id != 0) lost.push_back(fm);
     }
-    for (FusionModel* fm : lost) fusion_inactivate(f, fm);
+    for (FusionModel* fm : lost) {
+        int rc = fusion_inactivate(f, fm);
+        if (rc) return rc;
+    }
     for (size_t i = 1; i < f->models.size() && (int)i < n_data; ++i) {
         const float old_conf = f->models[i]->model->conf_threshold;
         const float avg = seg->model_data[i].avg_confidence;
@@ -2030,6 +2122,7 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
     }
     f->t_tracking_s = 0;
     f->redetections.clear();  // (mmf_fusion_last_redetections speaks of this call)
+    f->stored_ids.clear(), f->stored_views.clear(), f->stored_rows.clear();
     int rc = frame_begin(f, r);
     if (rc) return rc;
     const bool first = f->tick == 1;
@@ -2044,6 +2137,7 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
         }
         rc = r.track ? frame_track(f, r) : frame_dictated_pose(f, r);
         if (rc) return rc;
+        if (r.track) fusion_note_view_poses(f, true);
         if (r.track && f->cfg.enable_multiple_models) {
             rc = frame_segment(f, r);
             if (rc) return rc;
@@ -2051,6 +2145,7 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
         r.stamp(f, 2);
     }
     if (f->tracker) {
+        if (r.track && !first) fusion_note_view_poses(f, false);
         rc = frame_associate_tracks(f, first || !f->cfg.enable_multiple_models, r.track);
         if (rc) return rc;
     }
@@ -2422,6 +2517,7 @@ extern "C" int mmf_fusion_reset(mmf_fusion* f) {
     f->kp_next = false;
     f->redetections.clear();
     f->trk_ids.clear(), f->trk_T.clear();
+    f->view_poses.clear(), f->stored_ids.clear(), f->stored_views.clear(), f->stored_rows.clear();
     std::memset(f->mask_map, 0, sizeof(f->mask_map));  // (the table speaks of the models of the map that ends here)
     f->mask_valid = false;
     std::vector<FusionModel*> all(f->preallocated);

@@ -46,6 +46,11 @@ struct mmf_viewstore {
     float *q_pin = nullptr, *q_dev = nullptr;  // queries handed in on the host (the fusion's keypoints)
     size_t q_cap = 0;
     int last_launches = 0;
+    // mmf_viewstore_store_device: per-tile first packed row (device) and the coordinates on their way to `coords` (pinned)
+    int* src0_dev = nullptr;
+    size_t src0_cap = 0;
+    float* co_pin = nullptr;
+    size_t co_cap = 0;
 };
 
 extern "C" int mmf_viewstore_create(mmf_ctx* c, mmf_viewstore** out) {
@@ -69,6 +74,8 @@ extern "C" void mmf_viewstore_destroy(mmf_viewstore* vs) {
     if (vs->out_row) (void)hipHostFree(vs->out_row);
     if (vs->out_dist) (void)hipHostFree(vs->out_dist);
     if (vs->q_pin) (void)hipHostFree(vs->q_pin);
+    (void)hipFree(vs->src0_dev);
+    if (vs->co_pin) (void)hipHostFree(vs->co_pin);
     delete vs;
 }
 
@@ -143,6 +150,76 @@ extern "C" int mmf_viewstore_store(mmf_viewstore* vs, int model_id, int n_views,
                            (int)padded, kRdDim, vs->tn + vs->n_rows);
         MMF_HIP_TRY(hipGetLastError());
         MMF_HIP_TRY(hipStreamSynchronize(st));  // `block` leaves scope
+        vs->n_rows += padded;
+    }
+    if (stored) *stored = 1;
+    return MMF_OK;
+}
+
+// mmf_viewstore_store with the views' rows on the DEVICE (mmf_tracker_model_views): counts = HOST, descriptor / coordinate =
+// DEVICE, packed.  A kernel scatters the rows to their 32-row-padded places and writes the padding; tiles and norms as above;
+// the coordinates reach `coords` through pinned memory.  One wait at the end.  The store is then what mmf_viewstore_store
+// leaves with the same views downloaded.
+extern "C" int mmf_viewstore_store_device(mmf_viewstore* vs, int model_id, int n_views, const int* counts, const float* descriptor,
+                                          const float* coordinate, int* stored) {
+    MMF_REQUIRE(vs && n_views >= 0 && (counts || n_views == 0), "mmf_viewstore_store_device: bad argument");
+    if (stored) *stored = 0;
+    if (viewstore_has_model(vs, model_id)) return MMF_OK;
+    size_t total = 0, padded = 0;
+    for (int v = 0; v < n_views; ++v) {
+        MMF_REQUIRE(counts[v] >= 0, "mmf_viewstore_store_device: negative view size");
+        total += (size_t)counts[v], padded += ((size_t)counts[v] + 31) / 32 * 32;
+    }
+    MMF_REQUIRE(total == 0 || (descriptor && coordinate), "mmf_viewstore_store_device: null descriptors or coordinates");
+    MMF_REQUIRE(((uintptr_t)descriptor & 15u) == 0, "mmf_viewstore_store_device: 16-byte aligned rows");
+    MMF_REQUIRE(vs->n_rows + padded < (size_t)1 << 31, "mmf_viewstore_store_device: more than 2^31 rows");
+    MMF_HIP_TRY(hipSetDevice(vs->ctx->device));
+    hipStream_t st = vs->ctx->stream;
+    if (padded) {
+        int rc = viewstore_reserve(vs, padded);
+        if (rc) return rc;
+        if (padded / 32 > vs->src0_cap) {  // (every earlier store has been awaited)
+            (void)hipFree(vs->src0_dev);
+            vs->src0_dev = nullptr, vs->src0_cap = 0;
+            MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&vs->src0_dev), padded / 32 * 2 * sizeof(int)));
+            vs->src0_cap = padded / 32 * 2;
+        }
+        if (total * 3 > vs->co_cap) {
+            if (vs->co_pin) (void)hipHostFree(vs->co_pin);
+            vs->co_pin = nullptr, vs->co_cap = 0;
+            MMF_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&vs->co_pin), total * 6 * sizeof(float), hipHostMallocDefault));
+            vs->co_cap = total * 6;
+        }
+    }
+    const size_t first_tile = vs->tiles_host.size(), first_view = vs->views.size();
+    std::vector<int> src0;
+    size_t src = 0, dst = 0;
+    for (int v = 0; v < n_views; ++v) {
+        const size_t n = (size_t)counts[v];
+        vs->views.push_back(RdView{model_id, v, counts[v], vs->n_rows + dst, vs->coords.size() / 3 + src});
+        for (size_t r = 0; r < n; r += 32) {
+            vs->tiles_host.push_back(mmf::RdTile{(int)vs->views.size() - 1, (int)std::min<size_t>(32, n - r)});
+            src0.push_back((int)(src + r));
+        }
+        src += n, dst += (n + 31) / 32 * 32;
+    }
+    if (padded) {
+        hipError_t e = hipMemcpyAsync(vs->tiles + first_tile, vs->tiles_host.data() + first_tile, padded / 32 * sizeof(mmf::RdTile), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(vs->src0_dev, src0.data(), src0.size() * sizeof(int), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(mmf::rd_scatter_views_kernel, dim3((unsigned)(padded / 32)), dim3(256), 0, st, descriptor,
+                               (const mmf::RdTile*)(vs->tiles + first_tile), (const int*)vs->src0_dev, vs->desc + vs->n_rows * kRdDim);
+            hipLaunchKernelGGL(mmf::rd_train_norms_kernel, dim3((unsigned)(padded / 32)), dim3(64), 0, st, vs->desc + vs->n_rows * kRdDim,
+                               (int)padded, kRdDim, vs->tn + vs->n_rows);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(vs->co_pin, coordinate, total * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);  // `src0` leaves scope; the coordinates have arrived
+        if (e != hipSuccess) {  // nothing of the model stays in the books
+            vs->views.resize(first_view), vs->tiles_host.resize(first_tile);
+            MMF_HIP_TRY(e);
+        }
+        vs->coords.insert(vs->coords.end(), vs->co_pin, vs->co_pin + total * 3);
         vs->n_rows += padded;
     }
     if (stored) *stored = 1;

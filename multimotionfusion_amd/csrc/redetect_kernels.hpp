@@ -139,4 +139,20 @@ __global__ __launch_bounds__(256) void rd_gather_labels_kernel(const uint8_t* __
     label[i] = (x >= 0 && x < width && y >= 0 && y < height) ? (int)mask[(size_t)y * width + x] : -1;
 }
 
+// the packed rows of a model's views (DEVICE, one view after the other) to their places in the store: workgroup = one tile
+// of 32 rows, four waves of 64 lanes x 16 B; row j of the tile comes from packed row src0[tile] + j, the rows past the
+// tile's valid ones are the zero padding.  dim = 256.
+__global__ __launch_bounds__(256) void rd_scatter_views_kernel(const float* __restrict__ packed, const RdTile* __restrict__ tiles,
+                                                               const int* __restrict__ src0, float* __restrict__ dst) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int tile = blockIdx.x;
+    const int valid = tiles[tile].valid;
+    const size_t s0 = (size_t)src0[tile];
+    for (int j = w; j < 32; j += 4) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (j < valid) v = reinterpret_cast<const float4*>(packed + (s0 + j) * 256)[lane];
+        reinterpret_cast<float4*>(dst + ((size_t)tile * 32 + j) * 256)[lane] = v;
+    }
+}
+
 }  // namespace mmf

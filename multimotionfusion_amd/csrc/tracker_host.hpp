@@ -4,6 +4,7 @@
 // Everything is enqueued on the context's stream.  The host keeps only an UPPER BOUND of the number of tracks (it grows
 // by the keypoints of every add and becomes exact whenever a call waits: pairs, visible, status, download): the search
 // of an add runs on that many gathered rows, the ones past the active tracks being padding no keypoint can match.
+// The stamp of the newest frame (adds since creation / reset) is exact on the host: the view log's slots go by it.
 #pragma once
 
 #include "tracker_kernels.hpp"
@@ -29,6 +30,15 @@ struct mmf_tracker {
     int bound = 0;  // no fewer than the tracks of the table
     int last_launches = 0;
     std::vector<void*> device_allocs;
+    // the view log (mmf_tracker_set_view_log) and the views built from it (mmf_tracker_model_views)
+    mmf::TrkLog log{};        // all null while the log is off
+    long long frame = 0;      // adds since creation / reset = the stamp of the newest frame
+    long long log_first = 0;  // the first stamp the ring can hold: the log was switched on, or the tracker reset, before it
+    int view_cap = 0;         // views the request / row / count buffers hold
+    mmf::TrkViewRequest *req_pin = nullptr, *req_dev = nullptr;
+    int *view_count_pin = nullptr, *view_count_dev = nullptr, *view_row = nullptr;
+    float *view_co = nullptr, *view_out_desc = nullptr, *view_out_co = nullptr;
+    size_t view_out_rows = 0;
 };
 
 template <typename P>
@@ -47,7 +57,28 @@ static int tracker_clear(mmf_tracker* t) {
     MMF_HIP_TRY(hipStreamSynchronize(st));
     std::memset(t->rec, 0, sizeof(mmf::TrkRecord));
     t->bound = 0, t->cur = 0, t->last_launches = 0;
+    t->frame = 0, t->log_first = 1;  // (the stream has been awaited: no slot of the ring is of interest any more)
     return MMF_OK;
+}
+
+static void tracker_free_log(mmf_tracker* t) {
+    (void)hipFree(t->log.count);
+    (void)hipFree(t->log.stamp);
+    (void)hipFree(t->log.uid);
+    (void)hipFree(t->log.co);
+    (void)hipFree(t->log.desc);
+    t->log = mmf::TrkLog{};
+}
+
+static void tracker_free_views(mmf_tracker* t) {
+    if (t->req_pin) (void)hipHostFree(t->req_pin);
+    if (t->view_count_pin) (void)hipHostFree(t->view_count_pin);
+    (void)hipFree(t->req_dev);
+    (void)hipFree(t->view_count_dev);
+    (void)hipFree(t->view_row);
+    (void)hipFree(t->view_co);
+    t->req_pin = t->req_dev = nullptr, t->view_count_pin = t->view_count_dev = t->view_row = nullptr, t->view_co = nullptr;
+    t->view_cap = 0;
 }
 
 extern "C" void mmf_tracker_destroy(mmf_tracker* t) {
@@ -55,6 +86,10 @@ extern "C" void mmf_tracker_destroy(mmf_tracker* t) {
     (void)hipSetDevice(t->ctx->device);
     (void)hipStreamSynchronize(t->ctx->stream);
     for (void* p : t->device_allocs) (void)hipFree(p);
+    tracker_free_log(t);
+    tracker_free_views(t);
+    (void)hipFree(t->view_out_desc);
+    (void)hipFree(t->view_out_co);
     if (t->rec) (void)hipHostFree(t->rec);
     if (t->p0) (void)hipHostFree(t->p0);
     if (t->p1) (void)hipHostFree(t->p1);
@@ -142,9 +177,123 @@ extern "C" int mmf_tracker_add_keypoints(mmf_tracker* t, int n, const int* xy, c
                        (const int*)t->train_idx, (const int*)t->active_idx, timestamp, t->dest_row);
     hipLaunchKernelGGL(trk_scatter_rows_kernel, dim3(tracker_row_blocks(std::max(n, 1))), dim3(256), 0, st, descriptor, n,
                        (const int*)t->dest_row, t->desc[t->cur], t->capacity);
-    MMF_HIP_TRY(hipGetLastError());
     t->last_launches = 7;
+    t->frame += 1;
+    if (t->log.frames > 0) {  // the frame's visible set into its slot of the ring: two more launches, nothing read back
+        const int slot = (int)(t->frame % t->log.frames);
+        hipLaunchKernelGGL(trk_log_kernel, dim3(1), dim3(kTrkBlock), 0, st, t->T, t->log, slot, t->frame, t->map);
+        hipLaunchKernelGGL(trk_gather_rows_kernel, dim3(tracker_row_blocks(t->max_keypoints)), dim3(256), 0, st,
+                           (const float*)t->desc[t->cur], (const int*)t->map, (const int*)(t->log.count + slot),
+                           t->log.desc + (size_t)slot * t->max_keypoints * kTrkDim, t->capacity);
+        t->last_launches = 9;
+    }
+    MMF_HIP_TRY(hipGetLastError());
     t->bound = (int)std::min<long long>(t->capacity, (long long)t->bound + n);
+    return MMF_OK;
+}
+
+// the view log: frames = 0 switches it off (the default) and frees the ring; any other value allocates a ring of that many
+// slots HERE, behind a wait for the stream (work in flight may still write the old ring), never in the frame path.  It starts
+// empty: the first frame it can hold is the next add.
+extern "C" int mmf_tracker_set_view_log(mmf_tracker* t, int frames) {
+    MMF_REQUIRE(t && frames >= 0 && frames <= (1 << 16), "mmf_tracker_set_view_log: frames must be 0 .. 65536");
+    MMF_HIP_TRY(hipSetDevice(t->ctx->device));
+    if (frames == 0 && t->log.frames == 0) return MMF_OK;
+    hipStream_t st = t->ctx->stream;
+    MMF_HIP_TRY(hipStreamSynchronize(st));
+    tracker_free_log(t);
+    t->log_first = t->frame + 1;
+    if (frames == 0) return MMF_OK;
+    const size_t F = (size_t)frames, K = (size_t)t->max_keypoints;
+    mmf::TrkLog L{};
+    L.frames = frames, L.max_kp = t->max_keypoints;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&L.count), F * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&L.stamp), F * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&L.uid), F * K * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&L.co), F * K * 3 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&L.desc), F * K * mmf::kTrkDim * sizeof(float));
+    if (e == hipSuccess) e = hipMemsetAsync(L.count, 0, F * sizeof(int), st);
+    if (e == hipSuccess) e = hipMemsetAsync(L.stamp, 0xff, F * sizeof(long long), st);  // -1: no frame
+    t->log = L;
+    if (e != hipSuccess) {
+        tracker_free_log(t);
+        MMF_HIP_TRY(e);
+    }
+    return MMF_OK;
+}
+
+extern "C" int mmf_tracker_frame(mmf_tracker* t) { return t ? (int)t->frame : -1; }
+
+// the frame `stamp` is in the ring: logged since the log was switched on / the tracker reset, and not yet overwritten
+static bool tracker_in_log(const mmf_tracker* t, long long stamp) {
+    return t->log.frames > 0 && stamp >= t->log_first && stamp <= t->frame && stamp > t->frame - t->log.frames;
+}
+
+// Model::store's views (Model.cpp:1617-1644, computeTrackProjectionFirstFrame :508-522, project_kp :130-141, the filter of
+// getBestMatch :806-811) of one model from the log: view v = the logged keypoints of frame frames[v], in log order, whose
+// track is in the table and in the model NOW, in the frame poses[v] maps the camera frame to, the non-finite ones dropped.
+// One launch (flags, compaction, coordinates, counts), ONE wait, one launch that packs the rows.  *counts = pinned HOST
+// [n_views], *descriptor / *coordinate = DEVICE, the views' rows one after the other; valid until the tracker's next call.
+// *missing = the views whose frame is not in the ring (they are empty).
+extern "C" int mmf_tracker_model_views(mmf_tracker* t, int model_id, int n_views, const int* frames, const float* poses,
+                                       const int** counts, const float** descriptor, const float** coordinate, int* missing) {
+    MMF_REQUIRE(t && n_views >= 0 && n_views <= 65535 && ((frames && poses) || n_views == 0), "mmf_tracker_model_views: bad argument");
+    MMF_REQUIRE(model_id >= 0 && model_id < mmf::kTrkMaxModels, "mmf_tracker_model_views: model ids are 0 .. 255");
+    MMF_HIP_TRY(hipSetDevice(t->ctx->device));
+    hipStream_t st = t->ctx->stream;
+    using namespace mmf;
+    const size_t K = (size_t)t->max_keypoints;
+    if (std::max(n_views, 1) > t->view_cap) {  // (every earlier views call has been awaited; what packed its rows may still run)
+        MMF_HIP_TRY(hipStreamSynchronize(st));
+        tracker_free_views(t);
+        const size_t cap = (size_t)std::max(16, 2 * n_views);
+        MMF_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&t->req_pin), cap * sizeof(TrkViewRequest), hipHostMallocDefault));
+        MMF_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&t->view_count_pin), cap * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->req_dev), cap * sizeof(TrkViewRequest)));
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->view_count_dev), cap * sizeof(int)));
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->view_row), cap * K * sizeof(int)));
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->view_co), cap * K * 3 * sizeof(float)));
+        t->view_cap = (int)cap;
+    }
+    int absent = 0;
+    for (int v = 0; v < n_views; ++v) {
+        TrkViewRequest& r = t->req_pin[v];
+        const bool in = tracker_in_log(t, frames[v]);
+        absent += in ? 0 : 1;
+        r.slot = in ? (int)(frames[v] % t->log.frames) : -1, r.pad_ = 0, r.stamp = frames[v];
+        std::memcpy(r.pose, poses + 16 * (size_t)v, sizeof(r.pose));
+        t->view_count_pin[v] = 0;
+    }
+    if (n_views > 0)
+        MMF_HIP_TRY(hipMemcpyAsync(t->req_dev, t->req_pin, (size_t)n_views * sizeof(TrkViewRequest), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(trk_views_kernel, dim3((unsigned)std::max(n_views, 1)), dim3(kTrkBlock), 0, st, t->T, t->log,
+                       (const TrkViewRequest*)t->req_dev, n_views, model_id, t->view_row, t->view_co, t->view_count_pin, t->view_count_dev);
+    MMF_HIP_TRY(hipGetLastError());
+    MMF_HIP_TRY(wait_stream(st));
+    size_t total = 0;
+    int most = 0;
+    for (int v = 0; v < n_views; ++v) {
+        MMF_REQUIRE(t->view_count_pin[v] >= 0 && (size_t)t->view_count_pin[v] <= K, "mmf_tracker_model_views: a view's count is out of range");
+        total += (size_t)t->view_count_pin[v], most = std::max(most, t->view_count_pin[v]);
+    }
+    if (std::max<size_t>(total, 1) > t->view_out_rows) {  // (the stream is idle: nothing reads the old buffers)
+        (void)hipFree(t->view_out_desc);
+        (void)hipFree(t->view_out_co);
+        t->view_out_desc = t->view_out_co = nullptr, t->view_out_rows = 0;
+        const size_t cap = std::max<size_t>(64, total + total / 2);
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->view_out_desc), cap * kTrkDim * sizeof(float)));
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->view_out_co), cap * 3 * sizeof(float)));
+        t->view_out_rows = cap;
+    }
+    hipLaunchKernelGGL(trk_views_pack_kernel, dim3(tracker_row_blocks(std::max(most, 1)), (unsigned)std::max(n_views, 1)), dim3(256), 0, st,
+                       t->log, (const int*)t->view_count_dev, n_views, (const int*)t->view_row, (const float*)t->view_co, t->view_out_desc,
+                       t->view_out_co);
+    MMF_HIP_TRY(hipGetLastError());
+    t->last_launches = 2;
+    if (counts) *counts = t->view_count_pin;
+    if (descriptor) *descriptor = t->view_out_desc;
+    if (coordinate) *coordinate = t->view_out_co;
+    if (missing) *missing = absent;
     return MMF_OK;
 }
 

@@ -14,6 +14,9 @@
 // bandwidth): ordered compactions from 64-bit ballots and a scan over the 16 wave totals.  Descriptor rows (1 KB) move
 // in grid kernels, one wave of 64 lanes x 16 B per row.  The counters the host reads go to a pinned record with
 // ordinary stores at the end of the kernel that changes them.
+//
+// The view log (off unless switched on) is the bounded history Model::store's views are built from: a ring of the visible
+// sets of the last adds, and a model's views from it (the second half of this file).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -381,6 +384,133 @@ __global__ __launch_bounds__(kTrkBlock) void trk_visible_kernel(TrkTable T, TrkR
     if (tid == 0) {
         *count = base;
         rec->n_visible = base, rec->n_tracks = nt, rec->length = T.head->length, rec->dropped = T.head->dropped;
+    }
+}
+
+// ---- the view log: a ring of the visible sets of the last `frames` adds (Model::store's views come from it) -------------
+struct TrkLog {  // slot s = stamp % frames; all null while the log is off
+    int frames, max_kp;
+    int* count;        // [frames]
+    long long* stamp;  // [frames] the add that wrote the slot, -1: none
+    long long* uid;    // [frames][max_kp]
+    float* co;         // [frames][max_kp][3] camera frame
+    float* desc;       // [frames][max_kp][256] the descriptor of THAT frame's keypoint
+};
+
+// add, step 5 (log on): the visible set after the add, in table order, into slot `slot`; map[d] = the table row whose
+// descriptor is row d of the slot (trk_gather_rows_kernel moves it), *slot_count rows.  A visible set never exceeds the
+// keypoints of the add; rows past max_kp are dropped all the same.
+__global__ __launch_bounds__(kTrkBlock) void trk_log_kernel(TrkTable T, TrkLog L, int slot, long long stamp, int* __restrict__ map) {
+    const int tid = threadIdx.x;
+    const int nt = min(T.head->n_tracks, T.capacity);
+    long long* uid = L.uid + (size_t)slot * L.max_kp;
+    float* co = L.co + (size_t)slot * L.max_kp * 3;
+    int base = 0;
+    for (int i0 = 0; i0 < nt; i0 += kTrkBlock) {
+        const int i = i0 + tid;
+        const bool vis = i < nt && T.ok[0][i];
+        int tot;
+        const int rank = trk_block_rank(vis, &tot);
+        if (vis && base + rank < L.max_kp) {
+            const size_t d = (size_t)(base + rank);
+            map[d] = i;
+            uid[d] = T.uid[i];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) co[3 * d + k] = T.co[0][3 * i + k];
+        }
+        base += tot;
+    }
+    if (tid == 0) L.count[slot] = min(base, L.max_kp), L.stamp[slot] = stamp;
+}
+
+struct TrkViewRequest {  // one view of mmf_tracker_model_views, uploaded by the host
+    int slot;            // the ring slot of its frame, -1: the frame is not in the ring
+    int pad_;
+    long long stamp;     // the frame; the slot must carry it
+    float pose[16];      // row-major 4 x 4, camera frame -> model frame at that frame
+};
+
+// project_kp (Model.cpp:130-141): float -> double, ((r0 x + r1 y) + r2 z) + t with every product and sum rounded on its own,
+// -> float
+__device__ __forceinline__ float trk_project_row(const float* __restrict__ p, int r, double x, double y, double z) {
+    const double a = __dmul_rn((double)p[4 * r], x), b = __dmul_rn((double)p[4 * r + 1], y), c = __dmul_rn((double)p[4 * r + 2], z);
+    return (float)__dadd_rn(__dadd_rn(__dadd_rn(a, b), c), (double)p[4 * r + 3]);
+}
+
+// a model's views, step 1: workgroup v = view v walks its slot in chunks.  A logged keypoint is taken when its uid is in
+// the table now (binary search: the table is sorted by uid -- appends take ascending uids, prune is a stable compaction),
+// that track has bit `model` now, and its coordinate in the model's frame is finite.  Ordered compaction -> row[v][k] =
+// the ring row of the k-th keypoint of the view, co[v][k] its coordinate; the count goes to pinned memory and to dev_count.
+__global__ __launch_bounds__(kTrkBlock) void trk_views_kernel(TrkTable T, TrkLog L, const TrkViewRequest* __restrict__ req, int n_views,
+                                                              int model, int* __restrict__ row, float* __restrict__ co,
+                                                              int* __restrict__ pinned_count, int* __restrict__ dev_count) {
+    const int tid = threadIdx.x, v = blockIdx.x;
+    if (v >= n_views) return;
+    const int nt = min(T.head->n_tracks, T.capacity);
+    const int slot = req[v].slot;
+    int n = 0;
+    if (slot >= 0 && slot < L.frames && L.stamp[slot] == req[v].stamp) n = min(max(L.count[slot], 0), L.max_kp);
+    const float* pose = req[v].pose;
+    int base = 0;
+    for (int k0 = 0; k0 < n; k0 += kTrkBlock) {
+        const int k = k0 + tid;
+        bool take = false;
+        float out[3] = {};
+        if (k < n) {
+            const size_t e = (size_t)slot * L.max_kp + k;
+            const long long u = L.uid[e];
+            int lo = 0, hi = nt;  // the first row with uid >= u
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (T.uid[mid] < u) lo = mid + 1;
+                else hi = mid;
+            }
+            if (lo < nt && T.uid[lo] == u && ((T.member[kTrkWords * (size_t)lo + (model >> 5)] >> (model & 31)) & 1u)) {
+                const double x = (double)L.co[3 * e], y = (double)L.co[3 * e + 1], z = (double)L.co[3 * e + 2];
+#pragma unroll
+                for (int r = 0; r < 3; ++r) out[r] = trk_project_row(pose, r, x, y, z);
+                take = trk_finite3(out);
+            }
+        }
+        int tot;
+        const int rank = trk_block_rank(take, &tot);
+        if (take) {
+            const size_t d = (size_t)v * L.max_kp + base + rank;
+            row[d] = slot * L.max_kp + k;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) co[3 * d + r] = out[r];
+        }
+        base += tot;
+    }
+    if (tid == 0) pinned_count[v] = base, dev_count[v] = base;
+}
+
+// a model's views, step 2: the rows of view blockIdx.y, one after the other behind the rows of the views before it
+// (descriptors: one wave of 64 lanes x 16 B per row)
+__global__ __launch_bounds__(256) void trk_views_pack_kernel(TrkLog L, const int* __restrict__ dev_count, int n_views,
+                                                             const int* __restrict__ row, const float* __restrict__ co,
+                                                             float* __restrict__ out_desc, float* __restrict__ out_co) {
+    __shared__ int part[256];
+    const int v = blockIdx.y;
+    if (v >= n_views) return;
+    int s = 0;
+    for (int k = threadIdx.x; k < v; k += 256) s += dev_count[k];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
+        __syncthreads();
+    }
+    const size_t off = (size_t)part[0];
+    const int n = min(dev_count[v], L.max_kp);
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), waves = gridDim.x * 4;
+    const size_t ring_rows = (size_t)L.frames * L.max_kp;
+    for (int k = wave; k < n; k += waves) {
+        const size_t d = (size_t)v * L.max_kp + k;
+        const size_t src = min((size_t)max(row[d], 0), ring_rows - 1);
+        reinterpret_cast<float4*>(out_desc + (off + k) * kTrkDim)[lane] = reinterpret_cast<const float4*>(L.desc + src * kTrkDim)[lane];
+        if (lane < 3) out_co[(off + k) * 3 + lane] = co[3 * d + lane];
     }
 }
 

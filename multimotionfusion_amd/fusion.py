@@ -346,6 +346,15 @@ class MultiMotionFusion:
         """Model::store of an inactive model's keypoint views (redetection.ViewStore.store)"""
         return self.getViewStore().store(model_id, views)
 
+    def getLastStoredViews(self):
+        """what the last processFrame stored on deactivation (a tracker with a view log attached, redetection on):
+        [dict(model_id, n_views, rows)]"""
+        n = C.c_int()
+        check(self.ctx.lib.mmf_fusion_last_stored_views(self.handle, None, None, None, 0, C.byref(n)))
+        ids, nv, rows = (np.zeros(max(n.value, 1), np.int32) for _ in range(3))
+        check(self.ctx.lib.mmf_fusion_last_stored_views(self.handle, ids.ctypes.data, nv.ctypes.data, rows.ctypes.data, n.value, C.byref(n)))
+        return [dict(model_id=int(ids[k]), n_views=int(nv[k]), rows=int(rows[k])) for k in range(n.value)]
+
     def getLastRedetections(self):
         from .redetection import last_redetections
         return last_redetections(self.ctx, self.handle)

@@ -40,6 +40,20 @@ class ViewStore:
                                                coord.ctypes.data, C.byref(stored)))
         return bool(stored.value)
 
+    def storeDevice(self, model_id, counts, descriptor: torch.Tensor, coordinate: torch.Tensor):
+        """store() with the views' rows on the device (DevicePointTracker.modelViewsDevice): counts [n_views] host,
+        descriptor [rows,256] / coordinate [rows,3] float32 CUDA tensors, the views one after the other"""
+        counts = np.ascontiguousarray(np.asarray(counts, np.int32).reshape(-1))
+        rows = int(counts.sum())
+        assert descriptor.is_cuda and coordinate.is_cuda and descriptor.dtype == torch.float32 and coordinate.dtype == torch.float32
+        assert descriptor.shape == (rows, DIM) and coordinate.shape == (rows, 3)
+        descriptor, coordinate = descriptor.contiguous(), coordinate.contiguous()
+        stored = C.c_int()
+        check(self.ctx.lib.mmf_viewstore_store_device(self.handle, int(model_id), counts.size, counts.ctypes.data,
+                                                      _p(descriptor) if rows else None, _p(coordinate) if rows else None,
+                                                      C.byref(stored)))
+        return bool(stored.value)
+
     def forget(self, model_id):
         check(self.ctx.lib.mmf_viewstore_forget(self.handle, int(model_id)))
 

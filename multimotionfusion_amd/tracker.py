@@ -73,6 +73,43 @@ class DevicePointTracker:
     def reset(self):
         check(self.ctx.lib.mmf_tracker_reset(self.handle))
 
+    # ----- the view log: what Model::store's views are built from
+    def setViewLog(self, frames):
+        """keep the visible sets of the last `frames` adds on the device (0: off, the default).  The ring is allocated here."""
+        check(self.ctx.lib.mmf_tracker_set_view_log(self.handle, int(frames)))
+
+    def frame(self):
+        """adds since creation / reset = the stamp of the newest frame"""
+        return self.ctx.lib.mmf_tracker_frame(self.handle)
+
+    def modelViewsDevice(self, model_id, frames, poses):
+        """-> (counts int32 [n_views] host, descriptor [rows,256] / coordinate [rows,3] CUDA tensors over the tracker's
+        buffers, valid until its next call, missing)"""
+        from .model import _as_tensor
+        fr = np.ascontiguousarray(np.asarray(frames, np.int32).reshape(-1))
+        po = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(fr.size, 16))
+        cnt, de, co, missing = C.POINTER(C.c_int)(), C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.c_int()
+        check(self.ctx.lib.mmf_tracker_model_views(self.handle, int(model_id), fr.size, fr.ctypes.data, po.ctypes.data,
+                                                   C.byref(cnt), C.byref(de), C.byref(co), C.byref(missing)))
+        counts = np.array([cnt[v] for v in range(fr.size)], np.int32)
+        rows = int(counts.sum())
+        if rows == 0:
+            return counts, torch.zeros((0, 256), dtype=torch.float32, device=self._dev), torch.zeros((0, 3), dtype=torch.float32, device=self._dev), missing.value
+        d = _as_tensor(C.cast(de, C.c_void_p).value, rows * 1024, torch.float32, (rows, 256), self.ctx.device, self)
+        c = _as_tensor(C.cast(co, C.c_void_p).value, rows * 12, torch.float32, (rows, 3), self.ctx.device, self)
+        return counts, d, c, missing.value
+
+    def modelViews(self, model_id, frames, poses):
+        """Model::store's views of one model from the log -> ([(descriptor [n,256], coordinate [n,3])] per listed frame, host
+        arrays, and the number of frames that are not in the log).  frames: stamps (frame()), poses: [n,4,4] camera -> model"""
+        counts, d, c, missing = self.modelViewsDevice(model_id, frames, poses)
+        d, c = d.cpu().numpy(), c.cpu().numpy()
+        out, o = [], 0
+        for n in counts:
+            out.append((d[o:o + n].copy(), c[o:o + n].copy()))
+            o += int(n)
+        return out, missing
+
     # ----- the models' track sets
     @staticmethod
     def _ids(model_ids):
@@ -159,9 +196,13 @@ class NativeKeypointFrontEnd:
     features -> DevicePointTracker -> processFrame, which initialises EVERY active model from its own tracks and keeps the
     models' track sets up to date from the frame's segmentation (fusion.setTracker)."""
 
-    def __init__(self, ctx: Context, fusion, kp_predictor, intrinsics, icp_refine=True, capacity=4096, max_keypoints=1024):
+    def __init__(self, ctx: Context, fusion, kp_predictor, intrinsics, icp_refine=True, capacity=4096, max_keypoints=1024,
+                 view_log=0):
+        """view_log: frames of the tracker's view log (0: none).  With it and fusion.setEnableRedetection(True) a model that
+        leaves the active list stores its keypoint views by itself: redetection needs no history kept by the caller."""
         self.ctx, self.fusion, self.kp = ctx, fusion, kp_predictor
         self.tracker = DevicePointTracker(ctx, fusion.width, fusion.height, intrinsics, capacity, max_keypoints)
+        self.tracker.setViewLog(view_log)
         fusion.setTracker(self.tracker, odom_init_kp=True, icp_refine=icp_refine)
 
     def processFrame(self, rgb, depth, timestamp, weightMultiplier=1.0, **frame):
