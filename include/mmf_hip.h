@@ -204,7 +204,8 @@ int mmf_odom_get_covariance(mmf_odom *o, double cov[36]);
 
 /* Introspection for parity tests: device pointer of an internal pyramid buffer.
  * names: vmaps_curr nmaps_curr vmaps_g_prev nmaps_g_prev last_depth next_depth depth_pyr cloud
- *        last_image next_image last_next_image dIdx dIdy corres */
+ *        last_image next_image last_next_image dIdx dIdy corres; for tests only (level ignored): extent (the 20 64-bit words of
+ *        csrc/extent.hpp) and prep_box (two slots of four ints: the boxes an object model's last two boxed preparations stored) */
 int mmf_odom_buffer(mmf_odom *o, const char *name, int level, void **dev_ptr, size_t *bytes);
 /* synchronous copy of that buffer into host memory (host_bytes must equal its size) */
 int mmf_odom_download(mmf_odom *o, const char *name, int level, void *host_dst, size_t host_bytes);
@@ -572,6 +573,37 @@ int mmf_debug_set_pass_batch(int mode);
  * that every buffer stays what a whole-frame preparation writes (1, the default) -- or the whole frame (0); -1 = the default
  * (MMF_PREP_RECT).  Same buffers, bit for bit.  Process wide. */
 int mmf_debug_set_prep_rect(int on);
+/* test hook: from how many destination pixels on a preparation job's workgroups take four 64 x 4 tiles each, one below the other
+ * (csrc/prep_batch.hpp: PrepJob::reps).  n > 0 = that many pixels (1: every job), 0 = never, -1 = the default (MMF_PREP_BIG, else
+ * 200 000).  Same buffers, bit for bit.  Process wide. */
+int mmf_debug_set_prep_big(int n);
+/* test entry: the batched frame preparation (csrc/prep_batch.hpp) on n >= 1 stand-alone odometries of one context and size, as ONE
+ * set of four stages filled by the collectors the orchestrator uses, launched on the context's stream; the gradients it wrote
+ * are adopted, so that "dIdx" / "dIdy" download them.  preds[k] is odometry k's prediction: RGBA32F vertex / normal images, an
+ * interleaved 8-bit image of `channels` (3 or 4) bytes per pixel, the pose (HOST, row-major 4 x 4), all dense; optionally the
+ * source choice taken on the device (sel != NULL, a DEVICE int: the alt_* images are read when *sel != 0 or, with sel_total
+ * != 0, when *sel / sel_total < sel_ratio); ext_gen != 0: the extent words are noted under that generation; pred_box != NULL
+ * (DEVICE, four ints {x0, y0, x1, y1}; only without sel): the box the prediction is non-zero in -- the jobs cover the hull of
+ * that box and of the previous preparation's (mmf_debug_set_prep_rect).  depth_filtered / rgb (device; either may be NULL)
+ * with `sides` (1 = image side, 2 = depth side) are the sensor frame, prepared into odoms[0]: with n = 1 and both sides the
+ * model side shares its four launches (prep_collect_all), otherwise the sensor side's jobs come first in each stage and every
+ * odometry's model side follows (prep_collect_sensor, prep_collect_model).  No sensor frame: depth_filtered = rgb = NULL.
+ * Nothing of this runs outside tests. */
+typedef struct mmf_debug_prep_prediction {
+    const float *vertex, *normal;
+    const unsigned char *image;
+    int channels;
+    const float *pose;
+    const int *sel;
+    const float *alt_vertex, *alt_normal;
+    const unsigned char *alt_image;
+    int sel_total;
+    float sel_ratio;
+    unsigned ext_gen;
+    const int *pred_box;
+} mmf_debug_prep_prediction;
+int mmf_debug_odom_prepare(mmf_odom *const *odoms, const mmf_debug_prep_prediction *preds, int n, const float *depth_filtered,
+                           float depth_cutoff, const unsigned char *rgb, int rgb_channels, int sides);
 /* test / A-B hook: when a frame's model side is prepared at the end of the call before it (one model per process, the next frame
  * handed in), the beginning of its tracking (odom_begin_kernel: RGBDOdometry.cpp:221-228, 237, 252-255, 316-328) rides the
  * preparation's last launch on one more workgroup (1, the default: csrc/track_kernels.hpp, prep_batch_begin_kernel) or is a launch

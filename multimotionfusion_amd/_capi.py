@@ -51,6 +51,13 @@ class mmf_odom_timing(C.Structure):
                 ("chain_us_sum", C.c_double), ("chains", C.c_int)]
 
 
+class mmf_debug_prep_prediction(C.Structure):
+    _fields_ = [("vertex", C.c_void_p), ("normal", C.c_void_p), ("image", C.c_void_p), ("channels", C.c_int),
+                ("pose", C.POINTER(C.c_float)), ("sel", C.c_void_p), ("alt_vertex", C.c_void_p), ("alt_normal", C.c_void_p),
+                ("alt_image", C.c_void_p), ("sel_total", C.c_int), ("sel_ratio", C.c_float), ("ext_gen", C.c_uint),
+                ("pred_box", C.c_void_p)]
+
+
 class mmf_segmentation_model(C.Structure):
     _fields_ = [("id", C.c_uint), ("super_pixel_count", C.c_uint), ("avg_confidence", C.c_float),
                 ("depth_mean", C.c_float), ("depth_std", C.c_float)]
@@ -261,6 +268,8 @@ SIGNATURES = {
     "mmf_debug_set_sparse_check": (_i, [_i]),
     "mmf_debug_set_pass_batch": (_i, [_i]),
     "mmf_debug_set_prep_rect": (_i, [_i]),
+    "mmf_debug_set_prep_big": (_i, [_i]),
+    "mmf_debug_odom_prepare": (_i, [C.POINTER(_vp), C.POINTER(mmf_debug_prep_prediction), _i, _vp, _f, _vp, _i, _i]),
     "mmf_debug_set_xcd": (_i, [_i]),
     "mmf_debug_xcd_block": (C.c_uint, [C.c_uint, C.c_uint]),
     "mmf_debug_set_begin_rider": (_i, [_i]),

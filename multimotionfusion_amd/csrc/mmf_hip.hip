@@ -1139,8 +1139,14 @@ extern "C" int mmf_odom_init_first_rgb(mmf_odom* o, const uint8_t* rgb, size_t s
 }
 
 // ---- the whole per-frame preparation in four launches (prep_batch.hpp) -------------------------
+static std::atomic<long> g_prep_big{-1};  // -1: MMF_PREP_BIG decides; 0: never; n > 0: that many pixels (mmf_debug_set_prep_big)
+extern "C" int mmf_debug_set_prep_big(int n) {
+    g_prep_big.store(n < 0 ? -1L : (long)n);
+    return MMF_OK;
+}
 static size_t prep_big_job() {  // pixels from which a job's workgroups take four tiles each; MMF_PREP_BIG=0: never
-    const long n = tunables().prep_big;
+    const long forced = g_prep_big.load();
+    const long n = forced < 0 ? tunables().prep_big : forced;
     return n < 0 ? (size_t)200000 : (n > 0 ? (size_t)n : ~(size_t)0);
 }
 struct PrepBuilder {  // the jobs of one stage (possibly of several models); launched kMaxPrepJobs at a time
@@ -1441,6 +1447,49 @@ static int odom_prepare_sensor(mmf_odom* o, const PrepSensorFrame& fr, int sides
     PrepStages stages;
     prep_collect_sensor(stages, o, fr, sides);
     return q ? stages.launch(*q) : stages.launch(o->ctx->stream);
+}
+
+// Test entry: the batched preparation of n stand-alone odometries as ONE set of stages, filled the way the orchestrator fills
+// them (fusion_orchestrator.hpp: fusion_collect_prep) -- host plumbing around the collectors above, no kernel of its own.
+extern "C" int mmf_debug_odom_prepare(mmf_odom* const* odoms, const mmf_debug_prep_prediction* preds, int n, const float* depth_filtered,
+                                      float depth_cutoff, const unsigned char* rgb, int rgb_channels, int sides) {
+    MMF_REQUIRE(odoms && preds && n >= 1, "mmf_debug_odom_prepare: null argument, or no odometry");
+    const bool sensor = depth_filtered != nullptr || rgb != nullptr;
+    MMF_REQUIRE(!sensor || (sides & ~(PREP_INPUT_IMAGE | PREP_INPUT_DEPTH)) == 0, "mmf_debug_odom_prepare: sides is a mask of 1 (image) and 2 (depth)");
+    MMF_REQUIRE(!sensor || (((sides & PREP_INPUT_DEPTH) == 0 || depth_filtered) && ((sides & PREP_INPUT_IMAGE) == 0 || rgb)),
+                "mmf_debug_odom_prepare: a side is asked for without its input");
+    MMF_REQUIRE(!sensor || (sides & PREP_INPUT_IMAGE) == 0 || rgb_channels == 3 || rgb_channels == 4, "mmf_debug_odom_prepare: rgb_channels must be 3 or 4");
+    for (int k = 0; k < n; ++k) {
+        const mmf_debug_prep_prediction& d = preds[k];
+        MMF_REQUIRE(odoms[k] && odoms[k]->slab && odoms[k]->ctx == odoms[0]->ctx, "mmf_debug_odom_prepare: odometries of one context");
+        MMF_REQUIRE(odoms[k]->width == odoms[0]->width && odoms[k]->height == odoms[0]->height, "mmf_debug_odom_prepare: odometries of one size");
+        MMF_REQUIRE(d.vertex && d.normal && d.image && d.pose && (d.channels == 3 || d.channels == 4), "mmf_debug_odom_prepare: incomplete prediction");
+        MMF_REQUIRE(!d.sel || (d.alt_vertex && d.alt_normal && d.alt_image && d.sel_total >= 0), "mmf_debug_odom_prepare: sel without the alt images");
+    }
+    mmf_ctx* c = odoms[0]->ctx;
+    MMF_HIP_TRY(hipSetDevice(c->device));
+    auto prediction = [&](int k) {
+        const mmf_debug_prep_prediction& d = preds[k];
+        PrepPrediction p;
+        p.vertex = d.vertex, p.normal = d.normal, p.image = d.image, p.channels = d.channels, p.pose = d.pose;
+        p.depth_l0 = depth_filtered;
+        p.sel = d.sel, p.alt_vertex = d.alt_vertex, p.alt_normal = d.alt_normal, p.alt_image = d.alt_image;
+        p.sel_total = d.sel_total, p.sel_ratio = d.sel_ratio;
+        p.ext_gen = d.ext_gen, p.pred_box = d.pred_box;
+        return p;
+    };
+    PrepSensorFrame fr;
+    fr.depth_filtered = depth_filtered, fr.depth_cutoff = depth_cutoff, fr.rgb = rgb, fr.channels = rgb_channels;
+    PrepStages stages;
+    if (sensor && n == 1 && sides == (PREP_INPUT_IMAGE | PREP_INPUT_DEPTH)) {
+        prep_collect_all(stages, odoms[0], fr, prediction(0));
+    } else {
+        if (sensor) prep_collect_sensor(stages, odoms[0], fr, sides);
+        for (int k = 0; k < n; ++k) prep_collect_model(stages, odoms[k], prediction(k));
+    }
+    if (int rc = stages.launch(c->stream)) return rc;
+    for (int k = 0; k < n; ++k) odom_adopt_gradients(odoms[k]);
+    return MMF_OK;
 }
 
 static IcpArgs odom_icp_args(mmf_odom* o, int level, float* err_map) {
@@ -2373,6 +2422,8 @@ extern "C" int mmf_odom_buffer(mmf_odom* o, const char* name, int level, void** 
     else if (s == "corres") p = o->corres[level], b = n * sizeof(mmf_dataterm);
     else if (s == "icp_error") p = o->icp_err, b = (size_t)o->width * o->height * 4;  // Model::icpError / rgbError (R32F, full size;
     else if (s == "rgb_error") p = o->rgb_err, b = (size_t)o->width * o->height * 4;  // `level` is ignored)
+    else if (s == "extent") p = o->extent, b = kExtentWords * sizeof(unsigned long long);  // extent.hpp's words (tests; `level` is ignored)
+    else if (s == "prep_box") p = o->prep_box, b = 8 * sizeof(int);                        // PrepJob::rect_store's two slots
     else return fail(MMF_ERR_INVALID, "mmf_odom_buffer: unknown buffer name '" + s + "'");
     *dev_ptr = p;
     *bytes = b;

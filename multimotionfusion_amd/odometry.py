@@ -11,7 +11,7 @@ import weakref
 import numpy as np
 import torch
 
-from ._capi import check, fptr, mmf_odom_stats, MMF_NUM_PYRS
+from ._capi import check, fptr, mmf_debug_prep_prediction, mmf_odom_stats, MMF_NUM_PYRS
 from .cudafuncs import Context, _p, _step
 
 
@@ -113,6 +113,10 @@ class RGBDOdometry:
         check(self.ctx.lib.mmf_odom_download(self.handle, name.encode(), level, C.c_void_p(host.ctypes.data),
                                              nbytes.value))
         cols, rows = self.width >> level, self.height >> level
+        if name == "extent":  # csrc/extent.hpp: the model's 20 words, gen << 32 | value
+            return host.view(np.uint64).copy()
+        if name == "prep_box":  # the boxes {x0, y0, x1, y1} the last two boxed preparations stored, slot = number & 1
+            return host.view(np.int32).reshape(2, 4).copy()
         if name in ("cloud", "cloud4", "prev_packed"):  # per-pixel records
             return host.view(np.float32).reshape(rows, cols, {"cloud": 3, "cloud4": 4, "prev_packed": 6}[name])
         if name == "corres":
@@ -153,3 +157,40 @@ class RGBDOdometry:
             self.close()
         except Exception:
             pass
+
+
+def debugPrepare(odoms, predictions, sensor=None, sides=3):
+    """Test entry (mmf_debug_odom_prepare): the batched frame preparation of csrc/prep_batch.hpp on stand-alone odometries,
+    one set of stages for all of them, filled by the collectors processFrame uses.
+
+    predictions[k]: dict of odometry k's prediction -- "vertex", "normal" (CUDA float32 [H, W, 4]), "image" (CUDA uint8
+    [H, W, 3 or 4]), "pose" (4 x 4), optionally "sel" (CUDA int32 [1]) with "alt_vertex", "alt_normal", "alt_image",
+    "sel_total", "sel_ratio"; "ext_gen"; "pred_box" (CUDA int32 [4]).  sensor: dict of "depth" (CUDA float32 [H, W], filtered),
+    "cutoff", "rgb" (CUDA uint8 [H, W, 3 or 4]), prepared into odoms[0]; sides: 1 = its image side, 2 = its depth side.
+    Returns when the device has finished."""
+    ctx = odoms[0].ctx
+    n = len(odoms)
+    assert n >= 1 and n == len(predictions)
+    handles = (C.c_void_p * n)(*[o.handle.value for o in odoms])
+    preds = (mmf_debug_prep_prediction * n)()
+    poses = []
+    for k, d in enumerate(predictions):
+        poses.append(np.ascontiguousarray(np.asarray(d["pose"], np.float32).reshape(16)))
+        p = preds[k]
+        p.vertex, p.normal, p.image = d["vertex"].data_ptr(), d["normal"].data_ptr(), d["image"].data_ptr()
+        p.channels = d["image"].shape[2]
+        p.pose = fptr(poses[-1])
+        if d.get("sel") is not None:
+            p.sel = d["sel"].data_ptr()
+            p.alt_vertex, p.alt_normal, p.alt_image = d["alt_vertex"].data_ptr(), d["alt_normal"].data_ptr(), d["alt_image"].data_ptr()
+            assert d["alt_image"].shape[2] == p.channels
+            p.sel_total, p.sel_ratio = int(d.get("sel_total", 0)), float(d.get("sel_ratio", 0.0))
+        p.ext_gen = int(d.get("ext_gen", 0))
+        if d.get("pred_box") is not None:
+            p.pred_box = d["pred_box"].data_ptr()
+    depth = sensor.get("depth") if sensor else None
+    rgb = sensor.get("rgb") if sensor else None
+    torch.cuda.synchronize()  # (the inputs were written on torch's stream, the preparation runs on the context's)
+    check(ctx.lib.mmf_debug_odom_prepare(handles, preds, n, _p(depth), float(sensor["cutoff"]) if sensor else 0.0, _p(rgb),
+                                         rgb.shape[2] if rgb is not None else 0, int(sides)))
+    torch.cuda.synchronize()
