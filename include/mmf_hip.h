@@ -1031,6 +1031,78 @@ int mmf_fusion_set_tracker(mmf_fusion *f, mmf_tracker *tracker, int odom_init_kp
 int mmf_fusion_last_track_transforms(mmf_fusion *f, float *T, int capacity, int *n_out);
 int mmf_fusion_last_stored_views(mmf_fusion *f, int *model_ids, int *n_views, int *rows, int capacity, int *n_out);
 
+/* ---- RigidRANSAC for batches of independent problems on the device (csrc/ransac_kernels.hpp) ----
+ * The contract, per problem and bit for bit: mmf_ransac_create(cfg); mmf_ransac_estimate(p0, p1, n, NULL, ...);
+ * mmf_ransac_destroy -- a FRESH object per problem, no mask.  One wave per problem runs the arithmetic of the host class
+ * (one source, csrc/rigid_ransac.hpp); the rows a hypothesis is fitted to come from a table the host builds at creation
+ * with the class's own std::shuffle, so the device draws no random numbers.
+ *   mmf_ransac_batch_create    3 <= max_points <= 1024, 1 <= cfg->iterations <= 32.  Builds and uploads the table (about
+ *                         30 ms at 1024 points and 10 iterations: at creation, never per frame), allocates the results in
+ *                         pinned memory.  Waits for the stream.
+ *   mmf_ransac_batch_estimate  p0 / p1 = DEVICE [offsets[n_problems]][3], problem p = rows offsets[p] .. offsets[p + 1]
+ *                         (HOST, offsets[0] = 0, ascending); results = HOST [n_problems]; inlier (optional) = HOST
+ *                         [offsets[n_problems]], per problem over its HASH-SORTED rows like mmf_ransac_estimate's.  Sizes
+ *                         are checked before anything is launched; a problem with fewer than 3 or more than max_points
+ *                         rows gets its status (T identity, error +inf, no inliers) and leaves its neighbours alone.
+ *                         One launch, one wait.
+ *   mmf_ransac_batch_max_points / _last_launches   what the object was created with; launches of the last estimate
+ * Test hooks: mmf_debug_hash_float = the restated std::hash<float> beside the library's; mmf_debug_ransac_core_host = one
+ * problem through table + hash + sort + core on the host, outputs as mmf_ransac_estimate; mmf_debug_rounded_ops = out[i] =
+ * op(a[i], b[i]) on the DEVICE as the core spells it: 0 sqrt (double), 1 / (double), 2 sqrt (float), 3 rintf, 4 / (float),
+ * 5 float / int. */
+#define MMF_RANSAC_OK 0
+#define MMF_RANSAC_TOO_FEW 1  /* fewer than 3 correspondences */
+#define MMF_RANSAC_TOO_MANY 2 /* more than max_points */
+typedef struct mmf_ransac_batch mmf_ransac_batch;
+typedef struct {
+    float T[16];    /* row-major 4x4 of T_01; the all-points fit when no hypothesis was accepted */
+    float error;    /* mean inlier distance of the best hypothesis, +inf when none was accepted */
+    int n_inliers;  /* inliers of the best hypothesis, 0 when none */
+    int has_inlier; /* 0: Result::inlier is empty */
+    int status;     /* MMF_RANSAC_* */
+} mmf_ransac_result;
+int mmf_ransac_batch_create(mmf_ctx *ctx, const mmf_ransac_config *cfg, int max_points, mmf_ransac_batch **out);
+void mmf_ransac_batch_destroy(mmf_ransac_batch *b);
+int mmf_ransac_batch_estimate(mmf_ransac_batch *b, const float *p0_dev, const float *p1_dev, const int *offsets, int n_problems,
+                              mmf_ransac_result *results, unsigned char *inlier);
+int mmf_ransac_batch_max_points(mmf_ransac_batch *b);
+int mmf_ransac_batch_last_launches(mmf_ransac_batch *b);
+/* The view store with a verifier (keypoint redetection, above):
+ *   mmf_viewstore_set_verifier   attaches a batch object (NULL detaches it; it belongs to the caller, shares the store's context
+ *                         and outlives its attachment).  With one attached the store keeps its coordinates and its view table
+ *                         on the device as well -- views stored before the call are uploaded here, growth copies them like the
+ *                         descriptors and old buffers are kept until destroy -- and the match writes its rows to device memory
+ *                         too.  Without one nothing of this is allocated, written or launched, and a match stays 3 launches.
+ *   mmf_viewstore_best_match_device   the outputs of mmf_viewstore_best_match with coordinate = DEVICE [nq][3], nq <= max_points,
+ *                         under the PER-VIEW rule: every view's estimate is that of a fresh RigidRANSAC{cfg of the batch
+ *                         object} (mmf_viewstore_best_match runs ONE object's engine on from view to view).  The three match
+ *                         launches, then a verify launch with grid = sets x views (views with fewer than 3 matches, empty
+ *                         views and views of other models return at once) and a launch that picks per (set, model) the
+ *                         smallest error over the model's views in ascending index, the first of equals, estimates without
+ *                         inliers dropped: 5 launches whatever the store holds, one record through pinned memory, one wait.
+ *                         MMF_ERR_STATE without a verifier.
+ * Inside processFrame:
+ *   mmf_fusion_set_redetection_verifier   mode 0 = host (default: the path of mmf_fusion_set_redetection, untouched), 1 =
+ *                         device: the fusion creates a batch object {10, 0.03, 0.8}, max_points 1024, and attaches it to its
+ *                         store.  A frame then stages the segments' coordinates with their descriptors and enqueues, behind
+ *                         the matches of all segments, the two verification launches for ALL (segment, inactive model)
+ *                         pairs before the one wait for the matches; the unchanged decision block reads the records (a model
+ *                         that an earlier segment of the frame activated is skipped).  Still two waits per such frame.  A
+ *                         segment with more than max_points finite keypoints is verified by the host core under the same
+ *                         per-view rule and counted.  MMF_ERR_STATE with world > 1.
+ *   mmf_fusion_redetection_host_verified  segments verified on the host in mode 1 since creation (-1: null) */
+int mmf_viewstore_set_verifier(mmf_viewstore *vs, mmf_ransac_batch *b);
+int mmf_viewstore_best_match_device(mmf_viewstore *vs, int model_id, const float *query, const float *coordinate, int nq,
+                                    float T[16], float *error, int *inliers, int *view, int *n_matches, unsigned char *inlier,
+                                    int *found);
+int mmf_fusion_set_redetection_verifier(mmf_fusion *f, int mode);
+int mmf_fusion_redetection_host_verified(mmf_fusion *f);
+int mmf_debug_set_redetect_max_points(int max_points); /* the max_points of verifiers created from now on by the setter above (tests) */
+int mmf_debug_hash_float(const float *x, int n, unsigned long long *restated, unsigned long long *libstdcxx);
+int mmf_debug_ransac_core_host(const mmf_ransac_config *cfg, const float *p0, const float *p1, int n, float T[16], float *error,
+                               unsigned char *inlier, int *has_inlier);
+int mmf_debug_rounded_ops(mmf_ctx *ctx, int op, const void *a_dev, const void *b_dev, size_t n, void *out_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -106,6 +106,11 @@ class mmf_ransac_config(C.Structure):
     _fields_ = [("iterations", C.c_int), ("inlier_threshold", C.c_float), ("inlier_fraction", C.c_float)]
 
 
+class mmf_ransac_result(C.Structure):
+    _fields_ = [("T", C.c_float * 16), ("error", C.c_float), ("n_inliers", C.c_int), ("has_inlier", C.c_int),
+                ("status", C.c_int)]
+
+
 SEGMENTATION_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(mmf_frame), C.POINTER(mmf_segmentation))
 
 
@@ -324,6 +329,19 @@ SIGNATURES = {
     "mmf_fusion_set_tracker": (_i, [_vp, _vp, _i, _i]),
     "mmf_fusion_last_stored_views": (_i, [_vp, _vp, _vp, _vp, _i, _ip]),
     "mmf_fusion_last_track_transforms": (_i, [_vp, _vp, _i, _ip]),
+    "mmf_ransac_batch_create": (_i, [_vp, C.POINTER(mmf_ransac_config), _i, C.POINTER(_vp)]),
+    "mmf_ransac_batch_destroy": (None, [_vp]),
+    "mmf_ransac_batch_estimate": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "mmf_ransac_batch_max_points": (_i, [_vp]),
+    "mmf_ransac_batch_last_launches": (_i, [_vp]),
+    "mmf_viewstore_set_verifier": (_i, [_vp, _vp]),
+    "mmf_viewstore_best_match_device": (_i, [_vp, _i, _vp, _vp, _i, _vp, _fp, _ip, _ip, _ip, _vp, _ip]),
+    "mmf_fusion_set_redetection_verifier": (_i, [_vp, _i]),
+    "mmf_fusion_redetection_host_verified": (_i, [_vp]),
+    "mmf_debug_set_redetect_max_points": (_i, [_i]),
+    "mmf_debug_hash_float": (_i, [_vp, _i, _vp, _vp]),
+    "mmf_debug_ransac_core_host": (_i, [C.POINTER(mmf_ransac_config), _vp, _vp, _i, _vp, _fp, _vp, _ip]),
+    "mmf_debug_rounded_ops": (_i, [_vp, _i, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

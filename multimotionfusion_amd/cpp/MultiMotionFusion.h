@@ -650,6 +650,9 @@ class MultiMotionFusion {
     void setSuperpixelEngine(bool v) { other_["superpixelEngine"] = v, mmf::check(mmf_fusion_set_superpixel_engine(f_, v ? 1 : 0), "mmf_fusion_set_superpixel_engine"); }
     // redetection of inactive models by their stored keypoint views (:489-559), inside processFrame; off until switched on
     void setEnableRedetection(bool v) { other_["enableRedetection"] = v, mmf::check(mmf_fusion_set_redetection(f_, v ? 1 : 0), "mmf_fusion_set_redetection"); }
+    // where the redetection candidates are verified: 0 = host (default), 1 = device, a fresh RigidRANSAC per view (mmf_hip.h)
+    void setRedetectionVerifier(int mode) { mmf::check(mmf_fusion_set_redetection_verifier(f_, mode), "mmf_fusion_set_redetection_verifier"); }
+    int getRedetectionHostVerified() { return mmf_fusion_redetection_host_verified(f_); }
     // the last keypoint of every visible track (track->back(), :428-436) for the next processFrame: xy [n][2] pixels,
     // coordinate [n][3] camera frame, descriptor [n][256]
     void setKeypoints(int n, const int* xy, const float* coordinate, const float* descriptor) {

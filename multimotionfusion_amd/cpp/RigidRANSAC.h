@@ -41,6 +41,36 @@ class RigidRANSAC {
     mmf_ransac* r_ = nullptr;
 };
 
+// RigidRANSAC::estimate for a ragged batch of independent problems on the device (mmf_ransac_batch_*): per problem, bit
+// for bit, what a fresh RigidRANSAC(config) returns without a mask.  p0 / p1 are DEVICE arrays [offsets[n]][3].
+class RigidRANSACBatch {
+   public:
+    RigidRANSACBatch(mmf::Context& ctx, const RigidRANSAC::Config& c, int max_points) {
+        const mmf_ransac_config cfg{c.iterations, c.inlier_threshold, c.inlier_fraction};
+        mmf::check(mmf_ransac_batch_create(ctx.get(), &cfg, max_points, &b_), "mmf_ransac_batch_create");
+    }
+    ~RigidRANSACBatch() { mmf_ransac_batch_destroy(b_); }
+    RigidRANSACBatch(const RigidRANSACBatch&) = delete;
+    RigidRANSACBatch& operator=(const RigidRANSACBatch&) = delete;
+
+    // results[p].status: MMF_RANSAC_OK / _TOO_FEW / _TOO_MANY; inlier (optional) = offsets[n] bytes over the hash-sorted rows
+    std::vector<mmf_ransac_result> estimate(const float* p0_dev, const float* p1_dev, const std::vector<int>& offsets,
+                                            std::vector<unsigned char>* inlier = nullptr) {
+        const int n = (int)offsets.size() - 1;
+        std::vector<mmf_ransac_result> results((size_t)(n > 0 ? n : 0));
+        if (inlier) inlier->assign((size_t)(n >= 0 ? offsets.back() : 0), 0);
+        if (n <= 0) return results;
+        mmf::check(mmf_ransac_batch_estimate(b_, p0_dev, p1_dev, offsets.data(), n, results.data(), inlier ? inlier->data() : nullptr),
+                   "mmf_ransac_batch_estimate");
+        return results;
+    }
+    int maxPoints() { return mmf_ransac_batch_max_points(b_); }
+    mmf_ransac_batch* get() { return b_; }
+
+   private:
+    mmf_ransac_batch* b_ = nullptr;
+};
+
 namespace tracker {
 // cv::BFMatcher(cv::NORM_L2, true).match(current, previous, matches) + the distance test of PointTracker.cpp:108,
 // on device-resident descriptor rows; trainIdx[q] = row of `previous` or -1

@@ -105,6 +105,9 @@ struct mmf_fusion {
     std::vector<mmf_segmentation_model> mask_models;
     // keypoint redetection of inactive models (MultiMotionFusion.cpp:489-559; redetect_host.hpp): off unless switched on
     bool redetect_on = false;
+    int redetect_verifier = 0;             // mmf_fusion_set_redetection_verifier: 0 = host, 1 = device
+    mmf_ransac_batch* verifier = nullptr;  // owned; attached to `views` while the mode is 1
+    int host_verified = 0;                 // segments too large for the verifier, verified on the host under its rule
     mmf_viewstore* views = nullptr;  // the stored keypoint views of the inactive models (created on first use)
     bool kp_next = false;            // mmf_fusion_set_keypoints: the NEXT frame's keypoints
     std::vector<int> kp_xy;
@@ -382,6 +385,7 @@ extern "C" void mmf_fusion_destroy(mmf_fusion* f) {
     if (f->ev_sp_done) (void)hipEventDestroy(f->ev_sp_done);
     if (f->sp_stream) (void)hipStreamDestroy(f->sp_stream);
     mmf_viewstore_destroy(f->views);
+    mmf_ransac_batch_destroy(f->verifier);
     if (f->kp_xy_pin) (void)hipHostFree(f->kp_xy_pin);
     if (f->kp_label_pin) (void)hipHostFree(f->kp_label_pin);
     (void)hipFree(f->mask_boxes);
@@ -451,6 +455,7 @@ extern "C" int mmf_fusion_set_shard(mmf_fusion* f, int rank, int world) {
     MMF_REQUIRE(f && world >= 1 && rank >= 0 && rank < world, "mmf_fusion_set_shard: bad argument");
     MMF_REQUIRE(f->models.size() == 1 && f->inactive.empty(), "mmf_fusion_set_shard: call it before the first object model is spawned");
     if (world > 1 && f->redetect_on) return fail(MMF_ERR_STATE, "mmf_fusion_set_shard: redetection is on (sharded redetection is not supported)");
+    if (world > 1 && f->redetect_verifier) return fail(MMF_ERR_STATE, "mmf_fusion_set_shard: the redetection verifier is on (not supported on a shard)");
     f->shard_rank = rank, f->shard_world = world;
     // models created ahead of their use (preallocateModels): the ones this rank will not own shrink to bookkeeping
     for (FusionModel*& fm : f->preallocated) {
@@ -1625,6 +1630,37 @@ extern "C" int mmf_fusion_set_redetection(mmf_fusion* f, int on) {
     f->redetect_on = on != 0;
     return MMF_OK;
 }
+// where the geometric verification of the redetection candidates runs: 0 = on the host, one RigidRANSAC per (segment, model)
+// running on from view to view (the default); 1 = on the device, a fresh one per view (ransac_kernels.hpp)
+static std::atomic<int> g_redetect_max_points{mmf::kRansacMaxPoints};
+extern "C" int mmf_debug_set_redetect_max_points(int max_points) {
+    MMF_REQUIRE(max_points >= 3 && max_points <= mmf::kRansacMaxPoints, "mmf_debug_set_redetect_max_points: 3 .. 1024");
+    g_redetect_max_points.store(max_points);
+    return MMF_OK;
+}
+extern "C" int mmf_fusion_set_redetection_verifier(mmf_fusion* f, int mode) {
+    MMF_REQUIRE(f && (mode == 0 || mode == 1), "mmf_fusion_set_redetection_verifier: mode is 0 (host) or 1 (device)");
+    if (mode && f->shard_world > 1) return fail(MMF_ERR_STATE, "mmf_fusion_set_redetection_verifier: not supported on a shard (world > 1)");
+    if (mode == f->redetect_verifier) return MMF_OK;
+    int rc = fusion_viewstore(f);
+    if (rc) return rc;
+    if (mode) {
+        const mmf_ransac_config cfg{kRedetectRansac.iterations, kRedetectRansac.inlier_threshold, kRedetectRansac.inlier_fraction};
+        rc = mmf_ransac_batch_create(f->ctx, &cfg, g_redetect_max_points.load(), &f->verifier);
+        if (rc) return rc;
+        rc = mmf_viewstore_set_verifier(f->views, f->verifier);
+        if (rc) return rc;
+    } else {
+        rc = mmf_viewstore_set_verifier(f->views, nullptr);
+        if (rc) return rc;
+        mmf_ransac_batch_destroy(f->verifier);  // (waits for the stream)
+        f->verifier = nullptr;
+    }
+    f->redetect_verifier = mode;
+    return MMF_OK;
+}
+extern "C" int mmf_fusion_redetection_host_verified(mmf_fusion* f) { return f ? f->host_verified : -1; }
+
 // the last keypoint of every currently visible track (track->back(), :428-436) for the NEXT processFrame only: HOST arrays
 // xy [n][2] integer pixels, coordinate [n][3] camera frame (non-finite allowed), descriptor [n][256].  Copied.
 extern "C" int mmf_fusion_set_keypoints(mmf_fusion* f, int n, const int* xy, const float* coordinate, const float* descriptor) {
@@ -1754,14 +1790,54 @@ static int frame_redetect(mmf_fusion* f, bool* has_new) {
         }
     }
     MMF_HIP_TRY(hipMemcpyAsync(vs->q_dev, vs->q_pin, total_q * kRdDim * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    const bool on_device = f->redetect_verifier == 1 && vs->verifier;
+    if (on_device) {  // the segments' coordinates travel with their descriptors
+        if (total_q * 3 > vs->qc_cap) {  // (every earlier verification has been awaited)
+            if (vs->qc_pin) (void)hipHostFree(vs->qc_pin);
+            (void)hipFree(vs->qc_dev);
+            vs->qc_pin = vs->qc_dev = nullptr, vs->qc_cap = 0;
+            const size_t cap = total_q * 3 + total_q * 3 / 2 + 192;
+            MMF_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&vs->qc_pin), cap * sizeof(float), hipHostMallocDefault));
+            MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&vs->qc_dev), cap * sizeof(float)));
+            vs->qc_cap = cap;
+        }
+        std::memcpy(vs->qc_pin, coords.data(), total_q * 3 * sizeof(float));
+        MMF_HIP_TRY(hipMemcpyAsync(vs->qc_dev, vs->qc_pin, total_q * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    }
     rc = viewstore_enqueue(vs, c->stream, sets.data(), (int)sets.size());
     if (rc) return rc;
-    MMF_HIP_TRY(wait_stream(c->stream));  // wait 2: the matches of every segment against every view
+    // device verifier: behind the matches of all segments the two verification launches for ALL (segment, inactive model)
+    // pairs of the frame, before the one wait.  (No match launched -- a store of empty views: nothing can be found.)
+    std::vector<int> asked;
+    const bool verified = on_device && vs->last_launches > 0;
+    if (verified) {
+        std::vector<mmf::RdVerifySet> vsets(sets.size());
+        for (size_t s = 0; s < sets.size(); ++s) vsets[s] = mmf::RdVerifySet{vs->qc_dev + sets[s].q0 * 3, sets[s].nq, (int)sets[s].q0};
+        for (const FusionModel* im : f->inactive) asked.push_back((int)im->model->id);
+        rc = viewstore_enqueue_verify(vs, c->stream, vsets.data(), (int)vsets.size(), asked.data(), (int)asked.size());
+        if (rc) return rc;
+    }
+    MMF_HIP_TRY(wait_stream(c->stream));  // wait 2: the matches of every segment against every view (and their verification)
     for (size_t s = 0; s < sets.size(); ++s) {
         const int label = set_label[s];
+        const bool too_large = on_device && sets[s].nq > vs->verifier->max_points;  // verified here, under the verifier's rule
+        if (too_large) ++f->host_verified;
         for (size_t mi = 0; mi < f->inactive.size();) {
             FusionModel* im = f->inactive[mi];
-            const RdBest best = viewstore_best(vs, (int)im->model->id, sets[s], coords.data() + sets[s].q0 * 3, kRedetectRansac);
+            RdBest best;
+            if (!on_device) {
+                best = viewstore_best(vs, (int)im->model->id, sets[s], coords.data() + sets[s].q0 * 3, kRedetectRansac);
+            } else if (too_large) {
+                best = viewstore_best_fresh(vs, (int)im->model->id, sets[s], coords.data() + sets[s].q0 * 3, vs->verifier->cfg);
+            } else if (verified) {  // the record of (segment, model): a model an earlier segment activated has left the list
+                const size_t a = (size_t)(std::find(asked.begin(), asked.end(), (int)im->model->id) - asked.begin());
+                const mmf::RdRecord& rec = vs->rec_pin[s * asked.size() + a];
+                best.found = rec.found != 0, best.error = rec.error, best.inliers = rec.inliers, best.view = rec.view, best.n_matches = rec.n_matches;
+                for (int r = 0; r < 3; ++r) {
+                    for (int q = 0; q < 3; ++q) best.transformation.R[r * 3 + q] = rec.T[r * 4 + q];
+                    best.transformation.t[r] = rec.T[r * 4 + 3];
+                }
+            }
             if (!(best.found && (double)best.error < 0.01 && best.inliers > 5)) {  // :516
                 ++mi;
                 continue;

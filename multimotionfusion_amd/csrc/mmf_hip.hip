@@ -3330,9 +3330,12 @@ extern "C" int mmf_match_descriptors(mmf_ctx* c, const float* query, int nq, con
 }
 
 // =============================================================================================
-// RigidRANSAC (Core/Utils/RigidRANSAC.{h,cpp}): host code, see rigid_ransac.hpp
+// RigidRANSAC (Core/Utils/RigidRANSAC.{h,cpp}): host code, see rigid_ransac.hpp; batches of
+// independent problems on the device, see ransac_kernels.hpp
 // =============================================================================================
-#include "rigid_ransac.hpp"
+#include <functional>
+
+#include "ransac_kernels.hpp"
 
 struct mmf_ransac {
     mmf::RigidRANSAC impl;
@@ -3384,6 +3387,158 @@ extern "C" int mmf_ransac_estimate(mmf_ransac* r, const float* p0, const float* 
     if (has_inlier) *has_inlier = res.inlier.empty() ? 0 : 1;
     if (inlier)
         for (int i = 0; i < n; ++i) inlier[i] = res.inlier.empty() ? 0 : res.inlier[i];
+    return MMF_OK;
+}
+
+// test hooks of the shared core (host code, no device): the restated hash beside std::hash<float>, and one problem
+// through table + hash + sort + core as the device verifier runs it
+extern "C" int mmf_debug_hash_float(const float* x, int n, unsigned long long* restated, unsigned long long* libstdcxx) {
+    MMF_REQUIRE(x && restated && libstdcxx && n >= 0, "mmf_debug_hash_float: bad argument");
+    for (int i = 0; i < n; ++i) {
+        restated[i] = mmf::ransac_core::hash_float_bits(mmf::ransac_core::float_bits(x[i]));
+        libstdcxx[i] = (unsigned long long)std::hash<float>()(x[i]);
+    }
+    return MMF_OK;
+}
+
+static bool ransac_config_ok(const mmf_ransac_config* cfg) {
+    return cfg && cfg->iterations >= 1 && cfg->iterations <= mmf::kRansacMaxIterations;
+}
+
+extern "C" int mmf_debug_ransac_core_host(const mmf_ransac_config* cfg, const float* p0, const float* p1, int n, float T[16],
+                                          float* error, unsigned char* inlier, int* has_inlier) {
+    MMF_REQUIRE(ransac_config_ok(cfg) && p0 && p1 && T && error, "mmf_debug_ransac_core_host: bad argument");
+    MMF_REQUIRE(n >= 3 && n <= 65535, "mmf_debug_ransac_core_host: needs 3 .. 65535 correspondences");
+    std::vector<unsigned short> triples(3 * (size_t)cfg->iterations);
+    mmf::ransac_triples(cfg->iterations, n, triples.data());
+    mmf::Isometry3f I;
+    const int count = mmf::ransac_core_host({cfg->iterations, cfg->inlier_threshold, cfg->inlier_fraction}, triples.data(), p0, p1, n,
+                                            &I, error, inlier);
+    isometry_to_4x4(I, T);
+    if (has_inlier) *has_inlier = count > 0 ? 1 : 0;
+    return MMF_OK;
+}
+
+extern "C" int mmf_debug_rounded_ops(mmf_ctx* c, int op, const void* a_dev, const void* b_dev, size_t n, void* out_dev) {
+    MMF_REQUIRE(c && a_dev && out_dev && n > 0 && op >= 0 && op <= 5, "mmf_debug_rounded_ops: bad argument");
+    MMF_REQUIRE(b_dev || op == 0 || op == 2 || op == 3, "mmf_debug_rounded_ops: the operation takes two arguments");
+    MMF_HIP_TRY(hipSetDevice(c->device));
+    hipLaunchKernelGGL(mmf::ransac_ops_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, op, a_dev, b_dev, n, out_dev);
+    MMF_HIP_TRY(hipGetLastError());
+    return MMF_OK;
+}
+
+// ---- mmf_ransac_batch: ragged batches of independent problems, one wave each (ransac_kernels.hpp) --------------------
+struct mmf_ransac_batch {
+    mmf_ctx* ctx = nullptr;
+    mmf::RigidRANSAC::Config cfg{10, 0.03f, 0.8f};
+    int max_points = 0;
+    std::vector<unsigned short> table;  // the host core of an oversized problem reads it too
+    unsigned short* table_dev = nullptr;
+    int *off_pin = nullptr, *off_dev = nullptr;  // offsets on their way to the device
+    size_t off_cap = 0;
+    mmf_ransac_result* res_pin = nullptr;  // host memory the device writes
+    size_t res_cap = 0;
+    unsigned char* inl_pin = nullptr;
+    size_t inl_cap = 0;
+    int last_launches = 0;
+
+    mmf::RansacDeviceConfig device_config() const {
+        return mmf::RansacDeviceConfig{cfg.iterations, cfg.inlier_threshold, cfg.inlier_fraction, max_points, (max_points + 63) / 64 * 64, table_dev};
+    }
+};
+
+extern "C" void mmf_ransac_batch_destroy(mmf_ransac_batch* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->ctx->device);
+    (void)hipStreamSynchronize(b->ctx->stream);
+    (void)hipFree(b->table_dev);
+    (void)hipFree(b->off_dev);
+    if (b->off_pin) (void)hipHostFree(b->off_pin);
+    if (b->res_pin) (void)hipHostFree(b->res_pin);
+    if (b->inl_pin) (void)hipHostFree(b->inl_pin);
+    delete b;
+}
+
+// pinned buffers for n problems of `total` rows (every earlier estimate has been awaited)
+static int ransac_batch_reserve(mmf_ransac_batch* b, size_t n, size_t total) {
+    if (n + 1 > b->off_cap) {
+        if (b->off_pin) (void)hipHostFree(b->off_pin);
+        (void)hipFree(b->off_dev);
+        b->off_pin = nullptr, b->off_dev = nullptr, b->off_cap = 0;
+        const size_t cap = (n + 1) * 2;
+        MMF_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->off_pin), cap * sizeof(int), hipHostMallocDefault));
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b->off_dev), cap * sizeof(int)));
+        b->off_cap = cap;
+    }
+    if (n > b->res_cap) {
+        if (b->res_pin) (void)hipHostFree(b->res_pin);
+        b->res_pin = nullptr, b->res_cap = 0;
+        MMF_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->res_pin), n * 2 * sizeof(mmf_ransac_result), hipHostMallocMapped | hipHostMallocCoherent));
+        b->res_cap = n * 2;
+    }
+    if (total + 1 > b->inl_cap) {
+        if (b->inl_pin) (void)hipHostFree(b->inl_pin);
+        b->inl_pin = nullptr, b->inl_cap = 0;
+        MMF_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->inl_pin), (total + 1) * 2, hipHostMallocMapped | hipHostMallocCoherent));
+        b->inl_cap = (total + 1) * 2;
+    }
+    return MMF_OK;
+}
+
+extern "C" int mmf_ransac_batch_create(mmf_ctx* c, const mmf_ransac_config* cfg, int max_points, mmf_ransac_batch** out) {
+    MMF_REQUIRE(c && out, "mmf_ransac_batch_create: null argument");
+    MMF_REQUIRE(ransac_config_ok(cfg), "mmf_ransac_batch_create: 1 <= iterations <= 32");
+    MMF_REQUIRE(max_points >= 3 && max_points <= mmf::kRansacMaxPoints, "mmf_ransac_batch_create: 3 <= max_points <= 1024");
+    MMF_HIP_TRY(hipSetDevice(c->device));
+    mmf_ransac_batch* b = new (std::nothrow) mmf_ransac_batch();
+    MMF_REQUIRE(b != nullptr, "mmf_ransac_batch_create: out of host memory");
+    b->ctx = c;
+    b->cfg = {cfg->iterations, cfg->inlier_threshold, cfg->inlier_fraction};
+    b->max_points = max_points;
+    b->table = mmf::ransac_triple_table(cfg->iterations, max_points);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&b->table_dev), b->table.size() * sizeof(unsigned short));
+    if (e == hipSuccess) e = hipMemcpyAsync(b->table_dev, b->table.data(), b->table.size() * sizeof(unsigned short), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    int rc = MMF_OK;
+    if (e == hipSuccess) rc = ransac_batch_reserve(b, 64, 64 * 64);
+    if (e != hipSuccess || rc != MMF_OK) {
+        mmf_ransac_batch_destroy(b);
+        if (rc != MMF_OK) return rc;
+        MMF_HIP_TRY(e);
+    }
+    *out = b;
+    return MMF_OK;
+}
+
+extern "C" int mmf_ransac_batch_max_points(mmf_ransac_batch* b) { return b ? b->max_points : -1; }
+extern "C" int mmf_ransac_batch_last_launches(mmf_ransac_batch* b) { return b ? b->last_launches : -1; }
+
+// p0 / p1 = DEVICE [offsets[n]][3]; offsets = HOST [n + 1], offsets[0] = 0, ascending; results = HOST [n]; inlier (optional) =
+// HOST [offsets[n]] over each problem's hash-sorted rows.  One launch, one wait.
+extern "C" int mmf_ransac_batch_estimate(mmf_ransac_batch* b, const float* p0_dev, const float* p1_dev, const int* offsets,
+                                         int n_problems, mmf_ransac_result* results, unsigned char* inlier) {
+    MMF_REQUIRE(b && offsets && n_problems >= 0 && (results || n_problems == 0), "mmf_ransac_batch_estimate: bad argument");
+    b->last_launches = 0;
+    MMF_REQUIRE(offsets[0] == 0, "mmf_ransac_batch_estimate: offsets start at 0");
+    for (int p = 0; p < n_problems; ++p) MMF_REQUIRE(offsets[p + 1] >= offsets[p], "mmf_ransac_batch_estimate: offsets must ascend");
+    const size_t total = (size_t)offsets[n_problems];
+    MMF_REQUIRE(total == 0 || (p0_dev && p1_dev), "mmf_ransac_batch_estimate: null points");
+    if (n_problems == 0) return MMF_OK;
+    MMF_HIP_TRY(hipSetDevice(b->ctx->device));
+    int rc = ransac_batch_reserve(b, (size_t)n_problems, total);
+    if (rc) return rc;
+    hipStream_t st = b->ctx->stream;
+    std::memcpy(b->off_pin, offsets, ((size_t)n_problems + 1) * sizeof(int));
+    MMF_HIP_TRY(hipMemcpyAsync(b->off_dev, b->off_pin, ((size_t)n_problems + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    const mmf::RansacDeviceConfig dc = b->device_config();
+    hipLaunchKernelGGL(mmf::ransac_batch_kernel, dim3((unsigned)n_problems), dim3(64), mmf::ransac_lds_bytes(dc.cap, false), st, p0_dev,
+                       p1_dev, (const int*)b->off_dev, dc, b->res_pin, b->inl_pin);
+    MMF_HIP_TRY(hipGetLastError());
+    b->last_launches = 1;
+    MMF_HIP_TRY(wait_stream(st));
+    std::memcpy(results, b->res_pin, (size_t)n_problems * sizeof(mmf_ransac_result));
+    if (inlier && total) std::memcpy(inlier, b->inl_pin, total);
     return MMF_OK;
 }
 

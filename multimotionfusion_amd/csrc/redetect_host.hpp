@@ -51,6 +51,28 @@ struct mmf_viewstore {
     size_t src0_cap = 0;
     float* co_pin = nullptr;
     size_t co_cap = 0;
+    // the device verifier (mmf_viewstore_set_verifier; nothing below is allocated, written or launched without one): the
+    // books again on the device, the match rows, the per-view estimates and the records the host reads
+    mmf_ransac_batch* verifier = nullptr;
+    float* coords_dev = nullptr;  // `coords`
+    size_t coords_cap = 0;        // points
+    mmf::RdViewDev* views_dev = nullptr;
+    size_t views_cap = 0;
+    int* rows_dev = nullptr;  // rd_cross_kernel's rows, laid out as out_row
+    size_t rows_cap = 0;
+    mmf::RdViewResult* per_view = nullptr;
+    size_t per_view_cap = 0;
+    unsigned char* per_view_inlier = nullptr;
+    size_t per_view_inlier_cap = 0;
+    unsigned char *arg_pin = nullptr, *arg_dev = nullptr;  // the sets and the asked models on their way to the device
+    size_t arg_cap = 0;
+    mmf::RdRecord* rec_pin = nullptr;  // host memory the device writes: [set][asked model]
+    size_t rec_cap = 0;
+    unsigned char* rec_inlier_pin = nullptr;
+    size_t rec_inlier_cap = 0;
+    float *qc_pin = nullptr, *qc_dev = nullptr;  // query coordinates handed in on the host (the fusion's keypoints)
+    size_t qc_cap = 0;
+    int rec_stride = 0, rec_asked = 0;  // layout of the last verification's records
 };
 
 extern "C" int mmf_viewstore_create(mmf_ctx* c, mmf_viewstore** out) {
@@ -76,6 +98,17 @@ extern "C" void mmf_viewstore_destroy(mmf_viewstore* vs) {
     if (vs->q_pin) (void)hipHostFree(vs->q_pin);
     (void)hipFree(vs->src0_dev);
     if (vs->co_pin) (void)hipHostFree(vs->co_pin);
+    (void)hipFree(vs->coords_dev);
+    (void)hipFree(vs->views_dev);
+    (void)hipFree(vs->rows_dev);
+    (void)hipFree(vs->per_view);
+    (void)hipFree(vs->per_view_inlier);
+    (void)hipFree(vs->arg_dev);
+    (void)hipFree(vs->qc_dev);
+    if (vs->arg_pin) (void)hipHostFree(vs->arg_pin);
+    if (vs->rec_pin) (void)hipHostFree(vs->rec_pin);
+    if (vs->rec_inlier_pin) (void)hipHostFree(vs->rec_inlier_pin);
+    if (vs->qc_pin) (void)hipHostFree(vs->qc_pin);
     delete vs;
 }
 
@@ -107,6 +140,42 @@ static int viewstore_reserve(mmf_viewstore* vs, size_t rows) {
     return MMF_OK;
 }
 
+// With a verifier attached the store keeps its coordinates and its view table on the device as well: the points from
+// `first_point` on are uploaded (growth copies the earlier ones like the descriptors and retires the old buffer), the view
+// table -- small -- whole.  Waits for the stream: the sources are pageable.  Without a verifier: nothing.
+static int viewstore_device_books(mmf_viewstore* vs, size_t first_point) {
+    if (!vs->verifier) return MMF_OK;
+    hipStream_t st = vs->ctx->stream;
+    const size_t P = vs->coords.size() / 3, V = vs->views.size();
+    if (P > vs->coords_cap) {
+        size_t cap = vs->coords_cap ? vs->coords_cap * 2 : 4096;
+        while (cap < P) cap *= 2;
+        float* fresh = nullptr;
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&fresh), cap * 3 * sizeof(float)));
+        if (vs->coords_dev && first_point)
+            MMF_HIP_TRY(hipMemcpyAsync(fresh, vs->coords_dev, first_point * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (vs->coords_dev) vs->retired.push_back(vs->coords_dev);
+        vs->coords_dev = fresh, vs->coords_cap = cap;
+    }
+    if (P > first_point)
+        MMF_HIP_TRY(hipMemcpyAsync(vs->coords_dev + 3 * first_point, vs->coords.data() + 3 * first_point, (P - first_point) * 3 * sizeof(float),
+                                   hipMemcpyHostToDevice, st));
+    if (V > vs->views_cap) {
+        size_t cap = vs->views_cap ? vs->views_cap * 2 : 256;
+        while (cap < V) cap *= 2;
+        mmf::RdViewDev* fresh = nullptr;
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&fresh), cap * sizeof(mmf::RdViewDev)));
+        if (vs->views_dev) vs->retired.push_back(vs->views_dev);
+        vs->views_dev = fresh, vs->views_cap = cap;
+    }
+    std::vector<mmf::RdViewDev> table(V);
+    for (size_t v = 0; v < V; ++v)
+        table[v] = mmf::RdViewDev{vs->views[v].model, vs->views[v].index, vs->views[v].rows, (int)vs->views[v].row0, (int)vs->views[v].coord0};
+    if (V) MMF_HIP_TRY(hipMemcpyAsync(vs->views_dev, table.data(), V * sizeof(mmf::RdViewDev), hipMemcpyHostToDevice, st));
+    MMF_HIP_TRY(hipStreamSynchronize(st));
+    return MMF_OK;
+}
+
 // Model::store (Model.cpp:1617-1632): the views of one model.  counts[n_views] valid keypoints per view (0 allowed);
 // descriptor / coordinate = the views' rows one after the other.  *stored = 0: the model has stored views already and
 // this call changed nothing (:1618-1621).
@@ -129,7 +198,7 @@ extern "C" int mmf_viewstore_store(mmf_viewstore* vs, int model_id, int n_views,
         if (rc) return rc;
     }
     std::vector<float> block(padded * kRdDim, 0.f);  // the views' rows with their zero padding
-    const size_t first_tile = vs->tiles_host.size();
+    const size_t first_tile = vs->tiles_host.size(), first_point = vs->coords.size() / 3;
     size_t src = 0, dst = 0;
     for (int v = 0; v < n_views; ++v) {
         const size_t n = (size_t)counts[v];
@@ -152,6 +221,8 @@ extern "C" int mmf_viewstore_store(mmf_viewstore* vs, int model_id, int n_views,
         MMF_HIP_TRY(hipStreamSynchronize(st));  // `block` leaves scope
         vs->n_rows += padded;
     }
+    int rc = viewstore_device_books(vs, first_point);
+    if (rc) return rc;
     if (stored) *stored = 1;
     return MMF_OK;
 }
@@ -191,7 +262,7 @@ extern "C" int mmf_viewstore_store_device(mmf_viewstore* vs, int model_id, int n
             vs->co_cap = total * 6;
         }
     }
-    const size_t first_tile = vs->tiles_host.size(), first_view = vs->views.size();
+    const size_t first_tile = vs->tiles_host.size(), first_view = vs->views.size(), first_point = vs->coords.size() / 3;
     std::vector<int> src0;
     size_t src = 0, dst = 0;
     for (int v = 0; v < n_views; ++v) {
@@ -222,6 +293,8 @@ extern "C" int mmf_viewstore_store_device(mmf_viewstore* vs, int model_id, int n
         vs->coords.insert(vs->coords.end(), vs->co_pin, vs->co_pin + total * 3);
         vs->n_rows += padded;
     }
+    int rc = viewstore_device_books(vs, first_point);
+    if (rc) return rc;
     if (stored) *stored = 1;
     return MMF_OK;
 }
@@ -229,9 +302,25 @@ extern "C" int mmf_viewstore_store_device(mmf_viewstore* vs, int model_id, int n
 // a model that no longer exists: its views stay where they are (nothing moves) but belong to nobody
 extern "C" int mmf_viewstore_forget(mmf_viewstore* vs, int model_id) {
     MMF_REQUIRE(vs != nullptr, "mmf_viewstore_forget: null store");
+    bool changed = false;
     for (RdView& v : vs->views)
-        if (v.model == model_id) v.model = -1;
+        if (v.model == model_id) v.model = -1, changed = true;
+    if (changed && vs->verifier) {
+        MMF_HIP_TRY(hipSetDevice(vs->ctx->device));
+        return viewstore_device_books(vs, vs->coords.size() / 3);
+    }
     return MMF_OK;
+}
+
+// attaches the device verifier (NULL detaches it): views stored before the call are uploaded here.  The batch object belongs
+// to the caller and outlives its attachment.
+extern "C" int mmf_viewstore_set_verifier(mmf_viewstore* vs, mmf_ransac_batch* b) {
+    MMF_REQUIRE(vs != nullptr, "mmf_viewstore_set_verifier: null store");
+    MMF_REQUIRE(!b || b->ctx == vs->ctx, "mmf_viewstore_set_verifier: the batch object belongs to another context");
+    vs->verifier = b;
+    if (!b) return MMF_OK;
+    MMF_HIP_TRY(hipSetDevice(vs->ctx->device));
+    return viewstore_device_books(vs, 0);
 }
 
 extern "C" int mmf_viewstore_num_views(mmf_viewstore* vs) { return vs ? (int)vs->views.size() : -1; }
@@ -266,6 +355,13 @@ static int viewstore_enqueue(mmf_viewstore* vs, hipStream_t st, const RdSet* set
         for (size_t e = 0; e < n_out; ++e) vs->out_row[e] = -1, vs->out_dist[e] = 0.f;
         return MMF_OK;
     }
+    if (vs->verifier && n_out > vs->rows_cap) {  // (every earlier verification has been awaited)
+        (void)hipFree(vs->rows_dev);
+        vs->rows_dev = nullptr, vs->rows_cap = 0;
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&vs->rows_dev), (n_out + n_out / 2) * sizeof(int)));
+        vs->rows_cap = n_out + n_out / 2;
+    }
+    int* rows_dev = vs->verifier ? vs->rows_dev : nullptr;
     const size_t need = 8 * (n_out + (size_t)n_sets * R) + 4 * total_q;
     if (need > vs->ws_bytes) {
         (void)hipFree(vs->ws);
@@ -291,7 +387,7 @@ static int viewstore_enqueue(mmf_viewstore* vs, hipStream_t st, const RdSet* set
                            (const float*)qn, (const float*)vs->tn, (const mmf::RdTile*)vs->tiles, nq, kRdDim, row_best, col_best);
         hipLaunchKernelGGL(mmf::rd_cross_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st,
                            (const unsigned long long*)row_best, (const unsigned long long*)col_best, nq, nk,
-                           vs->out_row + V * sets[s].q0, vs->out_dist + V * sets[s].q0);
+                           vs->out_row + V * sets[s].q0, vs->out_dist + V * sets[s].q0, rows_dev ? rows_dev + V * sets[s].q0 : (int*)nullptr);
         vs->last_launches += 3;
     }
     MMF_HIP_TRY(hipGetLastError());
@@ -392,6 +488,144 @@ extern "C" int mmf_viewstore_best_match(mmf_viewstore* vs, int model_id, const f
         for (int i = 0; i < best.n_matches && i < nq; ++i) inlier[i] = best.inlier[(size_t)i];
     if (found) *found = best.found ? 1 : 0;
     return MMF_OK;
+}
+
+// ---- the device verifier (ransac_kernels.hpp) -------------------------------------------------------------
+template <class T>
+static int viewstore_grow_dev(T** p, size_t* cap, size_t need) {  // (every earlier verification has been awaited)
+    if (need <= *cap) return MMF_OK;
+    (void)hipFree(*p);
+    *p = nullptr, *cap = 0;
+    MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), (need + need / 2) * sizeof(T)));
+    *cap = need + need / 2;
+    return MMF_OK;
+}
+template <class T>
+static int viewstore_grow_pin(T** p, size_t* cap, size_t need, unsigned flags) {
+    if (need <= *cap) return MMF_OK;
+    if (*p) (void)hipHostFree(*p);
+    *p = nullptr, *cap = 0;
+    MMF_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(p), (need + need / 2) * sizeof(T), flags));
+    *cap = need + need / 2;
+    return MMF_OK;
+}
+
+// Behind viewstore_enqueue of the same sets (same order, same q0) on `st`: the verify launch, grid = views x sets, and the
+// launch that picks per (set, asked model).  sets[s].coordinate = DEVICE; every nq <= the verifier's max_points (a larger
+// set's blocks return at once and its records say "not found").  Records: rec_pin[s * n_asked + a], the winner's inlier
+// flags at rec_inlier_pin[(s * n_asked + a) * rec_stride].  Needs views with rows (viewstore_enqueue launched something).
+static int viewstore_enqueue_verify(mmf_viewstore* vs, hipStream_t st, const mmf::RdVerifySet* sets, int n_sets, const int* asked, int n_asked) {
+    const size_t V = vs->views.size();
+    int stride = 1;
+    for (int s = 0; s < n_sets; ++s) stride = std::max(stride, sets[s].nq);
+    const size_t pairs = (size_t)n_sets * V, recs = (size_t)n_sets * (size_t)n_asked;
+    const size_t arg_bytes = (size_t)n_sets * sizeof(mmf::RdVerifySet) + (size_t)n_asked * sizeof(int);
+    int rc = viewstore_grow_dev(&vs->per_view, &vs->per_view_cap, pairs);
+    if (!rc) rc = viewstore_grow_dev(&vs->per_view_inlier, &vs->per_view_inlier_cap, pairs * (size_t)stride);
+    if (rc) return rc;
+    if (arg_bytes > vs->arg_cap) {
+        (void)hipFree(vs->arg_dev);
+        if (vs->arg_pin) (void)hipHostFree(vs->arg_pin);
+        vs->arg_dev = vs->arg_pin = nullptr, vs->arg_cap = 0;
+        MMF_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&vs->arg_pin), arg_bytes * 2, hipHostMallocDefault));
+        MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&vs->arg_dev), arg_bytes * 2));
+        vs->arg_cap = arg_bytes * 2;
+    }
+    if (!rc) rc = viewstore_grow_pin(&vs->rec_pin, &vs->rec_cap, recs, hipHostMallocMapped | hipHostMallocCoherent);
+    if (!rc) rc = viewstore_grow_pin(&vs->rec_inlier_pin, &vs->rec_inlier_cap, recs * (size_t)stride, hipHostMallocMapped | hipHostMallocCoherent);
+    if (rc) return rc;
+    std::memcpy(vs->arg_pin, sets, (size_t)n_sets * sizeof(mmf::RdVerifySet));
+    std::memcpy(vs->arg_pin + (size_t)n_sets * sizeof(mmf::RdVerifySet), asked, (size_t)n_asked * sizeof(int));
+    MMF_HIP_TRY(hipMemcpyAsync(vs->arg_dev, vs->arg_pin, arg_bytes, hipMemcpyHostToDevice, st));
+    const mmf::RdVerifySet* sets_dev = reinterpret_cast<const mmf::RdVerifySet*>(vs->arg_dev);
+    const int* asked_dev = reinterpret_cast<const int*>(vs->arg_dev + (size_t)n_sets * sizeof(mmf::RdVerifySet));
+    const mmf::RansacDeviceConfig dc = vs->verifier->device_config();
+    hipLaunchKernelGGL(mmf::rd_verify_kernel, dim3((unsigned)V, (unsigned)n_sets), dim3(64), mmf::ransac_lds_bytes(dc.cap, true), st,
+                       (const mmf::RdViewDev*)vs->views_dev, (int)V, sets_dev, asked_dev, n_asked, (const int*)vs->rows_dev,
+                       (const float*)vs->coords_dev, dc, vs->per_view, vs->per_view_inlier, stride);
+    hipLaunchKernelGGL(mmf::rd_pick_kernel, dim3((unsigned)n_asked, (unsigned)n_sets), dim3(64), 0, st, (const mmf::RdViewDev*)vs->views_dev,
+                       (int)V, asked_dev, n_asked, (const mmf::RdViewResult*)vs->per_view, (const unsigned char*)vs->per_view_inlier, stride,
+                       vs->rec_pin, vs->rec_inlier_pin);
+    MMF_HIP_TRY(hipGetLastError());
+    vs->last_launches += 2;
+    vs->rec_stride = stride, vs->rec_asked = n_asked;
+    return MMF_OK;
+}
+
+// mmf_viewstore_best_match with the geometric verification on the device, under the per-view rule (a fresh RigidRANSAC per
+// view): query = DEVICE [nq][256], coordinate = DEVICE [nq][3], nq <= the verifier's max_points.  The three
+// match launches and two more whatever the store holds, one record through pinned memory, one wait.
+extern "C" int mmf_viewstore_best_match_device(mmf_viewstore* vs, int model_id, const float* query, const float* coordinate, int nq,
+                                               float T[16], float* error, int* inliers, int* view, int* n_matches,
+                                               unsigned char* inlier, int* found) {
+    MMF_REQUIRE(vs && T && error && nq >= 0 && ((query && coordinate) || nq == 0), "mmf_viewstore_best_match_device: bad argument");
+    MMF_REQUIRE(((uintptr_t)query & 15u) == 0, "mmf_viewstore_best_match_device: 16-byte aligned rows");
+    if (!vs->verifier) return fail(MMF_ERR_STATE, "mmf_viewstore_best_match_device: no verifier attached (mmf_viewstore_set_verifier)");
+    MMF_REQUIRE(nq <= vs->verifier->max_points, "mmf_viewstore_best_match_device: more query rows than the verifier's max_points");
+    MMF_HIP_TRY(hipSetDevice(vs->ctx->device));
+    mmf::RdRecord rec;
+    std::memset(&rec, 0, sizeof(rec));
+    for (int k = 0; k < 16; k += 5) rec.T[k] = 1.f;
+    rec.error = std::numeric_limits<float>::infinity(), rec.view = -1;
+    vs->last_launches = 0;
+    if (viewstore_has_model(vs, model_id) && model_id >= 0 && nq > 0) {
+        const RdSet set{query, nq, 0};
+        int rc = viewstore_enqueue(vs, vs->ctx->stream, &set, 1);
+        if (rc) return rc;
+        if (vs->last_launches) {  // (a store of empty views: nothing was launched, nothing can match)
+            const mmf::RdVerifySet vset{coordinate, nq, 0};
+            rc = viewstore_enqueue_verify(vs, vs->ctx->stream, &vset, 1, &model_id, 1);
+            if (rc) return rc;
+            MMF_HIP_TRY(wait_stream(vs->ctx->stream));
+            rec = vs->rec_pin[0];
+            if (inlier && rec.found)
+                for (int i = 0; i < rec.n_matches && i < nq; ++i) inlier[i] = vs->rec_inlier_pin[i];
+        }
+    }
+    std::memcpy(T, rec.T, sizeof(rec.T));
+    *error = rec.error;
+    if (inliers) *inliers = rec.inliers;
+    if (view) *view = rec.view;
+    if (n_matches) *n_matches = rec.n_matches;
+    if (found) *found = rec.found;
+    return MMF_OK;
+}
+
+// Model::getBestMatch of `model` on the HOST under the per-view rule: what the device verifier computes, for a set that
+// does not fit it (more rows than max_points).  From the results of a set that has been matched and awaited.
+static RdBest viewstore_best_fresh(const mmf_viewstore* vs, int model, const RdSet& set, const float* coordinate,
+                                   const mmf::RigidRANSAC::Config& cfg) {
+    RdBest best;
+    const size_t V = vs->views.size();
+    std::vector<float> query, train;
+    std::vector<unsigned short> triples(3 * (size_t)cfg.iterations);
+    for (size_t v = 0; v < V; ++v) {
+        const RdView& view = vs->views[v];
+        if (view.model != model || view.rows == 0) continue;
+        const int* rows = vs->out_row + V * set.q0 + v * (size_t)set.nq;
+        query.clear(), train.clear();
+        for (int i = 0; i < set.nq; ++i) {
+            if (rows[i] < 0) continue;
+            const float* p = vs->coords.data() + 3 * (view.coord0 + (size_t)rows[i] - view.row0);
+            query.insert(query.end(), coordinate + 3 * i, coordinate + 3 * i + 3);
+            train.insert(train.end(), p, p + 3);
+        }
+        const int n = (int)(query.size() / 3);
+        if (n < 3 || n > 65535) continue;
+        mmf::ransac_triples(cfg.iterations, n, triples.data());
+        mmf::Isometry3f T;
+        float error;
+        std::vector<unsigned char> inl((size_t)n);
+        const int count = mmf::ransac_core_host(cfg, triples.data(), query.data(), train.data(), n, &T, &error, inl.data());
+        if (count == 0) continue;
+        if (!best.found || error < best.error) {
+            best.found = true;
+            best.transformation = T, best.error = error, best.inliers = count;
+            best.view = view.index, best.n_matches = n;
+            best.inlier.swap(inl);
+        }
+    }
+    return best;
 }
 
 // pinned + device staging for `rows` query rows handed in on the host (every earlier match has been awaited)

@@ -108,10 +108,12 @@ __global__ __launch_bounds__(64) void rd_tile_kernel(const float* __restrict__ q
     }
 }
 
-// crossCheck for every (view, query row): train_row[v * nq + i] = STORE row of the match or -1, distance = sqrt(max(d2, 0))
+// crossCheck for every (view, query row): train_row[v * nq + i] = STORE row of the match or -1, distance = sqrt(max(d2, 0));
+// train_row_dev (null unless a verifier is attached to the store): the rows again, in device memory, for rd_verify_kernel
 __global__ __launch_bounds__(256) void rd_cross_kernel(const unsigned long long* __restrict__ row_best,
                                                        const unsigned long long* __restrict__ col_best, int nq, size_t n,
-                                                       int* __restrict__ train_row, float* __restrict__ distance) {
+                                                       int* __restrict__ train_row, float* __restrict__ distance,
+                                                       int* __restrict__ train_row_dev) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= n) return;
     const int i = (int)(e % (size_t)nq);
@@ -128,6 +130,7 @@ __global__ __launch_bounds__(256) void rd_cross_kernel(const unsigned long long*
     }
     train_row[e] = j;
     distance[e] = d;
+    if (train_row_dev) train_row_dev[e] = j;
 }
 
 // label of every keypoint = the id image at its pixel (MultiMotionFusion.cpp:428-434); -1: outside the image (:432)

@@ -326,6 +326,15 @@ class MultiMotionFusion:
         keypoints (setKeypoints) of a segment of the frame"""
         check(self.ctx.lib.mmf_fusion_set_redetection(self.handle, 1 if on else 0))
 
+    def setRedetectionVerifier(self, mode):
+        """where the redetection candidates are verified: 0 = host (the default), 1 = device (a fresh RigidRANSAC per view,
+        all segments and inactive models of a frame in two launches)"""
+        check(self.ctx.lib.mmf_fusion_set_redetection_verifier(self.handle, int(mode)))
+
+    def redetectionHostVerified(self):
+        """segments with more keypoints than the device verifier takes, verified on the host under its rule, so far"""
+        return self.ctx.lib.mmf_fusion_redetection_host_verified(self.handle)
+
     def setKeypoints(self, xy, coordinate, descriptor):
         """the last keypoint of every currently visible track, for the NEXT processFrame only: xy [n,2] integer pixels,
         coordinate [n,3] camera frame (non-finite allowed), descriptor [n,256]"""

@@ -94,6 +94,28 @@ class ViewStore:
         return dict(found=bool(found.value), transformation=T, error=err.value, inliers=inl.value, view=view.value,
                     n_matches=nm.value, inlier=mask[:nm.value].astype(bool))
 
+    def setVerifier(self, batch):
+        """attaches a ransac.RansacBatch (None detaches it): the store then keeps its coordinates on the device as well and
+        bestMatchDevice verifies there.  The batch object must outlive its attachment."""
+        self._verifier = batch
+        check(self.ctx.lib.mmf_viewstore_set_verifier(self.handle, batch.handle if batch is not None else None))
+
+    def bestMatchDevice(self, model_id, query: torch.Tensor, coordinate: torch.Tensor):
+        """bestMatch with the geometric verification on the device, one fresh RigidRANSAC per view: query [nq,256] and
+        coordinate [nq,3] float32 CUDA tensors -> the dict of bestMatch"""
+        assert query.dtype == torch.float32 and query.is_cuda and coordinate.dtype == torch.float32 and coordinate.is_cuda
+        query, coordinate = query.contiguous(), coordinate.contiguous()
+        nq = query.shape[0]
+        assert coordinate.numel() == 3 * nq
+        T = np.zeros((4, 4), np.float32)
+        err, inl, view, nm, found = C.c_float(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        mask = np.zeros(max(nq, 1), np.uint8)
+        check(self.ctx.lib.mmf_viewstore_best_match_device(self.handle, int(model_id), _p(query) if nq else None,
+                                                           _p(coordinate) if nq else None, nq, T.ctypes.data, C.byref(err), C.byref(inl),
+                                                           C.byref(view), C.byref(nm), mask.ctypes.data, C.byref(found)))
+        return dict(found=bool(found.value), transformation=T, error=err.value, inliers=inl.value, view=view.value,
+                    n_matches=nm.value, inlier=mask[:nm.value].astype(bool))
+
     def close(self):
         if self._own and self.handle and self.ctx.handle:
             self.ctx.lib.mmf_viewstore_destroy(self.handle)
