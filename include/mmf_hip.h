@@ -666,6 +666,27 @@ int mmf_superpoint_download(mmf_superpoint *sp, int which, float *host, size_t c
 int mmf_superpoint_get_features(mmf_superpoint *sp, const uint8_t *image, int width, int height, int channels,
                                 float conf_thresh, int nms_dist, int border, int *xy, float *conf, float *desc,
                                 int *count);
+/* The same WITHOUT the host: enqueues on the context's stream and returns -- no wait, nothing read back, no
+ * host memory a second call could overwrite, and a number of launches (mmf_superpoint_last_launches) that depends on
+ * (width, height) alone.  The suppression compacts the candidates, runs a fixed few passes over that list and lets ONE
+ * workgroup walk what is left to the fixed point under a trip cap of listed + 1; the kept set is ranked by counting on the key
+ * (~bits(conf), row-major index) and the strongest max_keypoints go to slot `rank`; max_keypoints workgroups sample the
+ * descriptors, workgroup k leaving when k >= count.  Results equal mmf_superpoint_get_features' bit for bit.  (A heat map
+ * of ties across the whole image leaves nearly everything to that one workgroup: 2.2 s at 640x480 where the host-facing call
+ * needs 28 ms)
+ *   mmf_superpoint_device_features   where they are: DEVICE pointers owned by sp, rewritten by its next call.  *count one int,
+ *                       *xy [max_keypoints][2], *conf [max_keypoints], *desc [max_keypoints][256] (rows 16-byte aligned);
+ *                       rows at or beyond *count are unspecified.
+ *   mmf_superpoint_device_status     the suppression's status word, one DEVICE int owned by sp: 0 = converged, 1 = the cap
+ *                       was hit -- then *count is 0 and no keypoint is handed on (mmf_tracker_set_keypoint_status takes it).
+ *   mmf_superpoint_last_features     waits; the same into HOST arrays (any of xy / conf / desc may be NULL); tests, tools */
+int mmf_superpoint_get_features_device(mmf_superpoint *sp, const uint8_t *image, int width, int height, int channels,
+                                       float conf_thresh, int nms_dist, int border);
+int mmf_superpoint_device_features(mmf_superpoint *sp, const int **count, const int **xy, const float **conf,
+                                   const float **desc, int *max_keypoints);
+int mmf_superpoint_device_status(mmf_superpoint *sp, const int **status);
+int mmf_superpoint_last_features(mmf_superpoint *sp, int *count, int *status, int *xy, float *conf, float *desc);
+int mmf_superpoint_last_launches(mmf_superpoint *sp);
 /* one convolution layer (tests / tools): in [H][W][cin], out [H][W][cout] (or [H/2][W/2][cout] with pool) on
  * the device, channels-last; w [cout][cin][k][k], bias [cout] on the HOST; taps = 9 (3x3, zero pad 1) or 1;
  * cin a multiple of 32; nt = output-channel tiles of 32 per workgroup (1, 2, 4; 0 = automatic). Synchronous. */
@@ -1030,6 +1051,37 @@ int mmf_tracker_model_views(mmf_tracker *t, int model_id, int n_views, const int
 int mmf_fusion_set_tracker(mmf_fusion *f, mmf_tracker *tracker, int odom_init_kp, int icp_refine);
 int mmf_fusion_last_track_transforms(mmf_fusion *f, float *T, int capacity, int *n_out);
 int mmf_fusion_last_stored_views(mmf_fusion *f, int *model_ids, int *n_views, int *rows, int capacity, int *n_out);
+/* The add with the number of keypoints on the DEVICE: semantics and launches (7, 9 with the view log) of
+ * mmf_tracker_add_keypoints, but the kernels read n from *n_dev, clamped to [0, max_keypoints]; nothing waits.  Grids and the
+ * search's layouts are those of max_keypoints keypoints; rows k >= n of xy / descriptor (stale data of earlier frames)
+ * enter no minimum, start no track and are not scattered: the table afterwards equals the host-n call's bit for bit.  The
+ * host's bound of the track count grows by max_keypoints per such add (tightened by every call that waits); the padding
+ * rows are fillers nothing matches.
+ *   mmf_tracker_set_keypoint_status  a DEVICE int the device-count adds read from now on (NULL: none): while it is not 0 --
+ *                       the keypoint source did not converge -- an add is a frame WITHOUT keypoints and counts as failed
+ *   mmf_tracker_keypoint_failures    waits; such adds since creation / reset */
+int mmf_tracker_add_keypoints_device(mmf_tracker *t, const int *n_dev, const int *xy, const float *descriptor,
+                                     const float *depth, long long timestamp, float min_feature_distance, int history);
+int mmf_tracker_set_keypoint_status(mmf_tracker *t, const int *status_dev);
+int mmf_tracker_keypoint_failures(mmf_tracker *t, int *failures);
+/* The keypoint front end INSIDE processFrame (MultiMotionFusion.cpp:223-248; off by default, sp = NULL switches it off, and
+ * so does every mmf_fusion_set_tracker).  Needs an attached tracker (MMF_ERR_STATE otherwise, and with world > 1), a network
+ * of the fusion's context that serves the frame size and returns no more keypoints than the tracker takes (MMF_ERR_INVALID).
+ * With it on every mmf_fusion_process_frame* call first runs, on the frame's own device rgb (u8 x 3) and raw depth,
+ * mmf_superpoint_get_features_device, the device-count add with the frame's timestamp (the network's status word attached)
+ * and mmf_tracker_prune(prune_min_kps, max(timestamp - prune_window_ns, 0)): all enqueued, none awaited -- the frame's
+ * first wait stays the pairs call of `-init kp`.  A frame for which the caller added keypoints itself: MMF_ERR_INVALID.
+ * Off: nothing is enqueued, allocated or waited for.  Pyramid level 0 only, as the tracker. */
+typedef struct {
+    float conf_thresh;
+    int nms_dist, border;
+    float min_feature_distance;
+    int history;
+    int prune_min_kps;
+    long long prune_window_ns;
+} mmf_keypoint_frontend_config; /* defaults 0.015, 4, 4, 0.7, 30, 30, 1e9 */
+int mmf_keypoint_frontend_default_config(mmf_keypoint_frontend_config *cfg);
+int mmf_fusion_set_keypoint_frontend(mmf_fusion *f, mmf_superpoint *sp, const mmf_keypoint_frontend_config *cfg);
 
 /* ---- RigidRANSAC for batches of independent problems on the device (csrc/ransac_kernels.hpp) ----
  * The contract, per problem and bit for bit: mmf_ransac_create(cfg); mmf_ransac_estimate(p0, p1, n, NULL, ...);

@@ -106,6 +106,11 @@ class mmf_ransac_config(C.Structure):
     _fields_ = [("iterations", C.c_int), ("inlier_threshold", C.c_float), ("inlier_fraction", C.c_float)]
 
 
+class mmf_keypoint_frontend_config(C.Structure):
+    _fields_ = [("conf_thresh", C.c_float), ("nms_dist", C.c_int), ("border", C.c_int), ("min_feature_distance", C.c_float),
+                ("history", C.c_int), ("prune_min_kps", C.c_int), ("prune_window_ns", C.c_longlong)]
+
+
 class mmf_ransac_result(C.Structure):
     _fields_ = [("T", C.c_float * 16), ("error", C.c_float), ("n_inliers", C.c_int), ("has_inlier", C.c_int),
                 ("status", C.c_int)]
@@ -177,6 +182,11 @@ SIGNATURES = {
     "mmf_superpoint_forward": (_i, [_vp, _vp, _i, _i, _i]),
     "mmf_superpoint_download": (_i, [_vp, _i, _vp, _sz]),
     "mmf_superpoint_get_features": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _ip]),
+    "mmf_superpoint_get_features_device": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _i]),
+    "mmf_superpoint_device_features": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _ip]),
+    "mmf_superpoint_device_status": (_i, [_vp, C.POINTER(_vp)]),
+    "mmf_superpoint_last_features": (_i, [_vp, _ip, _ip, _vp, _vp, _vp]),
+    "mmf_superpoint_last_launches": (_i, [_vp]),
     "mmf_superpoint_conv": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mmf_slic_downsample": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp]),
     "mmf_slic_downsample_rgb": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
@@ -327,6 +337,11 @@ SIGNATURES = {
     "mmf_tracker_frame": (_i, [_vp]),
     "mmf_tracker_model_views": (_i, [_vp, _i, _i, _vp, _vp, C.POINTER(_ip), C.POINTER(_fp), C.POINTER(_fp), _ip]),
     "mmf_fusion_set_tracker": (_i, [_vp, _vp, _i, _i]),
+    "mmf_tracker_add_keypoints_device": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_longlong, _f, _i]),
+    "mmf_tracker_set_keypoint_status": (_i, [_vp, _vp]),
+    "mmf_tracker_keypoint_failures": (_i, [_vp, _ip]),
+    "mmf_keypoint_frontend_default_config": (_i, [C.POINTER(mmf_keypoint_frontend_config)]),
+    "mmf_fusion_set_keypoint_frontend": (_i, [_vp, _vp, C.POINTER(mmf_keypoint_frontend_config)]),
     "mmf_fusion_last_stored_views": (_i, [_vp, _vp, _vp, _vp, _i, _ip]),
     "mmf_fusion_last_track_transforms": (_i, [_vp, _vp, _i, _ip]),
     "mmf_ransac_batch_create": (_i, [_vp, C.POINTER(mmf_ransac_config), _i, C.POINTER(_vp)]),

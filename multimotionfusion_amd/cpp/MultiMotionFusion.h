@@ -509,7 +509,7 @@ class MultiMotionFusion {
                       void* /*GroundTruthOdometryInterface*/ = nullptr, const bool bootstrap = false) {
         const FrameData next = next_;  // announced by announceNextFrame (one call only)
         next_ = FrameData();
-        if (kp_predictor_ && frame.rgb && frame.depth && frame.timestamp >= 0 && !addFrameKeypoints(frame)) return false;
+        if (kp_predictor_ && !kp_on_device_ && frame.rgb && frame.depth && frame.timestamp >= 0 && !addFrameKeypoints(frame)) return false;
         return finish(mmf_fusion_process_frame_host_next(f_, frame.rgb, frame.depth, frame.mask, frame.hasNewLabel, frame.timestamp, inPose,
                                                          weightMultiplier, bootstrap, next.rgb, next.depth),
                       "mmf_fusion_process_frame_host");
@@ -691,6 +691,10 @@ class MultiMotionFusion {
         pushTracker();
     }
     tracker::PointTracker* getTracker() { return tracker_.get(); }
+    // not in the reference: with it on, features, add and prune run INSIDE the library call on the frame it uploads (once),
+    // enqueued and not awaited (mmf_fusion_set_keypoint_frontend); addFrameKeypoints -- its wait, its second upload and
+    // the conversions to double and back -- is skipped.  The predictor must return no more keypoints than max_keypoints.
+    void setKeypointFrontEndOnDevice(bool v) { kp_on_device_ = v, pushTracker(); }
     // the transformations the last frame's models were initialised with, list order (row-major 4x4 each)
     std::vector<float> getLastTrackTransforms() {
         int n = 0;
@@ -745,6 +749,12 @@ class MultiMotionFusion {
         mmf::check(mmf_fusion_set_tracker(f_, kp_predictor_ && tracker_ ? tracker_->handle() : nullptr, odom_cfg_.init == "kp" ? 1 : 0,
                                           odom_cfg_.icp_refine ? 1 : 0),
                    "mmf_fusion_set_tracker");
+        other_["keypointFrontEndOnDevice"] = kp_on_device_;
+        if (kp_on_device_ && kp_predictor_ && tracker_) {  // (set_tracker switched it off)
+            mmf_keypoint_frontend_config k;
+            mmf::check(mmf_keypoint_frontend_default_config(&k), "mmf_keypoint_frontend_default_config");
+            mmf::check(mmf_fusion_set_keypoint_frontend(f_, kp_predictor_->handle(), &k), "mmf_fusion_set_keypoint_frontend");
+        }
     }
     // MultiMotionFusion.cpp:223-248 at level 0: the frame's features into the tracker (device copies of rgb and depth of its own)
     bool addFrameKeypoints(const FrameData& frame) {
@@ -780,6 +790,7 @@ class MultiMotionFusion {
     mmf_ctx* ctx_ = nullptr;
     float fx_ = 0, fy_ = 0, cx_ = 0, cy_ = 0;
     SuperPoint* kp_predictor_ = nullptr;
+    bool kp_on_device_ = false;
     std::unique_ptr<tracker::PointTracker> tracker_;
     unsigned char* kp_rgb_ = nullptr;
     float* kp_depth_ = nullptr;

@@ -58,6 +58,15 @@ class PointTracker {
                    "mmf_tracker_add_keypoints");
     }
 
+    // the same with everything on the DEVICE, the number of keypoints included (SuperPoint::deviceFeatures): nothing waits;
+    // rows from *n_dev on are not read
+    void addKeypointsDevice(const int* n_dev, const int* xy_dev, const float* descriptor_dev, int64_t timestamp, const float* depth_dev,
+                            float min_feature_distance = 0.7f, int history = 30) {
+        mmf::check(mmf_tracker_add_keypoints_device(t_, n_dev, xy_dev, descriptor_dev, depth_dev, (long long)timestamp,
+                                                    min_feature_distance, history),
+                   "mmf_tracker_add_keypoints_device");
+    }
+
     // prune(min_kps, min_time) (:170-203)
     void prune(size_t min_kps, uint64_t min_time) {
         mmf::check(mmf_tracker_prune(t_, (int)min_kps, (long long)min_time), "mmf_tracker_prune");

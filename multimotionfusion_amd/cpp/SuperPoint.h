@@ -44,6 +44,26 @@ class SuperPoint {
         return std::make_tuple(std::move(coordinates), std::move(descriptors));
     }
 
+    // getFeatures without the host: enqueued on the context's stream, nothing awaited or read back.  The keypoints stay on
+    // the device (deviceFeatures: pointers owned by this object, rows from *count on unspecified)
+    void getFeaturesDevice(const unsigned char* image_dev, int width, int height, int channels, float conf_thresh = 0.015f,
+                           int nms_dist = 4, int border = 4) {
+        mmf::check(mmf_superpoint_get_features_device(sp_, image_dev, width, height, channels, conf_thresh, nms_dist, border),
+                   "mmf_superpoint_get_features_device");
+    }
+    struct DeviceFeatures {
+        const int *count, *status, *xy;  // status: 0 = the suppression converged, 1 = it did not (then *count is 0)
+        const float *conf, *desc;
+    };
+    DeviceFeatures deviceFeatures() {
+        DeviceFeatures d{};
+        mmf::check(mmf_superpoint_device_features(sp_, &d.count, &d.xy, &d.conf, &d.desc, nullptr), "mmf_superpoint_device_features");
+        mmf::check(mmf_superpoint_device_status(sp_, &d.status), "mmf_superpoint_device_status");
+        return d;
+    }
+    int maxKeypoints() const { return max_kp_; }
+    mmf_superpoint* handle() const { return sp_; }
+
    private:
     mmf_superpoint* sp_ = nullptr;
     int max_kp_ = 0;

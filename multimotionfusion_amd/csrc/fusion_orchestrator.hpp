@@ -120,6 +120,10 @@ struct mmf_fusion {
     bool trk_init_kp = false, trk_icp_refine = true;
     std::vector<int> trk_ids;      // the active models' ids at the last association
     std::vector<float> trk_T;      // the transformations the last frame's models were initialised with, list order
+    // the keypoint front end inside processFrame (mmf_fusion_set_keypoint_frontend): not owned, off unless set
+    mmf_superpoint* kpfe_sp = nullptr;
+    mmf_keypoint_frontend_config kpfe_cfg{};
+    long long kpfe_caller_adds = 0;  // the tracker's caller_adds when the front end last looked
     // the models' keypoint views on deactivation (Model::store, Model.cpp:1617-1644): active only with redetection on and an
     // attached tracker that keeps a view log.  Per object model the list of (tracker stamp, pose after that frame's tracking)
     // -- Model::poses, host memory, trimmed to the log's length -- and what the last frame stored
@@ -1554,11 +1558,61 @@ extern "C" int mmf_fusion_set_tracker(mmf_fusion* f, mmf_tracker* tracker, int o
     MMF_REQUIRE(!tracker || (tracker->ctx == f->ctx && tracker->width == f->width && tracker->height == f->height),
                 "mmf_fusion_set_tracker: the tracker must share the fusion's context and image size");
     f->tracker = tracker;
+    f->kpfe_sp = nullptr;  // (the in-frame front end belongs to the tracker that leaves)
     f->trk_init_kp = tracker && odom_init_kp != 0, f->trk_icp_refine = icp_refine != 0;
     f->trk_ids.clear(), f->trk_T.clear();
     f->view_poses.clear();  // (the entries carry the stamps of the tracker that leaves)
     return MMF_OK;
 }
+
+// ---- the keypoint front end inside processFrame (MultiMotionFusion.cpp:223-248) -------------------------------------------
+extern "C" int mmf_keypoint_frontend_default_config(mmf_keypoint_frontend_config* cfg) {
+    MMF_REQUIRE(cfg != nullptr, "mmf_keypoint_frontend_default_config: null argument");
+    cfg->conf_thresh = 0.015f, cfg->nms_dist = 4, cfg->border = 4;
+    cfg->min_feature_distance = 0.7f, cfg->history = 30;  // addKeypoints(..., 0.7f, 30), :240
+    cfg->prune_min_kps = 30, cfg->prune_window_ns = 1000000000ll;  // prune(30, t - 1 s), :246
+    return MMF_OK;
+}
+
+extern "C" int mmf_fusion_set_keypoint_frontend(mmf_fusion* f, mmf_superpoint* sp, const mmf_keypoint_frontend_config* cfg) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_set_keypoint_frontend: null fusion object");
+    if (!sp) {
+        f->kpfe_sp = nullptr;
+        return MMF_OK;
+    }
+    MMF_REQUIRE(cfg != nullptr, "mmf_fusion_set_keypoint_frontend: null configuration");
+    if (f->shard_world > 1) return fail(MMF_ERR_STATE, "mmf_fusion_set_keypoint_frontend: sharded use is not supported (world > 1)");
+    if (!f->tracker) return fail(MMF_ERR_STATE, "mmf_fusion_set_keypoint_frontend: no tracker is attached (mmf_fusion_set_tracker)");
+    MMF_REQUIRE(sp->ctx == f->ctx, "mmf_fusion_set_keypoint_frontend: the network must share the fusion's context");
+    MMF_REQUIRE(f->width <= sp->max_w && f->height <= sp->max_h && f->width % 8 == 0 && f->height % 8 == 0,
+                "mmf_fusion_set_keypoint_frontend: the frame is larger than the network was created for (or its sides are no multiples of 8)");
+    MMF_REQUIRE(sp->max_kp <= f->tracker->max_keypoints, "mmf_fusion_set_keypoint_frontend: the network returns more keypoints than the tracker takes");
+    MMF_REQUIRE(cfg->nms_dist >= 0 && cfg->border >= 0 && cfg->history >= 0, "mmf_fusion_set_keypoint_frontend: negative radius or history");
+    f->kpfe_sp = sp, f->kpfe_cfg = *cfg;
+    f->kpfe_caller_adds = f->tracker->caller_adds;
+    return MMF_OK;
+}
+
+// the frame's keypoints, first thing in the call: features, add, prune on the frame's own device buffers -- all of it
+// enqueued, none of it awaited (the frame's first wait stays the pairs call of frame_track_transforms)
+static int frame_keypoints(mmf_fusion* f, const mmf_frame* fr) {
+    mmf_tracker* t = f->tracker;
+    if (!t) return fail(MMF_ERR_STATE, "mmf_fusion_process_frame: the keypoint front end is on but no tracker is attached");
+    if (t->caller_adds != f->kpfe_caller_adds) {
+        f->kpfe_caller_adds = t->caller_adds;
+        return fail(MMF_ERR_INVALID, "mmf_fusion_process_frame: the keypoint front end is on (mmf_fusion_set_keypoint_frontend): "
+                                     "the caller must not add keypoints to the tracker itself");
+    }
+    const mmf_keypoint_frontend_config& k = f->kpfe_cfg;
+    mmf_superpoint* sp = f->kpfe_sp;
+    int rc = mmf_superpoint_get_features_device(sp, fr->rgb, f->width, f->height, 3, k.conf_thresh, k.nms_dist, k.border);
+    if (rc) return rc;
+    rc = tracker_add_counted(t, reinterpret_cast<const int*>(&sp->counters[4]), reinterpret_cast<const int*>(&sp->counters[5]),
+                             sp->sel_xy, sp->kp_desc, fr->depth, fr->timestamp, k.min_feature_distance, k.history);
+    if (rc) return rc;
+    return mmf_tracker_prune(t, k.prune_min_kps, std::max(fr->timestamp - k.prune_window_ns, 0ll));
+}
+
 // what the last frame stored on deactivation: per model its id, the number of views and their rows in all
 extern "C" int mmf_fusion_last_stored_views(mmf_fusion* f, int* model_ids, int* n_views, int* rows, int capacity, int* n_out) {
     MMF_REQUIRE(f && n_out && capacity >= 0, "mmf_fusion_last_stored_views: bad argument");
@@ -2183,6 +2237,10 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
     r.host_trace = tunables().host_trace;
     r.have_init = fr->init_transforms != nullptr && fr->n_init_transforms > 0;
     r.track = f->tick > 1 && (fr->bootstrap || !fr->in_pose);
+    if (f->kpfe_sp && !(f->tracker && r.have_init)) {  // (a frame the check below refuses adds nothing)
+        int rc = frame_keypoints(f, fr);
+        if (rc) return rc;
+    }
     mmf_frame fr_kp;  // the frame with the transformations of the attached tracker (odom_cfg.init == "kp")
     if (f->tracker) {
         MMF_REQUIRE(!r.have_init, "mmf_fusion_process_frame: a tracker is attached (mmf_fusion_set_tracker): the frame cannot bring init_transforms");

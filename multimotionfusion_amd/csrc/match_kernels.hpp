@@ -73,15 +73,15 @@ __device__ __forceinline__ f32x16 gram_tile(const float* __restrict__ ra, const 
 // is the same fmaf chain as the oracle's (a lane-per-row scalar loop took 30 us per set for 1024 rows).
 // One wave per 32 rows of the concatenation [query ; train]; out = [qn ; tn].
 // also resets the arg-min keys of its rows (row_best for query blocks, col_best for train blocks) to `empty`
-__global__ __launch_bounds__(64) void row_norms_kernel(const float* __restrict__ q, int nq, const float* __restrict__ t, int nt,
-                                                       int dim, float* __restrict__ qn, float* __restrict__ tn,
-                                                       unsigned long long* __restrict__ row_best,
-                                                       unsigned long long* __restrict__ col_best, unsigned long long empty) {
+__device__ __forceinline__ void row_norms_body(const float* __restrict__ q, int nq, int qblocks, const float* __restrict__ t, int nt,
+                                               int dim, float* __restrict__ qn, float* __restrict__ tn,
+                                               unsigned long long* __restrict__ row_best,
+                                               unsigned long long* __restrict__ col_best, unsigned long long empty) {
     const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
-    const int qblocks = (nq + 31) / 32;
     const bool is_q = (int)blockIdx.x < qblocks;
     const float* x = is_q ? q : t;
     const int n = is_q ? nq : nt, i0 = (is_q ? blockIdx.x : blockIdx.x - qblocks) * 32;
+    if (i0 >= n) return;  // (a block past its set; wave uniform)
     float* out = is_q ? qn : tn;
     if (h == 0 && i0 + r < n) (is_q ? row_best : col_best)[i0 + r] = empty;
     const float* row = x + (size_t)min(i0 + r, n - 1) * dim;
@@ -93,6 +93,29 @@ __global__ __launch_bounds__(64) void row_norms_kernel(const float* __restrict__
         const int lr = (v & 3) + 8 * (v >> 2) + 4 * h;
         if (lr == r && i0 + r < n) out[i0 + r] = acc[v];
     }
+}
+
+__global__ __launch_bounds__(64) void row_norms_kernel(const float* __restrict__ q, int nq, const float* __restrict__ t, int nt,
+                                                       int dim, float* __restrict__ qn, float* __restrict__ tn,
+                                                       unsigned long long* __restrict__ row_best,
+                                                       unsigned long long* __restrict__ col_best, unsigned long long empty) {
+    row_norms_body(q, nq, (nq + 31) / 32, t, nt, dim, qn, tn, row_best, col_best, empty);
+}
+
+// A query count that lives on the device (mmf_tracker_add_keypoints_device): *nq_dev clamped to [0, nq_max], forced to
+// 0 while *fail_dev (may be null) is set.  The kernels below are the ones above with that count: their grids and the
+// [query ; train] layouts are those of nq_max queries, the rows from the count on are never read.
+__device__ __forceinline__ int device_count(const int* __restrict__ n_dev, const int* __restrict__ fail_dev, int n_max) {
+    if (fail_dev && *fail_dev) return 0;
+    return min(max(*n_dev, 0), n_max);
+}
+
+__global__ __launch_bounds__(64) void row_norms_counted_kernel(const float* __restrict__ q, const int* __restrict__ nq_dev,
+                                                               const int* __restrict__ fail_dev, int nq_max,
+                                                               const float* __restrict__ t, int nt, int dim, float* __restrict__ qn,
+                                                               float* __restrict__ tn, unsigned long long* __restrict__ row_best,
+                                                               unsigned long long* __restrict__ col_best, unsigned long long empty) {
+    row_norms_body(q, device_count(nq_dev, fail_dev, nq_max), (nq_max + 31) / 32, t, nt, dim, qn, tn, row_best, col_best, empty);
 }
 
 // one wave (64 threads) per 32 x 32 tile; grid = (ceil(nt / 32), ceil(nq / 32)); dim % 8 == 0
@@ -140,11 +163,10 @@ __global__ __launch_bounds__(64) void match_tile_kernel(const float* __restrict_
 // ascending order: the accumulation is the same fmaf chain, the results stay bit-identical.  dim % 32 == 0.
 constexpr int kMatchSlab = 32, kMatchPitch = kMatchSlab + 1;  // +1 float: rows of a slab fall into different banks
 
-__global__ __launch_bounds__(256) void match_tile64_kernel(const float* __restrict__ q, const float* __restrict__ t,
-                                                           const float* __restrict__ qn, const float* __restrict__ tn,
-                                                           int nq, int nt, int dim,
-                                                           unsigned long long* __restrict__ row_best,
-                                                           unsigned long long* __restrict__ col_best) {
+__device__ __forceinline__ void match_tile64_body(const float* __restrict__ q, const float* __restrict__ t,
+                                                  const float* __restrict__ qn, const float* __restrict__ tn, int nq, int nt,
+                                                  int dim, unsigned long long* __restrict__ row_best,
+                                                  unsigned long long* __restrict__ col_best) {
     __shared__ float As[2][64][kMatchPitch], Bs[2][64][kMatchPitch];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
     const int wr = w >> 1, wc = w & 1;
@@ -211,11 +233,29 @@ __global__ __launch_bounds__(256) void match_tile64_kernel(const float* __restri
     }
 }
 
+__global__ __launch_bounds__(256) void match_tile64_kernel(const float* __restrict__ q, const float* __restrict__ t,
+                                                           const float* __restrict__ qn, const float* __restrict__ tn,
+                                                           int nq, int nt, int dim,
+                                                           unsigned long long* __restrict__ row_best,
+                                                           unsigned long long* __restrict__ col_best) {
+    match_tile64_body(q, t, qn, tn, nq, nt, dim, row_best, col_best);
+}
+
+__global__ __launch_bounds__(256) void match_tile64_counted_kernel(const float* __restrict__ q, const float* __restrict__ t,
+                                                                   const float* __restrict__ qn, const float* __restrict__ tn,
+                                                                   const int* __restrict__ nq_dev, const int* __restrict__ fail_dev,
+                                                                   int nq_max, int nt, int dim,
+                                                                   unsigned long long* __restrict__ row_best,
+                                                                   unsigned long long* __restrict__ col_best) {
+    const int nq = device_count(nq_dev, fail_dev, nq_max);
+    if ((int)blockIdx.y * 64 >= nq) return;  // workgroup uniform: no query row in this block
+    match_tile64_body(q, t, qn, tn, nq, nt, dim, row_best, col_best);
+}
+
 // crossCheck + distance gate (PointTracker.cpp:108)
-__global__ __launch_bounds__(256) void match_cross_check_kernel(unsigned long long* __restrict__ row_best,
-                                                                const unsigned long long* __restrict__ col_best, int nq,
-                                                                float max_distance, int* __restrict__ train_idx,
-                                                                float* __restrict__ distance) {
+__device__ __forceinline__ void match_cross_check_body(unsigned long long* __restrict__ row_best,
+                                                       const unsigned long long* __restrict__ col_best, int nq, float max_distance,
+                                                       int* __restrict__ train_idx, float* __restrict__ distance) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= nq) return;
     const unsigned long long key = row_best[i];
@@ -231,6 +271,23 @@ __global__ __launch_bounds__(256) void match_cross_check_kernel(unsigned long lo
     }
     train_idx[i] = j;
     distance[i] = j >= 0 ? d : 0.f;
+}
+
+
+__global__ __launch_bounds__(256) void match_cross_check_kernel(unsigned long long* __restrict__ row_best,
+                                                                const unsigned long long* __restrict__ col_best, int nq,
+                                                                float max_distance, int* __restrict__ train_idx,
+                                                                float* __restrict__ distance) {
+    match_cross_check_body(row_best, col_best, nq, max_distance, train_idx, distance);
+}
+
+__global__ __launch_bounds__(256) void match_cross_check_counted_kernel(unsigned long long* __restrict__ row_best,
+                                                                        const unsigned long long* __restrict__ col_best,
+                                                                        const int* __restrict__ nq_dev,
+                                                                        const int* __restrict__ fail_dev, int nq_max,
+                                                                        float max_distance, int* __restrict__ train_idx,
+                                                                        float* __restrict__ distance) {
+    match_cross_check_body(row_best, col_best, device_count(nq_dev, fail_dev, nq_max), max_distance, train_idx, distance);
 }
 
 }  // namespace mmf

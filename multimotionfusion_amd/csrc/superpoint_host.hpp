@@ -101,6 +101,11 @@ struct mmf_superpoint {
     unsigned* host_counters = nullptr;  // pinned
     int* kp_xy = nullptr;
     float *kp_conf = nullptr, *kp_desc = nullptr;
+    // mmf_superpoint_get_features_device: the chosen keypoints (their descriptors are kp_desc), counters[4] = their number,
+    // counters[5] = the suppression's status
+    int* sel_xy = nullptr;
+    float* sel_conf = nullptr;
+    int fwd_launches = 0, last_launches = 0;
     int cur_w = 0, cur_h = 0;
     void* slab = nullptr;
 };
@@ -186,6 +191,7 @@ extern "C" int mmf_superpoint_create(mmf_ctx* c, const float* const* weights, in
     const size_t o_flags = carve(npix * 4), o_prefix = carve(npix * 4);
     const size_t o_bsum = carve(((npix + mmf::kScanTile - 1) / mmf::kScanTile + 1) * 4), o_cnt = carve(64);
     const size_t o_xy = carve(npix * 8), o_conf = carve(npix * 4), o_kdesc = carve((size_t)max_keypoints * 256 * 4);
+    const size_t o_sxy = carve((size_t)max_keypoints * 8), o_sconf = carve((size_t)max_keypoints * 4);
     if (!rc) {
         hipError_t e = hipMalloc(&sp->slab, off);
         if (e != hipSuccess) rc = fail(MMF_ERR_HIP, std::string("mmf_superpoint_create: hipMalloc: ") + hipGetErrorString(e));
@@ -205,6 +211,14 @@ extern "C" int mmf_superpoint_create(mmf_ctx* c, const float* const* weights, in
     sp->flags = (unsigned*)(base + o_flags), sp->prefix = (unsigned*)(base + o_prefix);
     sp->block_sums = (unsigned*)(base + o_bsum), sp->counters = (unsigned*)(base + o_cnt);
     sp->kp_xy = (int*)(base + o_xy), sp->kp_conf = (float*)(base + o_conf), sp->kp_desc = (float*)(base + o_kdesc);
+    sp->sel_xy = (int*)(base + o_sxy), sp->sel_conf = (float*)(base + o_sconf);
+    {  // (no keypoints and a clean status before the first device-side call)
+        hipError_t e = hipMemsetAsync(sp->counters, 0, 64, c->stream);
+        if (e != hipSuccess) {
+            mmf_superpoint_destroy(sp);
+            return fail(MMF_ERR_HIP, std::string("mmf_superpoint_create: hipMemsetAsync: ") + hipGetErrorString(e));
+        }
+    }
     *out = sp;
     return MMF_OK;
 }
@@ -232,6 +246,7 @@ extern "C" int mmf_superpoint_forward(mmf_superpoint* sp, const uint8_t* image, 
     sp_launch_conv(s, sp->L[5], sp->act1, 128, sp->act0, 128, H / 8, W / 8);    // conv4a
     sp_launch_conv(s, sp->L[6], sp->act0, 128, sp->act1, 128, H / 8, W / 8);    // conv4b
     sp_launch_conv(s, sp->L[7], sp->act1, 128, sp->head, 512, H / 8, W / 8);    // convPa | convDa
+    sp->fwd_launches = 11 + ((sp->L[8].nt == 1 && sp->L[9].nt == 1) ? 1 : 2);  // conv1a, these eight, the heads, two below
     if (sp->L[8].nt == 1 && sp->L[9].nt == 1) {  // convPb + convDb: one launch
         sp_launch_head_pair(s, sp_conv_args(sp->L[8], sp->head, 512, sp->semi, 65, H / 8, W / 8),
                             sp_conv_args(sp->L[9], sp->head + 256, 512, sp->desc, 256, H / 8, W / 8));
@@ -323,6 +338,94 @@ extern "C" int mmf_superpoint_get_features(mmf_superpoint* sp, const uint8_t* im
     *count = n;
     return MMF_OK;
 }
+
+// ---- the same without the host: mmf_superpoint_get_features_device -------------------------------------------------
+// Enqueues on the context's stream and returns: no wait, nothing read back, no host memory a second call could overwrite.
+// The launches depend on (width, height) alone: the forward pass, the initialisation, the compaction of the candidates
+// (5), kSpFixedPasses passes over that list, the finisher workgroup, the compaction of the kept set (5), the ranking and
+// the sampling over max_keypoints workgroups.  The candidate list lives in kp_xy, which the kept set's compaction
+// overwrites only after the finisher has run.
+static constexpr int kSpFixedPasses = 8;
+
+extern "C" int mmf_superpoint_get_features_device(mmf_superpoint* sp, const uint8_t* image, int width, int height, int channels,
+                                                  float conf_thresh, int nms_dist, int border) {
+    MMF_REQUIRE(sp != nullptr, "mmf_superpoint_get_features_device: null argument");
+    MMF_REQUIRE(nms_dist >= 0 && border >= 0, "mmf_superpoint_get_features_device: negative radius");
+    int rc = mmf_superpoint_forward(sp, image, width, height, channels);
+    if (rc) return rc;
+    mmf_ctx* c = sp->ctx;
+    hipStream_t s = c->stream;
+    const int H = height, W = width, npix = H * W;
+    using namespace mmf;
+    int* count = reinterpret_cast<int*>(&sp->counters[4]);
+    int* status = reinterpret_cast<int*>(&sp->counters[5]);
+    int launches = sp->fwd_launches;
+    hipLaunchKernelGGL(sp_nms_init_kernel, grid1d(npix), dim3(256), 0, s, sp->heat, npix, conf_thresh, sp->state);
+    hipLaunchKernelGGL(sp_undecided_flag_kernel, grid1d(npix), dim3(256), 0, s, sp->state, npix, sp->flags);
+    rc = device_scan(c, sp->flags, (unsigned)npix, sp->prefix, sp->block_sums, &sp->counters[3]);
+    if (rc) return rc;
+    hipLaunchKernelGGL(sp_list_scatter_kernel, grid1d(npix), dim3(256), 0, s, sp->flags, sp->prefix, npix, sp->kp_xy);
+    for (int k = 0; k < kSpFixedPasses; ++k)
+        hipLaunchKernelGGL(sp_nms_list_pass_kernel, grid1d(npix), dim3(256), 0, s, sp->heat, H, W, nms_dist, sp->state,
+                           (const int*)sp->kp_xy, (const unsigned*)&sp->counters[3]);
+    hipLaunchKernelGGL(sp_nms_finish_kernel, dim3(1), dim3(kSpFinishBlock), 0, s, sp->heat, H, W, nms_dist, sp->state,
+                       (const int*)sp->kp_xy, (const unsigned*)&sp->counters[3], status);
+    launches += 1 + kSpFixedPasses + 5 + 1;
+    hipLaunchKernelGGL(sp_keep_flag_kernel, grid1d(npix), dim3(256), 0, s, sp->state, H, W, border, sp->flags);
+    rc = device_scan(c, sp->flags, (unsigned)npix, sp->prefix, sp->block_sums, &sp->counters[2]);
+    if (rc) return rc;
+    hipLaunchKernelGGL(sp_keep_scatter_kernel, grid1d(npix), dim3(256), 0, s, sp->flags, sp->prefix, sp->heat, npix, W, npix,
+                       sp->kp_xy, sp->kp_conf);
+    hipLaunchKernelGGL(sp_rank_select_kernel, dim3((unsigned)((npix + kSpRankRows - 1) / kSpRankRows)), dim3(256), 0, s, (const int*)sp->kp_xy, (const float*)sp->kp_conf,
+                       (const unsigned*)&sp->counters[2], npix, W, sp->max_kp, (const int*)status, sp->sel_xy, sp->sel_conf, count);
+    hipLaunchKernelGGL(sp_sample_counted_kernel, dim3(sp->max_kp), dim3(256), 0, s, sp->desc, H / 8, W / 8, (const int*)sp->sel_xy,
+                       (const int*)count, H, W, sp->kp_desc);
+    launches += 5 + 2;
+    MMF_HIP_TRY(hipGetLastError());
+    sp->last_launches = launches;
+    return MMF_OK;
+}
+
+// the results of the last mmf_superpoint_get_features_device where they are: DEVICE pointers that belong to the object
+extern "C" int mmf_superpoint_device_features(mmf_superpoint* sp, const int** count, const int** xy, const float** conf,
+                                              const float** desc, int* max_keypoints) {
+    MMF_REQUIRE(sp != nullptr, "mmf_superpoint_device_features: null argument");
+    if (count) *count = reinterpret_cast<const int*>(&sp->counters[4]);
+    if (xy) *xy = sp->sel_xy;
+    if (conf) *conf = sp->sel_conf;
+    if (desc) *desc = sp->kp_desc;
+    if (max_keypoints) *max_keypoints = sp->max_kp;
+    return MMF_OK;
+}
+
+// the DEVICE status word of the last mmf_superpoint_get_features_device's suppression (0 converged, 1 cap hit), owned by sp
+extern "C" int mmf_superpoint_device_status(mmf_superpoint* sp, const int** status) {
+    MMF_REQUIRE(sp && status, "mmf_superpoint_device_status: null argument");
+    *status = reinterpret_cast<const int*>(&sp->counters[5]);
+    return MMF_OK;
+}
+
+// the same on the host (tests, tools): waits for the stream.  xy [max_keypoints][2], conf [max_keypoints], desc
+// [max_keypoints][256] HOST arrays (any may be null); *count rows are written
+extern "C" int mmf_superpoint_last_features(mmf_superpoint* sp, int* count, int* status, int* xy, float* conf, float* desc) {
+    MMF_REQUIRE(sp && count, "mmf_superpoint_last_features: null argument");
+    MMF_HIP_TRY(hipSetDevice(sp->ctx->device));
+    hipStream_t s = sp->ctx->stream;
+    int cs[2] = {0, 0};
+    MMF_HIP_TRY(hipMemcpyAsync(cs, &sp->counters[4], sizeof(cs), hipMemcpyDeviceToHost, s));
+    MMF_HIP_TRY(hipStreamSynchronize(s));
+    MMF_REQUIRE(cs[0] >= 0 && cs[0] <= sp->max_kp, "mmf_superpoint_last_features: the count is out of range");
+    *count = cs[0];
+    if (status) *status = cs[1];
+    const size_t n = (size_t)cs[0];
+    if (n == 0) return MMF_OK;
+    if (xy) MMF_HIP_TRY(hipMemcpy(xy, sp->sel_xy, n * 2 * sizeof(int), hipMemcpyDeviceToHost));
+    if (conf) MMF_HIP_TRY(hipMemcpy(conf, sp->sel_conf, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (desc) MMF_HIP_TRY(hipMemcpy(desc, sp->kp_desc, n * 256 * sizeof(float), hipMemcpyDeviceToHost));
+    return MMF_OK;
+}
+
+extern "C" int mmf_superpoint_last_launches(mmf_superpoint* sp) { return sp ? sp->last_launches : -1; }
 
 // one convolution layer by itself (tests, tools): in [H][W][cin] and out on the device, w [cout][cin][k][k]
 // and bias on the HOST; taps = 9 or 1; pool: 2x2 max after the ReLU; nt = 0 picks the tile width.

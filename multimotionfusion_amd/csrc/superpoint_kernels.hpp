@@ -367,11 +367,8 @@ __global__ __launch_bounds__(256) void sp_nms_init_kernel(const float* __restric
     if (i < n) state[i] = heat[i] >= conf_thresh ? SP_UNDECIDED : SP_NONE;
 }
 
-__global__ __launch_bounds__(256) void sp_nms_pass_kernel(const float* __restrict__ heat, int H, int W, int dist,
-                                                          uint8_t* state, unsigned* __restrict__ undecided) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= H * W) return;
-    if (__builtin_nontemporal_load(&state[i]) != SP_UNDECIDED) return;
+// one candidate's step of the fixed point; true while it stays undecided
+__device__ __forceinline__ bool sp_nms_decide(const float* __restrict__ heat, int H, int W, int dist, uint8_t* state, int i) {
     const int y = i / W, x = i - y * W;
     const float ci = heat[i];
     bool stronger_kept = false, stronger_open = false;
@@ -390,7 +387,78 @@ __global__ __launch_bounds__(256) void sp_nms_pass_kernel(const float* __restric
     else if (!stronger_open)
         __hip_atomic_store(&state[i], (uint8_t)SP_KEPT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else
-        atomicAdd(undecided, 1u);
+        return true;
+    return false;
+}
+
+__global__ __launch_bounds__(256) void sp_nms_pass_kernel(const float* __restrict__ heat, int H, int W, int dist,
+                                                          uint8_t* state, unsigned* __restrict__ undecided) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= H * W) return;
+    if (__builtin_nontemporal_load(&state[i]) != SP_UNDECIDED) return;
+    if (sp_nms_decide(heat, H, W, dist, state, i)) atomicAdd(undecided, 1u);
+}
+
+// ---- the suppression to its fixed point without the host (mmf_superpoint_get_features_device) ---------------
+// The candidates are compacted once (flag, scan, scatter: row-major order); a fixed few passes walk that list
+// with the whole chip -- they decide nearly every candidate of a real heat map -- and ONE workgroup walks what
+// is left to the fixed point: a barrier between passes, state at agent scope as above, no grid barrier and so no
+// assumption about co-residency.  Every pass decides at least the strongest undecided candidate, so `listed`
+// passes suffice; the loop makes at most listed + 1 and says in *status whether that was enough (0) or not (1:
+// the consumers then see no keypoints).
+constexpr int kSpFinishBlock = 1024;
+
+__global__ __launch_bounds__(256) void sp_undecided_flag_kernel(const uint8_t* __restrict__ state, int n,
+                                                                unsigned* __restrict__ flags) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) flags[i] = state[i] == SP_UNDECIDED ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void sp_list_scatter_kernel(const unsigned* __restrict__ flags,
+                                                              const unsigned* __restrict__ prefix, int n,
+                                                              int* __restrict__ list) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || !flags[i]) return;
+    const unsigned k = prefix[i];
+    if (k < (unsigned)n) list[k] = i;
+}
+
+// one pass over the list; the grid covers the image, workgroups past the list leave at once
+__global__ __launch_bounds__(256) void sp_nms_list_pass_kernel(const float* __restrict__ heat, int H, int W, int dist,
+                                                               uint8_t* state, const int* __restrict__ list,
+                                                               const unsigned* __restrict__ listed) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= (int)min(*listed, (unsigned)(H * W))) return;
+    const int i = min(max(list[k], 0), H * W - 1);
+    if (__hip_atomic_load(&state[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != SP_UNDECIDED) return;
+    (void)sp_nms_decide(heat, H, W, dist, state, i);
+}
+
+// Lane t walks entries t, t + 1024, ... of the list every trip and skips what is decided.
+__global__ __launch_bounds__(kSpFinishBlock) void sp_nms_finish_kernel(const float* __restrict__ heat, int H, int W, int dist,
+                                                                       uint8_t* state, const int* __restrict__ list,
+                                                                       const unsigned* __restrict__ listed,
+                                                                       int* __restrict__ status) {
+    __shared__ int open_s;
+    const int tid = threadIdx.x, npix = H * W;
+    const int n = (int)min(*listed, (unsigned)npix);
+    int open = 0;
+    for (int trip = 0; trip <= n; ++trip) {  // the cap: listed + 1 passes
+        if (tid == 0) open_s = 0;
+        __syncthreads();
+        int mine = 0;
+        for (int k = tid; k < n; k += kSpFinishBlock) {
+            const int i = min(max(list[k], 0), npix - 1);
+            if (__hip_atomic_load(&state[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != SP_UNDECIDED) continue;
+            mine += sp_nms_decide(heat, H, W, dist, state, i) ? 1 : 0;
+        }
+        if (mine) atomicAdd(&open_s, mine);
+        __syncthreads();
+        open = open_s;  // (workgroup uniform)
+        __syncthreads();
+        if (open == 0) break;
+    }
+    if (tid == 0) *status = open ? 1 : 0;
 }
 
 // kept and outside the border band -> flag (row-major order)
@@ -414,10 +482,63 @@ __global__ __launch_bounds__(256) void sp_keep_scatter_kernel(const unsigned* __
     conf[k] = heat[i];
 }
 
+// ---- strongest first on the device: rank by counting ------------------------------------------------------
+// key = (~bits(conf), row-major index) as one 64-bit integer: confidences are positive floats, so the order of
+// their bits is the order of their values, and the index breaks ties like the stable sort of the host path.
+// Keys are distinct, so the ranks are a permutation: keypoint i goes to slot rank(i) when that is below
+// max_out.  Workgroup b ranks kept keypoints 64 b .. 64 b + 63 against all of them, tiled through LDS in tiles
+// of 256: lane r of wave p compares keypoint r with quarter p of every tile (the whole wave reads the same key: a
+// broadcast), and the four partial ranks are added at the end.  A few thousand kept keypoints are then a few
+// dozen workgroups of short loops.  Workgroups past the kept set leave at once.  No atomics, any kept count up to
+// the image.  *count = min(kept, max_out), or 0 when the suppression did not converge.
+constexpr int kSpRankRows = 64;
+
+__device__ __forceinline__ unsigned long long sp_rank_key(float conf, int x, int y, int W) {
+    return ((unsigned long long)(~__float_as_uint(conf)) << 32) | (unsigned)(y * W + x);
+}
+
+__global__ __launch_bounds__(256) void sp_rank_select_kernel(const int* __restrict__ xy, const float* __restrict__ conf,
+                                                             const unsigned* __restrict__ kept, int npix, int W, int max_out,
+                                                             const int* __restrict__ status, int* __restrict__ out_xy,
+                                                             float* __restrict__ out_conf, int* __restrict__ count) {
+    __shared__ unsigned long long tile[256];
+    __shared__ int partial[4][kSpRankRows];
+    const int tid = threadIdx.x, r = tid & 63, part = tid >> 6;
+    const int m = (int)min(*kept, (unsigned)npix);
+    if (blockIdx.x == 0 && tid == 0) *count = *status ? 0 : min(m, max_out);
+    const int i0 = blockIdx.x * kSpRankRows;
+    if (i0 >= m) return;  // workgroup uniform
+    const int i = i0 + r;
+    const bool in = i < m;
+    int x = 0, y = 0;
+    float c = 0.f;
+    if (in) x = xy[2 * i], y = xy[2 * i + 1], c = conf[i];
+    const unsigned long long key = in ? sp_rank_key(c, x, y, W) : ~0ull;
+    int rank = 0;
+    // the next tile's keys are fetched while this one is compared
+    unsigned long long next = tid < m ? sp_rank_key(conf[tid], xy[2 * tid], xy[2 * tid + 1], W) : ~0ull;
+    for (int t0 = 0; t0 < m; t0 += 256) {
+        __syncthreads();  // the previous tile has been read
+        tile[tid] = next;
+        __syncthreads();
+        const int j = t0 + 256 + tid;
+        next = j < m ? sp_rank_key(conf[j], xy[2 * j], xy[2 * j + 1], W) : ~0ull;
+#pragma unroll 8
+        for (int q = 0; q < 64; ++q) rank += tile[part * 64 + q] < key ? 1 : 0;
+    }
+    partial[part][r] = rank;
+    __syncthreads();
+    if (part != 0) return;
+    rank = ((partial[0][r] + partial[1][r]) + partial[2][r]) + partial[3][r];
+    if (in && rank < max_out) {
+        out_xy[2 * rank] = x, out_xy[2 * rank + 1] = y;
+        out_conf[rank] = c;
+    }
+}
+
 // ---- descriptor sampling: one workgroup per keypoint, one thread per channel ------------------------------
-__global__ __launch_bounds__(256) void sp_sample_kernel(const float* __restrict__ desc, int Hc, int Wc,
-                                                        const int* __restrict__ xy, int H, int W,
-                                                        float* __restrict__ out) {
+__device__ __forceinline__ void sp_sample_body(const float* __restrict__ desc, int Hc, int Wc, const int* __restrict__ xy, int H,
+                                               int W, float* __restrict__ out) {
     __shared__ float vals[256];
     __shared__ float norm;
     const int k = blockIdx.x, c = threadIdx.x;
@@ -442,6 +563,21 @@ __global__ __launch_bounds__(256) void sp_sample_kernel(const float* __restrict_
     }
     __syncthreads();
     out[(size_t)k * 256 + c] = v / norm;
+}
+
+
+__global__ __launch_bounds__(256) void sp_sample_kernel(const float* __restrict__ desc, int Hc, int Wc,
+                                                        const int* __restrict__ xy, int H, int W,
+                                                        float* __restrict__ out) {
+    sp_sample_body(desc, Hc, Wc, xy, H, W, out);
+}
+
+// the same for a keypoint count on the device: the grid covers the most there can be, workgroup k leaves when k >= *count
+__global__ __launch_bounds__(256) void sp_sample_counted_kernel(const float* __restrict__ desc, int Hc, int Wc,
+                                                                const int* __restrict__ xy, const int* __restrict__ count, int H,
+                                                                int W, float* __restrict__ out) {
+    if ((int)blockIdx.x >= *count) return;  // workgroup uniform
+    sp_sample_body(desc, Hc, Wc, xy, H, W, out);
 }
 
 }  // namespace mmf

@@ -2,7 +2,8 @@
 // mmf_hip.hip (it uses that file's helpers, match_kernels.hpp and rigid_ransac.hpp).
 //
 // Everything is enqueued on the context's stream.  The host keeps only an UPPER BOUND of the number of tracks (it grows
-// by the keypoints of every add and becomes exact whenever a call waits: pairs, visible, status, download): the search
+// by the keypoints of every add -- by max_keypoints where their number is known to the device alone -- and becomes exact
+// whenever a call waits: pairs, visible, status, download): the search
 // of an add runs on that many gathered rows, the ones past the active tracks being padding no keypoint can match.
 // The stamp of the newest frame (adds since creation / reset) is exact on the host: the view log's slots go by it.
 #pragma once
@@ -28,6 +29,8 @@ struct mmf_tracker {
     float *p0 = nullptr, *p1 = nullptr;  // pinned [pair_models][capacity][3]
     int pair_models = 0;
     int bound = 0;  // no fewer than the tracks of the table
+    const int* kp_status = nullptr;  // DEVICE word the device-count add reads (mmf_tracker_set_keypoint_status); null: none
+    long long caller_adds = 0;       // adds through the public calls (the fusion's in-frame front end tells its own from them)
     int last_launches = 0;
     std::vector<void*> device_allocs;
     // the view log (mmf_tracker_set_view_log) and the views built from it (mmf_tracker_model_views)
@@ -147,6 +150,23 @@ extern "C" int mmf_tracker_last_launches(mmf_tracker* t) { return t ? t->last_la
 // the host has waited for the stream: the record is what the table holds
 static void tracker_refresh(mmf_tracker* t) { t->bound = std::min(t->capacity, std::max(0, t->rec->n_tracks)); }
 
+// the end of an add: the stamp, and with the view log on the frame's visible set into its slot of the ring (two more
+// launches, nothing read back)
+static void tracker_add_tail(mmf_tracker* t) {
+    using namespace mmf;
+    hipStream_t st = t->ctx->stream;
+    t->last_launches = 7;
+    t->frame += 1;
+    if (t->log.frames > 0) {
+        const int slot = (int)(t->frame % t->log.frames);
+        hipLaunchKernelGGL(trk_log_kernel, dim3(1), dim3(kTrkBlock), 0, st, t->T, t->log, slot, t->frame, t->map);
+        hipLaunchKernelGGL(trk_gather_rows_kernel, dim3(tracker_row_blocks(t->max_keypoints)), dim3(256), 0, st,
+                           (const float*)t->desc[t->cur], (const int*)t->map, (const int*)(t->log.count + slot),
+                           t->log.desc + (size_t)slot * t->max_keypoints * kTrkDim, t->capacity);
+        t->last_launches = 9;
+    }
+}
+
 extern "C" int mmf_tracker_add_keypoints(mmf_tracker* t, int n, const int* xy, const float* descriptor, const float* depth,
                                          long long timestamp, float min_feature_distance, int history) {
     MMF_REQUIRE(t && n >= 0 && depth && ((xy && descriptor) || n == 0), "mmf_tracker_add_keypoints: null argument");
@@ -177,18 +197,71 @@ extern "C" int mmf_tracker_add_keypoints(mmf_tracker* t, int n, const int* xy, c
                        (const int*)t->train_idx, (const int*)t->active_idx, timestamp, t->dest_row);
     hipLaunchKernelGGL(trk_scatter_rows_kernel, dim3(tracker_row_blocks(std::max(n, 1))), dim3(256), 0, st, descriptor, n,
                        (const int*)t->dest_row, t->desc[t->cur], t->capacity);
-    t->last_launches = 7;
-    t->frame += 1;
-    if (t->log.frames > 0) {  // the frame's visible set into its slot of the ring: two more launches, nothing read back
-        const int slot = (int)(t->frame % t->log.frames);
-        hipLaunchKernelGGL(trk_log_kernel, dim3(1), dim3(kTrkBlock), 0, st, t->T, t->log, slot, t->frame, t->map);
-        hipLaunchKernelGGL(trk_gather_rows_kernel, dim3(tracker_row_blocks(t->max_keypoints)), dim3(256), 0, st,
-                           (const float*)t->desc[t->cur], (const int*)t->map, (const int*)(t->log.count + slot),
-                           t->log.desc + (size_t)slot * t->max_keypoints * kTrkDim, t->capacity);
-        t->last_launches = 9;
-    }
+    tracker_add_tail(t);
     MMF_HIP_TRY(hipGetLastError());
     t->bound = (int)std::min<long long>(t->capacity, (long long)t->bound + n);
+    t->caller_adds += 1;
+    return MMF_OK;
+}
+
+// mmf_tracker_add_keypoints with the number of keypoints in DEVICE memory: the same 7 (9) launches, the `counted` forms of
+// the kernels that take n.  Their grids, and the [query ; train] layouts of keys / norms, are those of max_keypoints
+// queries; rows from n on (stale keypoints of earlier frames) are read by none of them.  The host's bound grows by the
+// most there can be: the padding rows that costs are fillers nothing matches.
+static int tracker_add_counted(mmf_tracker* t, const int* n_dev, const int* fail_dev, const int* xy, const float* descriptor,
+                               const float* depth, long long timestamp, float min_feature_distance, int history) {
+    MMF_HIP_TRY(hipSetDevice(t->ctx->device));
+    hipStream_t st = t->ctx->stream;
+    using namespace mmf;
+    const int K = t->max_keypoints;
+    const int nt_pad = std::min(t->cap_pad, std::max(64, (t->bound + 63) / 64 * 64));
+    hipLaunchKernelGGL(trk_begin_counted_kernel, dim3(1), dim3(kTrkBlock), 0, st, t->T, n_dev, fail_dev, K, xy, depth, t->width,
+                       t->height, t->fx, t->fy, t->cx, t->cy, history, t->q_co, t->active_idx);
+    hipLaunchKernelGGL(trk_gather_kernel, dim3(tracker_row_blocks(nt_pad)), dim3(256), 0, st, t->T, (const float*)t->desc[t->cur],
+                       (const int*)t->active_idx, t->train, nt_pad);
+    unsigned long long *row_best = t->keys, *col_best = t->keys + K;
+    float *qn = t->norms, *tn = t->norms + K;
+    hipLaunchKernelGGL(row_norms_counted_kernel, dim3((K + 31) / 32 + (nt_pad + 31) / 32), dim3(64), 0, st, descriptor, n_dev, fail_dev, K,
+                       (const float*)t->train, nt_pad, kTrkDim, qn, tn, row_best, col_best, kNoMatchKey);
+    hipLaunchKernelGGL(match_tile64_counted_kernel, dim3((nt_pad + 63) / 64, (K + 63) / 64), dim3(256), 0, st, descriptor,
+                       (const float*)t->train, (const float*)qn, (const float*)tn, n_dev, fail_dev, K, nt_pad, kTrkDim, row_best, col_best);
+    hipLaunchKernelGGL(match_cross_check_counted_kernel, dim3((K + 255) / 256), dim3(256), 0, st, row_best,
+                       (const unsigned long long*)col_best, n_dev, fail_dev, K, min_feature_distance, t->train_idx, t->q_dist);
+    hipLaunchKernelGGL(trk_finish_counted_kernel, dim3(1), dim3(kTrkBlock), 0, st, t->T, t->rec, n_dev, fail_dev, K, xy,
+                       (const float*)t->q_co, (const int*)t->train_idx, (const int*)t->active_idx, timestamp, t->dest_row);
+    hipLaunchKernelGGL(trk_scatter_rows_counted_kernel, dim3(tracker_row_blocks(K)), dim3(256), 0, st, descriptor, n_dev, fail_dev, K,
+                       (const int*)t->dest_row, t->desc[t->cur], t->capacity);
+    tracker_add_tail(t);
+    MMF_HIP_TRY(hipGetLastError());
+    t->bound = (int)std::min<long long>(t->capacity, (long long)t->bound + K);
+    return MMF_OK;
+}
+
+extern "C" int mmf_tracker_add_keypoints_device(mmf_tracker* t, const int* n_dev, const int* xy, const float* descriptor,
+                                                const float* depth, long long timestamp, float min_feature_distance, int history) {
+    MMF_REQUIRE(t && n_dev && xy && descriptor && depth, "mmf_tracker_add_keypoints_device: null argument");
+    MMF_REQUIRE(history >= 0, "mmf_tracker_add_keypoints_device: negative history");
+    MMF_REQUIRE(((uintptr_t)descriptor & 15u) == 0, "mmf_tracker_add_keypoints_device: 16-byte aligned descriptor rows");
+    const int rc = tracker_add_counted(t, n_dev, t->kp_status, xy, descriptor, depth, timestamp, min_feature_distance, history);
+    if (!rc) t->caller_adds += 1;
+    return rc;
+}
+
+// the status word of whatever produces *n_dev (mmf_superpoint_device_features' neighbour, say): a DEVICE int the device-count
+// adds read from now on; while it is not 0 an add is a frame without keypoints and counts as failed.  NULL: none.
+extern "C" int mmf_tracker_set_keypoint_status(mmf_tracker* t, const int* status_dev) {
+    MMF_REQUIRE(t != nullptr, "mmf_tracker_set_keypoint_status: null tracker");
+    t->kp_status = status_dev;
+    return MMF_OK;
+}
+
+// waits: the device-count adds since creation / reset whose status word was set
+extern "C" int mmf_tracker_keypoint_failures(mmf_tracker* t, int* failures) {
+    MMF_REQUIRE(t && failures, "mmf_tracker_keypoint_failures: null argument");
+    MMF_HIP_TRY(hipSetDevice(t->ctx->device));
+    MMF_HIP_TRY(wait_stream(t->ctx->stream));
+    tracker_refresh(t);
+    *failures = t->rec->kp_failed;
     return MMF_OK;
 }
 

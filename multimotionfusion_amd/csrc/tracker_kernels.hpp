@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "match_kernels.hpp"
+
 namespace mmf {
 
 constexpr int kTrkDim = 256;     // SuperPoint descriptors
@@ -32,10 +34,11 @@ constexpr float kTrkFiller = 1e30f;  // a padding row of the gathered train set:
 struct TrkHead {  // on the device
     int n_tracks, length, dropped, n_active;
     long long next_uid;
+    int kp_failed, pad_;  // adds whose keypoint source had failed (mmf_tracker_add_keypoints_device)
 };
 
 struct TrkRecord {  // pinned host memory the kernels write
-    int n_tracks, length, dropped, dropped_last, n_visible, pad_;
+    int n_tracks, length, dropped, dropped_last, n_visible, kp_failed;
     int pair_count[kTrkMaxModels];
 };
 
@@ -86,10 +89,9 @@ __device__ __forceinline__ bool trk_finite3(const float* p) { return isfinite(p[
 // add, step 1: the keypoints of the frame (PointTracker.cpp:35-56, float operation for float operation: the build has
 // -ffp-contract=off), the ordered compaction of the active tracks (getLastActiveKeypoints, :205-224) and the shift of
 // every track by one null keypoint (:71-73).  An empty table is not shifted: its length restarts at 1 (:61-66).
-__global__ __launch_bounds__(kTrkBlock) void trk_begin_kernel(TrkTable T, int n, const int* __restrict__ q_xy,
-                                                              const float* __restrict__ depth, int width, int height, float fx,
-                                                              float fy, float cx, float cy, int history,
-                                                              float* __restrict__ q_co, int* __restrict__ active_idx) {
+__device__ __forceinline__ void trk_begin_body(TrkTable T, int n, const int* __restrict__ q_xy, const float* __restrict__ depth,
+                                               int width, int height, float fx, float fy, float cx, float cy, int history,
+                                               float* __restrict__ q_co, int* __restrict__ active_idx) {
     const int tid = threadIdx.x;
     const int nt = min(T.head->n_tracks, T.capacity);
     for (int q = tid; q < n; q += kTrkBlock) {
@@ -130,6 +132,23 @@ __global__ __launch_bounds__(kTrkBlock) void trk_begin_kernel(TrkTable T, int n,
     }
 }
 
+__global__ __launch_bounds__(kTrkBlock) void trk_begin_kernel(TrkTable T, int n, const int* __restrict__ q_xy,
+                                                              const float* __restrict__ depth, int width, int height, float fx,
+                                                              float fy, float cx, float cy, int history,
+                                                              float* __restrict__ q_co, int* __restrict__ active_idx) {
+    trk_begin_body(T, n, q_xy, depth, width, height, fx, fy, cx, cy, history, q_co, active_idx);
+}
+
+// the same with the number of keypoints on the device (device_count, match_kernels.hpp): rows from it on are not read
+__global__ __launch_bounds__(kTrkBlock) void trk_begin_counted_kernel(TrkTable T, const int* __restrict__ n_dev,
+                                                                      const int* __restrict__ fail_dev, int n_max,
+                                                                      const int* __restrict__ q_xy, const float* __restrict__ depth,
+                                                                      int width, int height, float fx, float fy, float cx, float cy,
+                                                                      int history, float* __restrict__ q_co,
+                                                                      int* __restrict__ active_idx) {
+    trk_begin_body(T, device_count(n_dev, fail_dev, n_max), q_xy, depth, width, height, fx, fy, cx, cy, history, q_co, active_idx);
+}
+
 // add, step 2: the descriptors of the active tracks, in order, as the train set of the search; the rows from n_active
 // to nt_pad (what the host knows to be no less than the number of tracks) are padding that nothing matches
 __global__ __launch_bounds__(256) void trk_gather_kernel(TrkTable T, const float* __restrict__ desc,
@@ -150,11 +169,10 @@ __global__ __launch_bounds__(256) void trk_gather_kernel(TrkTable T, const float
 // add, step 3 (after the search): matched tracks get their keypoint (:107-112), unmatched keypoints start tracks in
 // ascending query index (:116-121); appends past the capacity are dropped and counted.  dest_row[q] = the row the
 // descriptor of keypoint q goes to, or -1.
-__global__ __launch_bounds__(kTrkBlock) void trk_finish_kernel(TrkTable T, TrkRecord* __restrict__ rec, int n,
-                                                               const int* __restrict__ q_xy, const float* __restrict__ q_co,
-                                                               const int* __restrict__ train_idx,
-                                                               const int* __restrict__ active_idx, long long timestamp,
-                                                               int* __restrict__ dest_row) {
+__device__ __forceinline__ void trk_finish_body(TrkTable T, TrkRecord* __restrict__ rec, int n, const int* __restrict__ q_xy,
+                                                const float* __restrict__ q_co, const int* __restrict__ train_idx,
+                                                const int* __restrict__ active_idx, long long timestamp,
+                                                int* __restrict__ dest_row) {
     const int tid = threadIdx.x;
     const int nt = min(T.head->n_tracks, T.capacity), na = min(T.head->n_active, T.capacity);
     const long long uid0 = T.head->next_uid;
@@ -206,10 +224,33 @@ __global__ __launch_bounds__(kTrkBlock) void trk_finish_kernel(TrkTable T, TrkRe
     }
 }
 
+__global__ __launch_bounds__(kTrkBlock) void trk_finish_kernel(TrkTable T, TrkRecord* __restrict__ rec, int n,
+                                                               const int* __restrict__ q_xy, const float* __restrict__ q_co,
+                                                               const int* __restrict__ train_idx,
+                                                               const int* __restrict__ active_idx, long long timestamp,
+                                                               int* __restrict__ dest_row) {
+    trk_finish_body(T, rec, n, q_xy, q_co, train_idx, active_idx, timestamp, dest_row);
+}
+
+// the same with the number of keypoints on the device; a source that had failed (*fail_dev set: the frame is one without
+// keypoints) is counted in the head and the record
+__global__ __launch_bounds__(kTrkBlock) void trk_finish_counted_kernel(TrkTable T, TrkRecord* __restrict__ rec,
+                                                                       const int* __restrict__ n_dev,
+                                                                       const int* __restrict__ fail_dev, int n_max,
+                                                                       const int* __restrict__ q_xy, const float* __restrict__ q_co,
+                                                                       const int* __restrict__ train_idx,
+                                                                       const int* __restrict__ active_idx, long long timestamp,
+                                                                       int* __restrict__ dest_row) {
+    trk_finish_body(T, rec, device_count(n_dev, fail_dev, n_max), q_xy, q_co, train_idx, active_idx, timestamp, dest_row);
+    if (threadIdx.x == 0) {
+        if (fail_dev && *fail_dev) T.head->kp_failed += 1;
+        rec->kp_failed = T.head->kp_failed;
+    }
+}
+
 // descriptor rows of a set of keypoints to their rows of the table (dest_row < 0: nowhere)
-__global__ __launch_bounds__(256) void trk_scatter_rows_kernel(const float* __restrict__ q_desc, int n,
-                                                               const int* __restrict__ dest_row, float* __restrict__ desc,
-                                                               int capacity) {
+__device__ __forceinline__ void trk_scatter_rows_body(const float* __restrict__ q_desc, int n, const int* __restrict__ dest_row,
+                                                      float* __restrict__ desc, int capacity) {
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), waves = gridDim.x * 4;
     for (int q = wave; q < n; q += waves) {
@@ -217,6 +258,19 @@ __global__ __launch_bounds__(256) void trk_scatter_rows_kernel(const float* __re
         if (d < 0 || d >= capacity) continue;
         reinterpret_cast<float4*>(desc + (size_t)d * kTrkDim)[lane] = reinterpret_cast<const float4*>(q_desc + (size_t)q * kTrkDim)[lane];
     }
+}
+
+__global__ __launch_bounds__(256) void trk_scatter_rows_kernel(const float* __restrict__ q_desc, int n,
+                                                               const int* __restrict__ dest_row, float* __restrict__ desc,
+                                                               int capacity) {
+    trk_scatter_rows_body(q_desc, n, dest_row, desc, capacity);
+}
+
+__global__ __launch_bounds__(256) void trk_scatter_rows_counted_kernel(const float* __restrict__ q_desc, const int* __restrict__ n_dev,
+                                                                       const int* __restrict__ fail_dev, int n_max,
+                                                                       const int* __restrict__ dest_row, float* __restrict__ desc,
+                                                                       int capacity) {
+    trk_scatter_rows_body(q_desc, device_count(n_dev, fail_dev, n_max), dest_row, desc, capacity);
 }
 
 // prune (:170-203): tracks with fewer than min_kps keypoints whose last keypoint is older than min_time go; the others

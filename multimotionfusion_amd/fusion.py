@@ -373,10 +373,33 @@ class MultiMotionFusion:
         """attach a tracker.DevicePointTracker (None: detach; the default).  The caller adds and prunes a frame's keypoints
         before processFrame; processFrame then initialises every active model from its own tracks (odom_init_kp; the dense
         tracker refines when icp_refine), associates the tracks with the models by the frame's id image and, with
-        redetection on and no setKeypoints for the frame, takes the tracker's visible keypoints."""
+        redetection on and no setKeypoints for the frame, takes the tracker's visible keypoints.  Every call, also one
+        that only changes a flag, switches the in-frame keypoint front end off: call setKeypointFrontEnd again after it."""
         check(self.ctx.lib.mmf_fusion_set_tracker(self.handle, tracker.handle if tracker is not None else None,
                                                   int(bool(odom_init_kp)), int(bool(icp_refine))))
         self._tracker = tracker  # (the fusion does not own it: kept alive here)
+        self._kp_predictor = None  # (mmf_fusion_set_tracker has switched the front end off)
+
+    def setKeypointFrontEnd(self, kp_predictor, conf_thresh=None, nms_dist=None, border=None, min_feature_distance=0.7, history=30,
+                            prune_min_kps=30, prune_window_ns=int(1e9)):
+        """run the keypoint half of processFrame (MultiMotionFusion.cpp:223-248) inside every processFrame call, on the
+        frame's own device buffers and without a wait: superpoint.SuperPoint features -> the attached tracker's add ->
+        prune.  kp_predictor = None: off (the default).  Thresholds default to the predictor's.  Needs setTracker first,
+        and a later setTracker call switches it off again."""
+        from ._capi import mmf_keypoint_frontend_config
+        if kp_predictor is None:
+            check(self.ctx.lib.mmf_fusion_set_keypoint_frontend(self.handle, None, None))
+            self._kp_predictor = None
+            return
+        cfg = mmf_keypoint_frontend_config()
+        check(self.ctx.lib.mmf_keypoint_frontend_default_config(C.byref(cfg)))
+        cfg.conf_thresh = float(kp_predictor.conf_thresh if conf_thresh is None else conf_thresh)
+        cfg.nms_dist = int(kp_predictor.nms_dist if nms_dist is None else nms_dist)
+        cfg.border = int(kp_predictor.border if border is None else border)
+        cfg.min_feature_distance, cfg.history = float(min_feature_distance), int(history)
+        cfg.prune_min_kps, cfg.prune_window_ns = int(prune_min_kps), int(prune_window_ns)
+        check(self.ctx.lib.mmf_fusion_set_keypoint_frontend(self.handle, kp_predictor.handle, C.byref(cfg)))
+        self._kp_predictor = kp_predictor  # (not owned: kept alive here)
 
     def getLastTrackTransforms(self):
         """the transformations the last frame's models were initialised with, [n,4,4] in list order (n = 0: none)"""

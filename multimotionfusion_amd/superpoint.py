@@ -104,6 +104,34 @@ class SuperPoint:
                                                    xy.ctypes.data, conf.ctypes.data, desc.ctypes.data, C.byref(n)))
         return xy[:n.value].copy(), conf[:n.value].copy(), desc[:n.value].copy()
 
+    def getFeaturesDevice(self, img):
+        """keypoints(img) without the host: enqueued on the context's stream, nothing awaited or read back.  The results stay
+        on the device (deviceFeatures); lastFeatures() fetches them."""
+        img, H, W, ch = self._image(img)
+        check(self.lib.mmf_superpoint_get_features_device(self.handle, _p(img), W, H, ch, self.conf_thresh, self.nms_dist, self.border))
+
+    def deviceFeatures(self):
+        """DEVICE addresses of the last getFeaturesDevice's results, owned by this object: (count, status, xy, conf, desc)"""
+        cnt, status, xy, conf, desc = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(self.lib.mmf_superpoint_device_features(self.handle, C.byref(cnt), C.byref(xy), C.byref(conf), C.byref(desc), None))
+        check(self.lib.mmf_superpoint_device_status(self.handle, C.byref(status)))
+        return cnt.value, status.value, xy.value, conf.value, desc.value
+
+    def lastFeatures(self):
+        """waits: (xy [n,2] int32, conf [n] float32, desc [n,256] float32, status) of the last getFeaturesDevice; status 0 =
+        the suppression converged, 1 = it did not (then n = 0)"""
+        xy = np.empty((self.max_keypoints, 2), np.int32)
+        conf = np.empty(self.max_keypoints, np.float32)
+        desc = np.empty((self.max_keypoints, 256), np.float32)
+        n, status = C.c_int(0), C.c_int(0)
+        check(self.lib.mmf_superpoint_last_features(self.handle, C.byref(n), C.byref(status), xy.ctypes.data, conf.ctypes.data,
+                                                    desc.ctypes.data))
+        return xy[:n.value].copy(), conf[:n.value].copy(), desc[:n.value].copy(), status.value
+
+    def lastLaunches(self):
+        """kernel launches of the last getFeaturesDevice"""
+        return self.lib.mmf_superpoint_last_launches(self.handle)
+
     def getFeatures(self, img):
         """SuperPoint::getFeatures as MultiMotionFusion.cpp:233 consumes it: (coordinates [n,2] float64 normalised
         by (width, height), descriptors [n,256] float64)."""

@@ -55,6 +55,29 @@ class DevicePointTracker:
         check(self.ctx.lib.mmf_tracker_add_keypoints(self.handle, n, _p(xy) if n else None, _p(de) if n else None, _p(depth),
                                                      int(timestamp), float(min_feature_distance), int(history)))
 
+    def addKeypointsDevice(self, n_dev, xy, descriptors, timestamp, depth, min_feature_distance=0.7, history=30):
+        """addKeypointsPixels with the number of keypoints on the device and no wait.  n_dev: int32 CUDA tensor (its first
+        element) or a device address; xy [max_keypoints,2] int32 / descriptors [max_keypoints,256] float32 CUDA tensors or
+        device addresses (superpoint.SuperPoint.deviceFeatures) whose rows from n on may hold anything."""
+        assert depth.is_cuda and depth.dtype == torch.float32 and depth.shape == (self.height, self.width) and depth.is_contiguous()
+        for a, dt in ((n_dev, torch.int32), (xy, torch.int32), (descriptors, torch.float32)):
+            assert not torch.is_tensor(a) or (a.is_cuda and a.dtype == dt and a.is_contiguous())
+        ptr = lambda a: _p(a) if torch.is_tensor(a) else a
+        check(self.ctx.lib.mmf_tracker_add_keypoints_device(self.handle, ptr(n_dev), ptr(xy), ptr(descriptors), _p(depth),
+                                                            int(timestamp), float(min_feature_distance), int(history)))
+
+    def setKeypointStatus(self, status_dev):
+        """the DEVICE status word of the keypoint source (int32 CUDA tensor, device address or None): while it is not 0 an
+        addKeypointsDevice is a frame without keypoints and counts as failed"""
+        self._status = status_dev  # (kept alive)
+        check(self.ctx.lib.mmf_tracker_set_keypoint_status(self.handle, _p(status_dev) if torch.is_tensor(status_dev) else status_dev))
+
+    def keypointFailures(self):
+        """waits: the addKeypointsDevice calls since creation / reset whose status word was set"""
+        n = C.c_int()
+        check(self.ctx.lib.mmf_tracker_keypoint_failures(self.handle, C.byref(n)))
+        return n.value
+
     def prune(self, min_kps, min_time):
         check(self.ctx.lib.mmf_tracker_prune(self.handle, int(min_kps), int(min_time)))
 
@@ -197,20 +220,29 @@ class NativeKeypointFrontEnd:
     models' track sets up to date from the frame's segmentation (fusion.setTracker)."""
 
     def __init__(self, ctx: Context, fusion, kp_predictor, intrinsics, icp_refine=True, capacity=4096, max_keypoints=1024,
-                 view_log=0):
+                 view_log=0, on_device=False):
         """view_log: frames of the tracker's view log (0: none).  With it and fusion.setEnableRedetection(True) a model that
-        leaves the active list stores its keypoint views by itself: redetection needs no history kept by the caller."""
-        self.ctx, self.fusion, self.kp = ctx, fusion, kp_predictor
+        leaves the active list stores its keypoint views by itself: redetection needs no history kept by the caller.
+        on_device: features, add and prune run inside fusion.processFrame on the frame's device buffers, nothing awaited
+        (fusion.setKeypointFrontEnd; kp_predictor must be a superpoint.SuperPoint with max_keypoints <= the tracker's)."""
+        self.ctx, self.fusion, self.kp, self.on_device = ctx, fusion, kp_predictor, bool(on_device)
         self.tracker = DevicePointTracker(ctx, fusion.width, fusion.height, intrinsics, capacity, max_keypoints)
         self.tracker.setViewLog(view_log)
         fusion.setTracker(self.tracker, odom_init_kp=True, icp_refine=icp_refine)
+        if self.on_device:
+            fusion.setKeypointFrontEnd(kp_predictor)
 
     def processFrame(self, rgb, depth, timestamp, weightMultiplier=1.0, **frame):
+        if self.on_device:
+            self.fusion.processFrame(rgb, depth, timestamp=timestamp, weightMultiplier=weightMultiplier, **frame)
+            return
         coordinates, descriptors = self.kp.getFeatures(rgb)
         self.tracker.addKeypoints(coordinates, descriptors, timestamp, depth, 0.7, 30)
         self.tracker.prune(30, max(int(timestamp) - int(1e9), 0))  # :246
         self.fusion.processFrame(rgb, depth, timestamp=timestamp, weightMultiplier=weightMultiplier, **frame)
 
     def close(self):
+        if self.on_device:
+            self.fusion.setKeypointFrontEnd(None)
         self.fusion.setTracker(None)
         self.tracker.close()
