@@ -1,6 +1,7 @@
 // fusion_orchestrator.hpp -- MultiMotionFusion::processFrame / predict (Core/MultiMotionFusion.cpp:207-854,
 // 863-875) for a list of rigid-body models: the global (camera) model plus the object models the segmentation
-// spawns.  Textually included at the end of mmf_hip.hip (it uses that file's static helpers).
+// spawns.  Textually included at the end of mmf_hip.hip (it uses that file's static helpers and
+// model_host.hpp's enqueuers of the surfel passes).
 //
 // The segmentation is handed in per frame (mmf_segmentation: the reference's gSLICr + dense CRF), pulled through a
 // callback at the point where the reference calls performSegmentation (:412), computed from the frame's raw label image

@@ -1,4 +1,4 @@
-"""-m gpu: the object models' restricted passes (csrc/pass_rect.hpp, models_*_rect in csrc/mmf_hip.hip) against the passes
+"""-m gpu: the object models' restricted passes (csrc/pass_rect.hpp, models_*_rect in csrc/model_host.hpp) against the passes
 model by model, as test_gpu_multimodel.py::test_batched_passes_equal_passes_model_by_model compares them -- here with id
 masks made by the test (surfel_shapes.py) on a static scene, so that the device-resident boxes take the values a rendered
 object well inside a 320 x 240 frame never gives them: clipped at column / row 0 and at cols - 1 / rows - 1, the whole frame,
