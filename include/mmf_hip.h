@@ -1155,6 +1155,68 @@ int mmf_debug_ransac_core_host(const mmf_ransac_config *cfg, const float *p0, co
                                unsigned char *inlier, int *has_inlier);
 int mmf_debug_rounded_ops(mmf_ctx *ctx, int op, const void *a_dev, const void *b_dev, size_t n, void *out_dev);
 
+/* ---- dense optical flow after Farneback (csrc/flow_kernels.hpp, csrc/flow_host.hpp) ------------------
+ * The stage of the reference's flow_crf segmentation that turns a frame pair into a dense flow field
+ * (Core/Segmentation/Segmentation.cpp:779-804: both frames scaled down by 4, cv::calcOpticalFlowFarneback(.., 0.2, 1, 20, 2,
+ * 5, 15/50.0, 0)), as an engine of its own.  The flow_crf mode itself is NOT here.  The arithmetic is the one DESIGN.md 4.8
+ * writes out -- Farneback's algorithm, one level, box window -- and tests/flow_oracle.py restates; parity with OpenCV is not
+ * pinned.  Frames are DEVICE interleaved u8 RGB [height][width][3]; the flow image has w = width / div by h = height / div
+ * pixels; prev(y, x) ~ next(y + flow.y, x + flow.x), in flow-image pixels.
+ *   mmf_flow_default_config  div 4, levels 1, winsize 20, iterations 2, poly_n 5, poly_sigma 0.3
+ *   mmf_flow_create          MMF_ERR_INVALID -- before any device is touched, never a fall back -- for levels != 1, div not in
+ *                        {1, 2, 4}, a width or height div does not divide, a flow image under 8 x 8, winsize outside [2, 33],
+ *                        poly_n outside [3, 7], iterations outside [1, 10], poly_sigma <= 0
+ *   mmf_flow_compute         a stateless pair (it ends the sequence of mmf_flow_next: the buffers are shared)
+ *   mmf_flow_next            the next frame of a sequence: the first call after create / reset / compute yields no flow
+ *                        (*has_flow = 0), every later one the flow from the frame before it.  The engine keeps the last
+ *                        frame's expansion: a frame pays stages 1-4 once.
+ *   mmf_flow_result          DEVICE pointers: flow [h][w][2] = {x, y}, magnitude [h][w] = sqrtf(x x + y y), motion [h][w] =
+ *                        clamp((magnitude - 0.2) / 4.8, 0, 1) (Segmentation.cpp:1193-1197); valid until the next compute /
+ *                        next.  w, h are written in any case; MMF_ERR_STATE while there is no flow.
+ *   mmf_flow_download        a stage image to HOST memory, for tests: "gray" / "smooth" (the latest frame; "gray0" / "smooth0":
+ *                        the pair's first frame) u8 / f32 [h][w]; "R0" / "R1" (the pair's expansions) and "M" (the matrices
+ *                        the last iteration read) f32 [h][w][5]; "flow_<i>" (behind iteration i) f32 [h][w][2]; "magnitude",
+ *                        "motion".  bytes must be the image's size.  Synchronous.
+ *   mmf_flow_tables          the tables the kernels read: g, xg, xxg [poly_n + 1], ig [4] = {ig11, ig03, ig33, ig55}
+ *   mmf_flow_make_tables     the tables of an engine with (poly_n, poly_sigma): host arithmetic, no device
+ *   mmf_flow_last_launches   kernel launches of the last compute / next: 1 + 2 * iterations for a pair (1 for the first frame
+ *                        of a sequence), whatever the size
+ * compute and next are asynchronous on the context's stream.
+ * Inside processFrame:
+ *   mmf_fusion_set_optical_flow   cfg != NULL: every frame's flow from the frame before it is computed from the frame's RGB by
+ *                        an engine of the fusion's own (mmf_flow_next), on a stream of its own beside the tracking, behind the
+ *                        point of the fusion's stream where the frame's RGB is on the device, and joined by the fusion's stream
+ *                        before the call returns.  NULL (the default): off -- the engine, its stream and events are freed, and
+ *                        no frame allocates, enqueues or waits for anything.  Poses, maps and masks are the same bits either
+ *                        way.  mmf_fusion_reset starts a new sequence.  MMF_ERR_INVALID as mmf_flow_create; MMF_ERR_STATE on a
+ *                        sharded fusion (world > 1).
+ *   mmf_fusion_last_flow          the last call's flow (as mmf_flow_result; pointers into the fusion's engine, valid until the
+ *                        next frame); *has_flow = 0 and null pointers after the first frame of a sequence.  MMF_ERR_STATE
+ *                        while the hook is off. */
+typedef struct mmf_flow mmf_flow;
+typedef struct {
+    int div;          /* the flow image is the frame scaled down by 1, 2 or 4 (area mean) */
+    int levels;       /* 1 */
+    int winsize;      /* the averaging window is (2 (winsize / 2) + 1)^2 */
+    int iterations;
+    int poly_n;       /* radius of the polynomial expansion */
+    float poly_sigma; /* its Gaussian's standard deviation */
+} mmf_flow_config;
+int mmf_flow_default_config(mmf_flow_config *cfg);
+int mmf_flow_create(mmf_ctx *ctx, int width, int height, const mmf_flow_config *cfg, mmf_flow **out);
+void mmf_flow_destroy(mmf_flow *flow);
+int mmf_flow_compute(mmf_flow *flow, const uint8_t *prev_rgb, const uint8_t *next_rgb);
+int mmf_flow_next(mmf_flow *flow, const uint8_t *rgb, int *has_flow);
+int mmf_flow_reset(mmf_flow *flow);
+int mmf_flow_result(mmf_flow *flow, const float **flow_dev, const float **magnitude_dev, const float **motion_dev, int *w, int *h);
+int mmf_flow_download(mmf_flow *flow, const char *name, void *host_dst, size_t bytes);
+int mmf_flow_tables(mmf_flow *flow, float *g, float *xg, float *xxg, float *ig);
+int mmf_flow_make_tables(int poly_n, float poly_sigma, float *g, float *xg, float *xxg, float *ig);
+int mmf_flow_last_launches(mmf_flow *flow);
+int mmf_fusion_set_optical_flow(mmf_fusion *f, const mmf_flow_config *cfg);
+int mmf_fusion_last_flow(mmf_fusion *f, const float **flow_dev, const float **magnitude_dev, const float **motion_dev, int *w,
+                         int *h, int *has_flow);
+
 #ifdef __cplusplus
 }
 #endif

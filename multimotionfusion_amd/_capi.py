@@ -116,6 +116,11 @@ class mmf_ransac_result(C.Structure):
                 ("status", C.c_int)]
 
 
+class mmf_flow_config(C.Structure):
+    _fields_ = [("div", C.c_int), ("levels", C.c_int), ("winsize", C.c_int), ("iterations", C.c_int), ("poly_n", C.c_int),
+                ("poly_sigma", C.c_float)]
+
+
 SEGMENTATION_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(mmf_frame), C.POINTER(mmf_segmentation))
 
 
@@ -357,6 +362,19 @@ SIGNATURES = {
     "mmf_debug_hash_float": (_i, [_vp, _i, _vp, _vp]),
     "mmf_debug_ransac_core_host": (_i, [C.POINTER(mmf_ransac_config), _vp, _vp, _i, _vp, _fp, _vp, _ip]),
     "mmf_debug_rounded_ops": (_i, [_vp, _i, _vp, _vp, _sz, _vp]),
+    "mmf_flow_default_config": (_i, [C.POINTER(mmf_flow_config)]),
+    "mmf_flow_create": (_i, [_vp, _i, _i, C.POINTER(mmf_flow_config), C.POINTER(_vp)]),
+    "mmf_flow_destroy": (None, [_vp]),
+    "mmf_flow_compute": (_i, [_vp, _vp, _vp]),
+    "mmf_flow_next": (_i, [_vp, _vp, _ip]),
+    "mmf_flow_reset": (_i, [_vp]),
+    "mmf_flow_result": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _ip, _ip]),
+    "mmf_flow_download": (_i, [_vp, C.c_char_p, _vp, _sz]),
+    "mmf_flow_tables": (_i, [_vp, _fp, _fp, _fp, _fp]),
+    "mmf_flow_make_tables": (_i, [_i, _f, _fp, _fp, _fp, _fp]),
+    "mmf_flow_last_launches": (_i, [_vp]),
+    "mmf_fusion_set_optical_flow": (_i, [_vp, C.POINTER(mmf_flow_config)]),
+    "mmf_fusion_last_flow": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _ip, _ip, _ip]),
 }
 
 _lib = None

@@ -648,6 +648,39 @@ class MultiMotionFusion {
     // the built-in segmentation's super-pixels from the frame's RGB on the device (the engine that replaces gSLICr,
     // cpp/Slic.h) instead of the regular grid; sp_size must divide the frame size
     void setSuperpixelEngine(bool v) { other_["superpixelEngine"] = v, mmf::check(mmf_fusion_set_superpixel_engine(f_, v ? 1 : 0), "mmf_fusion_set_superpixel_engine"); }
+    // Every frame's dense optical flow from the frame before it (the flow stage of "flow_crf", Segmentation.cpp:779-804:
+    // Farneback on the pair scaled down by four, the reference's settings), computed beside the tracking; off until
+    // switched on.  Only the flow field: the flow_crf segmentation itself is not here.  getLastFlow(): the last frame's
+    // field in host memory, `valid` false after the first frame of a sequence (creation, reset) and while the hook is off.
+    struct OpticalFlow {
+        bool valid = false;
+        int width = 0, height = 0;            // the flow image: the frame's size / 4
+        std::vector<float> flow;              // [height][width][2] = {x, y}: prev(y, x) ~ next(y + flow.y, x + flow.x)
+        std::vector<float> magnitude, motion; // [height][width]; motion = clamp((magnitude - 0.2) / 4.8, 0, 1) (:1193-1197)
+    };
+    void setOpticalFlow(bool v) {
+        mmf_flow_config c;
+        mmf::check(mmf_flow_default_config(&c), "mmf_flow_default_config");
+        mmf::check(mmf_fusion_set_optical_flow(f_, v ? &c : nullptr), "mmf_fusion_set_optical_flow");
+        other_["opticalFlow"] = v, flow_on_ = v;
+    }
+    OpticalFlow getLastFlow() {
+        OpticalFlow out;
+        if (!flow_on_) return out;
+        const float *flow = nullptr, *magnitude = nullptr, *motion = nullptr;
+        int has = 0;
+        mmf::check(mmf_fusion_last_flow(f_, &flow, &magnitude, &motion, &out.width, &out.height, &has), "mmf_fusion_last_flow");
+        if (!has) return out;
+        mmf::check(mmf_ctx_synchronize(ctx_), "mmf_ctx_synchronize");  // (the fusion's stream has joined the flow's)
+        const size_t px = (size_t)out.width * out.height;
+        out.flow.resize(2 * px), out.magnitude.resize(px), out.motion.resize(px);
+        if (hipMemcpy(out.flow.data(), flow, 2 * px * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(out.magnitude.data(), magnitude, px * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(out.motion.data(), motion, px * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+            mmf::check(MMF_ERR_HIP, "getLastFlow: download");
+        out.valid = true;
+        return out;
+    }
     // redetection of inactive models by their stored keypoint views (:489-559), inside processFrame; off until switched on
     void setEnableRedetection(bool v) { other_["enableRedetection"] = v, mmf::check(mmf_fusion_set_redetection(f_, v ? 1 : 0), "mmf_fusion_set_redetection"); }
     // where the redetection candidates are verified: 0 = host (default), 1 = device, a fresh RigidRANSAC per view (mmf_hip.h)
@@ -791,6 +824,7 @@ class MultiMotionFusion {
     float fx_ = 0, fy_ = 0, cx_ = 0, cy_ = 0;
     SuperPoint* kp_predictor_ = nullptr;
     bool kp_on_device_ = false;
+    bool flow_on_ = false;
     std::unique_ptr<tracker::PointTracker> tracker_;
     unsigned char* kp_rgb_ = nullptr;
     float* kp_depth_ = nullptr;

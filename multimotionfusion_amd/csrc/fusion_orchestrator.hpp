@@ -96,6 +96,14 @@ struct mmf_fusion {
     hipEvent_t ev_sp_done = nullptr;   // engine stream: this frame's labels are complete
     bool sp_enqueued = false;          // ev_sp_done is recorded and nothing has waited for it yet
     const int* sp_last = nullptr;      // the label image the last segmentation used (handed in, the engine's, or the grid)
+    // the optical-flow engine (mmf_fusion_set_optical_flow; flow_host.hpp): every frame's dense flow from the frame before
+    // it, on a stream of its own beside the tracking chains; nothing below exists while the hook is off
+    mmf_flow* flow = nullptr;            // owned
+    hipStream_t flow_stream = nullptr;
+    hipEvent_t ev_flow_begin = nullptr;  // fusion stream: the frame's RGB is on the device, the last flow's readers are done
+    hipEvent_t ev_flow_done = nullptr;   // flow stream: this frame's flow is complete
+    bool flow_pending = false;           // ev_flow_done is recorded and the fusion's stream has not waited for it yet
+    bool flow_has = false;               // the last frame produced a flow (not the first frame, nor the first after a reset)
     std::vector<mmf_segmentation_model> crf_models;
     // the segmentation from the frame's raw label image (mmf_fusion_set_mask_segmentation): off unless configured
     bool mask_on = false;
@@ -370,6 +378,17 @@ extern "C" int mmf_fusion_preallocate_models(mmf_fusion* f, unsigned count) {
     return MMF_OK;
 }
 
+// the optical-flow hook's engine, stream and events, once the stream has run dry
+static void fusion_flow_release(mmf_fusion* f) {
+    if (!f->flow) return;
+    flow_destroy_on(f->flow, f->flow_stream);
+    (void)hipEventDestroy(f->ev_flow_begin);
+    (void)hipEventDestroy(f->ev_flow_done);
+    (void)hipStreamDestroy(f->flow_stream);
+    f->flow = nullptr, f->flow_stream = nullptr, f->ev_flow_begin = f->ev_flow_done = nullptr;
+    f->flow_pending = f->flow_has = false;
+}
+
 extern "C" void mmf_fusion_destroy(mmf_fusion* f) {
     if (!f) return;
     (void)hipSetDevice(f->ctx->device);
@@ -389,6 +408,7 @@ extern "C" void mmf_fusion_destroy(mmf_fusion* f) {
     if (f->ev_sp_begin) (void)hipEventDestroy(f->ev_sp_begin);
     if (f->ev_sp_done) (void)hipEventDestroy(f->ev_sp_done);
     if (f->sp_stream) (void)hipStreamDestroy(f->sp_stream);
+    fusion_flow_release(f);
     mmf_viewstore_destroy(f->views);
     mmf_ransac_batch_destroy(f->verifier);
     if (f->kp_xy_pin) (void)hipHostFree(f->kp_xy_pin);
@@ -461,6 +481,7 @@ extern "C" int mmf_fusion_set_shard(mmf_fusion* f, int rank, int world) {
     MMF_REQUIRE(f->models.size() == 1 && f->inactive.empty(), "mmf_fusion_set_shard: call it before the first object model is spawned");
     if (world > 1 && f->redetect_on) return fail(MMF_ERR_STATE, "mmf_fusion_set_shard: redetection is on (sharded redetection is not supported)");
     if (world > 1 && f->redetect_verifier) return fail(MMF_ERR_STATE, "mmf_fusion_set_shard: the redetection verifier is on (not supported on a shard)");
+    if (world > 1 && f->flow) return fail(MMF_ERR_STATE, "mmf_fusion_set_shard: the optical-flow hook is on (not supported on a shard)");
     f->shard_rank = rank, f->shard_world = world;
     // models created ahead of their use (preallocateModels): the ones this rank will not own shrink to bookkeeping
     for (FusionModel*& fm : f->preallocated) {
@@ -645,6 +666,48 @@ extern "C" int mmf_fusion_last_superpixels(mmf_fusion* f, int* labels_out) {
     MMF_HIP_TRY(hipMemcpyAsync(labels_out, f->sp_last, (size_t)f->width * f->height * sizeof(int), hipMemcpyDeviceToDevice, f->ctx->stream));
     MMF_HIP_TRY(hipStreamSynchronize(f->ctx->stream));
     return MMF_OK;
+}
+// The optical-flow hook: cfg != NULL creates the fusion's own engine for its frame size (a second call replaces it: a new
+// sequence), NULL frees it with its stream and events.  Off by default; while off no frame allocates, enqueues or waits for
+// anything of it.  The configuration is checked before the device is touched.
+extern "C" int mmf_fusion_set_optical_flow(mmf_fusion* f, const mmf_flow_config* cfg) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_set_optical_flow: null fusion object");
+    if (cfg) {
+        if (int rc = flow_check_config(f->width, f->height, cfg, "mmf_fusion_set_optical_flow")) return rc;
+        if (f->shard_world > 1) return fail(MMF_ERR_STATE, "mmf_fusion_set_optical_flow: not available on a sharded fusion");
+    }
+    MMF_HIP_TRY(hipSetDevice(f->ctx->device));
+    fusion_flow_release(f);
+    if (!cfg) return MMF_OK;
+    if (int rc = flow_create_impl(f->ctx, f->width, f->height, cfg, &f->flow, "mmf_fusion_set_optical_flow")) return rc;
+    hipError_t e = hipStreamCreateWithFlags(&f->flow_stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_flow_begin, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_flow_done, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        if (f->ev_flow_begin) (void)hipEventDestroy(f->ev_flow_begin);
+        if (f->flow_stream) (void)hipStreamDestroy(f->flow_stream);
+        flow_destroy_on(f->flow, nullptr);
+        f->flow = nullptr, f->flow_stream = nullptr, f->ev_flow_begin = f->ev_flow_done = nullptr;
+        return fail(MMF_ERR_HIP, std::string("mmf_fusion_set_optical_flow: ") + hipGetErrorString(e));
+    }
+    return MMF_OK;
+}
+// The flow of the last processFrame call from the frame before it: DEVICE pointers into the hook's engine (flow [h][w][2],
+// magnitude and motion [h][w]), complete for work enqueued on the context's stream behind that call (or after
+// mmf_ctx_synchronize) and valid until the next frame, reset or setter call.  *has_flow = 0 (and null pointers) after the
+// first frame of a sequence.  MMF_ERR_STATE while the hook is off.
+extern "C" int mmf_fusion_last_flow(mmf_fusion* f, const float** flow_dev, const float** magnitude_dev, const float** motion_dev, int* w,
+                                    int* h, int* has_flow) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_last_flow: null fusion object");
+    if (!f->flow) return fail(MMF_ERR_STATE, "mmf_fusion_last_flow: the optical-flow hook is off (mmf_fusion_set_optical_flow)");
+    if (flow_dev) *flow_dev = nullptr;
+    if (magnitude_dev) *magnitude_dev = nullptr;
+    if (motion_dev) *motion_dev = nullptr;
+    if (w) *w = f->flow->geo.W;
+    if (h) *h = f->flow->geo.H;
+    if (has_flow) *has_flow = f->flow_has ? 1 : 0;
+    if (!f->flow_has) return MMF_OK;
+    return mmf_flow_result(f->flow, flow_dev, magnitude_dev, motion_dev, nullptr, nullptr);
 }
 extern "C" int mmf_fusion_last_segmentation(mmf_fusion* f, mmf_crf_info* info, mmf_segmentation_model* models, int capacity,
                                             float* unaries, float* q, uint8_t* raw_map, uint8_t* map) {
@@ -938,6 +1001,8 @@ struct FrameRun {
     bool early_snapshot_valid = false;
     int pass_mode = 0;  // fusion_batch_mode, once the frame's model list is final
     bool superpixels = false;  // the super-pixel engine runs for this frame (ev_sp_begin is recorded)
+    bool flow = false;         // the optical-flow engine runs for this frame (ev_flow_begin is recorded) ...
+    bool flow_enqueued = false;  // ... and its launches are on the flow stream
 
     // MMF_HOST_TRACE=1: where the calling thread is, in us after the call began (averages over 100 calls)
     void stamp(mmf_fusion* f, int i) const {
@@ -1399,6 +1464,37 @@ static int frame_superpixels_enqueue(mmf_fusion* f, const FrameRun& r) {
     return MMF_OK;
 }
 
+// The optical flow of this frame from the one before it (mmf_fusion_set_optical_flow).  Like the label image it depends on
+// the frame's RGB only.  ev_flow_begin is recorded on the fusion's stream when the call begins: the RGB is on the device
+// there (a host frame's upload has been joined), and whatever read the last frame's flow on that stream is done.  The
+// launches go to the flow stream behind that event -- on a tracked frame once the chains are enqueued, as the super-pixel
+// engine's do -- and the fusion's stream joins them at the end of the call (frame_flow_join).
+static int frame_flow_begin(mmf_fusion* f, FrameRun& r) {
+    mmf_ctx* c = f->ctx;
+    if (f->flow_pending) {  // a frame that failed between the enqueue and the join
+        MMF_HIP_TRY(hipStreamWaitEvent(c->stream, f->ev_flow_done, 0));
+        f->flow_pending = false;
+    }
+    MMF_HIP_TRY(hipEventRecord(f->ev_flow_begin, c->stream));
+    r.flow = true;
+    return MMF_OK;
+}
+static int frame_flow_enqueue(mmf_fusion* f, FrameRun& r) {
+    MMF_HIP_TRY(hipStreamWaitEvent(f->flow_stream, f->ev_flow_begin, 0));
+    int has = 0;
+    f->flow_has = false;
+    if (int rc = flow_next_on(f->flow, r.fr->rgb, f->flow_stream, &has)) return rc;
+    MMF_HIP_TRY(hipEventRecord(f->ev_flow_done, f->flow_stream));
+    f->flow_pending = true, f->flow_has = has != 0;
+    r.flow_enqueued = true;
+    return MMF_OK;
+}
+static int frame_flow_join(mmf_fusion* f) {
+    MMF_HIP_TRY(hipStreamWaitEvent(f->ctx->stream, f->ev_flow_done, 0));
+    f->flow_pending = false;
+    return MMF_OK;
+}
+
 // :299-400: every model's tracking, enqueued before the first result is awaited, then the bootstrap
 static int frame_track(mmf_fusion* f, FrameRun& r) {
     const mmf_frame* fr = r.fr;
@@ -1428,6 +1524,10 @@ static int frame_track(mmf_fusion* f, FrameRun& r) {
     }
     if (r.superpixels) {  // the super-pixel engine, beside the chains
         rc = frame_superpixels_enqueue(f, r);
+        if (rc) return rc;
+    }
+    if (r.flow) {  // the optical-flow engine, beside the chains
+        rc = frame_flow_enqueue(f, r);
         if (rc) return rc;
     }
     r.stamp(f, 0);
@@ -2258,9 +2358,18 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
     f->t_tracking_s = 0;
     f->redetections.clear();  // (mmf_fusion_last_redetections speaks of this call)
     f->stored_ids.clear(), f->stored_views.clear(), f->stored_rows.clear();
-    int rc = frame_begin(f, r);
+    int rc = MMF_OK;
+    if (f->flow) {
+        rc = frame_flow_begin(f, r);
+        if (rc) return rc;
+    }
+    rc = frame_begin(f, r);
     if (rc) return rc;
     const bool first = f->tick == 1;
+    if (r.flow && (first || !r.track)) {  // (a tracked frame enqueues it behind its chains: frame_track)
+        rc = frame_flow_enqueue(f, r);
+        if (rc) return rc;
+    }
     if (first) {
         rc = frame_first(f, r);
         if (rc) return rc;
@@ -2299,6 +2408,10 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
     frame_log_poses(f, r);
     rc = frame_end(f, r);
     if (rc) return rc;
+    if (r.flow_enqueued) {
+        rc = frame_flow_join(f);
+        if (rc) return rc;
+    }
     r.stamp(f, 5);
     if (r.host_trace && ++f->trace_calls % 100 == 0) {
         std::fprintf(stderr, "host us from call start: next image side enqueued %.0f, lanes waiting %.0f, preparation enqueued %.0f (batched chains), chains enqueued %.0f, "
@@ -2669,6 +2782,10 @@ extern "C" int mmf_fusion_reset(mmf_fusion* f) {
     }
     for (FusionModel* fm : all) fm->spec_valid = false;
     f->so3_stage_ready = -1, f->image_pre_rgb = nullptr;
+    if (f->flow) {  // the next frame is the first of a sequence: it yields no flow
+        (void)mmf_flow_reset(f->flow);
+        f->flow_has = false;
+    }
     f->tick = 1;
     return MMF_OK;
 }

@@ -3326,6 +3326,10 @@ extern "C" int mmf_debug_set_stamps(void* dev_buf) {
 }
 #endif
 
+// ---- dense optical flow after Farneback (flow_kernels.hpp, flow_host.hpp; Segmentation.cpp:779-804) ----
+#include "flow_kernels.hpp"
+#include "flow_host.hpp"
+
 // =============================================================================================
 // Orchestrator: MultiMotionFusion::processFrame / predict (Core/MultiMotionFusion.cpp:207-854, 863-875)
 // =============================================================================================

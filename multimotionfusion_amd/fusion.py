@@ -314,6 +314,28 @@ class MultiMotionFusion:
         check(self.ctx.lib.mmf_fusion_last_superpixels(self.handle, _p(out)))
         return out
 
+    def setOpticalFlow(self, config=True):
+        """every frame's dense optical flow from the frame before it, computed from its RGB on a stream of its own beside
+        the tracking (flow.FarnebackFlow's engine, DESIGN.md 4.8).  True: the reference's settings; a flow.FlowConfig: those;
+        False / None (the default state): off, the engine is freed.  Poses, maps and masks do not depend on it."""
+        from .flow import FlowConfig
+        if config is None or config is False:
+            check(self.ctx.lib.mmf_fusion_set_optical_flow(self.handle, None))
+            return
+        cfg = FlowConfig() if config is True else config
+        check(self.ctx.lib.mmf_fusion_set_optical_flow(self.handle, C.byref(cfg.c)))
+
+    def getLastFlow(self):
+        """(flow [h,w,2], magnitude [h,w], motion [h,w]) float32 CUDA tensors (copies) of the last frame, or None after the
+        first frame of a sequence (creation, reset)"""
+        from .flow import _result_tensors
+
+        def getter(*a):
+            has = C.c_int()
+            check(self.ctx.lib.mmf_fusion_last_flow(*a, C.byref(has)))
+            return bool(has.value)
+        return _result_tensors(self.ctx, getter, self.handle)
+
     def getLastSegmentation(self):
         """segmentation.last() of this fusion: unaries, Q, raw and filtered maps, model data, range, B4 flag"""
         import torch
