@@ -1217,6 +1217,120 @@ int mmf_fusion_set_optical_flow(mmf_fusion *f, const mmf_flow_config *cfg);
 int mmf_fusion_last_flow(mmf_fusion *f, const float **flow_dev, const float **magnitude_dev, const float **motion_dev, int *w,
                          int *h, int *has_flow);
 
+/* ---- the inference of the flow CRF (csrc/flowcrf_kernels.hpp, csrc/flowcrf_host.hpp) -----------------------
+ * The stage of the reference's flow_crf segmentation that turns tracks, flow, depth and the models' predictions into fused label
+ * probabilities and the MAP id image (Core/Segmentation/Segmentation.cpp:819-1263), as an engine of its own.  What follows it
+ * in the reference (contours, the largest blob, ModelData, hasNewLabel, spawning; :1270-1324) is NOT here, nor is the
+ * "flow_crf" mode.  The arithmetic is the one DESIGN.md 4.9 writes out and tests/flowcrf_oracle.py restates.  The CRF image has
+ * w = width / 4 by h = height / 4 cells, N = w h, and L = n_models + (allow_new ? 1 : 0) <= 32 labels, the new label last.
+ *   (a) track errors   per model m and track k (Model::computeTrackProjectionStartEnd with length 2, Model.cpp:524-579): the
+ *       start keypoint is the track's `prev` slot, the end its `cur` slot; a slot that is null, has stamp 0 or a non-finite
+ *       coordinate gives no keypoint.  T_start[m] / T_end[m] (the reference's poses[-2] pose^-1 and poses.back() pose^-1) are
+ *       widened to double and applied as ((r0 x + r1 y) + r2 z) + t; the pixel is round-half-away(c + (p.xy / p.z) f) in double.
+ *       A track with a keypoint missing, a non-finite transformed coordinate or a pixel outside the frame is skipped (a pixel
+ *       that is no number counts as outside).  v = |xy_end - xy_start| / ((t_end - t_start) 1e-9), the difference of the stamps
+ *       as uint64_t, in double, rounded to float.  Its cell is (rint(x_end / 4), rint(y_end / 4)), half to even, its index
+ *       cy w + cx AS THE REFERENCE WRITES IT: a column equal to w wraps into the next row, an index >= N is dropped (the
+ *       reference writes out of bounds there).  Several tracks on a cell: the highest table index wins.  E [L][N] starts at +inf.
+ *   (b) unaries        an active row's finite v becomes v > threshold ? 1 : 0; with allow_new the last row is any(v < threshold)
+ *       over the active rows where all of them are finite, +inf elsewhere.  p = softmax(-E) per cell; a cell whose exp sum is
+ *       not > 0 (all +inf, or a NaN from equal stamps) gets 1 / L.  U = -log p; +inf is legal and gives Q = 0.
+ *   (c) projection     per model |depth - z| at (4x, 4y) (z = channel 2 of the model's [height][width][4] vertex image), min(.,
+ *       max_err) (a NaN becomes max_err), exp(-d / max_err), divided by the sum over the models; 0 where depth < 1e-6 && z < 1e-6
+ *       for any model, 0 where < min_proj_prob.  The new label's row is 0 (the reference leaves it uninitialised).
+ *   (d) mean field     Q = softmax(-U); iterations x Q = softmax(-U + 4 weight_smoothness D_s K_s D_s Q + weight_appearance D_a K_a
+ *       D_a Q), K = exp(-|f_i - f_j|^2 / 2) over EVERY pair (j = i included), D = 1 / sqrt(sum_j K_ij + 1e-20); smoothness
+ *       features (x / 3, y / 3), appearance features ((float)(x / 40), (float)(y / 40)) -- integer divisions -- and 10 flow.
+ *       The smoothness sum is evaluated separably and skips factors that are exactly 0 in float (|dx| or |dy| >= 44).
+ *   (e) fusion         prob = 1 - (1 - Q motion)(1 - proj); label = the first maximum; ids [h][w] u8 = ids[label];
+ *       ids_full [height][width] u8 = ids scaled up by 4, nearest (what mmf_mask_segment takes).
+ *   mmf_flowcrf_default_config  div 4, iterations 10, weight_smoothness 40, weight_appearance 40, threshold 20 px/s, max_err 0.03 m,
+ *                        min_proj_prob 0.3
+ *   mmf_flowcrf_create       MMF_ERR_INVALID -- before any device is touched -- for div != 4, a width or height 4 does not divide,
+ *                        max_labels outside [1, 32], iterations outside [0, 50], weights, threshold or max_err that are not
+ *                        positive.  max_tracks: the most tracks (a tracker's capacity) an inference may be given.  fx .. cy: the
+ *                        camera of the frame.  The image need not fit in LDS (1280 x 960 works).
+ *   mmf_flowcrf_infer        one inference from plain DEVICE arrays of `count` tracks (tracks == NULL or count 0: no tracks, every
+ *                        unary is log L).  Asynchronous on the context's stream; every input is read by the enqueued work.
+ *   mmf_flowcrf_infer_tracker  the same from a tracker's table (its `cur` / `prev` slots: xy, coordinate, stamp, non-null flag;
+ *                        the number of tracks is read on the device).  NULL: no tracks.
+ *   mmf_flowcrf_result       DEVICE pointers, valid until the next inference: ids [h][w] u8, ids_full [height][width] u8, prob and
+ *                        Q f32 [L][N].  w, h are written in any case; MMF_ERR_STATE before the first inference.
+ *   mmf_flowcrf_download     a stage image to HOST memory, for tests: "E", "U", "proj", "Q", "prob" f32 [L][N]; "label" i32 [N];
+ *                        "ids", "invalid" u8 [N]; "ids_full" u8 [height][width]; "cell" i32 [n_models][max_tracks] (a track's cell
+ *                        index per model, -1: no sample).  Synchronous.
+ *   mmf_flowcrf_last_launches  kernel launches of the last inference: 5 + 3 iterations (4 at iterations 0), plus one memset,
+ *                        whatever the image size, the labels and the tracks.
+ * Inside processFrame:
+ *   mmf_fusion_set_flow_inference  cfg != NULL: every TRACKED frame that has a flow runs the inference where the reference
+ *                        segments -- behind the tracking, on the predictions the frame was tracked against -- with the active
+ *                        models in list order, the new label (id = the next model id) when enable_multiple_models is set,
+ *                        T_start = prev pose^-1 and T_end = pose pose^-1 per model, and the attached tracker's table
+ *                        (mmf_fusion_set_tracker; none: every unary is log L).  pose is the model's pose of this frame
+ *                        (poses.back(): tracked, or with the tracker's icp_refine off the keypoint-initialised one), prev the
+ *                        pose the frame before left it (poses[-2]) -- NOT Model::lastPose, which a keypoint initialisation
+ *                        overrides with this frame's initial pose.  A model's first tracked frame has prev = the pose it
+ *                        was created with.  It runs on the flow's stream behind the flow; the fusion's stream joins it before
+ *                        the call returns.  Observational: poses, maps and masks are the same bits with it on or off, and it
+ *                        fails no frame: one with more than 32 labels has no result.  NULL (the default): off -- the engine
+ *                        and its events are freed and no frame allocates, enqueues or waits for anything.  MMF_ERR_INVALID
+ *                        as mmf_flowcrf_create; MMF_ERR_STATE while the optical-flow hook is off, when it does not run at
+ *                        div 4, and on a sharded fusion.  mmf_fusion_set_optical_flow(NULL) switches this hook off too; a
+ *                        call that replaces the flow engine switches it on again with its configuration if the new engine
+ *                        runs at div 4 (no result until the second frame), else leaves it off.
+ *   mmf_fusion_last_flow_inference  the last call's id images (DEVICE pointers into the fusion's engine, valid until the next
+ *                        frame): ids [h][w], ids_full [height][width]; *has_result = 0 and null pointers after the first frame
+ *                        of a sequence, a frame that was not tracked or one with more than 32 labels.  MMF_ERR_STATE while
+ *                        the hook is off.
+ *   mmf_fusion_flow_inference_download  a stage image of that inference to HOST memory, as mmf_flowcrf_download, for tests.
+ *                        MMF_ERR_STATE while the hook is off and after a frame without a result. */
+typedef struct mmf_flowcrf mmf_flowcrf;
+typedef struct {
+    int div;        /* 4 */
+    int iterations; /* mean-field updates */
+    float weight_smoothness, weight_appearance;
+    float threshold;     /* pixels per second: a track faster than this in a model's frame is that model's outlier */
+    float max_err;       /* metres: the projection error is truncated here */
+    float min_proj_prob; /* projection probabilities under this become 0 */
+} mmf_flowcrf_config;
+typedef struct {
+    int n_models;             /* the active models, in list order; >= 1 */
+    int allow_new;            /* append the new label */
+    unsigned new_id;          /* its id */
+    const unsigned char *ids; /* HOST [n_models] */
+    const float *T_start;     /* HOST [n_models][16], row-major 4 x 4 */
+    const float *T_end;       /* HOST [n_models][16] */
+    const float *const *vertex; /* HOST array of n_models DEVICE pointers, f32 [height][width][4] each */
+    const float *depth;       /* DEVICE f32 [height][width], metres */
+    const float *flow;        /* DEVICE f32 [h][w][2] */
+    const float *motion;      /* DEVICE f32 [h][w] (mmf_flow_result's third image) */
+} mmf_flowcrf_input;
+typedef struct {
+    const int *xy_cur;         /* DEVICE [count][2] */
+    const float *co_cur;       /* DEVICE [count][3] */
+    const long long *ts_cur;   /* DEVICE [count] */
+    const int *ok_cur;         /* DEVICE [count], 0: a null slot */
+    const int *xy_prev;
+    const float *co_prev;
+    const long long *ts_prev;
+    const int *ok_prev;
+    int count;
+} mmf_flowcrf_tracks;
+int mmf_flowcrf_default_config(mmf_flowcrf_config *cfg);
+int mmf_flowcrf_create(mmf_ctx *ctx, int width, int height, int max_labels, int max_tracks, float fx, float fy, float cx, float cy,
+                       const mmf_flowcrf_config *cfg, mmf_flowcrf **out);
+void mmf_flowcrf_destroy(mmf_flowcrf *fc);
+int mmf_flowcrf_infer(mmf_flowcrf *fc, const mmf_flowcrf_input *in, const mmf_flowcrf_tracks *tracks);
+int mmf_flowcrf_infer_tracker(mmf_flowcrf *fc, const mmf_flowcrf_input *in, mmf_tracker *tracker);
+int mmf_flowcrf_result(mmf_flowcrf *fc, const uint8_t **ids_dev, const uint8_t **ids_full_dev, const float **prob_dev,
+                       const float **q_dev, int *w, int *h, int *n_labels);
+int mmf_flowcrf_download(mmf_flowcrf *fc, const char *name, void *host_dst, size_t bytes);
+int mmf_flowcrf_last_launches(mmf_flowcrf *fc);
+int mmf_fusion_set_flow_inference(mmf_fusion *f, const mmf_flowcrf_config *cfg);
+int mmf_fusion_last_flow_inference(mmf_fusion *f, const uint8_t **ids_dev, const uint8_t **ids_full_dev, int *w, int *h,
+                                   int *n_labels, int *has_result);
+int mmf_fusion_flow_inference_download(mmf_fusion *f, const char *name, void *host_dst, size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,23 @@ class mmf_flow_config(C.Structure):
                 ("poly_sigma", C.c_float)]
 
 
+class mmf_flowcrf_config(C.Structure):
+    _fields_ = [("div", C.c_int), ("iterations", C.c_int), ("weight_smoothness", C.c_float), ("weight_appearance", C.c_float),
+                ("threshold", C.c_float), ("max_err", C.c_float), ("min_proj_prob", C.c_float)]
+
+
+class mmf_flowcrf_input(C.Structure):
+    _fields_ = [("n_models", C.c_int), ("allow_new", C.c_int), ("new_id", C.c_uint), ("ids", C.POINTER(C.c_ubyte)),
+                ("T_start", C.POINTER(C.c_float)), ("T_end", C.POINTER(C.c_float)), ("vertex", C.POINTER(C.c_void_p)),
+                ("depth", C.c_void_p), ("flow", C.c_void_p), ("motion", C.c_void_p)]
+
+
+class mmf_flowcrf_tracks(C.Structure):
+    _fields_ = [("xy_cur", C.c_void_p), ("co_cur", C.c_void_p), ("ts_cur", C.c_void_p), ("ok_cur", C.c_void_p),
+                ("xy_prev", C.c_void_p), ("co_prev", C.c_void_p), ("ts_prev", C.c_void_p), ("ok_prev", C.c_void_p),
+                ("count", C.c_int)]
+
+
 SEGMENTATION_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(mmf_frame), C.POINTER(mmf_segmentation))
 
 
@@ -375,6 +392,17 @@ SIGNATURES = {
     "mmf_flow_last_launches": (_i, [_vp]),
     "mmf_fusion_set_optical_flow": (_i, [_vp, C.POINTER(mmf_flow_config)]),
     "mmf_fusion_last_flow": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _ip, _ip, _ip]),
+    "mmf_flowcrf_default_config": (_i, [C.POINTER(mmf_flowcrf_config)]),
+    "mmf_flowcrf_create": (_i, [_vp, _i, _i, _i, _i, _f, _f, _f, _f, C.POINTER(mmf_flowcrf_config), C.POINTER(_vp)]),
+    "mmf_flowcrf_destroy": (None, [_vp]),
+    "mmf_flowcrf_infer": (_i, [_vp, C.POINTER(mmf_flowcrf_input), C.POINTER(mmf_flowcrf_tracks)]),
+    "mmf_flowcrf_infer_tracker": (_i, [_vp, C.POINTER(mmf_flowcrf_input), _vp]),
+    "mmf_flowcrf_result": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _ip, _ip, _ip]),
+    "mmf_flowcrf_download": (_i, [_vp, C.c_char_p, _vp, _sz]),
+    "mmf_flowcrf_last_launches": (_i, [_vp]),
+    "mmf_fusion_set_flow_inference": (_i, [_vp, C.POINTER(mmf_flowcrf_config)]),
+    "mmf_fusion_last_flow_inference": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _ip, _ip, _ip, _ip]),
+    "mmf_fusion_flow_inference_download": (_i, [_vp, C.c_char_p, _vp, _sz]),
 }
 
 _lib = None

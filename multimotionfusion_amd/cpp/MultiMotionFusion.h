@@ -663,6 +663,9 @@ class MultiMotionFusion {
         mmf::check(mmf_flow_default_config(&c), "mmf_flow_default_config");
         mmf::check(mmf_fusion_set_optical_flow(f_, v ? &c : nullptr), "mmf_fusion_set_optical_flow");
         other_["opticalFlow"] = v, flow_on_ = v;
+        // (the inference reads the flow: off with it; setOpticalFlow(true) again replaces the flow engine -- a new sequence --
+        // and the library switches the inference back on with it, so the flag stands)
+        if (!v && flow_inference_on_) other_["flowInference"] = false, flow_inference_on_ = false;
     }
     OpticalFlow getLastFlow() {
         OpticalFlow out;
@@ -678,6 +681,38 @@ class MultiMotionFusion {
             hipMemcpy(out.magnitude.data(), magnitude, px * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(out.motion.data(), motion, px * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
             mmf::check(MMF_ERR_HIP, "getLastFlow: download");
+        out.valid = true;
+        return out;
+    }
+    // The inference of flow_crf (Segmentation.cpp:819-1263; mmf_fusion_set_flow_inference) on every tracked frame
+    // that has a flow; it needs setOpticalFlow(true).  Observational: the id image is handed out, the models do not use it.
+    // getLastFlowInference(): the last frame's id images in host memory, `valid` false after the first frame of a sequence,
+    // after a frame that was not tracked and while the hook is off.
+    struct FlowInference {
+        bool valid = false;
+        int width = 0, height = 0, labels = 0;  // the CRF image: the frame's size / 4
+        std::vector<unsigned char> ids;       // [height][width] model ids (the new label's: the next model id)
+        std::vector<unsigned char> ids_full;  // [4 height][4 width]: the same scaled up by 4
+    };
+    void setFlowInference(bool v) {
+        mmf_flowcrf_config c;
+        mmf::check(mmf_flowcrf_default_config(&c), "mmf_flowcrf_default_config");
+        mmf::check(mmf_fusion_set_flow_inference(f_, v ? &c : nullptr), "mmf_fusion_set_flow_inference");
+        other_["flowInference"] = v, flow_inference_on_ = v;
+    }
+    FlowInference getLastFlowInference() {
+        FlowInference out;
+        if (!flow_inference_on_) return out;
+        const uint8_t *ids = nullptr, *full = nullptr;
+        int has = 0;
+        mmf::check(mmf_fusion_last_flow_inference(f_, &ids, &full, &out.width, &out.height, &out.labels, &has), "mmf_fusion_last_flow_inference");
+        if (!has) return out;
+        mmf::check(mmf_ctx_synchronize(ctx_), "mmf_ctx_synchronize");  // (the fusion's stream has joined the flow's)
+        const size_t px = (size_t)out.width * out.height;
+        out.ids.resize(px), out.ids_full.resize(16 * px);
+        if (hipMemcpy(out.ids.data(), ids, px, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(out.ids_full.data(), full, 16 * px, hipMemcpyDeviceToHost) != hipSuccess)
+            mmf::check(MMF_ERR_HIP, "getLastFlowInference: download");
         out.valid = true;
         return out;
     }
@@ -825,6 +860,7 @@ class MultiMotionFusion {
     SuperPoint* kp_predictor_ = nullptr;
     bool kp_on_device_ = false;
     bool flow_on_ = false;
+    bool flow_inference_on_ = false;
     std::unique_ptr<tracker::PointTracker> tracker_;
     unsigned char* kp_rgb_ = nullptr;
     float* kp_depth_ = nullptr;

@@ -31,6 +31,10 @@ struct FusionModel {  // one ModelPointer of the reference's `models` list
     mmf_model* model = nullptr;
     mmf_odom* odom = nullptr;  // Model::frameToModel
     float last_pose[16];       // Model::lastPose
+    // the pose the model came into the running frame with, i.e. the one the frame before left it (frame_init_poses): while a
+    // frame runs this is the reference's poses[-2] -- overridePose changes pose and lastPose but logs nothing; every frame
+    // logs one pose per model, tracked (Model.cpp:430) or not (MultiMotionFusion.cpp:385).  Read by the flow inference only.
+    float prev_pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     int fill_in = 0;           // Model::allowsFillIn()
     long long unseen = 0;      // Model::unseenCount
     float* icp_error = nullptr;  // Model::icpError / rgbError (R32F, enableErrorRecording)
@@ -104,6 +108,14 @@ struct mmf_fusion {
     hipEvent_t ev_flow_done = nullptr;   // flow stream: this frame's flow is complete
     bool flow_pending = false;           // ev_flow_done is recorded and the fusion's stream has not waited for it yet
     bool flow_has = false;               // the last frame produced a flow (not the first frame, nor the first after a reset)
+    // the flow-CRF inference (mmf_fusion_set_flow_inference; flowcrf_host.hpp): on the flow stream behind the flow, on every
+    // tracked frame that has one; observational.  Nothing below exists while the hook is off
+    bool fi_on = false;
+    mmf_flowcrf_config fi_cfg{};
+    mmf_flowcrf* fi = nullptr;          // owned; created by the first frame that needs it, for its labels and the tracker's capacity
+    hipEvent_t ev_fi_begin = nullptr;   // fusion stream: the tracking is done, the track table and the predictions are as the frame met them
+    hipEvent_t ev_fi_inputs = nullptr;  // flow stream: the inference has read them
+    bool fi_has = false;                // the last frame produced an id image
     std::vector<mmf_segmentation_model> crf_models;
     // the segmentation from the frame's raw label image (mmf_fusion_set_mask_segmentation): off unless configured
     bool mask_on = false;
@@ -378,9 +390,20 @@ extern "C" int mmf_fusion_preallocate_models(mmf_fusion* f, unsigned count) {
     return MMF_OK;
 }
 
+// the flow-inference hook's engine and events, once the flow's stream has run dry
+static void fusion_flow_inference_release(mmf_fusion* f) {
+    if (!f->fi_on) return;
+    if (f->fi) flowcrf_destroy_on(f->fi, f->flow_stream);
+    (void)hipStreamSynchronize(f->flow_stream);
+    (void)hipEventDestroy(f->ev_fi_begin);
+    (void)hipEventDestroy(f->ev_fi_inputs);
+    f->fi = nullptr, f->ev_fi_begin = f->ev_fi_inputs = nullptr;
+    f->fi_on = f->fi_has = false;
+}
 // the optical-flow hook's engine, stream and events, once the stream has run dry
 static void fusion_flow_release(mmf_fusion* f) {
     if (!f->flow) return;
+    fusion_flow_inference_release(f);  // (it lives on the flow's stream and reads the flow)
     flow_destroy_on(f->flow, f->flow_stream);
     (void)hipEventDestroy(f->ev_flow_begin);
     (void)hipEventDestroy(f->ev_flow_done);
@@ -669,7 +692,9 @@ extern "C" int mmf_fusion_last_superpixels(mmf_fusion* f, int* labels_out) {
 }
 // The optical-flow hook: cfg != NULL creates the fusion's own engine for its frame size (a second call replaces it: a new
 // sequence), NULL frees it with its stream and events.  Off by default; while off no frame allocates, enqueues or waits for
-// anything of it.  The configuration is checked before the device is touched.
+// anything of it.  The configuration is checked before the device is touched.  The flow-inference hook lives on the engine
+// that leaves: NULL switches it off as well; a replacement at div 4 switches it on again with the configuration it had (a new
+// sequence for it too: no result until the second frame), a replacement at another div leaves it off.
 extern "C" int mmf_fusion_set_optical_flow(mmf_fusion* f, const mmf_flow_config* cfg) {
     MMF_REQUIRE(f != nullptr, "mmf_fusion_set_optical_flow: null fusion object");
     if (cfg) {
@@ -677,6 +702,8 @@ extern "C" int mmf_fusion_set_optical_flow(mmf_fusion* f, const mmf_flow_config*
         if (f->shard_world > 1) return fail(MMF_ERR_STATE, "mmf_fusion_set_optical_flow: not available on a sharded fusion");
     }
     MMF_HIP_TRY(hipSetDevice(f->ctx->device));
+    const bool rearm = f->fi_on && cfg && cfg->div == 4;
+    const mmf_flowcrf_config fi_cfg = f->fi_cfg;
     fusion_flow_release(f);
     if (!cfg) return MMF_OK;
     if (int rc = flow_create_impl(f->ctx, f->width, f->height, cfg, &f->flow, "mmf_fusion_set_optical_flow")) return rc;
@@ -690,7 +717,7 @@ extern "C" int mmf_fusion_set_optical_flow(mmf_fusion* f, const mmf_flow_config*
         f->flow = nullptr, f->flow_stream = nullptr, f->ev_flow_begin = f->ev_flow_done = nullptr;
         return fail(MMF_ERR_HIP, std::string("mmf_fusion_set_optical_flow: ") + hipGetErrorString(e));
     }
-    return MMF_OK;
+    return rearm ? mmf_fusion_set_flow_inference(f, &fi_cfg) : MMF_OK;
 }
 // The flow of the last processFrame call from the frame before it: DEVICE pointers into the hook's engine (flow [h][w][2],
 // magnitude and motion [h][w]), complete for work enqueued on the context's stream behind that call (or after
@@ -708,6 +735,55 @@ extern "C" int mmf_fusion_last_flow(mmf_fusion* f, const float** flow_dev, const
     if (has_flow) *has_flow = f->flow_has ? 1 : 0;
     if (!f->flow_has) return MMF_OK;
     return mmf_flow_result(f->flow, flow_dev, magnitude_dev, motion_dev, nullptr, nullptr);
+}
+
+// The flow-CRF inference hook: cfg != NULL switches it on (a second call replaces the configuration), NULL off -- the engine
+// and its events are freed, and no frame allocates, enqueues or waits for anything.  It reads the optical-flow hook's result.
+extern "C" int mmf_fusion_set_flow_inference(mmf_fusion* f, const mmf_flowcrf_config* cfg) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_set_flow_inference: null fusion object");
+    if (cfg) {
+        if (int rc = flowcrf_check_config(f->width, f->height, mmf::kCrfMaxLabels, 0, cfg, "mmf_fusion_set_flow_inference")) return rc;
+        if (f->shard_world > 1) return fail(MMF_ERR_STATE, "mmf_fusion_set_flow_inference: not available on a sharded fusion");
+        if (!f->flow) return fail(MMF_ERR_STATE, "mmf_fusion_set_flow_inference: the optical-flow hook is off (mmf_fusion_set_optical_flow)");
+        if (f->flow->cfg.div != 4) return fail(MMF_ERR_STATE, "mmf_fusion_set_flow_inference: the optical-flow hook must run at div 4");
+    }
+    MMF_HIP_TRY(hipSetDevice(f->ctx->device));
+    fusion_flow_inference_release(f);
+    if (!cfg) return MMF_OK;
+    hipError_t e = hipEventCreateWithFlags(&f->ev_fi_begin, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_fi_inputs, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        if (f->ev_fi_begin) (void)hipEventDestroy(f->ev_fi_begin);
+        f->ev_fi_begin = f->ev_fi_inputs = nullptr;
+        return fail(MMF_ERR_HIP, std::string("mmf_fusion_set_flow_inference: ") + hipGetErrorString(e));
+    }
+    f->fi_cfg = *cfg, f->fi_on = true;
+    return MMF_OK;
+}
+
+// The id images of the last processFrame call: DEVICE pointers into the hook's engine (ids [h][w], ids_full [height][width]),
+// complete on the fusion's stream and valid until the next frame, reset or setter call.  *has_result = 0 (and null pointers)
+// after a frame without a flow (the first of a sequence) or without tracking.
+extern "C" int mmf_fusion_last_flow_inference(mmf_fusion* f, const uint8_t** ids_dev, const uint8_t** ids_full_dev, int* w, int* h,
+                                              int* n_labels, int* has_result) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_last_flow_inference: null fusion object");
+    if (!f->fi_on) return fail(MMF_ERR_STATE, "mmf_fusion_last_flow_inference: the flow-inference hook is off (mmf_fusion_set_flow_inference)");
+    if (ids_dev) *ids_dev = nullptr;
+    if (ids_full_dev) *ids_full_dev = nullptr;
+    if (w) *w = f->width / 4;
+    if (h) *h = f->height / 4;
+    if (n_labels) *n_labels = 0;
+    if (has_result) *has_result = f->fi_has ? 1 : 0;
+    if (!f->fi_has) return MMF_OK;
+    return mmf_flowcrf_result(f->fi, ids_dev, ids_full_dev, nullptr, nullptr, nullptr, nullptr, n_labels);
+}
+// A stage image of the last call's inference to HOST memory, as mmf_flowcrf_download (tests: "E" shows the poses and the track
+// table the hook handed its engine).  MMF_ERR_STATE while the hook is off and after a frame without a result.
+extern "C" int mmf_fusion_flow_inference_download(mmf_fusion* f, const char* name, void* host_dst, size_t bytes) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_flow_inference_download: null fusion object");
+    if (!f->fi_on) return fail(MMF_ERR_STATE, "mmf_fusion_flow_inference_download: the flow-inference hook is off (mmf_fusion_set_flow_inference)");
+    if (!f->fi_has) return fail(MMF_ERR_STATE, "mmf_fusion_flow_inference_download: the last frame has no result");
+    return mmf_flowcrf_download(f->fi, name, host_dst, bytes);
 }
 extern "C" int mmf_fusion_last_segmentation(mmf_fusion* f, mmf_crf_info* info, mmf_segmentation_model* models, int capacity,
                                             float* unaries, float* q, uint8_t* raw_map, uint8_t* map) {
@@ -1225,6 +1301,7 @@ static int frame_init_poses(mmf_fusion* f, FrameRun& r) {
         FusionModel* fm = f->models[k];
         fm->tracking = false;
         if (!fusion_owns(f, k)) continue;
+        mmf_model_get_pose(fm->model, fm->prev_pose);  // (before the initialisation below replaces pose and last_pose)
         if (k > 0) {
             if (!r.will_batch) {
                 int rc = lane_wait(fm, f->ev_frame_ready);
@@ -1334,7 +1411,7 @@ static int frame_enqueue_tracking(mmf_fusion* f, FrameRun& r) {
         // The frame's first projection, enqueued right behind this chain (frame_enqueue_ahead), carries the hand-over to the
         // host and the fusion weight on one extra workgroup (frame_rider.hpp): the chain's last launch is the solve alone (13
         // -> 5.7 us on the stream a frame waits for).
-        fm->odom->defer_publish = tracked.size() == 1 && !fr->bootstrap && !r.have_init && !g.rgb_only && f->tracking_ok;
+        fm->odom->defer_publish = tracked.size() == 1 && !fr->bootstrap && !r.have_init && !g.rgb_only && f->tracking_ok && !f->fi_on;
         int rc = fusion_enqueue_chains(f, &fm, 1, false, false);
         if (rc) return rc;
     }
@@ -1351,6 +1428,7 @@ static int frame_enqueue_ahead(mmf_fusion* f, FrameRun& r) {
     const mmf_fusion_config& g = f->cfg;
     static_assert(std::is_trivially_copyable<mmf_model>::value, "the speculation rollback copies mmf_model by value");
     if (!(r.tracked.size() == 1 && !r.fr->bootstrap && !r.have_init && !g.rgb_only && f->tracking_ok)) return MMF_OK;
+    if (f->fi_on) return MMF_OK;  // (the flow inference reads the prediction the frame was tracked against: frame_flow_inference)
     FusionModel* fm = r.tracked[0];
     mmf_model* m = fm->model;
     r.early_snapshot = *m, r.early_snapshot_valid = true;
@@ -1492,6 +1570,65 @@ static int frame_flow_enqueue(mmf_fusion* f, FrameRun& r) {
 static int frame_flow_join(mmf_fusion* f) {
     MMF_HIP_TRY(hipStreamWaitEvent(f->ctx->stream, f->ev_flow_done, 0));
     f->flow_pending = false;
+    return MMF_OK;
+}
+
+// The flow-CRF inference of this frame (mmf_fusion_set_flow_inference), where the reference segments: behind the tracking, on
+// the predictions the frame was tracked against (nothing has rewritten them yet: frame_enqueue_ahead stands back while the
+// hook is on).  The active models in list order, the new label when models may spawn; T_start = prev_pose pose^-1 and
+// T_end = pose pose^-1 (Model.cpp:556-557: poses.back() is this frame's pose, tracked or -- with the refinement off --
+// initialised; poses[-2] is the pose the frame before ended with, whatever overridePose has done to lastPose since); the
+// attached tracker's table, if any.  On the flow stream behind the flow; the fusion's stream and the models' streams wait
+// until the inference has read the predictions and the table (two launches), the rest is joined with the flow
+// (frame_flow_join).  A frame with more labels than the engine takes has no result (has_result 0): the hook fails no frame.
+static int frame_flow_inference(mmf_fusion* f) {
+    mmf_ctx* c = f->ctx;
+    const int M = (int)f->models.size(), allow_new = f->cfg.enable_multiple_models ? 1 : 0, L = M + allow_new;
+    if (L > mmf::kCrfMaxLabels) return MMF_OK;
+    const int cap = f->tracker ? f->tracker->capacity : 0;
+    if (!f->fi || f->fi->max_labels < L || f->fi->max_tracks < cap) {
+        if (f->fi) flowcrf_destroy_on(f->fi, f->flow_stream);
+        f->fi = nullptr;
+        int rc = flowcrf_create_impl(c, f->width, f->height, std::max(4, flowcrf_pad_labels(L)), cap, f->fx, f->fy, f->cx, f->cy, &f->fi_cfg,
+                                     &f->fi, "mmf_fusion_process_frame (flow inference)");
+        if (rc) return rc;
+    }
+    unsigned char ids[mmf::kCrfMaxLabels];
+    const float* vertex[mmf::kCrfMaxLabels];
+    std::vector<float> T((size_t)2 * 16 * M);
+    for (int k = 0; k < M; ++k) {
+        FusionModel* fm = f->models[(size_t)k];
+        float pose[16], inv[16];
+        mmf_model_get_pose(fm->model, pose);
+        inverse4f_host(pose, inv);
+        mmf::host::matmul4(fm->prev_pose, inv, T.data() + 16 * (size_t)k);
+        mmf::host::matmul4(pose, inv, T.data() + 16 * (size_t)(M + k));
+        ids[k] = fm->model->id;
+        vertex[k] = reinterpret_cast<const float*>(fm->model->vertexConf);
+        if (fm->lane->stream != c->stream) {  // (its last prediction ran there)
+            MMF_HIP_TRY(hipEventRecord(fm->ev_done, fm->lane->stream));
+            MMF_HIP_TRY(hipStreamWaitEvent(f->flow_stream, fm->ev_done, 0));
+        }
+    }
+    mmf_flowcrf_input in;
+    std::memset(&in, 0, sizeof(in));
+    in.n_models = M, in.allow_new = allow_new, in.new_id = (unsigned)mmf_fusion_next_model_id(f), in.ids = ids;
+    in.T_start = T.data(), in.T_end = T.data() + 16 * (size_t)M, in.vertex = vertex, in.depth = f->frame_depth;
+    int rc = mmf_flow_result(f->flow, &in.flow, nullptr, &in.motion, nullptr, nullptr);
+    if (rc) return rc;
+    if (int bad = flowcrf_check_input(f->fi, &in, "mmf_fusion_process_frame (flow inference)")) return bad;
+    mmf::FcrfTracks tr;
+    rc = flowcrf_tracker_view(f->fi, f->tracker, &tr, "mmf_fusion_process_frame (flow inference)");
+    if (rc) return rc;
+    MMF_HIP_TRY(hipEventRecord(f->ev_fi_begin, c->stream));
+    MMF_HIP_TRY(hipStreamWaitEvent(f->flow_stream, f->ev_fi_begin, 0));
+    rc = flowcrf_run_on(f->fi, &in, tr, f->flow_stream, f->ev_fi_inputs);
+    if (rc) return rc;
+    MMF_HIP_TRY(hipEventRecord(f->ev_flow_done, f->flow_stream));  // (frame_flow_join waits for the inference as well)
+    MMF_HIP_TRY(hipStreamWaitEvent(c->stream, f->ev_fi_inputs, 0));
+    for (FusionModel* fm : f->models)
+        if (fm->lane->stream != c->stream) MMF_HIP_TRY(hipStreamWaitEvent(fm->lane->stream, f->ev_fi_inputs, 0));
+    f->fi_has = true;
     return MMF_OK;
 }
 
@@ -2360,6 +2497,7 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
     f->stored_ids.clear(), f->stored_views.clear(), f->stored_rows.clear();
     int rc = MMF_OK;
     if (f->flow) {
+        f->fi_has = false;
         rc = frame_flow_begin(f, r);
         if (rc) return rc;
     }
@@ -2382,6 +2520,10 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
         rc = r.track ? frame_track(f, r) : frame_dictated_pose(f, r);
         if (rc) return rc;
         if (r.track) fusion_note_view_poses(f, true);
+        if (f->fi_on && r.track && r.flow_enqueued && f->flow_has) {
+            rc = frame_flow_inference(f);
+            if (rc) return rc;
+        }
         if (r.track && f->cfg.enable_multiple_models) {
             rc = frame_segment(f, r);
             if (rc) return rc;
@@ -2784,7 +2926,7 @@ extern "C" int mmf_fusion_reset(mmf_fusion* f) {
     f->so3_stage_ready = -1, f->image_pre_rgb = nullptr;
     if (f->flow) {  // the next frame is the first of a sequence: it yields no flow
         (void)mmf_flow_reset(f->flow);
-        f->flow_has = false;
+        f->flow_has = f->fi_has = false;
     }
     f->tick = 1;
     return MMF_OK;

@@ -3330,6 +3330,10 @@ extern "C" int mmf_debug_set_stamps(void* dev_buf) {
 #include "flow_kernels.hpp"
 #include "flow_host.hpp"
 
+// ---- the inference of the flow CRF (flowcrf_kernels.hpp, flowcrf_host.hpp; Segmentation.cpp:819-1263) ----
+#include "flowcrf_kernels.hpp"
+#include "flowcrf_host.hpp"
+
 // =============================================================================================
 // Orchestrator: MultiMotionFusion::processFrame / predict (Core/MultiMotionFusion.cpp:207-854, 863-875)
 // =============================================================================================

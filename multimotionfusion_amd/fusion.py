@@ -336,6 +336,47 @@ class MultiMotionFusion:
             return bool(has.value)
         return _result_tensors(self.ctx, getter, self.handle)
 
+    def setFlowInference(self, config=True):
+        """the flow-CRF inference (flowcrf.FlowCrf's engine) on every tracked frame that has a flow, on the
+        flow's stream behind it; needs setOpticalFlow.  True: the reference's settings; a flowcrf.FlowCrfConfig: those;
+        False / None (the default state): off, the engine is freed.  Poses, maps and masks do not depend on it."""
+        from .flowcrf import FlowCrfConfig
+        if config is None or config is False:
+            check(self.ctx.lib.mmf_fusion_set_flow_inference(self.handle, None))
+            return
+        cfg = FlowCrfConfig() if config is True else config
+        check(self.ctx.lib.mmf_fusion_set_flow_inference(self.handle, C.byref(cfg.c)))
+
+    def getLastFlowInference(self):
+        """(ids [h/4,w/4], ids_full [h,w]) uint8 CUDA tensors (copies) of the last frame, or None after the first frame of a
+        sequence and after a frame that was not tracked"""
+        import torch
+        from .model import _as_tensor
+        p_ids, p_full = C.c_void_p(), C.c_void_p()
+        w, h, L, has = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        check(self.ctx.lib.mmf_fusion_last_flow_inference(self.handle, C.byref(p_ids), C.byref(p_full), C.byref(w), C.byref(h),
+                                                          C.byref(L), C.byref(has)))
+        if not has.value:
+            return None
+        self.ctx.synchronize()  # (the copies below run on torch's stream, which need not be the context's)
+        ids = _as_tensor(p_ids.value, w.value * h.value, torch.uint8, (h.value, w.value), self.ctx.device, None).clone()
+        full = _as_tensor(p_full.value, 16 * w.value * h.value, torch.uint8, (4 * h.value, 4 * w.value), self.ctx.device, None).clone()
+        return ids, full
+
+    def downloadFlowInference(self, name):
+        """a stage image of the last frame's inference as a numpy array (tests), as flowcrf.FlowCrf.download: E / U / proj /
+        Q / prob float32 [L,h/4,w/4]; label int32, ids / invalid uint8 [h/4,w/4]; ids_full uint8 [h,w]"""
+        w, h, L, has = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        check(self.ctx.lib.mmf_fusion_last_flow_inference(self.handle, None, None, C.byref(w), C.byref(h), C.byref(L), C.byref(has)))
+        if name in ("E", "U", "proj", "Q", "prob"):
+            out = np.empty((L.value, h.value, w.value), np.float32)
+        elif name == "ids_full":
+            out = np.empty((4 * h.value, 4 * w.value), np.uint8)
+        else:
+            out = np.empty((h.value, w.value), np.int32 if name == "label" else np.uint8)
+        check(self.ctx.lib.mmf_fusion_flow_inference_download(self.handle, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        return out
+
     def getLastSegmentation(self):
         """segmentation.last() of this fusion: unaries, Q, raw and filtered maps, model data, range, B4 flag"""
         import torch
