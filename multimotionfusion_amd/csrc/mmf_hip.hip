@@ -959,7 +959,7 @@ extern "C" int mmf_odom_create(mmf_ctx* c, int width, int height, float cx, floa
     return MMF_OK;
 }
 
-// The odometry of a model ANOTHER rank tracks (fusion_orchestrator.hpp: a shard rank's bookkeeping copies): the host
+// The odometry of a model ANOTHER rank tracks (fusion_state.hpp: a shard rank's bookkeeping copies): the host
 // struct only -- statistics as they arrive with the pose exchange -- no slab, no events, nothing a kernel could be given.
 static int odom_create_bookkeeping(mmf_ctx* c, int width, int height, float cx, float cy, float fx, float fy, mmf_odom** out) {
     mmf_odom* o = new (std::nothrow) mmf_odom();
@@ -3337,6 +3337,11 @@ extern "C" int mmf_debug_set_stamps(void* dev_buf) {
 // =============================================================================================
 // Orchestrator: MultiMotionFusion::processFrame / predict (Core/MultiMotionFusion.cpp:207-854, 863-875)
 // =============================================================================================
+#include "stream_lane.hpp"
+#include "fusion_state.hpp"
+#include "fusion_hooks.hpp"
+#include "fusion_keypoints.hpp"
+#include "fusion_ingest.hpp"
 #include "fusion_orchestrator.hpp"
 
 // =============================================================================================

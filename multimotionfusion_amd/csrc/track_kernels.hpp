@@ -924,7 +924,7 @@ __global__ void odom_begin_kernel(OdomState* st, BeginArgs a, BatchDelta bd, Beg
     odom_begin_model(sm, st, a, blockIdx.x > 0, (int)threadIdx.x);
 }
 // The last launch of a frame's model-side preparation (prep_batch.hpp) with the beginning of the tracking it prepares on one
-// more workgroup: when a frame is prepared at the end of the call before it (fusion_orchestrator.hpp: FusionModel::spec_valid)
+// more workgroup: when a frame is prepared at the end of the call before it (fusion_state.hpp: FusionModel::spec_valid)
 // the pose it starts from, the mode and the staged pre-alignment are known as well, and odom_begin_kernel -- 4-5 us of one
 // lane's bookkeeping between the preparation and the first Gauss-Newton launch on the stream a frame waits for -- runs beside
 // the preparation's last stage instead.  odom_enqueue_tracking skips its own launch when the arguments it would pass are

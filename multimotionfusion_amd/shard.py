@@ -17,7 +17,7 @@ import torch.distributed as dist
 
 def model_owner(model_id: int, world_size: int) -> int:
     """the model with id m lives on rank m mod G (the global model, id 0, on rank 0) -- by ID, not by position in the list:
-    a model that leaves the list moves nobody else (csrc/fusion_orchestrator.hpp: fusion_owner_of)."""
+    a model that leaves the list moves nobody else (csrc/fusion_state.hpp: fusion_owner_of)."""
     return model_id % world_size
 
 
