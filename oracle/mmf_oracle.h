@@ -162,6 +162,7 @@ void orc_synthesize_depth(const orc_surfel *s, int count, const float pose[16], 
 /* keypoint descriptor matcher (mmf_oracle_match.c): cv::BFMatcher(NORM_L2, crossCheck).match + distance gate */
 int orc_match_descriptors(const float *query, int nq, const float *train, int nt, int dim, float max_distance,
                           int *train_idx, float *distance);
+void orc_match_d2(const float *query, int nq, const float *train, int nt, int dim, float *d2_out);
 /* SuperPoint network + keypoint post-processing (mmf_oracle_superpoint.c; channels-last activations) */
 void orc_sp_conv(const float *in, int H, int W, int in_stride, int cin, const float *w, const float *bias, int cout, int taps,
                  int relu, float *out);

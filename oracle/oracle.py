@@ -538,6 +538,18 @@ def match_descriptors(query, train, max_distance=0.0):
     return idx, dist
 
 
+def match_d2(query, train):
+    """[nq, nt] float32: the squared distances d2(i, j) = (|q_i|^2 + |t_j|^2) - 2 <q_i, t_j> that match_descriptors takes
+    its minima of, by the same fmaf chains (negative, +inf and NaN entries as they come)."""
+    q, t = _f(query), _f(train)
+    nq, nt = q.shape[0], t.shape[0]
+    dim = q.shape[1] if nq else (t.shape[1] if nt else 0)
+    d2 = np.zeros((nq, nt), np.float32)
+    lib().orc_match_d2.restype = None
+    lib().orc_match_d2(_pf(q), nq, _pf(t), nt, dim, _pf(d2))
+    return d2
+
+
 # ---- SuperPoint (mmf_oracle_superpoint.c) ----------------------------------------------------------------
 SP_LAYERS = (("conv1a", 1, 64, 3), ("conv1b", 64, 64, 3), ("conv2a", 64, 64, 3), ("conv2b", 64, 64, 3),
              ("conv3a", 64, 128, 3), ("conv3b", 128, 128, 3), ("conv4a", 128, 128, 3), ("conv4b", 128, 128, 3),
