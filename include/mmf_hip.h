@@ -1220,8 +1220,8 @@ int mmf_fusion_last_flow(mmf_fusion *f, const float **flow_dev, const float **ma
 /* ---- the inference of the flow CRF (csrc/flowcrf_kernels.hpp, csrc/flowcrf_host.hpp) -----------------------
  * The stage of the reference's flow_crf segmentation that turns tracks, flow, depth and the models' predictions into fused label
  * probabilities and the MAP id image (Core/Segmentation/Segmentation.cpp:819-1263), as an engine of its own.  What follows it
- * in the reference (contours, the largest blob, ModelData, hasNewLabel, spawning; :1270-1324) is NOT here, nor is the
- * "flow_crf" mode.  The arithmetic is the one DESIGN.md 4.9 writes out and tests/flowcrf_oracle.py restates.  The CRF image has
+ * in the reference (contours, the largest blob, ModelData, hasNewLabel; :1270-1324) is mmf_flowseg_*, the "flow_crf" mode
+ * mmf_fusion_set_flow_segmentation (both below).  The arithmetic is the one DESIGN.md 4.9 writes out and tests/flowcrf_oracle.py restates.  The CRF image has
  * w = width / 4 by h = height / 4 cells, N = w h, and L = n_models + (allow_new ? 1 : 0) <= 32 labels, the new label last.
  *   (a) track errors   per model m and track k (Model::computeTrackProjectionStartEnd with length 2, Model.cpp:524-579): the
  *       start keypoint is the track's `prev` slot, the end its `cur` slot; a slot that is null, has stamp 0 or a non-finite
@@ -1264,7 +1264,8 @@ int mmf_fusion_last_flow(mmf_fusion *f, const float **flow_dev, const float **ma
  * Inside processFrame:
  *   mmf_fusion_set_flow_inference  cfg != NULL: every TRACKED frame that has a flow runs the inference where the reference
  *                        segments -- behind the tracking, on the predictions the frame was tracked against -- with the active
- *                        models in list order, the new label (id = the next model id) when enable_multiple_models is set,
+ *                        models in list order, the new label (id = the next model id) when enable_multiple_models is set (with
+                        mmf_fusion_set_flow_segmentation on: when a model may spawn, see there),
  *                        T_start = prev pose^-1 and T_end = pose pose^-1 per model, and the attached tracker's table
  *                        (mmf_fusion_set_tracker; none: every unary is log L).  pose is the model's pose of this frame
  *                        (poses.back(): tracked, or with the tracker's icp_refine off the keypoint-initialised one), prev the
@@ -1330,6 +1331,78 @@ int mmf_fusion_set_flow_inference(mmf_fusion *f, const mmf_flowcrf_config *cfg);
 int mmf_fusion_last_flow_inference(mmf_fusion *f, const uint8_t **ids_dev, const uint8_t **ids_full_dev, int *w, int *h,
                                    int *n_labels, int *has_result);
 int mmf_fusion_flow_inference_download(mmf_fusion *f, const char *name, void *host_dst, size_t bytes);
+
+/* ---- the blob stage of the flow_crf segmentation (csrc/flowseg_kernels.hpp, csrc/flowseg_host.hpp) ----------
+ * What the reference does with the MAP id image of the inference (Core/Segmentation/Segmentation.cpp:1270-1324): the largest
+ * blob per model, the filled contours, the resize, ModelData and hasNewLabel.  ids [h][w] u8 is what mmf_flowcrf_result hands
+ * out (w = width / 4, h = height / 4), the label table is the models' ids in list order, then the new id with allow_new.
+ *   (a) components     per id of the table the 8-connected components of ids == id; "component" = the raster index of a
+ *       component's first cell, -1 for a cell whose id is not in the table (such a cell is never drawn).
+ *   (b) area           area2 = 2 cv::contourArea of the component's outer border as cv::findContours(RETR_EXTERNAL,
+ *       CHAIN_APPROX_NONE) follows it from that first cell: an integer.
+ *   (c) winner         per id the component of maximal (area2, first cell): a tie -- all areas 0 included -- goes to the
+ *       component found LAST in raster order, which is the first of OpenCV's contour list (not pinned).
+ *       segm_count = rint(area2 / 2), half to even; an id without a cell has count 0 and draws nothing.
+ *   (d) fill           the winner's cells and every cell its border polygon winds around (its holes and what lies in them); ids
+ *       in ascending order onto a zero image, so a cell takes the highest id that covers it: segm [h][w] u8.
+ *   (e) full           full [height][width] u8 = segm scaled by 4, nearest.
+ *   (f) model data     per table entry: super_pixel_count = (unsigned)((float)segm_count 16.0f), avg_confidence, depth_mean =
+ *       sum d / n and depth_std = sqrt(max(sum d^2 / n - mean^2, 0)) over the pixels full == id, zero depth included, in
+ *       float64 and a fixed order (same input, same bits); both 0 for n = 0.
+ *   (g) new label      has_new_label = allow_new && (float)count(segm == new_id) / (float)(w h) > new_model_size; when it is
+ *       not, the new label's entry is dropped (n_entries = n_models).
+ *   mmf_flowseg_default_config  div 4, new_model_size 0.05, avg_confidence 0.4, model_spawn_offset 22, inhibit_new 0
+ *   mmf_flowseg_create       MMF_ERR_INVALID -- before any device is touched -- for div != 4, a width or height 4 does not
+ *                        divide, max_labels outside [1, 32], new_model_size outside [0, 1), a negative model_spawn_offset.
+ *   mmf_flowseg_run          asynchronous on the context's stream: ids_dev [h][w] u8 and depth_dev [height][width] f32 are
+ *                        DEVICE images read by the enqueued work; ids_host = the n_models >= 1 model ids (HOST, distinct,
+ *                        new_id not among them, new_id <= 255).  Eight kernel launches and two memsets whatever the image holds.
+ *   mmf_flowseg_result       waits for the run; segm / full: DEVICE pointers valid until the next run; *summary: a copy of the
+ *                        one pinned read.  w, h are written in any case; MMF_ERR_STATE before the first run.
+ *   mmf_flowseg_download     a stage image to HOST memory, for tests: "component", "area2" (of the cell's component) i32 [h][w];
+ *                        "winner" (1: the cell is of its id's winning component), "segm" u8 [h][w]; "full" u8 [height][width].
+ *   mmf_flowseg_last_launches  kernel launches of the last run.
+ * Inside processFrame (the reference's -segm_mode flow_crf):
+ *   mmf_fusion_set_flow_segmentation  cfg != NULL: a frame that brings no segmentation of its own is segmented from the
+ *                        flow-inference hook's id image, on the fusion's stream behind the inference, into the fusion's mask;
+ *                        one host wait for the summary.  The inference then runs with allow_new = spawnOffset >=
+ *                        cfg->model_spawn_offset (MultiMotionFusion.cpp:148) instead of enable_multiple_models; inhibit_new
+ *                        clears has_new_label afterwards.  A frame without an inference result (an untracked frame, one
+ *                        without a flow, one with more than 32 labels) gets a zero mask, no entries and no new label: nobody
+ *                        is counted unseen, no max depth or confidence threshold moves (the reference reads modelData out of
+ *                        bounds there).  NULL (the default): off, everything freed.  MMF_ERR_STATE while the flow-inference
+ *                        hook is off and on a sharded fusion; switching the flow or the inference hook off -- or replacing the
+ *                        flow engine -- switches this off too.
+ *   mmf_fusion_last_flow_segmentation  what the last frame this path handled computed: *summary (has_new_label as
+ *                        processFrame used it, after inhibit_new), *has_result = 0 for a frame without an inference result.
+ *                        MMF_ERR_STATE before the first such frame. */
+typedef struct mmf_flowseg mmf_flowseg;
+typedef struct {
+    int div;                /* 4 */
+    float new_model_size;   /* the new label's share of the cells above which it spawns (0.05) */
+    float avg_confidence;   /* every entry's avg_confidence (0.4) */
+    int model_spawn_offset; /* frames between spawns (22); processFrame only */
+    int inhibit_new;        /* setSetInhibit; processFrame only */
+} mmf_flowseg_config;
+typedef struct {
+    int n_entries;          /* entries of models: the table's, without the new label's when has_new_label == 0 */
+    int allow_new, has_new_label;
+    unsigned new_cells;     /* count(segm == new_id); 0 without allow_new */
+    mmf_segmentation_model models[32];
+    int area2[32];          /* per table entry: the winner's 2 x contour area; 0: none */
+    int first_cell[32];     /* ... and the raster index of its first cell; -1: the id has no cell */
+} mmf_flowseg_summary;
+int mmf_flowseg_default_config(mmf_flowseg_config *cfg);
+int mmf_flowseg_create(mmf_ctx *ctx, int width, int height, int max_labels, const mmf_flowseg_config *cfg, mmf_flowseg **out);
+void mmf_flowseg_destroy(mmf_flowseg *fs);
+int mmf_flowseg_run(mmf_flowseg *fs, const uint8_t *ids_dev, const float *depth_dev, const unsigned char *ids_host, int n_models,
+                    int allow_new, unsigned new_id);
+int mmf_flowseg_result(mmf_flowseg *fs, const uint8_t **segm_dev, const uint8_t **full_dev, mmf_flowseg_summary *summary, int *w,
+                       int *h);
+int mmf_flowseg_download(mmf_flowseg *fs, const char *name, void *host_dst, size_t bytes);
+int mmf_flowseg_last_launches(mmf_flowseg *fs);
+int mmf_fusion_set_flow_segmentation(mmf_fusion *f, const mmf_flowseg_config *cfg);
+int mmf_fusion_last_flow_segmentation(mmf_fusion *f, mmf_flowseg_summary *summary, int *has_result);
 
 #ifdef __cplusplus
 }

@@ -126,6 +126,16 @@ class mmf_flowcrf_config(C.Structure):
                 ("threshold", C.c_float), ("max_err", C.c_float), ("min_proj_prob", C.c_float)]
 
 
+class mmf_flowseg_config(C.Structure):
+    _fields_ = [("div", C.c_int), ("new_model_size", C.c_float), ("avg_confidence", C.c_float), ("model_spawn_offset", C.c_int),
+                ("inhibit_new", C.c_int)]
+
+
+class mmf_flowseg_summary(C.Structure):
+    _fields_ = [("n_entries", C.c_int), ("allow_new", C.c_int), ("has_new_label", C.c_int), ("new_cells", C.c_uint),
+                ("models", mmf_segmentation_model * 32), ("area2", C.c_int * 32), ("first_cell", C.c_int * 32)]
+
+
 class mmf_flowcrf_input(C.Structure):
     _fields_ = [("n_models", C.c_int), ("allow_new", C.c_int), ("new_id", C.c_uint), ("ids", C.POINTER(C.c_ubyte)),
                 ("T_start", C.POINTER(C.c_float)), ("T_end", C.POINTER(C.c_float)), ("vertex", C.POINTER(C.c_void_p)),
@@ -403,6 +413,15 @@ SIGNATURES = {
     "mmf_fusion_set_flow_inference": (_i, [_vp, C.POINTER(mmf_flowcrf_config)]),
     "mmf_fusion_last_flow_inference": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _ip, _ip, _ip, _ip]),
     "mmf_fusion_flow_inference_download": (_i, [_vp, C.c_char_p, _vp, _sz]),
+    "mmf_flowseg_default_config": (_i, [C.POINTER(mmf_flowseg_config)]),
+    "mmf_flowseg_create": (_i, [_vp, _i, _i, _i, C.POINTER(mmf_flowseg_config), C.POINTER(_vp)]),
+    "mmf_flowseg_destroy": (None, [_vp]),
+    "mmf_flowseg_run": (_i, [_vp, _vp, _vp, C.POINTER(C.c_ubyte), _i, _i, C.c_uint]),
+    "mmf_flowseg_result": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(mmf_flowseg_summary), _ip, _ip]),
+    "mmf_flowseg_download": (_i, [_vp, C.c_char_p, _vp, _sz]),
+    "mmf_flowseg_last_launches": (_i, [_vp]),
+    "mmf_fusion_set_flow_segmentation": (_i, [_vp, C.POINTER(mmf_flowseg_config)]),
+    "mmf_fusion_last_flow_segmentation": (_i, [_vp, C.POINTER(mmf_flowseg_summary), _ip]),
 }
 
 _lib = None

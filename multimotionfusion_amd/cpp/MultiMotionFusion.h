@@ -108,7 +108,7 @@ struct OdometryConfig {  // Core/Model/Model.h:45-61
     bool icp_refine = false;
     int segm_lvl = 0;
 };
-struct SegmentationConfiguration {  // Core/Segmentation/Segmentation.h:72-80 ("": the built-in dense CRF; "flow_crf": not here)
+struct SegmentationConfiguration {  // Core/Segmentation/Segmentation.h:72-80 ("": the built-in dense CRF; "flow_crf": flow + tracks + blobs)
     std::string mode;
     int sp_size = 16;
 };
@@ -440,6 +440,7 @@ class MultiMotionFusion {
         mmf::check(mmf_fusion_create(ctx.get(), width, height, cx, cy, fx, fy, cfg, &f_), "mmf_fusion_create");
         mmf::check(mmf_fusion_get_config(f_, &cfg_), "mmf_fusion_get_config");
         mmf::check(mmf_crf_default_config(&crf_), "mmf_crf_default_config");
+        mmf::check(mmf_flowseg_default_config(&flowseg_), "mmf_flowseg_default_config");
         pushCrf();
     }
     // The reference's own argument list (Core/MultiMotionFusion.h:54-61, .cpp:21-97): the frame geometry comes from the
@@ -474,12 +475,19 @@ class MultiMotionFusion {
         ctx_ = defaultContext().get(), fx_ = K.fx(), fy_ = K.fy(), cx_ = K.cx(), cy_ = K.cy();
         mmf::check(mmf_fusion_create(defaultContext().get(), width_, height_, K.cx(), K.cy(), K.fx(), K.fy(), &cfg, &f_), "mmf_fusion_create");
         mmf::check(mmf_fusion_get_config(f_, &cfg_), "mmf_fusion_get_config");
-        // the segmentation of a maskless multi-model frame: the built-in dense CRF in the default mode (""); "flow_crf"
-        // (Farneback flow + keypoint tracks) is not part of this path and keeps the error of a missing segmentation
+        // the segmentation of a maskless multi-model frame: the built-in dense CRF in the default mode (""); "flow_crf":
+        // Farneback flow, the flow-CRF inference on the keypoint tracks and the blob stage (Segmentation.cpp:779-1324); any
+        // other mode keeps the error of a missing segmentation
         mmf::check(mmf_crf_default_config(&crf_), "mmf_crf_default_config");
+        mmf::check(mmf_flowseg_default_config(&flowseg_), "mmf_flowseg_default_config");
         crf_.model_spawn_offset = (int)modelSpawnOffset, crf_.spixel_size = segm_cfg.sp_size;
-        mask_.model_spawn_offset = (int)modelSpawnOffset;
+        mask_.model_spawn_offset = (int)modelSpawnOffset, flowseg_.model_spawn_offset = (int)modelSpawnOffset;
         pushCrf();
+        if (segm_cfg_.mode == "flow_crf") {
+            setOpticalFlow(true);
+            setFlowInference(true);
+            pushFlowSeg();
+        }
     }
     static mmf::Context& defaultContext() {
         static mmf::Context ctx(0);
@@ -631,7 +639,8 @@ class MultiMotionFusion {
     void setFernThresh(const float& v) { other_["fernThresh"] = v; }
     void setModelSpawnOffset(const unsigned& v) {
         other_["modelSpawnOffset"] = (float)v, crf_.model_spawn_offset = (int)v, mask_.model_spawn_offset = (int)v;
-        pushCrf(), pushMask();
+        flowseg_.model_spawn_offset = (int)v;
+        pushCrf(), pushMask(), pushFlowSeg();
     }
     void setModelDeactivateCount(const unsigned& v) { other_["modelDeactivateCount"] = (float)v; }
     void setCrfPairwiseSigmaRGB(const float& v) { other_["crfPairwiseSigmaRGB"] = v, crf_.sigma_rgb = v, pushCrf(); }
@@ -650,7 +659,7 @@ class MultiMotionFusion {
     void setSuperpixelEngine(bool v) { other_["superpixelEngine"] = v, mmf::check(mmf_fusion_set_superpixel_engine(f_, v ? 1 : 0), "mmf_fusion_set_superpixel_engine"); }
     // Every frame's dense optical flow from the frame before it (the flow stage of "flow_crf", Segmentation.cpp:779-804:
     // Farneback on the pair scaled down by four, the reference's settings), computed beside the tracking; off until
-    // switched on.  Only the flow field: the flow_crf segmentation itself is not here.  getLastFlow(): the last frame's
+    // switched on (SegmentationConfiguration::mode == "flow_crf" switches it on).  getLastFlow(): the last frame's
     // field in host memory, `valid` false after the first frame of a sequence (creation, reset) and while the hook is off.
     struct OpticalFlow {
         bool valid = false;
@@ -666,6 +675,7 @@ class MultiMotionFusion {
         // (the inference reads the flow: off with it; setOpticalFlow(true) again replaces the flow engine -- a new sequence --
         // and the library switches the inference back on with it, so the flag stands)
         if (!v && flow_inference_on_) other_["flowInference"] = false, flow_inference_on_ = false;
+        flow_seg_on_ = false;  // (the library ends the flow_crf mode with the flow engine it read)
     }
     OpticalFlow getLastFlow() {
         OpticalFlow out;
@@ -699,6 +709,23 @@ class MultiMotionFusion {
         mmf::check(mmf_flowcrf_default_config(&c), "mmf_flowcrf_default_config");
         mmf::check(mmf_fusion_set_flow_inference(f_, v ? &c : nullptr), "mmf_fusion_set_flow_inference");
         other_["flowInference"] = v, flow_inference_on_ = v;
+        if (!v) flow_seg_on_ = false;
+    }
+    // What the flow_crf mode (SegmentationConfiguration::mode == "flow_crf"; mmf_fusion_set_flow_segmentation)
+    // made of the last frame it segmented: the SegmentationResult's model data, hasNewLabel as processFrame used it, and per
+    // label the winning blob.  `valid` false while the mode is off and before its first frame; `has_result` false for a frame
+    // without an inference result (a zero mask, no entries).
+    struct FlowSegmentation {
+        bool valid = false, has_result = false;
+        mmf_flowseg_summary summary{};
+    };
+    FlowSegmentation getLastFlowSegmentation() {
+        FlowSegmentation out;
+        if (!flow_seg_on_) return out;
+        int has = 0;
+        if (mmf_fusion_last_flow_segmentation(f_, &out.summary, &has) != MMF_OK) return out;  // (no frame yet)
+        out.valid = true, out.has_result = has != 0;
+        return out;
     }
     FlowInference getLastFlowInference() {
         FlowInference out;
@@ -772,8 +799,8 @@ class MultiMotionFusion {
         return out;
     }
     void setSetInhibit(bool v) {
-        other_["inhibitModels"] = v, crf_.inhibit_new = v ? 1 : 0, mask_.inhibit_new = v ? 1 : 0;
-        pushCrf(), pushMask();
+        other_["inhibitModels"] = v, crf_.inhibit_new = v ? 1 : 0, mask_.inhibit_new = v ? 1 : 0, flowseg_.inhibit_new = v ? 1 : 0;
+        pushCrf(), pushMask(), pushFlowSeg();
     }
     // not in the reference, where a frame with a mask always takes this branch (Segmentation.cpp:89): with it on,
     // FrameData::mask / FrameDataDevice::mask are RAW labels; processFrame maps them to model ids through a table it keeps,
@@ -811,6 +838,11 @@ class MultiMotionFusion {
     }
     void pushCrf() {
         mmf::check(mmf_fusion_set_crf_segmentation(f_, segm_cfg_.mode.empty() ? &crf_ : nullptr), "mmf_fusion_set_crf_segmentation");
+    }
+    void pushFlowSeg() {
+        if (segm_cfg_.mode != "flow_crf" || !flow_inference_on_) return;
+        mmf::check(mmf_fusion_set_flow_segmentation(f_, &flowseg_), "mmf_fusion_set_flow_segmentation");
+        flow_seg_on_ = true;
     }
     void pushTracker() {
         other_["odomInitKp"] = odom_cfg_.init == "kp", other_["hasKeypointPredictor"] = kp_predictor_ != nullptr;
@@ -861,6 +893,8 @@ class MultiMotionFusion {
     bool kp_on_device_ = false;
     bool flow_on_ = false;
     bool flow_inference_on_ = false;
+    bool flow_seg_on_ = false;
+    mmf_flowseg_config flowseg_{};
     std::unique_ptr<tracker::PointTracker> tracker_;
     unsigned char* kp_rgb_ = nullptr;
     float* kp_depth_ = nullptr;

@@ -103,6 +103,7 @@ extern "C" int mmf_fusion_set_optical_flow(mmf_fusion* f, const mmf_flow_config*
     MMF_HIP_TRY(hipSetDevice(f->ctx->device));
     const bool rearm = f->fi.on && cfg && cfg->div == 4;
     const mmf_flowcrf_config fi_cfg = f->fi.cfg;
+    f->fseg.reset();                 // (the flow_crf mode reads the inference: a replaced flow engine ends it as well)
     f->fi.reset(), f->flow.reset();  // (the inference lives on the flow's stream and reads the flow: it goes first)
     if (!cfg) return MMF_OK;
     if (int rc = flow_create_impl(f->ctx, f->width, f->height, cfg, &f->flow.engine, "mmf_fusion_set_optical_flow")) return rc;
@@ -142,6 +143,7 @@ extern "C" int mmf_fusion_set_flow_inference(mmf_fusion* f, const mmf_flowcrf_co
         if (f->flow.engine->cfg.div != 4) return fail(MMF_ERR_STATE, "mmf_fusion_set_flow_inference: the optical-flow hook must run at div 4");
     }
     MMF_HIP_TRY(hipSetDevice(f->ctx->device));
+    if (!cfg) f->fseg.reset();  // (the flow_crf mode reads this hook's id image)
     f->fi.reset();
     if (!cfg) return MMF_OK;
     hipError_t e = f->fi.begin.create();
@@ -229,7 +231,14 @@ static int frame_flow_enqueue(mmf_fusion* f, const uint8_t* rgb) {
 // A frame with more labels than the engine takes has no result (has_result 0): the hook fails no frame.
 static int frame_flow_inference(mmf_fusion* f) {
     mmf_ctx* c = f->ctx;
-    const int M = (int)f->models.size(), allow_new = f->cfg.enable_multiple_models ? 1 : 0, L = M + allow_new;
+    // under the flow_crf mode the new label is there when a model may spawn (MultiMotionFusion.cpp:148, with the count
+    // frame_segment is about to give this frame, :410), else whenever models may spawn at all
+    const bool mode = f->fseg.on && f->cfg.enable_multiple_models;
+    const int M = (int)f->models.size();
+    const unsigned spawn_after = (unsigned)f->fseg.cfg.model_spawn_offset;
+    const int allow_new = mode ? (f->seg.spawn_offset + (f->seg.spawn_offset < spawn_after ? 1u : 0u) >= spawn_after ? 1 : 0)
+                               : (f->cfg.enable_multiple_models ? 1 : 0);
+    const int L = M + allow_new;
     if (L > mmf::kCrfMaxLabels) return MMF_OK;
     const int cap = f->kp.tracker ? f->kp.tracker->capacity : 0;
     if (!f->fi.engine || f->fi.engine->max_labels < L || f->fi.engine->max_tracks < cap) {
@@ -272,6 +281,7 @@ static int frame_flow_inference(mmf_fusion* f) {
     for (FusionModel* fm : f->models)
         if (fm->lane->stream != c->stream) MMF_HIP_TRY(hipStreamWaitEvent(fm->lane->stream, f->fi.inputs.get(), 0));
     f->fi.has = true;
+    f->fi.allow_new = allow_new;
     return MMF_OK;
 }
 
@@ -365,5 +375,72 @@ static int fusion_mask_segment(mmf_fusion* f, const uint8_t* labels, mmf_segment
     f->seg.mask_info.n_models = s.n_models_out, f->seg.mask_info.allow_new = l.allow_new;
     f->seg.mask_info.has_new_label = out->has_new_label, f->seg.mask_info.new_label = s.new_label;
     f->seg.mask_valid = true;
+    return MMF_OK;
+}
+
+// The flow_crf mode (mmf_fusion_set_flow_segmentation): cfg != NULL switches it on (a second call replaces the configuration),
+// NULL off -- the engine is freed, and no frame allocates, enqueues or waits for anything.  It reads the inference hook's ids.
+extern "C" int mmf_fusion_set_flow_segmentation(mmf_fusion* f, const mmf_flowseg_config* cfg) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_set_flow_segmentation: null fusion object");
+    if (cfg) {
+        if (int rc = flowseg_check_config(f->width, f->height, mmf::kCrfMaxLabels, cfg, "mmf_fusion_set_flow_segmentation")) return rc;
+        if (f->shard_world > 1) return fail(MMF_ERR_STATE, "mmf_fusion_set_flow_segmentation: not available on a sharded fusion");
+        if (!f->fi.on) return fail(MMF_ERR_STATE, "mmf_fusion_set_flow_segmentation: the flow-inference hook is off (mmf_fusion_set_flow_inference)");
+    }
+    MMF_HIP_TRY(hipSetDevice(f->ctx->device));
+    f->fseg.reset();
+    if (!cfg) return MMF_OK;
+    f->fseg.cfg = *cfg, f->fseg.on = true;
+    return MMF_OK;
+}
+extern "C" int mmf_fusion_last_flow_segmentation(mmf_fusion* f, mmf_flowseg_summary* summary, int* has_result) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_last_flow_segmentation: null fusion object");
+    if (!f->fseg.valid) return fail(MMF_ERR_STATE, "mmf_fusion_last_flow_segmentation: no frame has been segmented by the flow_crf mode yet");
+    if (summary) *summary = f->fseg.last;
+    if (has_result) *has_result = f->fseg.has ? 1 : 0;
+    return MMF_OK;
+}
+
+// Segmentation.cpp:1270-1324 on the fusion's stream, into textures[MASK]: the blob stage on the id image the inference of this
+// frame left on the flow's lane (frame_flow_inference: the lane's event is joined here), one pinned read of the summary.  `out`
+// points at f->mask and f->fseg.models.  A frame without an inference result -- no flow yet, more than 32 labels -- gets a
+// zero mask, no entries and no new label (deviation 1): frame_segment then moves nobody's unseen count, max
+// depth or confidence threshold.
+static int fusion_flow_segment(mmf_fusion* f, mmf_segmentation* out) {
+    mmf_ctx* c = f->ctx;
+    std::memset(&f->fseg.last, 0, sizeof(f->fseg.last));
+    f->fseg.models.clear();
+    f->fseg.valid = true, f->fseg.has = false;
+    if (!f->fi.has) {
+        MMF_HIP_TRY(hipMemsetAsync(f->mask.get(), 0, (size_t)f->width * f->height, c->stream));
+        fusion_seg_result(f, 0, f->fseg.models, out);
+        out->model_data = nullptr;  // (an empty vector's data() may be anything)
+        return MMF_OK;
+    }
+    SegLabels l;
+    if (int rc = fusion_seg_labels(f, "mmf_fusion_process_frame: the flow_crf mode needs world == 1", f->fseg.cfg.model_spawn_offset, &l)) return rc;
+    const int M = (int)l.ids.size(), allow_new = f->fi.allow_new, L = M + allow_new;
+    if (!f->fseg.engine || f->fseg.engine->max_labels < L) {
+        flowseg_destroy_on(f->fseg.engine, nullptr);
+        f->fseg.engine = nullptr;
+        int rc = flowseg_create_impl(c, f->width, f->height, std::max(4, flowcrf_pad_labels(L)), &f->fseg.cfg, &f->fseg.engine,
+                                     "mmf_fusion_process_frame (flow_crf mode)");
+        if (rc) return rc;
+    }
+    unsigned char ids[mmf::kCrfMaxLabels];
+    for (int k = 0; k < M; ++k) ids[k] = (unsigned char)l.ids[(size_t)k];
+    mmf::FsegTable tab;
+    if (int rc = flowseg_table(f->fseg.engine, ids, M, allow_new, l.next_id, &tab, "mmf_fusion_process_frame (flow_crf mode)")) return rc;
+    const uint8_t* ids_dev = nullptr;
+    if (int rc = mmf_flowcrf_result(f->fi.engine, &ids_dev, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) return rc;
+    MMF_HIP_TRY(f->flow.lane.join(c->stream));  // the inference is complete before the blob stage reads its ids
+    if (int rc = flowseg_run_on(f->fseg.engine, ids_dev, f->frame_depth, tab, c->stream, f->mask.get())) return rc;
+    MMF_HIP_TRY(wait_stream(c->stream));
+    mmf_flowseg_summary s = *f->fseg.engine->sum_host;
+    f->fseg.models.assign(s.models, s.models + s.n_entries);
+    // inhibitModels (:413-415): the mask and the entry stay
+    s.has_new_label = s.has_new_label && !f->fseg.cfg.inhibit_new ? 1 : 0;
+    fusion_seg_result(f, s.has_new_label, f->fseg.models, out);
+    f->fseg.last = s, f->fseg.has = true;
     return MMF_OK;
 }

@@ -739,10 +739,17 @@ static int frame_segment(mmf_fusion* f, const FrameRun& r) {
     const mmf_segmentation* seg = fr->segmentation;
     // a frame that brings raw labels (Segmentation.cpp:89: `frame.mask.total()` is tested before anything else)
     const bool from_labels = f->seg.mask_on && seg && seg->mask && !seg->model_data;
-    const int spawn_after = from_labels ? f->seg.mask_cfg.model_spawn_offset : f->seg.crf_cfg.model_spawn_offset;
+    // ... and one that brings nothing while the flow_crf mode is on (mmf_fusion_set_flow_segmentation)
+    const bool from_flow = !from_labels && !seg && f->fseg.on;
+    const int spawn_after = from_labels ? f->seg.mask_cfg.model_spawn_offset
+                                        : (from_flow ? f->fseg.cfg.model_spawn_offset : f->seg.crf_cfg.model_spawn_offset);
     if (f->seg.spawn_offset < (unsigned)spawn_after) f->seg.spawn_offset++;  // (:410)
     if (from_labels) {
         int rc = fusion_mask_segment(f, seg->mask, &seg_cb);
+        if (rc) return rc;
+        seg = &seg_cb;
+    } else if (from_flow) {
+        int rc = fusion_flow_segment(f, &seg_cb);
         if (rc) return rc;
         seg = &seg_cb;
     } else if (!seg && f->seg.fn) {  // performSegmentation(frame) (:412)
@@ -755,13 +762,15 @@ static int frame_segment(mmf_fusion* f, const FrameRun& r) {
         seg = &seg_cb;
     }
     MMF_REQUIRE(seg && seg->mask, "mmf_fusion_process_frame: enableMultipleModels needs a segmentation "
-                                  "(mmf_frame::segmentation, mmf_fusion_set_segmentation_callback, mmf_fusion_set_crf_segmentation "
-                                  "or, for a frame that brings its labels, mmf_fusion_set_mask_segmentation)");
+                                  "(mmf_frame::segmentation, mmf_fusion_set_segmentation_callback, mmf_fusion_set_crf_segmentation, "
+                                  "mmf_fusion_set_flow_segmentation or, for a frame that brings its labels, mmf_fusion_set_mask_segmentation)");
     // textures[MASK]->Upload(fullSegmentation) (:416)
     if (seg->mask != f->mask.get())
         MMF_HIP_TRY(hipMemcpyAsync(f->mask.get(), seg->mask, (size_t)f->width * f->height, hipMemcpyDeviceToDevice, c->stream));
     f->mask_is_zero = false;
     MMF_HIP_TRY(hipEventRecord(f->ev_frame_ready.get(), c->stream));
+    // fewer entries than models (none at all from the flow_crf mode on a frame without an inference result): the models
+    // without an entry keep their max depth, unseen count and confidence threshold -- every loop below ends at n_data
     const int n_data = seg->model_data ? seg->n_models : 0;
     // redetection via keypoints (:489-559) runs BEFORE a model is spawned: a label it cancels (:522-524) consumes neither an id
     // nor a preallocated model (the reference spawns first and abandons newModel, :468-487, :565)
@@ -1080,7 +1089,7 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
         if (rc) return rc;
     } else {
         f->tracking_ok = 1;
-        if (f->sp.engine && r.track && f->cfg.enable_multiple_models && !fr->segmentation && !f->seg.fn && f->seg.crf_on && !f->sp.next) {
+        if (f->sp.engine && r.track && f->cfg.enable_multiple_models && !fr->segmentation && !f->fseg.on && !f->seg.fn && f->seg.crf_on && !f->sp.next) {
             rc = frame_superpixels_begin(f);
             if (rc) return rc;
             r.superpixels = true;

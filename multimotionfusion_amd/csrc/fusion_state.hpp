@@ -98,6 +98,7 @@ struct FlowInference {
     Event begin;                    // fusion stream: the tracking is done, the track table and the predictions are as the frame met them
     Event inputs;                   // flow stream: the inference has read them
     bool has = false;               // the last frame produced an id image
+    int allow_new = 0;              // ... with the new label as its last
     void reset() {
         if (on) {  // (once the flow's stream has run dry)
             flowcrf_destroy_on(engine, stream);
@@ -107,6 +108,24 @@ struct FlowInference {
         engine = nullptr, stream = nullptr, on = has = false;
     }
     ~FlowInference() { reset(); }
+};
+
+// the flow_crf segmentation mode (mmf_fusion_set_flow_segmentation; flowseg_host.hpp): the blob stage on the fusion's stream
+// behind the inference, for a frame that brings no segmentation of its own.  Nothing exists while the mode is off
+struct FlowSegmentation {
+    bool on = false;
+    mmf_flowseg_config cfg{};
+    mmf_flowseg* engine = nullptr;  // owned; created by the first frame that needs it, for its labels
+    bool valid = false;             // a frame went through this path (mmf_fusion_last_flow_segmentation)
+    bool has = false;               // ... and had an inference result
+    mmf_flowseg_summary last{};
+    std::vector<mmf_segmentation_model> models;
+    void reset() {
+        flowseg_destroy_on(engine, nullptr);
+        engine = nullptr, on = valid = has = false;
+        models.clear();
+    }
+    ~FlowSegmentation() { reset(); }
 };
 
 // keypoint redetection of inactive models (MultiMotionFusion.cpp:489-559; redetect_host.hpp): off unless switched on
@@ -265,6 +284,7 @@ struct mmf_fusion {
     SuperPixels sp;        // the super-pixel input and engine
     FlowHook flow;         // the optical-flow hook
     FlowInference fi;      // the flow inference.  Behind `flow`: it is released before the flow engine and the flow's stream
+    FlowSegmentation fseg; // the flow_crf mode: the blob stage behind the inference
     Redetection rd;        // redetection: view store, verifier, keypoint hand-over
     Keypoints kp;          // tracker, keypoint front end, view-pose log
     Prefetch pre;          // the next frame's prefetch on the side streams
@@ -627,6 +647,7 @@ extern "C" int mmf_fusion_reset(mmf_fusion* f) {
     f->kp.view_poses.clear(), f->kp.stored_ids.clear(), f->kp.stored_views.clear(), f->kp.stored_rows.clear();
     std::memset(f->seg.mask_map, 0, sizeof(f->seg.mask_map));  // (the table speaks of the models of the map that ends here)
     f->seg.mask_valid = false;
+    f->fseg.valid = f->fseg.has = false;
     std::vector<FusionModel*> all(f->preallocated);
     all.push_back(f->models[0]);
     for (FusionModel* fm : all) {

@@ -3334,6 +3334,10 @@ extern "C" int mmf_debug_set_stamps(void* dev_buf) {
 #include "flowcrf_kernels.hpp"
 #include "flowcrf_host.hpp"
 
+// ---- the blob stage of the flow_crf segmentation (flowseg_kernels.hpp, flowseg_host.hpp; Segmentation.cpp:1270-1324) ----
+#include "flowseg_kernels.hpp"
+#include "flowseg_host.hpp"
+
 // =============================================================================================
 // Orchestrator: MultiMotionFusion::processFrame / predict (Core/MultiMotionFusion.cpp:207-854, 863-875)
 // =============================================================================================

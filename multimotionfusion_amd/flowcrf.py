@@ -1,8 +1,9 @@
 """The inference of the flow CRF on the device: the host-side mirror of the stage of the reference's
 flow_crf segmentation that turns tracks, flow, depth and the models' predictions into fused label probabilities and the
 MAP id image (Core/Segmentation/Segmentation.cpp:819-1263), over the C ABI -- no fallback.  What follows it in the
-reference (contours, the largest blob, ModelData, spawning) and the flow_crf mode itself are not part of this library;
-the specification is the text of DESIGN.md 4.9, the oracle tests/flowcrf_oracle.py."""
+reference (contours, the largest blob, ModelData, hasNewLabel) is flowseg.FlowSegmentation, the flow_crf mode itself
+fusion.MultiMotionFusion.setFlowSegmentation; the specification of this stage is the text of
+DESIGN.md 4.9, the oracle tests/flowcrf_oracle.py."""
 import ctypes as C
 import weakref
 

@@ -6,6 +6,7 @@ import weakref
 
 import numpy as np
 
+from . import _capi
 from ._capi import check, fptr, mmf_frame, mmf_fusion_config, mmf_mask_info, mmf_segmentation, mmf_segmentation_model
 from .cudafuncs import Context, _p
 from .model import Model
@@ -375,6 +376,29 @@ class MultiMotionFusion:
         else:
             out = np.empty((h.value, w.value), np.int32 if name == "label" else np.uint8)
         check(self.ctx.lib.mmf_fusion_flow_inference_download(self.handle, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        return out
+
+    def setFlowSegmentation(self, config=True):
+        """the reference's -segm_mode flow_crf: a frame that brings no segmentation of its own is segmented
+        from the flow inference's id image -- the largest blob per model, filled, scaled up, with the model data and the new
+        label's 5 % rule (flowseg.FlowSegmentation's engine); needs setFlowInference.  True: the reference's settings; a
+        flowseg.FlowSegConfig: those; False / None (the default state): off, the engine is freed."""
+        from .flowseg import FlowSegConfig
+        if config is None or config is False:
+            check(self.ctx.lib.mmf_fusion_set_flow_segmentation(self.handle, None))
+            return
+        cfg = FlowSegConfig() if config is True else config
+        check(self.ctx.lib.mmf_fusion_set_flow_segmentation(self.handle, C.byref(cfg.c)))
+
+    def getLastFlowSegmentation(self):
+        """what the flow_crf mode computed for the last frame it handled, as flowseg.FlowSegmentation.summary(): model data,
+        allow_new, has_new_label as processFrame used it, new_cells, area2 and first_cell per table entry; has_result False
+        for a frame without an inference result (zero mask, no entries)"""
+        from .flowseg import summary_dict
+        s, has = _capi.mmf_flowseg_summary(), C.c_int()
+        check(self.ctx.lib.mmf_fusion_last_flow_segmentation(self.handle, C.byref(s), C.byref(has)))
+        out = summary_dict(s)
+        out["has_result"] = bool(has.value)
         return out
 
     def getLastSegmentation(self):

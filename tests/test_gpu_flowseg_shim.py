@@ -1,0 +1,22 @@
+"""-m gpu: the C++ shim on the flow_crf mode -- SegmentationConfiguration::mode == "flow_crf" through the reference's own
+constructor, MultiMotionFusion::getLastFlowSegmentation() over three frames, and the stand-alone cpp/FlowSegmentation.h
+(tests/cpp/flowseg_shim_sequence.cpp, compiled with g++ -Wall -Wextra -Werror against libmmf_hip.so)."""
+import os
+import subprocess
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_flow_crf_mode_through_the_fusion_shim(tmp_path):
+    pkg = os.path.join(REPO, "multimotionfusion_amd")
+    exe = tmp_path / "flowseg_shim_sequence"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-D__HIP_PLATFORM_AMD__", "-isystem", "/opt/rocm/include",
+                    os.path.join(REPO, "tests", "cpp", "flowseg_shim_sequence.cpp"), "-o", str(exe), f"-L{pkg}", "-lmmf_hip",
+                    "-lamdhip64", f"-Wl,-rpath,{pkg}", "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib"], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0, (r.stdout, r.stderr)
+    assert "flowseg shim sequence: ok" in r.stdout
