@@ -155,6 +155,53 @@ def blur_solve(M, m, dt=F32):
         return np.stack([(g11 * h2 - g12 * h1) * idet, (g22 * h1 - g12 * h2) * idet], axis=-1).astype(dt)
 
 
+def warp_positions(shape, flow, dt=F32):
+    """stage 5's view of a flow [H, W, 2] (None: zero): (x1f, y1f, inside, fracx, fracy) -- the floors as floats, the branch
+    taken and, where inside, the interpolation fractions.  The expressions of `matrices`, which does not hand them out."""
+    H, W = shape
+    ys, xs = np.mgrid[0:H, 0:W]
+    dx = np.zeros((H, W), dt) if flow is None else flow[..., 0]
+    dy = np.zeros((H, W), dt) if flow is None else flow[..., 1]
+    with np.errstate(invalid="ignore", over="ignore"):
+        fx, fy = xs.astype(dt) + dx, ys.astype(dt) + dy
+        x1f, y1f = np.floor(fx), np.floor(fy)
+        inside = (x1f >= 0) & (x1f < dt(W - 1)) & (y1f >= 0) & (y1f < dt(H - 1))
+        return x1f, y1f, inside, np.where(inside, fx - x1f, 0).astype(dt), np.where(inside, fy - y1f, 0).astype(dt)
+
+
+def box_means(M, m, dt=F32):
+    """stage 6 up to the solve: g11, g12, g22, h1, h2 as `blur_solve` sums them, [H, W, 5]"""
+    H, W = M.shape[:2]
+    P = np.pad(M, ((m, m), (m, m), (0, 0)), mode="edge")
+    hs = np.zeros((H + 2 * m, W, 5), dt)
+    for k in range(2 * m + 1):
+        hs = hs + P[:, k:k + W]
+    vs = np.zeros((H, W, 5), dt)
+    for k in range(2 * m + 1):
+        vs = vs + hs[k:k + H]
+    return vs * (dt(1) / dt((2 * m + 1) * (2 * m + 1)))
+
+
+def trace(out, cfg, dt=F32):
+    """What `pair` computes on the way and does not keep, from its result `out`: per iteration a dict of `det` =
+    g11*g22 - g12*g12 [H, W] (at `dt`, before the double addition of 1e-3), `idet`, the flow `flow_in` the iteration warps by
+    (None in front of the first) and `warp_positions` of it as x1f, y1f, inside, fracx, fracy.  `flow` is the iteration's
+    flow solved again from `det`: equal to out["flow_<i>"] bit for bit, or this function has drifted from `blur_solve`."""
+    its = []
+    flow = None
+    for it in range(cfg["iterations"]):
+        x1f, y1f, inside, fracx, fracy = warp_positions(out["R0"].shape[:2], flow, dt)
+        vs = box_means(matrices(out["R0"], out["R1"], flow, dt), cfg["winsize"] // 2, dt)
+        g11, g12, g22, h1, h2 = (vs[..., c] for c in range(5))
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            det = g11 * g22 - g12 * g12
+            idet = (1.0 / (det.astype(np.float64) + 1e-3)).astype(dt)
+            again = np.stack([(g11 * h2 - g12 * h1) * idet, (g22 * h1 - g12 * h2) * idet], axis=-1).astype(dt)
+        its.append(dict(det=det, idet=idet, flow_in=flow, x1f=x1f, y1f=y1f, inside=inside, fracx=fracx, fracy=fracy, flow=again))
+        flow = out[f"flow_{it}"]
+    return its
+
+
 def outputs(flow, dt=F32):
     """stage 8: magnitude, motion"""
     with np.errstate(invalid="ignore", over="ignore"):
