@@ -272,7 +272,7 @@ static int redetect_activate(mmf_fusion* f, FusionModel* fm, const float pose[16
     fm->unseen = 0;
     fm->tracking = false, fm->early_done = false, fm->early_fused = false;
     fm->spec_valid = false, fm->spec_hit = false;
-    fm->odom->so3_prefetched = false, fm->odom->so3_stage = nullptr;
+    fm->odom->so3.prefetched = false, fm->odom->so3.stage = nullptr;
     f->inactive.erase(std::find(f->inactive.begin(), f->inactive.end(), fm));
     f->models.push_back(fm);
     if (fusion_view_log_on(f)) {  // Model::activate (:1646-1656): one pose, the activation's

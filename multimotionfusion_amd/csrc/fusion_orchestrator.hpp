@@ -69,7 +69,7 @@ static void odom_alias_sensor_side(mmf_odom* o, const mmf_odom* primary) {
         o->dIdx[i] = primary->dIdx[i], o->dIdy[i] = primary->dIdy[i];
         o->depth_pyr[i] = primary->depth_pyr[i];
     }
-    o->depth_l0 = primary->depth_l0;
+    o->in.depth_l0 = primary->in.depth_l0;
 }
 
 // where an OBJECT model's latest prediction is non-zero (device, PassBoxes::spl_nz of its last resolve), for a model-side
@@ -98,14 +98,14 @@ static int fusion_predict_model(mmf_fusion* f, FusionModel* fm) {
 // library; the segmentation (:412) comes before it and reads the previous frame's prediction (as a segmentation callback
 // does here), a caller sees the images only between calls, and the fuse / clean passes read their own index maps.  Its images are overwritten by the second prediction before
 // anything can read them, so it is not enqueued (bit-identical poses, maps and images: every oracle parity test runs this
-// way, and tests/test_gpu_fusion.py compares the two).  MMF_MID_PREDICT=1 runs it as the reference does.
-static std::atomic<int> g_mid_predict{-1};  // -1: MMF_MID_PREDICT decides (default off); 0 / 1: mmf_debug_set_mid_predict
+// way, and tests/test_gpu_fusion.py compares the two).  mmf_debug_set_mid_predict(1) runs it as the reference does.
+static Override g_mid_predict;  // a hook only, no environment switch: unset = off; 0 / 1: mmf_debug_set_mid_predict
 extern "C" int mmf_debug_set_mid_predict(int on) {
-    g_mid_predict.store(on < 0 ? -1 : (on ? 1 : 0));
+    override_flag(g_mid_predict, on);
     return MMF_OK;
 }
 static bool fusion_mid_predict() {
-    return g_mid_predict.load() > 0;
+    return g_mid_predict.get(0) != 0;
 }
 
 // predictIndices -> fuse -> predictIndices -> clean of one model (:791-816 per model; models never read each
@@ -130,10 +130,10 @@ static int fusion_fuse_clean_model(mmf_fusion* f, FusionModel* fm, float weighti
 static float seg_max_depth(const mmf_segmentation_model& d) { return (float)((double)d.depth_mean + (double)d.depth_std * 1.2); }
 
 // test / A-B hook: how the object models' passes go out (fusion_batch_mode)
-static std::atomic<int> g_batch_passes{-1};  // -1: MMF_PASS_BATCH / the number of object models decide
+static Override g_batch_passes;  // unset: MMF_PASS_BATCH / the number of object models decide
 extern "C" int mmf_debug_set_pass_batch(int mode) {
     MMF_REQUIRE(mode == -1 || mode == 0 || mode == 2, "mmf_debug_set_pass_batch: mode must be -1, 0 or 2");
-    g_batch_passes.store(mode);
+    mode < 0 ? g_batch_passes.clear() : g_batch_passes.set(mode);
     return MMF_OK;
 }
 // 0: model by model; 2: one launch per pass, restricted to where the models are (pass_rect.hpp).  Neither the hook nor
@@ -143,8 +143,7 @@ extern "C" int mmf_debug_set_pass_batch(int mode) {
 // against 0.55-0.59)
 constexpr int kRectPassObjects = 4;
 static int fusion_batch_mode(const mmf_fusion* f) {
-    int v = g_batch_passes.load();
-    if (v < 0) v = tunables().pass_batch;
+    const int v = (int)g_batch_passes.get(tunables().pass_batch);
     if (v >= 0) return v;
     int objects = 0;
     for (size_t k = 1; k < f->models.size(); ++k) objects += fusion_owns(f, k) ? 1 : 0;
@@ -332,7 +331,7 @@ static int frame_begin(mmf_fusion* f, FrameRun& r) {
     f->pre.so3_ready = -1;
     f->pre.image_rgb = nullptr;
     if (so3_ready >= 0 && r.prefetched && r.track && !(r.have_init && !fr->icp_refine)) r.so3_stage = f->pre.so3_stage[so3_ready];
-    for (FusionModel* fm : f->models) fm->odom->so3_prefetched = false, fm->odom->so3_stage = nullptr;
+    for (FusionModel* fm : f->models) fm->odom->so3.prefetched = false, fm->odom->so3.stage = nullptr;
     if (r.prefetched) {  // the filter (:262) and the input-side preparation already ran on the side stream
         f->pre.cur ^= 1;
         f->depth_filtered = f->pre.filtered[f->pre.cur].get();
@@ -387,9 +386,9 @@ static int frame_track_sensor_side(mmf_fusion* f, FrameRun& r) {
         float pose_now[16];
         mmf_model_get_pose(fm->model, pose_now);
         fm->spec_hit = fm->spec_valid && fusion_owns(f, k) && !r.have_init && std::memcmp(pose_now, fm->spec_pose, sizeof(pose_now)) == 0 &&
-                       fm->model->tex_gen == fm->spec_tex_gen && fm->spec_f2f == g.frame_to_frame_rgb && fm->odom->prep_batched;
+                       fm->model->tex_gen == fm->spec_tex_gen && fm->spec_f2f == g.frame_to_frame_rgb && fm->odom->in.prep_batched;
         fm->spec_valid = false;
-        fm->odom->begin_spec_ok = fm->spec_hit;  // (the tracking's beginning rode that preparation: odom_begin_rider)
+        fm->odom->spec.ok = fm->spec_hit;  // (the tracking's beginning rode that preparation: odom_begin_rider)
         fm->early_done = fm->early_fused = false;
     }
     r.one_pass = n_models == 1 && !r.have_init && fusion_owns(f, 0) && !global->spec_hit;
@@ -499,7 +498,7 @@ static int frame_enqueue_tracking(mmf_fusion* f, FrameRun& r) {
     FusionModel* global = f->models[0];
     const std::vector<FusionModel*>& tracked = r.tracked;
     if (r.so3_stage)  // every chain enqueued below starts from the prefetched pre-alignment
-        for (FusionModel* fm : tracked) fm->odom->so3_prefetched = true, fm->odom->so3_stage = r.so3_stage;
+        for (FusionModel* fm : tracked) fm->odom->so3.prefetched = true, fm->odom->so3.stage = r.so3_stage;
     r.batched = tracked.size() > 1 && tracked.size() <= (size_t)kMaxBatch && !r.have_init && g.batch_tracking;
     const unsigned ext_gen = ++f->extent_seq;
     for (FusionModel* fm : tracked) fm->odom->sparse = fm != global && !fm->fill_in;  // an object model: extent.hpp, ChainGeom
@@ -517,7 +516,7 @@ static int frame_enqueue_tracking(mmf_fusion* f, FrameRun& r) {
         stages.set_critical(true);  // the model's stream
         for (FusionModel* fm : tracked) {
             if (fm->spec_hit) {
-                fm->odom->depth_l0 = f->depth_filtered;
+                fm->odom->in.depth_l0 = f->depth_filtered;
                 continue;
             }
             float pose[16];
@@ -541,7 +540,7 @@ static int frame_enqueue_tracking(mmf_fusion* f, FrameRun& r) {
             if (rc) return rc;
         }
         if (fm->spec_hit) {  // the model side was prepared at the end of the last frame; the sensor side by the prefetch
-            fm->odom->depth_l0 = f->depth_filtered;  // (or in frame_track_sensor_side)
+            fm->odom->in.depth_l0 = f->depth_filtered;  // (or in frame_track_sensor_side)
         } else if (!r.batched) {  // (a failed batch has prepared every model already)
             PrepStages stages;
             stages.set_critical(true);  // the model's stream
@@ -635,7 +634,7 @@ static int frame_pick_up_poses(mmf_fusion* f, FrameRun& r) {
         if (rc == kGnRetry && !retracked) {  // (at most once: the two-launch chain has no way to give up)
             // every chain of the frame is void with it (a batch is one chain; chains side by side are two-launch chains)
             for (FusionModel* t : r.tracked)
-                if (t->tracking && t != fm && t->odom->result_of) {  // drain what the other lanes' chains still publish
+                if (t->tracking && t != fm && t->odom->call.result_of) {  // drain what the other lanes' chains still publish
                     float tt[3], rr[9];
                     (void)odom_finish_tracking(t->odom, tt, rr);
                 }
@@ -989,7 +988,7 @@ static int frame_prepare_next(mmf_fusion* f, const FrameRun& r) {
                                         stage, &rider);
             }
         }
-        if (!ride) only->odom->begin_spec_valid = false;
+        if (!ride) only->odom->spec.valid = false;
         int rc = stages.launch(st, ride ? &rider : nullptr);
         if (rc) return rc;
         only->spec_tex_gen = m->tex_gen;

@@ -359,7 +359,7 @@ static int fusion_model_create(mmf_fusion* f, int id, float conf, int fill_in, b
         if (rc == MMF_OK && fm->ev_done.create() != hipSuccess) rc = fail(MMF_ERR_HIP, "mmf_fusion: hipEventCreate failed");
         // the prediction images (model slab) and the filtered depth (the fusion's buffer) are not written
         // between the init* calls of a frame and the end of its tracking
-        if (rc == MMF_OK) fm->odom->alias_inputs = true;
+        if (rc == MMF_OK) fm->odom->in.alias_inputs = true;
     }
     if (rc != MMF_OK) {
         const std::string keep = g_last_error;
@@ -655,8 +655,8 @@ extern "C" int mmf_fusion_reset(mmf_fusion* f) {
         if (rc) return rc;
         fm->model->conf_threshold = fm->model->id == 0 ? f->cfg.conf_global_init : f->cfg.conf_object_init;
         identity16(fm->last_pose);
-        fm->odom->so3_prefetched = false, fm->odom->so3_stage = nullptr;
-        fm->odom->have_tmp = false;
+        fm->odom->so3.prefetched = false, fm->odom->so3.stage = nullptr;
+        fm->odom->in.have_tmp = false;
         fm->unseen = 0;
         fm->pose_log.clear();
     }

@@ -76,12 +76,16 @@ static int fail(int code, const std::string& msg) {
     return code;
 }
 
-#define MMF_HIP_TRY(expr)                                                                         \
+// MMF_HIP_TRY(expr, cleanup): `cleanup` runs before the return -- a create function past its `new` hands the half-built
+// object to its destroy function
+#define MMF_HIP_TRY(expr, ...)                                                                    \
     do {                                                                                          \
         hipError_t e__ = (expr);                                                                  \
-        if (e__ != hipSuccess)                                                                    \
+        if (e__ != hipSuccess) {                                                                  \
+            __VA_ARGS__;                                                                          \
             return fail(MMF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__) + " (" +  \
                                          __FILE__ + ":" + std::to_string(__LINE__) + ")");        \
+        }                                                                                         \
     } while (0)
 
 #define MMF_REQUIRE(cond, msg)                                  \
@@ -136,7 +140,7 @@ struct mmf_ctx {
     int cu_count = 0;  // compute units of the device (the one-launch Gauss-Newton chain needs its grid resident at once)
 };
 
-static std::atomic<int> g_xcd_forced{-1};  // mmf_debug_set_xcd
+static Override g_xcd_forced;  // mmf_debug_set_xcd; else MMF_XCD
 extern "C" int mmf_ctx_create(int device, void* stream, int private_stream, mmf_ctx** out) {
     MMF_REQUIRE(out != nullptr, "mmf_ctx_create: out is null");
     int count = 0;
@@ -147,36 +151,37 @@ extern "C" int mmf_ctx_create(int device, void* stream, int private_stream, mmf_
     (void)tunables();  // the environment switches are read here, once
     mmf_ctx* c = new (std::nothrow) mmf_ctx();
     MMF_REQUIRE(c != nullptr, "mmf_ctx_create: out of host memory");
+    // from here on a failure unmakes what is there (mmf_ctx_destroy takes a half-built context)
     c->device = device;
     hipDeviceProp_t prop;
-    MMF_HIP_TRY(hipGetDeviceProperties(&prop, device));
+    MMF_HIP_TRY(hipGetDeviceProperties(&prop, device), mmf_ctx_destroy(c));
     std::snprintf(c->arch, sizeof(c->arch), "%s", prop.gcnArchName);
     c->cu_count = prop.multiProcessorCount;
     if (std::strncmp(c->arch, "gfx950", 6) != 0) {
         std::string m = std::string("mmf_ctx_create: this library is built for gfx950 only, device is ") + c->arch;
-        delete c;
+        mmf_ctx_destroy(c);
         return fail(MMF_ERR_NO_DEVICE, m);
     }
     if (private_stream) {
-        MMF_HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+        MMF_HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking), mmf_ctx_destroy(c));
         c->own_stream = true;
     } else {
         c->stream = (hipStream_t)stream;
     }
-    MMF_HIP_TRY(hipMalloc(&c->partials_f, sizeof(float) * kMaxGrid * kPartialStride));
-    MMF_HIP_TRY(hipMalloc(&c->partials_icp, sizeof(float) * kMaxIcpGrid * kPartialStride));
-    MMF_HIP_TRY(hipMalloc(&c->partials_res, sizeof(int2) * kMaxGrid));
-    MMF_HIP_TRY(hipMalloc(&c->ticket, sizeof(unsigned) * kTicketWords));
-    MMF_HIP_TRY(hipMemsetAsync(c->ticket, 0, sizeof(unsigned) * kTicketWords, c->stream));
-    MMF_HIP_TRY(hipMalloc(&c->scratch_state, sizeof(OdomState)));
-    MMF_HIP_TRY(hipMemsetAsync(c->scratch_state, 0, sizeof(OdomState), c->stream));
-    MMF_HIP_TRY(hipHostMalloc(&c->host_state, sizeof(OdomState), hipHostMallocDefault));
-    MMF_HIP_TRY(hipEventCreate(&c->ev0));
-    MMF_HIP_TRY(hipEventCreate(&c->ev1));
-    MMF_HIP_TRY(hipStreamSynchronize(c->stream));
+    MMF_HIP_TRY(hipMalloc(&c->partials_f, sizeof(float) * kMaxGrid * kPartialStride), mmf_ctx_destroy(c));
+    MMF_HIP_TRY(hipMalloc(&c->partials_icp, sizeof(float) * kMaxIcpGrid * kPartialStride), mmf_ctx_destroy(c));
+    MMF_HIP_TRY(hipMalloc(&c->partials_res, sizeof(int2) * kMaxGrid), mmf_ctx_destroy(c));
+    MMF_HIP_TRY(hipMalloc(&c->ticket, sizeof(unsigned) * kTicketWords), mmf_ctx_destroy(c));
+    MMF_HIP_TRY(hipMemsetAsync(c->ticket, 0, sizeof(unsigned) * kTicketWords, c->stream), mmf_ctx_destroy(c));
+    MMF_HIP_TRY(hipMalloc(&c->scratch_state, sizeof(OdomState)), mmf_ctx_destroy(c));
+    MMF_HIP_TRY(hipMemsetAsync(c->scratch_state, 0, sizeof(OdomState), c->stream), mmf_ctx_destroy(c));
+    MMF_HIP_TRY(hipHostMalloc(&c->host_state, sizeof(OdomState), hipHostMallocDefault), mmf_ctx_destroy(c));
+    MMF_HIP_TRY(hipEventCreate(&c->ev0), mmf_ctx_destroy(c));
+    MMF_HIP_TRY(hipEventCreate(&c->ev1), mmf_ctx_destroy(c));
+    MMF_HIP_TRY(hipStreamSynchronize(c->stream), mmf_ctx_destroy(c));
     {  // (surfel_kernels.hpp: xcd_block)
-        const int on = g_xcd_forced.load() < 0 ? (tunables().xcd_blocks ? 1 : 0) : g_xcd_forced.load();
-        MMF_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_xcd_blocks), &on, sizeof(on)));
+        const int on = (int)g_xcd_forced.get(tunables().xcd_blocks ? 1 : 0);
+        MMF_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_xcd_blocks), &on, sizeof(on)), mmf_ctx_destroy(c));
     }
     *out = c;
     return MMF_OK;
@@ -185,13 +190,14 @@ extern "C" int mmf_ctx_create(int device, void* stream, int private_stream, mmf_
 // round-robin as the workgroups are (0); -1 = the default (MMF_XCD).  A device-wide word: set while no pass is running.
 extern "C" unsigned mmf_debug_xcd_block(unsigned block, unsigned blocks) { return xcd_block_of(block, blocks); }  // (host: no device needed)
 extern "C" int mmf_debug_set_xcd(int on) {
-    g_xcd_forced.store(on < 0 ? -1 : (on ? 1 : 0));
-    const int v = on < 0 ? (tunables().xcd_blocks ? 1 : 0) : (on ? 1 : 0);
+    override_flag(g_xcd_forced, on);
+    const int v = (int)g_xcd_forced.get(tunables().xcd_blocks ? 1 : 0);
     MMF_HIP_TRY(hipDeviceSynchronize());
     MMF_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_xcd_blocks), &v, sizeof(v)));
     return MMF_OK;
 }
 
+// Safe on a half-built context (mmf_ctx_create's failure paths): null pointers free nothing, a stream that was not made is not ours.
 extern "C" void mmf_ctx_destroy(mmf_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
@@ -752,1718 +758,11 @@ extern "C" int mmf_compute_derivative_images(mmf_ctx* c, const uint8_t* src, siz
 }
 
 // ---------------------------------------------------------------------------------------------
-// RGBDOdometry object
+// RGBDOdometry: the object, the batched preparation, the Gauss-Newton chain
 // ---------------------------------------------------------------------------------------------
-constexpr int kMaxTimedLaunches = 48;  // 19 iterations x (producer + step)
-
-struct mmf_odom {
-    mmf_ctx* ctx = nullptr;
-    int width = 0, height = 0;
-    float cx = 0, cy = 0, fx = 0, fy = 0;
-    float dist_thres = 0, angle_thres = 0;
-    float sobel_scale = 0.125f;         // RGBDOdometry.cpp:31-32
-    float max_depth_delta_rgb = 0.07f;  // :33
-    float max_depth_rgb = 6.0f;         // :34
-    float min_grad[MMF_NUM_PYRS] = {5, 3, 1};  // :103-105
-
-    // one slab of HBM; every buffer below points into it
-    void* slab = nullptr;
-    size_t slab_bytes = 0;
-    float *vmaps_tmp = nullptr, *nmaps_tmp = nullptr;
-    float *vmaps_g_prev[MMF_NUM_PYRS], *nmaps_g_prev[MMF_NUM_PYRS];
-    float *vmaps_curr[MMF_NUM_PYRS], *nmaps_curr[MMF_NUM_PYRS];
-    float *last_depth[MMF_NUM_PYRS], *next_depth[MMF_NUM_PYRS], *depth_pyr[MMF_NUM_PYRS];
-    uint8_t *last_image[MMF_NUM_PYRS], *next_image[MMF_NUM_PYRS], *last_next_image[MMF_NUM_PYRS];
-    int16_t *dIdx[MMF_NUM_PYRS], *dIdy[MMF_NUM_PYRS];
-    float* cloud[MMF_NUM_PYRS];
-    float* cloud4[MMF_NUM_PYRS];  // the same points as {X, Y, Z, 1/Z} (16-byte records: what gn_iter_kernel gathers)
-    mmf_dataterm* corres[MMF_NUM_PYRS];
-    float* prev_packed[MMF_NUM_PYRS];  // model vertex + normal, pixel interleaved 24-byte records (the ICP gather side)
-    // reduction scratch of the Gauss-Newton loop and the two error images, inside the slab: every odometry object has
-    // its own (concurrent chains on different streams, or one batched chain addressing model m at slab(m) - slab(0))
-    float* gn_partials_f = nullptr;
-    float* gn_partials_icp = nullptr;
-    int2* gn_partials_res = nullptr;
-    unsigned* gn_ticket = nullptr;
-    float *icp_err = nullptr, *rgb_err = nullptr;  // Model::icpError / rgbError (R32F), written on the last level-0 iteration
-    // extent.hpp: three boxes of four words (extent_of_level), noted by the model-side preparation's depth jobs when the owner asks for it (extent_gen != 0:
-    // the number of the frame they were noted for), read by the two-launch chain's passes
-    unsigned long long* extent = nullptr;
-    unsigned extent_gen = 0;
-    // prep_batch.hpp (PrepJob::rect_*): the box an object model's model-side preparation last found its prediction non-zero
-    // in (device: two slots of four ints, the preparation's number & 1), and whether it describes the buffers (any
-    // preparation of the whole frame leaves it unknown)
-    int* prep_box = nullptr;
-    unsigned prep_gen = 0;
-    bool prep_box_known = false;
-    unsigned sensor_gen = 0;     // number of the last sensor-side depth preparation (its smallest depth: extent words 18 / 19)
-    float sensor_cutoff = 0.f;   // ... and the depth cut-off its vertex maps were made with
-    // an OBJECT model (set by the orchestrator): the two-launch chain walks its images with a quarter of the workgroups
-    // (track_kernels.hpp: ChainGeom), batched or alone
-    bool sparse = false;
-    // ... and the one-launch chain by its extents with a fraction of the workgroups (gn_fused.hpp: gn_iter_mixed_kernel), as
-    // many as the box of its own depth needed in its LAST chain plus a quarter (OdomState::gn_need; 0: no chain yet)
-    int gn_need[MMF_NUM_PYRS] = {0, 0, 0};
-    int last_gn_fault = 0;          // OdomState::gn_fault of the last result picked up (odom_finish_tracking)
-    GnTruncated* gn_truncated = nullptr;  // test hook (mmf_debug_gn_truncate): made by the first truncated chain
-    bool walked_by_extent = false;  // the last chain enqueued walked this model by its extents (gn_iter_mixed_kernel)
-    bool two_launch_once = false;  // the next chain this odometry leads is the two-launch chain (a frame tracked again)
-    OdomState* state = nullptr;  // device
-    OdomState* host_result = nullptr;  // pinned, device visible: odom_publish_kernel writes it, the host polls publish_seq
-    OdomState* host_result_dev = nullptr;
-    unsigned publish_seq = 0;          // sequence number of the last chain enqueued
-    bool defer_publish = false;        // set by the orchestrator: the hand-over to the host + the fusion weight ride on the
-    FrameRider rider;                  // frame's next resolve launch (frame_rider.hpp) instead of ending the chain
-    bool have_tmp = false;  // vmaps_tmp filled by an initICP* call (ordering contract)
-    // The reference COPIES its inputs at each init* call (RGBDOdometry.cpp:125,130; Model.cpp:359-388).
-    // An owner that guarantees the images stay untouched until getIncrementalTransformation returns
-    // (the native orchestrator: they live in its model / frame slabs) sets alias_inputs, and the three
-    // device-to-device copies per frame (2 x 4.9 MB + 1.2 MB at 640x480) become pointer assignments.
-    bool alias_inputs = false;
-    const float *vtmp = nullptr, *ntmp = nullptr;  // what populateRGBDData / copyMaps read: own copy or alias
-    const float* depth_l0 = nullptr;               // level 0 of the depth pyramid: own copy or alias
-    // set by the batched model-side preparation (prep_collect_model): gradients and point clouds are already built, and next_depth is
-    // last_depth (both come from the same prediction, RGBDOdometry.cpp:179 -- see odom_populate_rgbd)
-    bool prep_batched = false;
-    bool so3_prefetched = false;  // this frame's SO3 pre-alignment already ran (odom_prefetch_so3)
-    const OdomState* so3_stage = nullptr;  // ... in this state (nullptr: in this odometry's own)
-    // The gradient images are double buffered: the batched image-side preparation writes grad_w_*, the chain reads dIdx /
-    // dIdy, and odom_adopt_gradients swaps the two when a prepared frame becomes the frame that is tracked -- so that the
-    // NEXT frame's image side can be prepared while this frame's chain still reads its gradients.
-    int16_t *grad_w_dx[MMF_NUM_PYRS], *grad_w_dy[MMF_NUM_PYRS];
-    bool grad_pending = false;  // grad_w_* hold a prepared frame's gradients
-    // The one-launch-per-iteration chain has a barrier inside every launch: its workgroups must all become resident.  Two
-    // such launches from different streams can each hold part of the GPU and wait for the rest forever, so an owner that
-    // keeps several chains in flight at once (the orchestrator without batching) clears this and gets the two-launch chain.
-    bool exclusive_chain = true;
-    // the beginning of the next tracking already ran, with these arguments, on the last launch of the preparation enqueued ahead
-    // of it (track_kernels.hpp: prep_batch_begin_kernel); begin_spec_ok: the caller vouches that nothing touched the state since
-    bool begin_spec_valid = false, begin_spec_ok = false;
-    BeginArgs begin_spec;
-    bool retry_so3_prefetched = false;  // what the last odom_enqueue_tracking consumed (a chain that gives up is enqueued again)
-    const OdomState* retry_so3_stage = nullptr;
-    bool pending_icp = false, pending_so3 = false;  // mode of the tracking call that is in flight (enqueue -> finish)
-    hipStream_t track_stream = nullptr;             // the stream that call's chain runs on (the batch leader's)
-    mmf_odom* result_of = nullptr;                  // the odometry (batch leader) whose chain publishes this one's result
-    // measurement mode (mmf_odom_enable_timing): every producer / rgb_step launch of a tracking call carries its own
-    // start / stop events (hipExtLaunchKernelGGL: the dispatch's own begin / end timestamps), the whole chain two more
-    int timing = 0;  // 1: chain events only; 2: also every kernel of the chain
-    hipEvent_t ev_kernel[2 * kMaxTimedLaunches] = {};
-    int timed_kind[kMaxTimedLaunches] = {};  // level * 2 + (0 producer | 1 rgb_step)
-    int n_timed = 0;
-    hipEvent_t ev_chain[2] = {};
-    mmf_odom_timing timing_acc;
-    mmf_odom_stats stats;
-};
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-extern "C" int mmf_odom_create(mmf_ctx* c, int width, int height, float cx, float cy, float fx, float fy,
-                               float dist_thresh, float angle_thresh, mmf_odom** out) {
-    MMF_REQUIRE(c && out, "mmf_odom_create: null argument");
-    MMF_REQUIRE(width >= 32 && height >= 32 && width % 4 == 0 && height % 4 == 0 && width < 32768 && height < 32768,
-                "mmf_odom_create: width/height must be multiples of 4, >= 32");
-    MMF_HIP_TRY(hipSetDevice(c->device));
-    mmf_odom* o = new (std::nothrow) mmf_odom();
-    MMF_REQUIRE(o != nullptr, "mmf_odom_create: out of host memory");
-    o->ctx = c;
-    o->width = width;
-    o->height = height;
-    o->cx = cx;
-    o->cy = cy;
-    o->fx = fx;
-    o->fy = fy;
-    o->dist_thres = dist_thresh;
-    o->angle_thres = angle_thresh;
-    std::memset(&o->stats, 0, sizeof(o->stats));
-    std::memset(&o->timing_acc, 0, sizeof(o->timing_acc));
-    o->stats.lastICPCount = o->stats.lastRGBCount = o->stats.lastSO3Count = (float)(width * height);  // :24-28
-
-    // carve every pyramid buffer out of one allocation, each 256-byte aligned
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
-    const size_t n0 = (size_t)width * height;
-    size_t o_vt = carve(4 * n0 * 4), o_nt = carve(4 * n0 * 4);
-    size_t o_vgp[3], o_ngp[3], o_vc[3], o_nc[3], o_ld[3], o_nd[3], o_dp[3], o_li[3], o_ni[3], o_lni[3], o_dx[3],
-        o_dy[3], o_dx2[3], o_dy2[3], o_cl[3], o_c4[3], o_co[3], o_pp[3];
-    for (int i = 0; i < MMF_NUM_PYRS; ++i) {
-        const size_t n = (size_t)(width >> i) * (height >> i);
-        o_vgp[i] = carve(3 * n * 4);
-        o_ngp[i] = carve(3 * n * 4);
-        o_vc[i] = carve(3 * n * 4);
-        o_nc[i] = carve(3 * n * 4);
-        o_ld[i] = carve(n * 4);
-        o_nd[i] = carve(n * 4);
-        o_dp[i] = carve(n * 4);
-        o_li[i] = carve(n);
-        o_ni[i] = carve(n);
-        o_lni[i] = carve(n);
-        o_dx[i] = carve(n * 2);
-        o_dy[i] = carve(n * 2);
-        o_dx2[i] = carve(n * 2);
-        o_dy2[i] = carve(n * 2);
-        o_cl[i] = carve(3 * n * 4);
-        o_c4[i] = carve(4 * n * 4);
-        o_co[i] = carve(n * sizeof(mmf_dataterm));
-        o_pp[i] = carve(n * 6 * sizeof(float));
-    }
-    size_t o_state = carve(sizeof(OdomState));
-    const size_t o_pf = carve(sizeof(float) * kMaxGrid * kPartialStride), o_pi = carve(sizeof(float) * kMaxIcpGrid * kPartialStride),
-                 o_pr = carve(sizeof(int2) * kMaxGrid), o_tk = carve(sizeof(unsigned) * kTicketWords), o_ei = carve(n0 * 4),
-                 o_er = carve(n0 * 4), o_ex = carve(kExtentWords * sizeof(unsigned long long) + 64);  // (+ prep_box)
-    o->slab_bytes = off;
-    hipError_t e = hipMalloc(&o->slab, o->slab_bytes);
-    if (e != hipSuccess) {
-        delete o;
-        return fail(MMF_ERR_HIP, std::string("mmf_odom_create: hipMalloc: ") + hipGetErrorString(e));
-    }
-    MMF_HIP_TRY(hipMemsetAsync(o->slab, 0, o->slab_bytes, c->stream));
-    char* base = static_cast<char*>(o->slab);
-    o->vmaps_tmp = (float*)(base + o_vt);
-    o->nmaps_tmp = (float*)(base + o_nt);
-    for (int i = 0; i < MMF_NUM_PYRS; ++i) {
-        o->vmaps_g_prev[i] = (float*)(base + o_vgp[i]);
-        o->nmaps_g_prev[i] = (float*)(base + o_ngp[i]);
-        o->vmaps_curr[i] = (float*)(base + o_vc[i]);
-        o->nmaps_curr[i] = (float*)(base + o_nc[i]);
-        o->last_depth[i] = (float*)(base + o_ld[i]);
-        o->next_depth[i] = (float*)(base + o_nd[i]);
-        o->depth_pyr[i] = (float*)(base + o_dp[i]);
-        o->last_image[i] = (uint8_t*)(base + o_li[i]);
-        o->next_image[i] = (uint8_t*)(base + o_ni[i]);
-        o->last_next_image[i] = (uint8_t*)(base + o_lni[i]);
-        o->dIdx[i] = (int16_t*)(base + o_dx[i]);
-        o->dIdy[i] = (int16_t*)(base + o_dy[i]);
-        o->grad_w_dx[i] = (int16_t*)(base + o_dx2[i]);
-        o->grad_w_dy[i] = (int16_t*)(base + o_dy2[i]);
-        o->cloud[i] = (float*)(base + o_cl[i]);
-        o->cloud4[i] = (float*)(base + o_c4[i]);
-        o->corres[i] = (mmf_dataterm*)(base + o_co[i]);
-        o->prev_packed[i] = (float*)(base + o_pp[i]);
-    }
-    o->state = (OdomState*)(base + o_state);
-    o->gn_partials_f = (float*)(base + o_pf), o->gn_partials_icp = (float*)(base + o_pi);
-    o->gn_partials_res = (int2*)(base + o_pr), o->gn_ticket = (unsigned*)(base + o_tk);
-    o->icp_err = (float*)(base + o_ei), o->rgb_err = (float*)(base + o_er);
-    o->extent = (unsigned long long*)(base + o_ex);
-    o->prep_box = (int*)(base + o_ex + kExtentWords * sizeof(unsigned long long));
-    MMF_HIP_TRY(hipHostMalloc(&o->host_result, sizeof(OdomState), hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(o->host_result, 0, sizeof(OdomState));
-    MMF_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&o->host_result_dev), o->host_result, 0));
-    MMF_HIP_TRY(hipStreamSynchronize(c->stream));
-    *out = o;
-    return MMF_OK;
-}
-
-// The odometry of a model ANOTHER rank tracks (fusion_state.hpp: a shard rank's bookkeeping copies): the host
-// struct only -- statistics as they arrive with the pose exchange -- no slab, no events, nothing a kernel could be given.
-static int odom_create_bookkeeping(mmf_ctx* c, int width, int height, float cx, float cy, float fx, float fy, mmf_odom** out) {
-    mmf_odom* o = new (std::nothrow) mmf_odom();
-    MMF_REQUIRE(o != nullptr, "mmf_odom_create: out of host memory");
-    o->ctx = c;
-    o->width = width, o->height = height;
-    o->cx = cx, o->cy = cy, o->fx = fx, o->fy = fy;
-    std::memset(&o->stats, 0, sizeof(o->stats));
-    std::memset(&o->timing_acc, 0, sizeof(o->timing_acc));
-    o->stats.lastICPCount = o->stats.lastRGBCount = o->stats.lastSO3Count = (float)(width * height);
-    *out = o;
-    return MMF_OK;
-}
-
-extern "C" void mmf_odom_destroy(mmf_odom* o) {
-    if (!o) return;
-    (void)hipSetDevice(o->ctx->device);
-    (void)hipStreamSynchronize(o->ctx->stream);
-    (void)hipFree(o->slab);
-    if (o->gn_truncated) (void)hipFree(o->gn_truncated);
-    (void)hipHostFree(o->host_result);
-    for (hipEvent_t e : o->ev_kernel)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : o->ev_chain)
-        if (e) (void)hipEventDestroy(e);
-    delete o;
-}
-
-extern "C" int mmf_odom_build_depth_pyramid(mmf_odom* o, const float* depth_l0, size_t step) {
-    MMF_REQUIRE(o && depth_l0, "mmf_odom_build_depth_pyramid: null argument");
-    mmf_ctx* c = o->ctx;
-    MMF_HIP_TRY(hipSetDevice(c->device));
-    const size_t s = step ? step : (size_t)o->width * 4;
-    if (o->alias_inputs && s == (size_t)o->width * 4) {
-        o->depth_l0 = depth_l0;
-    } else {
-        MMF_HIP_TRY(hipMemcpy2DAsync(o->depth_pyr[0], (size_t)o->width * 4, depth_l0, s, (size_t)o->width * 4, o->height,
-                                     hipMemcpyDeviceToDevice, c->stream));
-        o->depth_l0 = o->depth_pyr[0];
-    }
-    for (int i = 1; i < MMF_NUM_PYRS; ++i) {  // Model.cpp:378-382
-        int rc = launch_pyrdown_f(c, i == 1 ? o->depth_l0 : o->depth_pyr[i - 1], o->width >> (i - 1), o->width >> (i - 1),
-                                  o->height >> (i - 1), o->depth_pyr[i], o->width >> i);
-        if (rc) return rc;
-    }
-    return MMF_OK;
-}
-
-extern "C" int mmf_odom_init_icp(mmf_odom* o, const float* const depth_pyr[MMF_NUM_PYRS],
-                                 const size_t steps[MMF_NUM_PYRS], float depth_cutoff) {
-    MMF_REQUIRE(o != nullptr, "mmf_odom_init_icp: null odometry");
-    mmf_ctx* c = o->ctx;
-    MMF_HIP_TRY(hipSetDevice(c->device));
-    for (int i = 0; i < MMF_NUM_PYRS; ++i) {  // RGBDOdometry.cpp:112-115
-        const int cols = o->width >> i, rows = o->height >> i;
-        const float* d = depth_pyr ? depth_pyr[i] : (i == 0 && o->depth_l0 ? o->depth_l0 : o->depth_pyr[i]);
-        MMF_REQUIRE(d != nullptr, "mmf_odom_init_icp: null pyramid level");
-        const int ds = (depth_pyr && steps && steps[i]) ? (int)(steps[i] / 4) : cols;
-        int rc = launch_create_vmap(c, level_intr(o->fx, o->fy, o->cx, o->cy, i), d, ds, cols, rows, o->vmaps_curr[i],
-                                    cols, depth_cutoff);
-        if (rc) return rc;
-        rc = launch_create_nmap(c, o->vmaps_curr[i], cols, cols, rows, o->nmaps_curr[i], cols);
-        if (rc) return rc;
-    }
-    return MMF_OK;
-}
-
-static int odom_take_prediction(mmf_odom* o, const float* vert_rgba, const float* norm_rgba, float** vdst,
-                                float** ndst) {
-    mmf_ctx* c = o->ctx;
-    o->prep_batched = false;
-    const size_t bytes = (size_t)4 * o->width * o->height * sizeof(float);
-    // the reference copies both textures into vmaps_tmp / nmaps_tmp (RGBDOdometry.cpp:125,130);
-    // vmaps_tmp is read again by initRGB*/populateRGBDData (:179)
-    if (o->alias_inputs) {
-        o->vtmp = vert_rgba, o->ntmp = norm_rgba;
-    } else {
-        MMF_HIP_TRY(hipMemcpyAsync(o->vmaps_tmp, vert_rgba, bytes, hipMemcpyDeviceToDevice, c->stream));
-        MMF_HIP_TRY(hipMemcpyAsync(o->nmaps_tmp, norm_rgba, bytes, hipMemcpyDeviceToDevice, c->stream));
-        o->vtmp = o->vmaps_tmp, o->ntmp = o->nmaps_tmp;
-    }
-    o->have_tmp = true;
-    int rc = launch_copy_maps(c, o->vtmp, o->ntmp, o->width, o->height, vdst[0], ndst[0], o->width);
-    if (rc) return rc;
-    for (int i = 1; i < MMF_NUM_PYRS; ++i) {
-        rc = launch_resize<false>(c, vdst[i - 1], o->width >> (i - 1), o->width >> (i - 1), o->height >> (i - 1),
-                                  vdst[i], o->width >> i);
-        if (rc) return rc;
-        rc = launch_resize<true>(c, ndst[i - 1], o->width >> (i - 1), o->width >> (i - 1), o->height >> (i - 1),
-                                 ndst[i], o->width >> i);
-        if (rc) return rc;
-    }
-    return MMF_OK;
-}
-
-extern "C" int mmf_odom_init_icp_from_prediction(mmf_odom* o, const float* vert_rgba, const float* norm_rgba,
-                                                 float depth_cutoff) {
-    (void)depth_cutoff;  // unused by the reference as well (RGBDOdometry.cpp:120-141)
-    MMF_REQUIRE(o && vert_rgba && norm_rgba, "mmf_odom_init_icp_from_prediction: null argument");
-    MMF_HIP_TRY(hipSetDevice(o->ctx->device));
-    return odom_take_prediction(o, vert_rgba, norm_rgba, o->vmaps_curr, o->nmaps_curr);
-}
-
-extern "C" int mmf_odom_init_icp_model(mmf_odom* o, const float* vert_rgba, const float* norm_rgba,
-                                       float depth_cutoff, const float pose[16]) {
-    (void)depth_cutoff;  // unused by the reference as well (RGBDOdometry.cpp:143-175)
-    MMF_REQUIRE(o && vert_rgba && norm_rgba && pose, "mmf_odom_init_icp_model: null argument");
-    MMF_HIP_TRY(hipSetDevice(o->ctx->device));
-    int rc = odom_take_prediction(o, vert_rgba, norm_rgba, o->vmaps_g_prev, o->nmaps_g_prev);
-    if (rc) return rc;
-    const float R[9] = {pose[0], pose[1], pose[2], pose[4], pose[5], pose[6], pose[8], pose[9], pose[10]};
-    const float t[3] = {pose[3], pose[7], pose[11]};
-    for (int i = 0; i < MMF_NUM_PYRS; ++i) {
-        const int cols = o->width >> i, rows = o->height >> i;
-        rc = launch_transform(o->ctx, o->vmaps_g_prev[i], o->nmaps_g_prev[i], cols, cols, rows, R, t,
-                              o->vmaps_g_prev[i], o->nmaps_g_prev[i], cols);
-        if (rc) return rc;
-        const int n = cols * rows;
-        hipLaunchKernelGGL(pack_prev_kernel, dim3((n + 255) / 256), dim3(256), 0, o->ctx->stream, o->vmaps_g_prev[i],
-                           o->nmaps_g_prev[i], n, o->prev_packed[i]);
-        MMF_HIP_TRY(hipGetLastError());
-    }
-    return MMF_OK;
-}
-
-// RGBDOdometry.cpp:177-194 (populateRGBDData); mask pyramids are never read and are omitted
-static int odom_populate_rgbd(mmf_odom* o, const uint8_t* rgb, size_t step, int channels, float** depths,
-                              uint8_t** images) {
-    mmf_ctx* c = o->ctx;
-    o->prep_batched = false;
-    if (!o->have_tmp)
-        return fail(MMF_ERR_STATE, "initRGB*/initRGBModel needs a preceding initICPModel / initICP(prediction): "
-                                   "it reads vmaps_tmp (RGBDOdometry.cpp:197,202)");
-    int rc = launch_vertices_to_depth(c, o->vtmp, o->width, o->height, o->max_depth_rgb, depths[0], o->width);
-    if (rc) return rc;
-    for (int i = 0; i + 1 < MMF_NUM_PYRS; ++i) {
-        rc = launch_pyrdown_f(c, depths[i], o->width >> i, o->width >> i, o->height >> i, depths[i + 1],
-                              o->width >> (i + 1));
-        if (rc) return rc;
-    }
-    rc = launch_intensity(c, rgb, step ? (int)step : o->width * channels, channels, o->width, o->height, images[0],
-                          o->width);
-    if (rc) return rc;
-    for (int i = 0; i + 1 < MMF_NUM_PYRS; ++i) {
-        rc = launch_pyrdown_u8(c, images[i], o->width >> i, o->width >> i, o->height >> i, images[i + 1],
-                               o->width >> (i + 1));
-        if (rc) return rc;
-    }
-    return MMF_OK;
-}
-
-extern "C" int mmf_odom_init_rgb(mmf_odom* o, const uint8_t* rgb, size_t step, int channels) {
-    MMF_REQUIRE(o && rgb && (channels == 3 || channels == 4), "mmf_odom_init_rgb: bad argument");
-    MMF_HIP_TRY(hipSetDevice(o->ctx->device));
-    return odom_populate_rgbd(o, rgb, step, channels, o->next_depth, o->next_image);
-}
-
-extern "C" int mmf_odom_init_rgb_model(mmf_odom* o, const uint8_t* rgb, size_t step, int channels) {
-    MMF_REQUIRE(o && rgb && (channels == 3 || channels == 4), "mmf_odom_init_rgb_model: bad argument");
-    MMF_HIP_TRY(hipSetDevice(o->ctx->device));
-    return odom_populate_rgbd(o, rgb, step, channels, o->last_depth, o->last_image);
-}
-
-extern "C" int mmf_odom_init_first_rgb(mmf_odom* o, const uint8_t* rgb, size_t step, int channels) {
-    MMF_REQUIRE(o && rgb && (channels == 3 || channels == 4), "mmf_odom_init_first_rgb: bad argument");
-    mmf_ctx* c = o->ctx;
-    MMF_HIP_TRY(hipSetDevice(c->device));
-    int rc = launch_intensity(c, rgb, step ? (int)step : o->width * channels, channels, o->width, o->height,
-                              o->last_next_image[0], o->width);
-    if (rc) return rc;
-    for (int i = 0; i + 1 < MMF_NUM_PYRS; ++i) {  // RGBDOdometry.cpp:212-214
-        rc = launch_pyrdown_u8(c, o->last_next_image[i], o->width >> i, o->width >> i, o->height >> i,
-                               o->last_next_image[i + 1], o->width >> (i + 1));
-        if (rc) return rc;
-    }
-    return MMF_OK;
-}
-
-// ---- the whole per-frame preparation in four launches (prep_batch.hpp) -------------------------
-static std::atomic<long> g_prep_big{-1};  // -1: MMF_PREP_BIG decides; 0: never; n > 0: that many pixels (mmf_debug_set_prep_big)
-extern "C" int mmf_debug_set_prep_big(int n) {
-    g_prep_big.store(n < 0 ? -1L : (long)n);
-    return MMF_OK;
-}
-static size_t prep_big_job() {  // pixels from which a job's workgroups take four tiles each; MMF_PREP_BIG=0: never
-    const long forced = g_prep_big.load();
-    const long n = forced < 0 ? tunables().prep_big : forced;
-    return n < 0 ? (size_t)200000 : (n > 0 ? (size_t)n : ~(size_t)0);
-}
-struct PrepBuilder {  // the jobs of one stage (possibly of several models); launched kMaxPrepJobs at a time
-    std::vector<PrepJob> jobs;
-    bool critical = false;  // PrepBatch::critical
-    PrepJob& add(int op, int cols, int rows) {
-        if (jobs.capacity() < 96) jobs.reserve(96);  // references handed out stay valid while a stage is being filled
-        jobs.emplace_back();
-        PrepJob& j = jobs.back();
-        std::memset(&j, 0, sizeof(j));
-        j.op = op;
-        j.cols = cols, j.rows = rows;
-        j.gx = (cols + kTileX - 1) / kTileX;
-        j.reps = (size_t)cols * rows >= prep_big_job() ? 4 : 1;  // (PrepJob::reps)
-        return j;
-    }
-    // rider: the beginning of the tracking these jobs prepare, on one more workgroup of the stage's LAST launch (BeginRider)
-    template <int CAP>
-    static int fill(PrepBatchT<CAP>& b, const std::vector<PrepJob>& jobs, size_t first, bool critical) {
-        b.njobs = 0;
-        b.critical = critical ? 1 : 0;
-        int blocks = 0;
-        for (size_t k = first; k < jobs.size() && b.njobs < CAP; ++k) {
-            PrepJob& j = b.job[b.njobs++];
-            j = jobs[k];
-            j.first_block = blocks;
-            blocks += j.rect_now ? j.rect_groups : j.gx * ((j.rows + kTileY * j.reps - 1) / (kTileY * j.reps));
-        }
-        return blocks;
-    }
-    int launch(Enqueuer& q, const BeginRider* rider = nullptr) {
-        if (jobs.size() > (size_t)kMaxPrepJobs && !rider) {  // several models' jobs: the wide table (prep_batch.hpp)
-            for (size_t first = 0; first < jobs.size(); first += kMaxPrepJobsWide) {
-                PrepBatchWide b;
-                const int blocks = fill(b, jobs, first, critical);
-                q.launch(prep_batch_wide_kernel, dim3(blocks), tile_block(), b);
-            }
-            jobs.clear();
-            return MMF_OK;
-        }
-        for (size_t first = 0; first < jobs.size(); first += kMaxPrepJobs) {
-            PrepBatch b;
-            const int blocks = fill(b, jobs, first, critical);
-            if (rider && first + kMaxPrepJobs >= jobs.size()) {
-                BeginRider r = *rider;
-                r.prep_blocks = blocks;
-                q.launch(prep_batch_begin_kernel, dim3(blocks + 1), tile_block(), b, r);
-            } else {
-                q.launch(prep_batch_kernel, dim3(blocks), tile_block(), b);
-            }
-        }
-        jobs.clear();
-        return MMF_OK;
-    }
-};
-struct PrepStages {  // the four dependent launches of a frame's preparation
-    PrepBuilder stage[4];
-    void set_critical(bool on) {
-        for (PrepBuilder& pb : stage) pb.critical = on;
-    }
-    int launch(Enqueuer& q, const BeginRider* rider = nullptr) {  // recorded; the caller flushes.  rider: on the last launch
-        int last = -1;
-        for (int k = 0; k < 4; ++k)
-            if (!stage[k].jobs.empty()) last = k;
-        for (int k = 0; k < 4; ++k)
-            if (int rc = stage[k].launch(q, k == last ? rider : nullptr)) return rc;
-        return MMF_OK;
-    }
-    int launch(hipStream_t stream, const BeginRider* rider = nullptr) {
-        Enqueuer q(stream);
-        if (int rc = launch(q, rider)) return rc;
-        MMF_HIP_TRY(q.flush());
-        return MMF_OK;
-    }
-    bool empty() const {
-        for (const PrepBuilder& pb : stage)
-            if (!pb.jobs.empty()) return false;
-        return true;
-    }
-};
-
-// Everything initICPModel + initRGBModel + generateCUDATextures/initICP + initRGB + the gradient and
-// point-cloud passes of getIncrementalTransformation compute (RGBDOdometry.cpp:108-235, 332-334;
-// Model.cpp:359-407), for inputs that stay untouched until tracking returns (the native orchestrator).
-// The jobs split into those that depend only on the NEW sensor frame (filtered depth, RGB: vertex / normal maps, depth
-// and intensity pyramids, gradients: prep_collect_sensor) and those that depend on the model's prediction and pose
-// (prep_collect_model).  The orchestrator can run the first group for frame t+1 on a second stream while frame t is still
-// being fused (mmf_fusion_prefetch_frame); PREP_ALL is both groups in the same four launches (prep_collect_all).
-// Which stage a job goes to, and where in it, is fixed (prep_batch.hpp: the one arrangement): a stage's list of jobs decides
-// which workgroup of the launch does what.
-enum PrepSide { PREP_INPUT_IMAGE = 1, PREP_INPUT_DEPTH = 2, PREP_MODEL_SIDE = 4, PREP_ALL = 7 };
-
-struct PrepSensorFrame {  // what the sensor side reads
-    const float* depth_filtered = nullptr;  // the depth side's input
-    float depth_cutoff = 0.f;
-    const uint8_t* rgb = nullptr;  // the image side's input: interleaved, `channels` bytes per pixel
-    int channels = 3;
-};
-struct PrepPrediction {  // what the model side reads: a model's prediction and the pose it is tracked from
-    const float *vertex = nullptr, *normal = nullptr;  // RGBA32F
-    const uint8_t* image = nullptr;
-    int channels = 4;
-    const float* pose = nullptr;      // row-major 4 x 4
-    const float* depth_l0 = nullptr;  // the frame's filtered depth, which the model's chain reads as level 0 of the depth pyramid
-    // optional device-side choice of the sources (PrepJob::sel): the alt_* images instead when *sel != 0 or, with sel_total
-    // != 0, when fewer than sel_ratio of the sel_total thumbnail samples are covered
-    const int* sel = nullptr;
-    const float *alt_vertex = nullptr, *alt_normal = nullptr;
-    const uint8_t* alt_image = nullptr;
-    int sel_total = 0;
-    float sel_ratio = 0.f;
-    unsigned ext_gen = 0;  // != 0: the jobs that write the model's depth and vertex pyramids note the extent of what is valid (extent.hpp)
-    // (device, level-0 pixels {x0, y0, x1, y1}; an OBJECT model prepared on its own only): where the prediction's images are
-    // non-zero -- the jobs then cover the hull of that box and of the one the previous preparation saw (PrepJob::rect_*)
-    const int* pred_box = nullptr;
-};
-
-static std::atomic<int> g_prep_rect{-1};  // -1: MMF_PREP_RECT decides (default on); 0 / 1: mmf_debug_set_prep_rect
-extern "C" int mmf_debug_set_prep_rect(int on) {
-    g_prep_rect.store(on < 0 ? -1 : (on ? 1 : 0));
-    return MMF_OK;
-}
-
-static void prep_intr_f(PrepJob& j, const mmf_odom* o, int lvl) {  // f = {1/fx, 1/fy, cx, cy} of a level
-    const LevelIntr in = level_intr(o->fx, o->fy, o->cx, o->cy, lvl);
-    j.f[0] = 1.f / in.fx, j.f[1] = 1.f / in.fy, j.f[2] = in.cx, j.f[3] = in.cy;
-}
-static void prep_pose_f(PrepJob& j, const float pose[16]) {  // f = {R[9], t[3]}
-    for (int r = 0; r < 3; ++r) {
-        for (int q = 0; q < 3; ++q) j.f[3 * r + q] = pose[4 * r + q];
-        j.f[9 + r] = pose[4 * r + 3];
-    }
-}
-static PrepJob& prep_pyr_step(PrepBuilder& pb, const mmf_odom* o, int op, const void* src, void* dst, int lvl) {  // level lvl-1 -> lvl
-    PrepJob& j = pb.add(op, o->width >> lvl, o->height >> lvl);
-    j.src0 = src, j.dst0 = dst;
-    j.scols = o->width >> (lvl - 1), j.srows = o->height >> (lvl - 1);
-    return j;
-}
-// the fill-in images a model-side job reads instead of the prediction's when the device says so (PrepPrediction::sel)
-static void prep_alt(PrepJob& j, const PrepPrediction& p, const void* alt0, const void* alt1 = nullptr) {
-    j.sel = p.sel, j.alt0 = alt0, j.alt1 = alt1;
-    if (p.sel && p.sel_total) j.sel_total = p.sel_total, j.sel_ratio = p.sel_ratio;  // *sel is a count (PrepJob::sel_total)
-}
-
-// depth side: stage k makes level k's vertex and normal maps and level k+1 of the depth pyramid -- three dependent launches
-static void prep_depth_jobs(PrepStages& stages, mmf_odom* o, const PrepSensorFrame& fr) {
-    const float* depth[MMF_NUM_PYRS] = {fr.depth_filtered, o->depth_pyr[1], o->depth_pyr[2]};
-    for (int lvl = 0; lvl < MMF_NUM_PYRS; ++lvl) {
-        PrepBuilder& pb = stages.stage[lvl];
-        if (lvl + 1 < MMF_NUM_PYRS) prep_pyr_step(pb, o, PREP_PYRDOWN_F, depth[lvl], o->depth_pyr[lvl + 1], lvl + 1);
-        PrepJob& j = pb.add(PREP_VMAP_NMAP, o->width >> lvl, o->height >> lvl);
-        j.src0 = depth[lvl], j.dst0 = o->vmaps_curr[lvl], j.dst1 = o->nmaps_curr[lvl];
-        prep_intr_f(j, o, lvl);
-        j.f[4] = fr.depth_cutoff;
-        if (lvl == 0) {  // (extent.hpp: the sensor frame's smallest valid depth, for the object models' error-image launches)
-            j.zmin = o->extent, j.zmin_gen = ++o->sensor_gen;
-            o->sensor_cutoff = fr.depth_cutoff;
-        }
-    }
-}
-// image side: the intensity image in stage 0, then stage k+1 makes level k's gradients and level k+1 of the pyramid -- four
-static void prep_image_jobs(PrepStages& stages, mmf_odom* o, const PrepSensorFrame& fr) {
-    PrepJob& in = stages.stage[0].add(PREP_INTENSITY, o->width, o->height);
-    in.src0 = fr.rgb, in.dst0 = o->next_image[0], in.scols = o->width * fr.channels, in.channels = fr.channels;
-    for (int lvl = 0; lvl < MMF_NUM_PYRS; ++lvl) {
-        PrepBuilder& pb = stages.stage[lvl + 1];
-        PrepJob& d = pb.add(PREP_DERIV, o->width >> lvl, o->height >> lvl);
-        d.src0 = o->next_image[lvl], d.dst0 = o->grad_w_dx[lvl], d.dst1 = o->grad_w_dy[lvl];  // (odom_adopt_gradients)
-        if (lvl + 1 < MMF_NUM_PYRS) prep_pyr_step(pb, o, PREP_PYRDOWN_U8, o->next_image[lvl], o->next_image[lvl + 1], lvl + 1);
-    }
-    o->grad_pending = true;
-}
-static void prep_collect_sensor(PrepStages& stages, mmf_odom* o, const PrepSensorFrame& fr, int sides) {
-    if (sides & PREP_INPUT_DEPTH) prep_depth_jobs(stages, o, fr);
-    if (sides & PREP_INPUT_IMAGE) prep_image_jobs(stages, o, fr);
-}
-
-// Model side, two dependent launches (stages 1 and 2).  Level 1 of the camera-frame model maps (before the transform into
-// the global frame) is the one thing a job stores for another: it lives behind level 0's place in the two 4*N-float staging
-// images, which this path does not need as copies.
-static float* prep_level1_of(float* staging, const mmf_odom* o) { return staging + 3 * (size_t)o->width * o->height; }
-// ... what is made from a level's images: the packed records and the point records of levels 0 and 1, level 0's depth and
-// intensity.  Nothing of the preparation reads level 0's, which come straight from the prediction: l0_stage is 2, beside the
-// small jobs of levels 1 and 2, so that the first launch is the three quarter-size pyramid jobs alone (1: with a sensor side
-// in the same launches)
-static void prep_model_level_jobs(PrepStages& stages, mmf_odom* o, const PrepPrediction& p, int l0_stage) {
-    const int W = o->width, H = o->height;
-    {
-        PrepBuilder& pb = stages.stage[l0_stage];
-        PrepJob& t = pb.add(PREP_TEX_TP, W, H);
-        t.src0 = p.vertex, t.src1 = p.normal, t.dst2 = o->prev_packed[0];
-        prep_alt(t, p, p.alt_vertex, p.alt_normal);
-        prep_pose_f(t, p.pose);
-        if (p.ext_gen) t.aabb = o->extent, t.ext_gen = p.ext_gen;  // (extent.hpp: the pixel box and depth range of the valid vertices)
-        PrepJob& c = pb.add(PREP_TEX_PROJECT, W, H);
-        c.src0 = p.vertex, c.dst1 = o->cloud4[0], c.dst2 = o->last_depth[0];
-        prep_alt(c, p, p.alt_vertex);
-        prep_intr_f(c, o, 0);
-        c.f[4] = o->max_depth_rgb;
-        if (p.ext_gen) c.ext = o->extent, c.ext_gen = p.ext_gen;  // (the depth jobs: extent.hpp, extent_of_level)
-        PrepJob& il = pb.add(PREP_INTENSITY, W, H);
-        il.src0 = p.image, il.dst0 = o->last_image[0], il.scols = W * p.channels, il.channels = p.channels;
-        prep_alt(il, p, p.alt_image);
-    }
-    {
-        PrepBuilder& pb = stages.stage[2];
-        PrepJob& t = pb.add(PREP_TRANSFORM_PACK, W >> 1, H >> 1);
-        t.src0 = prep_level1_of(o->vmaps_tmp, o), t.src1 = prep_level1_of(o->nmaps_tmp, o), t.dst2 = o->prev_packed[1];
-        prep_pose_f(t, p.pose);
-        PrepJob& c = pb.add(PREP_PROJECT, W >> 1, H >> 1);
-        c.src0 = o->last_depth[1], c.dst1 = o->cloud4[1];
-        prep_intr_f(c, o, 1);
-    }
-}
-// ... and the pyramid steps: level 1 from the prediction's images, level 2 -- with its records, in the same job -- from level 1
-static void prep_model_pyramid_jobs(PrepStages& stages, mmf_odom* o, const PrepPrediction& p) {
-    const int W = o->width, H = o->height;
-    {
-        PrepBuilder& pb = stages.stage[1];
-        PrepJob& d = pb.add(PREP_TEX_PYR_F, W >> 1, H >> 1);
-        d.src0 = p.vertex, d.scols = W, d.srows = H, d.dst0 = o->last_depth[1], d.f[0] = o->max_depth_rgb;
-        prep_alt(d, p, p.alt_vertex);
-        if (p.ext_gen) d.ext = o->extent + 4, d.ext_gen = p.ext_gen;
-        PrepJob& u = pb.add(PREP_TEX_PYR_U8, W >> 1, H >> 1);
-        u.src0 = p.image, u.scols = W, u.srows = H, u.channels = p.channels, u.dst0 = o->last_image[1];
-        prep_alt(u, p, p.alt_image);
-        PrepJob& r = pb.add(PREP_TEX_RESIZE, W >> 1, H >> 1);
-        r.src0 = p.vertex, r.src1 = p.normal, r.scols = W, r.srows = H;
-        r.dst0 = prep_level1_of(o->vmaps_tmp, o), r.dst1 = prep_level1_of(o->nmaps_tmp, o);
-        prep_alt(r, p, p.alt_vertex, p.alt_normal);
-    }
-    {
-        PrepBuilder& pb = stages.stage[2];
-        prep_pyr_step(pb, o, PREP_PYRDOWN_U8, o->last_image[1], o->last_image[2], 2);
-        PrepJob& t = prep_pyr_step(pb, o, PREP_RESIZE_TP, prep_level1_of(o->vmaps_tmp, o), nullptr, 2);
-        t.src1 = prep_level1_of(o->nmaps_tmp, o), t.dst2 = o->prev_packed[2];
-        prep_pose_f(t, p.pose);
-        PrepJob& c = prep_pyr_step(pb, o, PREP_PYR_PROJECT, o->last_depth[1], nullptr, 2);
-        c.dst1 = o->cloud4[2], c.dst2 = o->last_depth[2];
-        prep_intr_f(c, o, 2);
-        if (p.ext_gen) c.ext = o->extent + 8, c.ext_gen = p.ext_gen;
-    }
-}
-// what the odometry remembers of a model-side preparation.  from (null: not boxed): the jobs of `stages` from these counts
-// on are this preparation's, and they cover the prediction's box only (PrepPrediction::pred_box)
-static void prep_model_done(PrepStages& stages, mmf_odom* o, const PrepPrediction& p, const size_t* from) {
-    o->depth_l0 = p.depth_l0;
-    o->vtmp = p.vertex, o->ntmp = p.normal;
-    o->have_tmp = true;
-    o->extent_gen = p.ext_gen;
-    if (from) {
-        const unsigned g = ++o->prep_gen;
-        const int* prev = o->prep_box_known ? o->prep_box + 4 * ((g + 1u) & 1u) : nullptr;
-        bool first = true;
-        for (int k = 0; k < 4; ++k)
-            for (size_t q = from[k]; q < stages.stage[k].jobs.size(); ++q) {
-                PrepJob& j = stages.stage[k].jobs[q];
-                int lvl = 0;
-                while ((o->width >> lvl) > j.cols && lvl < MMF_NUM_PYRS - 1) ++lvl;
-                j.rect_now = p.pred_box, j.rect_prev = prev;
-                j.rect_level = lvl;
-                j.rect_groups = lvl == 0 ? 48 : (lvl == 1 ? 32 : 16);
-                j.rect_store = first ? o->prep_box + 4 * (g & 1u) : nullptr;
-                first = false;
-            }
-    }
-    o->prep_box_known = from != nullptr;
-    o->prep_batched = true;
-}
-static void prep_collect_model(PrepStages& stages, mmf_odom* o, const PrepPrediction& p) {
-    const bool rect_on = g_prep_rect.load() < 0 ? tunables().prep_rect : g_prep_rect.load() != 0;
-    const bool boxed = p.pred_box != nullptr && p.sel == nullptr && rect_on && o->prep_box != nullptr;
-    size_t from[4];
-    for (int k = 0; k < 4; ++k) from[k] = stages.stage[k].jobs.size();
-    prep_model_level_jobs(stages, o, p, 2);
-    prep_model_pyramid_jobs(stages, o, p);
-    prep_model_done(stages, o, p, boxed ? from : nullptr);
-}
-// One model and a sensor side not prepared ahead: both in the same four launches.  Within a stage: the depth side's jobs, what
-// the model makes from a level's images, the image side's jobs, the model's pyramid steps.
-static void prep_collect_all(PrepStages& stages, mmf_odom* o, const PrepSensorFrame& fr, const PrepPrediction& p) {
-    prep_depth_jobs(stages, o, fr);
-    prep_model_level_jobs(stages, o, p, 1);
-    prep_image_jobs(stages, o, fr);
-    prep_model_pyramid_jobs(stages, o, p);
-    prep_model_done(stages, o, p, nullptr);
-}
-// the gradients the batched preparation wrote last become the ones the chain reads
-static void odom_adopt_gradients(mmf_odom* o) {
-    if (!o->grad_pending) return;
-    o->grad_pending = false;
-    for (int i = 0; i < MMF_NUM_PYRS; ++i) std::swap(o->dIdx[i], o->grad_w_dx[i]), std::swap(o->dIdy[i], o->grad_w_dy[i]);
-}
-
-// one or both halves of a sensor frame's side, as launches of their own: recorded in q (the caller flushes) or on the context's stream
-static int odom_prepare_sensor(mmf_odom* o, const PrepSensorFrame& fr, int sides, Enqueuer* q = nullptr) {
-    PrepStages stages;
-    prep_collect_sensor(stages, o, fr, sides);
-    return q ? stages.launch(*q) : stages.launch(o->ctx->stream);
-}
-
-// Test entry: the batched preparation of n stand-alone odometries as ONE set of stages, filled the way the orchestrator fills
-// them (fusion_orchestrator.hpp: fusion_collect_prep) -- host plumbing around the collectors above, no kernel of its own.
-extern "C" int mmf_debug_odom_prepare(mmf_odom* const* odoms, const mmf_debug_prep_prediction* preds, int n, const float* depth_filtered,
-                                      float depth_cutoff, const unsigned char* rgb, int rgb_channels, int sides) {
-    MMF_REQUIRE(odoms && preds && n >= 1, "mmf_debug_odom_prepare: null argument, or no odometry");
-    const bool sensor = depth_filtered != nullptr || rgb != nullptr;
-    MMF_REQUIRE(!sensor || (sides & ~(PREP_INPUT_IMAGE | PREP_INPUT_DEPTH)) == 0, "mmf_debug_odom_prepare: sides is a mask of 1 (image) and 2 (depth)");
-    MMF_REQUIRE(!sensor || (((sides & PREP_INPUT_DEPTH) == 0 || depth_filtered) && ((sides & PREP_INPUT_IMAGE) == 0 || rgb)),
-                "mmf_debug_odom_prepare: a side is asked for without its input");
-    MMF_REQUIRE(!sensor || (sides & PREP_INPUT_IMAGE) == 0 || rgb_channels == 3 || rgb_channels == 4, "mmf_debug_odom_prepare: rgb_channels must be 3 or 4");
-    for (int k = 0; k < n; ++k) {
-        const mmf_debug_prep_prediction& d = preds[k];
-        MMF_REQUIRE(odoms[k] && odoms[k]->slab && odoms[k]->ctx == odoms[0]->ctx, "mmf_debug_odom_prepare: odometries of one context");
-        MMF_REQUIRE(odoms[k]->width == odoms[0]->width && odoms[k]->height == odoms[0]->height, "mmf_debug_odom_prepare: odometries of one size");
-        MMF_REQUIRE(d.vertex && d.normal && d.image && d.pose && (d.channels == 3 || d.channels == 4), "mmf_debug_odom_prepare: incomplete prediction");
-        MMF_REQUIRE(!d.sel || (d.alt_vertex && d.alt_normal && d.alt_image && d.sel_total >= 0), "mmf_debug_odom_prepare: sel without the alt images");
-    }
-    mmf_ctx* c = odoms[0]->ctx;
-    MMF_HIP_TRY(hipSetDevice(c->device));
-    auto prediction = [&](int k) {
-        const mmf_debug_prep_prediction& d = preds[k];
-        PrepPrediction p;
-        p.vertex = d.vertex, p.normal = d.normal, p.image = d.image, p.channels = d.channels, p.pose = d.pose;
-        p.depth_l0 = depth_filtered;
-        p.sel = d.sel, p.alt_vertex = d.alt_vertex, p.alt_normal = d.alt_normal, p.alt_image = d.alt_image;
-        p.sel_total = d.sel_total, p.sel_ratio = d.sel_ratio;
-        p.ext_gen = d.ext_gen, p.pred_box = d.pred_box;
-        return p;
-    };
-    PrepSensorFrame fr;
-    fr.depth_filtered = depth_filtered, fr.depth_cutoff = depth_cutoff, fr.rgb = rgb, fr.channels = rgb_channels;
-    PrepStages stages;
-    if (sensor && n == 1 && sides == (PREP_INPUT_IMAGE | PREP_INPUT_DEPTH)) {
-        prep_collect_all(stages, odoms[0], fr, prediction(0));
-    } else {
-        if (sensor) prep_collect_sensor(stages, odoms[0], fr, sides);
-        for (int k = 0; k < n; ++k) prep_collect_model(stages, odoms[k], prediction(k));
-    }
-    if (int rc = stages.launch(c->stream)) return rc;
-    for (int k = 0; k < n; ++k) odom_adopt_gradients(odoms[k]);
-    return MMF_OK;
-}
-
-static IcpArgs odom_icp_args(mmf_odom* o, int level, float* err_map) {
-    const int cols = o->width >> level, rows = o->height >> level;
-    IcpArgs a;
-    a.vmap_curr = MapView{o->vmaps_curr[level], cols};
-    a.nmap_curr = MapView{o->nmaps_curr[level], cols};
-    a.vmap_g_prev = MapView{o->vmaps_g_prev[level], cols};
-    a.nmap_g_prev = MapView{o->nmaps_g_prev[level], cols};
-    a.intr = level_intr(o->fx, o->fy, o->cx, o->cy, level);
-    a.dist_thres = o->dist_thres;
-    a.angle_thres = o->angle_thres;
-    a.cols = cols;
-    a.rows = rows;
-    a.prev_packed = o->prev_packed[level];
-    a.err_map = err_map;
-    a.err_stride = cols;
-    icp_args_derive(a);
-    return a;
-}
-
-// the ten launches of the SO3 pre-alignment (RGBDOdometry.cpp:239-310): last frame's image against this frame's
-// at level 2 -- no model, no pose
-static int odom_enqueue_so3(mmf_odom* o, Enqueuer& q, float* partials = nullptr, unsigned* ticket = nullptr, OdomState* state = nullptr) {
-    if (!partials) partials = o->gn_partials_f, ticket = o->gn_ticket;
-    if (!state) state = o->state;
-    const int lvl = 2, cols = o->width >> lvl, rows = o->height >> lvl;
-    So3Args a;
-    a.last_image = o->last_next_image[lvl];
-    a.next_image = o->next_image[lvl];
-    a.l_stride = a.n_stride = cols;
-    a.cols = cols;
-    a.rows = rows;
-    a.intr = level_intr(o->fx, o->fy, o->cx, o->cy, 2);
-    a.cols_magic = (unsigned)((1ull << 32) / (unsigned)cols) + 1u;
-    const int grid = reduce_grid(cols * rows, kBlock);
-    for (int i = 0; i < 10; ++i) q.launch((so3_kernel<FINISH_GN>), dim3(grid), dim3(kBlock), state, a, partials, ticket);
-    return MMF_OK;
-}
-
-// the SO3 pre-alignment of the NEXT frame ahead of its tracking, on `stream` (after that frame's intensity
-// pyramid): its begin part, then the ten launches; getIncrementalTransformation then skips both
-// `stage`: the state the pre-alignment runs in (its images are o's); the caller tells the consumer (mmf_odom::so3_stage)
-static int odom_prefetch_so3(mmf_odom* o, Enqueuer& q, float* partials, unsigned* ticket, OdomState* stage) {
-    q.launch(so3_begin_kernel, dim3(1), dim3(64), stage, level_intr(o->fx, o->fy, o->cx, o->cy, 2));
-    return odom_enqueue_so3(o, q, partials, ticket, stage);
-}
-
-// RGBDOdometry::getIncrementalTransformation (RGBDOdometry.cpp:217-477), device resident:
-// every kernel below is enqueued back to back on the context's stream; the data-dependent
-// `break`s of the reference (:285-292, :376-378) become flags in the device state that make the
-// remaining launches of that loop return immediately.
-// first half: everything up to and including the copy of the result towards the host is enqueued on the
-// context's stream, nothing waits.  The orchestrator enqueues the chains of all its models (one stream each)
-// before it waits for the first result.
-// The models one chain of launches tracks: o[0] leads (its stream, its launch arguments), the others ride at their
-// slab offsets (BatchDelta).  All share the sensor-side images (fusion_orchestrator.hpp) and the configuration.
-struct TrackBatch {
-    int n = 1;
-    mmf_odom* o[kMaxBatch];
-    BatchDelta bd;
-    BeginPoses poses;
-};
-
-// The tracking mode of one call, worked out once from the reference's five settings.
-struct TrackMode {
-    bool icp, rgb, rgb_only, so3;
-    float icp_weight;
-    int iterations[MMF_NUM_PYRS];  // Gauss-Newton iterations per level
-    int first_iter_level;          // the coarsest level that runs iterations (the ones below it all do)
-};
-static TrackMode track_mode(int rgb_only, float icp_weight, int pyramid, int fast_odom, int so3) {
-    TrackMode m;
-    m.icp = !rgb_only && icp_weight > 0;  // :221-222
-    m.rgb = rgb_only || icp_weight < 100;
-    m.rgb_only = rgb_only != 0;
-    m.so3 = so3 != 0;
-    m.icp_weight = icp_weight;
-    const int iterations[MMF_NUM_PYRS] = {fast_odom ? 3 : 10, pyramid ? 5 : 0, pyramid ? 4 : 0};  // :312-314
-    std::copy(iterations, iterations + MMF_NUM_PYRS, m.iterations);
-    m.first_iter_level = MMF_NUM_PYRS - 1;
-    while (m.first_iter_level > 0 && !m.iterations[m.first_iter_level]) --m.first_iter_level;
-    return m;
-}
-
-// The launch arguments of one pyramid level: the correspondence pass's and the ICP reduction's.  The error images are the
-// caller's (the chains write them in the last level-0 iteration only, the planner checks the odometry's own).
-struct LevelArgs {
-    int cols, rows;
-    LevelIntr in;
-    RgbResidualArgs ra;
-    IcpArgs ia;
-};
-static LevelArgs odom_level_args(mmf_odom* o, int i, float* rgb_err, float* icp_err) {
-    LevelArgs l;
-    l.cols = o->width >> i, l.rows = o->height >> i;
-    l.in = level_intr(o->fx, o->fy, o->cx, o->cy, i);
-    const float min_scale = (float)(std::pow((double)o->min_grad[i], 2.0) / std::pow((double)o->sobel_scale, 2.0));
-    l.ra = make_residual_args(min_scale, o->dIdx[i], 0, o->dIdy[i], 0, o->last_depth[i], 0,
-                              o->prep_batched ? o->last_depth[i] : o->next_depth[i], 0, o->last_image[i], 0, o->next_image[i],
-                              0, o->corres[i], o->max_depth_delta_rgb, l.cols, l.rows, rgb_err, 0);
-    l.ra.intr = l.in;
-    l.ia = odom_icp_args(o, i, icp_err);
-    return l;
-}
-
-// Launch geometry of gn_iter_kernel at a level of cols x rows pixels: a workgroup = the solver wave + the pixel waves.  The
-// launch is a chain of latencies -- records, solve, two memory round trips, the count barrier -- and every workgroup waits at
-// that barrier for the slowest one, so (measured on MI355X, tools/ab_libs.sh): at most one workgroup per CU (two on a CU
-// reach the barrier 1.6 us after the others); exactly four pixel waves, one per SIMD, where that fits (a fifth doubles up on
-// one SIMD and is the long pole of every arithmetic phase: what 640x480 suffered with four pixels per lane, 300 lanes in 256
-// workgroups); as few pixels per lane as those two allow (a lane's serial arithmetic is on the critical path).  Five pixels
-// per lane exist for 640x480: 240 workgroups x 256 lanes x 5.
-// MMF_GN_PX="p0,p1,p2" forces the pixels per lane of a level, MMF_GN_GROUPS the workgroup limit (tuning aids).
-struct GnGeometry {
-    int px, lanes, threads, groups;
-};
-// mixed: a launch that also carries object models walked by their extents (gn_iter_mixed_kernel).  Its register count allows
-// three waves per SIMD, and the GPU places a second 5-wave workgroup on a CU only with four (measured: tools/gn_mixed_probe.py
-// -- the object models' workgroups started when the camera model's had finished); workgroups of FOUR waves (the solver wave
-// + three pixel waves, 192 pixel lanes) take one wave slot per SIMD and three of them share a CU.  (256 lanes measured slower
-// at 2, 4 and 8 models: LABNOTES.md.)
-constexpr int kGnMixedLanes = 192;
-static_assert(kGnMixedLanes % 64 == 0 && kGnMixedLanes <= kGnSparseLanes,
-              "the sparse walk keeps a workgroup's correspondences in LDS, sized for kGnSparseLanes lanes");
-static bool gn_geometry(int level, int cols, int rows, GnGeometry* out, bool mixed = false) {
-    if (mixed) {
-        GnGeometry base;
-        if (!gn_geometry(level, cols, rows, &base, false) || base.lanes != kBlock) return false;
-        const int groups = (cols * rows / base.px + kGnMixedLanes - 1) / kGnMixedLanes;
-        if (groups > kGnMaxGroups) return false;
-        *out = GnGeometry{base.px, kGnMixedLanes, kGnMixedLanes + 64, groups};
-        return true;
-    }
-    const int* forced = tunables().gn_px;
-    const int max_groups = tunables().gn_groups;
-    const int n = cols * rows;
-    const int want = (level >= 0 && level < 3) ? forced[level] : 0;
-    // a lane's pixels lie in one row; the window words are 4-byte aligned columns
-    auto allowed = [&](int px) { return cols % px == 0 && cols % 4 == 0 && (!(want == 1 || want == 2 || want == 4 || want == 5) || px == want); };
-    static const int kPx[4] = {1, 2, 4, 5};
-    for (int k = 0; k < 4; ++k) {  // four pixel waves per workgroup (three, 192 lanes: no different, tools/ab_env.sh)
-        const int px = kPx[k];
-        const int groups = (n / px + kBlock - 1) / kBlock;
-        if (!allowed(px) || groups > max_groups || groups > kGnMaxGroups) continue;
-        *out = GnGeometry{px, kBlock, kBlock + 64, groups};
-        return true;
-    }
-    for (int k = 3; k >= 0; --k) {  // larger workgroups, as few of them as the limit asks for
-        const int px = kPx[k];
-        if (!allowed(px)) continue;
-        const int total = n / px;
-        const int lanes = std::max(kBlock, (total + max_groups - 1) / max_groups);
-        const int groups = (total + lanes - 1) / lanes;
-        if (lanes > 64 * (kGnMaxWaves - 1) || groups > kGnMaxGroups) continue;
-        *out = GnGeometry{px, lanes, (lanes + 63) / 64 * 64 + 64, groups};
-        return true;
-    }
-    return false;
-}
-// calls f(std::integral_constant<int, PX>) for the pixels per lane of a Gauss-Newton launch (1, 2, 4 or 5: gn_geometry)
-template <typename F>
-static auto with_gn_px(int px, F&& f) {
-    switch (px) {
-        case 5: return f(std::integral_constant<int, 5>{});
-        case 4: return f(std::integral_constant<int, 4>{});
-        case 2: return f(std::integral_constant<int, 2>{});
-        default: return f(std::integral_constant<int, 1>{});
-    }
-}
-// How the chain of one call runs: one launch per iteration (gn_iter_kernel) or two (producer + rgb_step), and how the one-launch
-// chain walks the models of a batch (gn_fused.hpp: GnBatchGeom).  Made by odom_plan_chain, the only place that decides it.
-struct GnChainPlan {
-    bool one_launch = false;
-    bool mixed = false;  // object models walked by their extents ride the launch (gn_iter_mixed_kernel)
-    unsigned sparse_mask = 0, ext_gen = 0;
-    GnGeometry geo[MMF_NUM_PYRS] = {};
-    int groups[MMF_NUM_PYRS][kMaxBatch] = {};  // workgroups of model m at level l
-};
-// workgroups of an OBJECT model per launch of the one-launch chain at pyramid level l (a property of the model, batched or
-// alone: its float sums keep their order): its photometric box must fit them in ONE pass (32 x 1280 pixels at 640x480 level 0,
-// a box of 200 x 200), its ICP rectangle takes as many passes as it needs
-static std::atomic<int> g_sparse_groups{0};  // test hook (mmf_debug_set_sparse_groups): that many at every level instead
-// need: the lanes the model's box took in its last chain (0: unknown -- 32 / 24 / 16 workgroups, a box of 200 x 200 at 640x480);
-// lanes: pixel lanes of a workgroup.  Returns dense_groups when the model is better walked like the camera model.
-static int gn_sparse_groups(int level, int dense_groups, int need, int lanes) {
-    static const int k[MMF_NUM_PYRS] = {32, 24, 16};
-    const int forced = g_sparse_groups.load();
-    if (forced > 0) return std::min(dense_groups, forced);
-    int want = k[level < MMF_NUM_PYRS ? level : MMF_NUM_PYRS - 1];
-    if (need > 0) want = std::max(8, (need + need / 4 + lanes - 1) / lanes + 1);
-    return want * 4 >= dense_groups * 3 ? dense_groups : want;
-}
-extern "C" int mmf_debug_set_sparse_groups(int n) {
-    g_sparse_groups.store(n > 0 ? n : 0);
-    return MMF_OK;
-}
-static std::atomic<bool> g_gn_latched_off{false};
-static std::atomic<int> g_track_cull{-1};  // -1: tunables().track_cull; 0 / 1: mmf_debug_set_track_cull
-extern "C" int mmf_debug_set_track_cull(int mode) {
-    g_track_cull.store(mode < 0 ? -1 : (mode ? 1 : 0));
-    return MMF_OK;
-}
-static std::atomic<int> g_gn_force_fault{0};
-static std::atomic<int> g_sparse_check{0};
-// test hooks of the object models' walk in the one-launch chain (gn_fused.hpp: gn_sparse_icp_box): checking mode on / off, and the
-// number of correspondences the last chain of an odometry accepted outside the rectangle it would have walked (must be 0)
-extern "C" int mmf_debug_set_sparse_check(int on) {
-    g_sparse_check.store(on ? 1 : 0);
-    return MMF_OK;
-}
-extern "C" int mmf_debug_odom_sparse_outside(mmf_odom* o, unsigned* outside, int* walked_by_extent, int rect[9]) {
-    if (!o || !o->host_result) return fail(MMF_ERR_INVALID, "mmf_debug_odom_sparse_outside: null argument");
-    if (outside) *outside = o->host_result->gn_dbg_outside;
-    if (walked_by_extent) *walked_by_extent = o->walked_by_extent ? 1 : 0;
-    if (rect) {
-        std::memcpy(rect, o->host_result->gn_dbg_rect, sizeof(int) * 6);
-        std::memcpy(rect + 6, o->gn_need, sizeof(int) * 3);
-    }
-    return MMF_OK;
-}
-static std::atomic<int> g_gn_recoveries{0};
-// odom_finish_tracking: the one-launch chain gave up; track again (odom_retrack_prepare).  A private sentinel, outside the
-// public mmf_status range (include/mmf_hip.h: 0 and small negatives): it never leaves the library (gn_retry_twice).
-constexpr int kGnRetry = 0x6e726574;
-static int gn_retry_twice() { return fail(MMF_ERR_STATE, "odometry: tracking gave up twice (the two-launch chain reported a fault)"); }
-
-static bool odom_sparse_on() { return (g_track_cull.load() < 0 ? tunables().track_cull : g_track_cull.load()) != 0; }
-static void odom_begin_rider_used();
-// what odom_begin_kernel is told (RGBDOdometry.cpp:221-228, 237, 252-255, 316-328); every byte defined (the blocks are compared)
-static BeginArgs odom_begin_args(const mmf_odom* o, const float trans[3], const float rot[9], const TrackMode& tm,
-                                 bool so3_prefetched, const OdomState* so3_stage, bool one_launch) {
-    BeginArgs b;
-    std::memset(&b, 0, sizeof(b));
-    std::memcpy(b.trans, trans, sizeof(b.trans));
-    std::memcpy(b.rot, rot, sizeof(b.rot));
-    b.rgb_only = tm.rgb_only ? 1 : 0;
-    b.icp = tm.icp ? 1 : 0;
-    b.rgb = tm.rgb ? 1 : 0;
-    b.so3 = tm.so3 ? 1 : 0;
-    b.icp_weight = tm.icp_weight;
-    b.so3_intr = level_intr(o->fx, o->fy, o->cx, o->cy, 2);
-    b.so3_prefetched = (tm.so3 && so3_prefetched) ? 1 : 0;
-    b.so3_stage = b.so3_prefetched ? so3_stage : nullptr;
-    // nothing runs between the beginning and the first level's begin unless the SO3 loop does: one launch
-    b.fold_level_begin = (!tm.so3 || so3_prefetched) ? 1 : 0;
-    // the one-launch chain has no per-level begin: its first launch reads what this one prepares
-    b.first_intr = level_intr(o->fx, o->fy, o->cx, o->cy, one_launch ? tm.first_iter_level : MMF_NUM_PYRS - 1);
-    return b;
-}
-
-// can several models ride one chain (every level on the fused producer path)?  Same tests as the two-launch chain.
-static bool odom_batchable(mmf_odom* o, const TrackMode& tm) {
-    if (!tm.icp || !tm.rgb || tm.rgb_only || !o->prep_batched) return false;
-    for (int i = 0; i <= tm.first_iter_level; ++i) {
-        const LevelArgs l = odom_level_args(o, i, nullptr, nullptr);
-        if (!residual_vec4_ok(l.ra) || !icp2_fits(l.ia, kBlock, std::min(2, icp_max_px(l.ia, 2)))) return false;
-    }
-    return true;
-}
-
-// can the chain run as one launch per iteration (gn_iter_kernel)?  Both terms on, four pixels per lane at every level,
-// every level's grid small enough to be resident at once (the count barrier inside the launch).  MMF_GN_FUSED=0 keeps the
-// two-launch chain (A/B runs, and the test that compares the two).
-static std::atomic<int> g_gn_fused{-1};  // -1: MMF_GN_FUSED decides (default on); 0 / 1: mmf_debug_set_gn_fused
-extern "C" int mmf_debug_set_gn_fused(int on) {
-    g_gn_fused.store(on < 0 ? -1 : (on ? 1 : 0));
-    if (on) g_gn_latched_off.store(false);  // (a test that asks for the one-launch chain again gets it)
-    return MMF_OK;
-}
-// test hook: the next n one-launch chains of this process give up at their third launch (the count barrier of that launch
-// polls zero times), as if a workgroup had never arrived: exercises the recovery below without another process on the GPU
-extern "C" int mmf_debug_force_gn_fault(int n) {
-    g_gn_force_fault.store(n < 0 ? 0 : n);
-    return MMF_OK;
-}
-// test hook: the next one-launch chain of this process runs n launches of gn_iter_kernel at pyramid level first_level and
-// nothing else, then ends (gn_truncated_final_kernel) and leaves its last launch's sums and the pose its last solve made in
-// a buffer of the odometry's (GnTruncated; read by mmf_debug_gn_truncated).  A call that cannot take the one-launch chain while this is armed fails.
-static std::atomic<int> g_gn_truncate{0};  // n << 8 | first_level
-extern "C" int mmf_debug_gn_truncate(int n, int first_level) {
-    if (n < 0 || n > 64 || first_level < 0 || first_level >= MMF_NUM_PYRS) return fail(MMF_ERR_INVALID, "mmf_debug_gn_truncate: bad argument");
-    g_gn_truncate.store(n ? (n << 8 | first_level) : 0);
-    return MMF_OK;
-}
-extern "C" int mmf_debug_gn_truncated(mmf_odom* o, double totals[58], unsigned count_sumsq[2], double rt[12], float pose[24]) {
-    MMF_REQUIRE(o && o->gn_truncated && totals && count_sumsq && rt && pose, "mmf_debug_gn_truncated: null argument, or no truncated chain ran");
-    MMF_HIP_TRY(hipSetDevice(o->ctx->device));
-    MMF_HIP_TRY(hipStreamSynchronize(o->ctx->stream));
-    GnTruncated h;
-    MMF_HIP_TRY(hipMemcpy(&h, o->gn_truncated, sizeof(h), hipMemcpyDeviceToHost));
-    std::memcpy(totals, h.tot, sizeof(h.tot));
-    std::memcpy(count_sumsq, h.cnt, sizeof(h.cnt));
-    std::memcpy(rt, h.rt, sizeof(h.rt));
-    std::memcpy(pose, h.pose, sizeof(h.pose));
-    return MMF_OK;
-}
-// how often a one-launch chain gave up and its frame was tracked again on the two-launch chain, and whether the one-launch
-// chain is still in use (it is latched off by the first such event: whatever kept its workgroups from being resident
-// together -- another process on this GPU -- is likely still there)
-extern "C" int mmf_gn_chain_status(int* recoveries, int* one_launch_chain_in_use) {
-    if (recoveries) *recoveries = g_gn_recoveries.load();
-    if (one_launch_chain_in_use) *one_launch_chain_in_use = g_gn_latched_off.load() ? 0 : 1;
-    return MMF_OK;
-}
-// the smaller occupancy of a launch shape's two variants (with and without the error images) bounds the chain
-template <typename K>
-static int gn_occupancy(K with_err, K without_err, int threads) {
-    int nb = 0, nb2 = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, with_err, threads, 0);
-    const hipError_t e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb2, without_err, threads, 0);
-    if (e != hipSuccess || e2 != hipSuccess) return (void)hipGetLastError(), 0;
-    return std::min(nb, nb2);
-}
-// How many workgroups of gn_iter_kernel<px, .> (mixed: gn_iter_mixed_kernel) with `threads` threads the device holds at once:
-// the occupancy the runtime reports for the kernel (registers, LDS) x the compute units.  The launch spins on its own
-// workgroups (count barrier), so a grid beyond this could only time out; such sizes, partitioned or smaller devices take the
-// two-launch chain.
-static long long gn_resident_groups(mmf_ctx* c, int px, bool mixed, int threads) {
-    static std::mutex mu;
-    static std::map<std::tuple<int, bool, int>, int> per_cu;
-    std::lock_guard<std::mutex> lock(mu);
-    const auto key = std::make_tuple(px, mixed, threads);
-    auto it = per_cu.find(key);
-    if (it == per_cu.end()) {
-        const int nb = with_gn_px(px, [&](auto PX) {
-            constexpr int P = decltype(PX)::value;
-            return mixed ? gn_occupancy(gn_iter_mixed_kernel<P, true>, gn_iter_mixed_kernel<P, false>, threads)
-                         : gn_occupancy(gn_iter_kernel<P, true>, gn_iter_kernel<P, false>, threads);
-        });
-        it = per_cu.emplace(key, nb).first;
-    }
-    return (long long)it->second * c->cu_count;
-}
-// The chain's plan for o (batch: the models riding with it, o first).  sparse_on: object models may be walked by their extents.
-static GnChainPlan odom_plan_chain(mmf_odom* o, const TrackMode& tm, const TrackBatch* batch, bool sparse_on) {
-    const int models = batch ? batch->n : 1;
-    const int forced = g_gn_fused.load();
-    const bool enabled = (forced < 0 ? tunables().gn_fused : forced != 0) && o->exclusive_chain && !g_gn_latched_off.load();
-    // (more than MMF_GN_FUSED_MAX models: the batched two-launch chain)
-    if (!enabled || !tm.icp || !tm.rgb || tm.rgb_only || models > tunables().gn_fused_max) return GnChainPlan();
-    // the models walked by their extents: object models whose preparation noted extents for THIS frame (one number for all)
-    GnChainPlan pl;
-    for (int m = 0; m < models && sparse_on; ++m) {
-        const mmf_odom* om = batch ? batch->o[m] : o;
-        if (!om->sparse || om->extent_gen == 0) continue;
-        if (pl.ext_gen == 0) pl.ext_gen = om->extent_gen;
-        if (om->extent_gen == pl.ext_gen) pl.sparse_mask |= 1u << m;
-    }
-    pl.mixed = pl.sparse_mask != 0;
-    for (int i = 0; i <= tm.first_iter_level; ++i) {
-        const LevelArgs l = odom_level_args(o, i, o->rgb_err, o->icp_err);
-        if (!residual_vec4_ok(l.ra) || icp_max_px(l.ia, 4) != 4 || !l.ia.prev_packed) return GnChainPlan();
-        GnGeometry& geo = pl.geo[i];
-        if (!gn_geometry(i, l.cols, l.rows, &geo, pl.mixed)) return GnChainPlan();
-        // the count barrier inside the launch needs every workgroup of it resident at once
-        long long total = 0;
-        for (int m = 0; m < models; ++m) {
-            const mmf_odom* om = batch ? batch->o[m] : o;
-            pl.groups[i][m] = ((pl.sparse_mask >> m) & 1u) ? gn_sparse_groups(i, geo.groups, om->gn_need[i], geo.lanes) : geo.groups;
-            total += pl.groups[i][m];
-        }
-        if (total > gn_resident_groups(o->ctx, geo.px, pl.mixed, geo.threads)) return GnChainPlan();
-    }
-    pl.one_launch = true;
-    return pl;
-}
-
-// The models one call tracks and what both forms of the chain need to know about them, worked out once.
-// Object models (extent.hpp): in the two-launch chain (track_kernels.hpp: ChainGeom) their passes skip what lies outside
-// the model's own depth when the preparation noted its extents for this frame, and they walk their images with a
-// quarter of the workgroups; in the one-launch chain (gn_fused.hpp: gn_iter_mixed_kernel) they walk their extents with a
-// fraction of the workgroups, which is what lets ALL models of a frame be resident in one launch.
-// MMF_TRACK_CULL=0 / mmf_debug_set_track_cull(0): every model like the first.
-struct ChainCall {
-    mmf_odom* o;  // the leader
-    const TrackBatch* batch;
-    TrackMode tm;
-    unsigned ny;  // models
-    BatchDelta bd;
-    BeginPoses poses;
-    float *icp_err, *rgb_err;  // the error images the last level-0 iteration writes (null: none)
-    bool sparse_on, lead_sparse, foll_sparse;
-    unsigned cull_gen;     // the extents the two-launch chain's passes skip by (0: none)
-    bool two_launch_once;  // (odom_retrack_prepare: this frame is being tracked again)
-    bool so3_ran_here;     // the SO3 loop runs in the chain, in the leader's state: shared with the others at the first level begin
-
-    mmf_odom* model(unsigned m) const { return batch ? batch->o[m] : o; }
-};
-static ChainCall odom_chain_call(mmf_odom* o, const TrackMode& tm, const TrackBatch* batch, float* icp_err, float* rgb_err) {
-    ChainCall x;
-    x.o = o, x.batch = batch, x.tm = tm;
-    x.ny = batch ? (unsigned)batch->n : 1u;
-    std::memset(&x.bd, 0, sizeof(x.bd));
-    std::memset(&x.poses, 0, sizeof(x.poses));
-    if (batch) x.bd = batch->bd, x.poses = batch->poses;
-    x.icp_err = icp_err, x.rgb_err = rgb_err;
-    x.two_launch_once = false;
-    for (unsigned m = 0; m < x.ny; ++m) {
-        x.two_launch_once = x.two_launch_once || x.model(m)->two_launch_once;
-        x.model(m)->two_launch_once = false;
-    }
-    x.sparse_on = odom_sparse_on();
-    x.lead_sparse = x.sparse_on && o->sparse;
-    x.foll_sparse = x.sparse_on && batch && x.ny > 1;
-    unsigned foll_gen = x.foll_sparse ? batch->o[1]->extent_gen : 0u;
-    for (unsigned m = 1; m < x.ny && x.foll_sparse; ++m) {
-        x.foll_sparse = batch->o[m]->sparse;
-        if (batch->o[m]->extent_gen != foll_gen) foll_gen = 0u;
-    }
-    if (!x.foll_sparse) foll_gen = 0u;
-    // (the kernels drop the first model's extent in a batch; a sparse model tracked alone keeps its own)
-    x.cull_gen = x.ny > 1 ? foll_gen : (x.lead_sparse ? o->extent_gen : 0u);
-    x.so3_ran_here = tm.so3 && !o->so3_prefetched;
-    return x;
-}
-
-// measurement mode 2: the next event pair of o's chain for a launch of `kind` (level * 2 + 0 producer | 1 rgb_step)
-static TimedSlot odom_timed_slot(mmf_odom* o, int kind) {
-    if (o->timing < 2 || o->n_timed >= kMaxTimedLaunches) return TimedSlot{};
-    const int k = o->n_timed++;
-    o->timed_kind[k] = kind;
-    return TimedSlot{o->ev_kernel[2 * k], o->ev_kernel[2 * k + 1]};
-}
-
-// What a chain leaves to odom_chain_publish.
-struct ChainTail {
-    bool end_folded = false;     // odom_end ran in the finishing lane of the frame's last rgb_step (or in gn_final_kernel)
-    bool final_pending = false;  // the one-launch chain's last solve (final_args) shares a launch with the hand-over
-    GnIterArgs final_args;
-};
-
-// begin: the derivatives (unless the batched preparation wrote them), odom_begin_kernel (unless it rode the preparation:
-// odom_begin_rider), the SO3 loop (:239-310)
-static int odom_chain_begin(const ChainCall& x, const float trans[3], const float rot[9], bool one_launch, Enqueuer& q) {
-    mmf_odom* o = x.o;
-    mmf_ctx* c = o->ctx;
-    if (x.tm.rgb && !o->prep_batched)
-        for (int i = 0; i < MMF_NUM_PYRS; ++i) {  // :230-235
-            int rc = launch_derivative(c, o->next_image[i], o->width >> i, o->width >> i, o->height >> i, o->dIdx[i],
-                                       o->width >> i, o->dIdy[i], o->width >> i);
-            if (rc) return rc;
-        }
-    const BeginArgs b = odom_begin_args(o, trans, rot, x.tm, o->so3_prefetched, o->so3_stage, one_launch);
-    o->n_timed = 0;
-    if (o->timing) MMF_HIP_TRY(hipEventRecord(o->ev_chain[0], c->stream));
-    // from here to the last step: kernels only, enqueued one by one in call order (Enqueuer keeps the first error)
-    // (the beginning may have run already, on the last launch of the preparation enqueued ahead of this frame: odom_begin_rider)
-    const bool begun = o->begin_spec_valid && o->begin_spec_ok && !x.batch && std::memcmp(&b, &o->begin_spec, sizeof(b)) == 0;
-    o->begin_spec_valid = o->begin_spec_ok = false;
-    if (!begun)
-        q.launch(odom_begin_kernel, dim3(x.ny), dim3(64), o->state, b, x.bd, x.poses);
-    else
-        odom_begin_rider_used();
-    o->retry_so3_prefetched = o->so3_prefetched, o->retry_so3_stage = o->so3_stage;  // (odom_retrack_prepare)
-    if (x.so3_ran_here) {
-        int rc = odom_enqueue_so3(o, q);
-        if (rc) return rc;
-    }
-    o->so3_prefetched = false;
-    o->so3_stage = nullptr;
-    return MMF_OK;
-}
-
-// both terms on and every level fits: ONE launch per iteration (gn_fused.hpp) instead of producer + step, at the plan's
-// geometry.  (More than three models: the batched two-launch chain is as fast (four) or faster -- 8 models 1.40 ms against
-// 1.60 -- because a model's workgroups hold their CUs at the count barrier while the next models' wait for a place.)
-static int odom_one_launch_chain(const ChainCall& x, const GnChainPlan& plan, Enqueuer& q, ChainTail* tail, bool truncated = false) {
-    mmf_odom* o = x.o;
-    GnIterArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.poll_sleep = tunables().gn_sleep;
-    a.max_polls = kGnMaxPolls;
-    a.check_sparse = g_sparse_check.load();
-    bool force_fault = false;
-    for (int n = g_gn_force_fault.load(); n > 0 && !force_fault;) force_fault = g_gn_force_fault.compare_exchange_weak(n, n - 1);
-    int it = 0;
-    for (int i = x.tm.first_iter_level; i >= 0; --i) {
-        const LevelArgs l = odom_level_args(o, i, nullptr, nullptr);
-        LevelArgs last = l;  // the last level-0 iteration also writes the error images
-        last.ra.err_map = x.rgb_err, last.ia.err_map = x.icp_err;
-        if (!o->prep_batched) {  // :332-334
-            MMF_HIP_TRY(q.flush());
-            int rc = launch_project(o->ctx, o->last_depth[i], l.cols, l.cols, l.rows, l.in, o->cloud[i], o->cloud4[i]);
-            if (rc) return rc;
-        }
-        if (i == x.tm.first_iter_level && x.so3_ran_here)  // the SO3 loop ran in between: seed resultRt from its result now
-            q.launch(gn_level_begin_kernel, dim3(x.ny), dim3(64), o->state, 1, l.in, x.bd, 1);
-        const GnGeometry& geo = plan.geo[i];
-        a.lanes = geo.lanes;
-        a.cloud4 = reinterpret_cast<const float4*>(o->cloud4[i]);
-        a.fx = l.in.fx, a.fy = l.in.fy, a.sobel_scale = o->sobel_scale;
-        a.intr = l.in;
-        a.ifx = 1.0 / (double)l.in.fx, a.ify = 1.0 / (double)l.in.fy;
-        // object models walked by their extents: one one-dimensional grid, a geometry per model (GnBatchGeom)
-        GnBatchGeom gg;
-        std::memset(&gg, 0, sizeof(gg));
-        if (plan.mixed) {
-            for (unsigned m = 0; m < (unsigned)kMaxBatch; ++m) gg.start[m + 1] = gg.start[m] + (m < x.ny ? plan.groups[i][m] : 0);
-            gg.sparse_mask = plan.sparse_mask, gg.ext_gen = plan.ext_gen, gg.level = i, gg.extent = o->extent;
-            gg.sensor = o->extent, gg.sensor_gen = o->sensor_gen, gg.sensor_cutoff = o->sensor_cutoff;
-            gg.rotate = gg.start[1];  // the object models' workgroups first (the first model of a batch is the camera model)
-        }
-        for (int j = 0; j < x.tm.iterations[i]; ++j) {
-            const bool last_l0 = (i == 0 && j == x.tm.iterations[i] - 1);
-            a.ra = last_l0 ? last.ra : l.ra;
-            a.ia = last_l0 ? last.ia : l.ia;
-            a.it = it;
-            a.max_polls = (it == 2 && force_fault) ? 0 : kGnMaxPolls;
-            const bool err = last_l0 && (x.icp_err || x.rgb_err);
-            const TimedSlot slot = odom_timed_slot(o, i * 2);
-            with_gn_px(geo.px, [&](auto PX) {
-                constexpr int P = decltype(PX)::value;
-                if (plan.mixed)
-                    q.launch(slot, err ? gn_iter_mixed_kernel<P, true> : gn_iter_mixed_kernel<P, false>, dim3(gg.start[kMaxBatch]),
-                             dim3(geo.threads), o->state, a, x.bd, gg);
-                else
-                    q.launch(slot, err ? gn_iter_kernel<P, true> : gn_iter_kernel<P, false>, dim3(geo.groups, x.ny), dim3(geo.threads),
-                             o->state, a, x.bd);
-            });
-            ++it;
-        }
-    }
-    if (truncated) {  // (mmf_debug_gn_truncate) no solve behind the last launch: its sums and the pose it ran with, then the frame's end
-        tail->end_folded = true;
-        a.it = it;
-        a.intr = level_intr(o->fx, o->fy, o->cx, o->cy, x.tm.first_iter_level);  // the level the launches ran at (the loop went on to level 0)
-        a.ifx = 1.0 / (double)a.intr.fx, a.ify = 1.0 / (double)a.intr.fy;
-        q.launch(gn_truncated_final_kernel, dim3(1), dim3(64), o->state, a, o->gn_truncated);
-        return MMF_OK;
-    }
-    // the last solve + RGBDOdometry.cpp:464-467: one workgroup per model
-    a.it = it;
-    a.intr = level_intr(o->fx, o->fy, o->cx, o->cy, 0);
-    a.ifx = 1.0 / (double)a.intr.fx, a.ify = 1.0 / (double)a.intr.fy;
-    tail->end_folded = true;
-    // the chain's last solve shares a launch with the hand-over of the result to the host (odom_chain_publish), unless the
-    // chain is being timed as such (its closing event lies between the two)
-    if (o->timing)
-        q.launch(gn_final_kernel, dim3(x.ny), dim3(kBlock), o->state, a, x.bd);
-    else
-        tail->final_pending = true, tail->final_args = a;
-    return MMF_OK;
-}
-
-// producer (ICP reduction + correspondence pass, or the two apart) + rgb_step per iteration
-static int odom_two_launch_chain(const ChainCall& x, Enqueuer& q, ChainTail* tail) {
-    mmf_odom* o = x.o;
-    const TrackMode& tm = x.tm;
-    auto quarter = [](int full) { return std::max(std::min(full, 32), (full + 3) / 4); };
-    bool begin_folded = !x.so3_ran_here;  // this level's gn_level_begin already ran (in odom_begin_kernel, or in the
-                                          // last rgb_step of the level before)
-    for (int i = MMF_NUM_PYRS - 1; i >= 0; --i) {
-        const bool first_level = i == MMF_NUM_PYRS - 1;
-        const int cols = o->width >> i, rows = o->height >> i;
-        const LevelIntr in = level_intr(o->fx, o->fy, o->cx, o->cy, i);
-        if (tm.rgb && !o->prep_batched) {  // :332-334
-            MMF_HIP_TRY(q.flush());
-            int rc = launch_project(o->ctx, o->last_depth[i], cols, cols, rows, in, o->cloud[i], o->cloud4[i]);
-            if (rc) return rc;
-        }
-        if (!begin_folded)
-            q.launch(gn_level_begin_kernel, dim3(x.ny), dim3(64), o->state, first_level ? 1 : 0, in, x.bd,
-                     (first_level && x.so3_ran_here) ? 1 : 0);
-        begin_folded = false;
-        if (!tm.iterations[i]) continue;
-
-        LevelArgs l = odom_level_args(o, i, nullptr, nullptr);
-        l.ra.extent = x.cull_gen ? o->extent : nullptr, l.ra.extent_gen = x.cull_gen, l.ra.extent_level = i;
-        LevelArgs last = l;  // the last level-0 iteration also writes the error images
-        last.ra.err_map = x.rgb_err, last.ia.err_map = x.icp_err;
-        RgbStepArgs step;  // :418-423, then :425-460 in the finishing workgroup
-        step.residual_partials = o->gn_partials_res;
-        step.icp_partials = o->gn_partials_icp;
-        step.corres = o->corres[i];
-        step.cloud = nullptr, step.cloud4 = reinterpret_cast<const float4*>(o->cloud4[i]);
-        step.fx = in.fx;
-        step.fy = in.fy;
-        step.dIdx = o->dIdx[i];
-        step.dIdy = o->dIdy[i];
-        step.d_stride = cols;
-        step.sobel_scale = o->sobel_scale;
-        step.cols = cols;
-        step.rows = rows;
-        step.cols_magic = l.ra.cols_magic;
-        step.extent = l.ra.extent, step.extent_gen = l.ra.extent_gen, step.extent_level = l.ra.extent_level;
-
-        for (int j = 0; j < tm.iterations[i]; ++j) {
-            const bool last_l0 = (i == 0 && j == tm.iterations[i] - 1);
-            const RgbResidualArgs& ra = last_l0 ? last.ra : l.ra;
-            const IcpArgs& ia = last_l0 ? last.ia : l.ia;
-            const bool res_vec4 = tm.rgb && residual_vec4_ok(ra);
-            int res_records = tm.rgb ? reduce_grid(cols * rows, res_vec4 ? kBlock * 4 : kBlock) : 0, icp_records = 0;
-            const int ipx = tm.icp ? std::min(2, icp_max_px(ia, 2)) : 1;
-            ChainGeom geom;
-            std::memset(&geom, 0, sizeof(geom));
-            const bool fuse_producers = tm.rgb && tm.icp && res_vec4 && icp2_fits(ia, kBlock, ipx);
-            if (fuse_producers) {  // ICP reduction + correspondence pass side by side in one launch
-                icp_records = (cols * rows + kBlock * ipx - 1) / (kBlock * ipx);
-                if (x.lead_sparse)  // (every model of this launch, then)
-                    res_records = quarter(res_records);
-                else if (x.foll_sparse)
-                    geom.res_f = (unsigned)quarter(res_records);
-                q.launch(odom_timed_slot(o, i * 2), ipx == 2 ? track_producer_kernel<2, true> : track_producer_kernel<1, true>,
-                         dim3(icp_records + res_records, x.ny), dim3(kBlock), o->state, ia, (unsigned)icp_records, ra,
-                         o->gn_partials_icp, o->gn_partials_res, x.bd, geom);
-            } else {
-                MMF_REQUIRE(x.ny == 1, "odom_enqueue_tracking: this level cannot be batched");
-                if (tm.rgb)
-                    q.launch(res_vec4 ? rgb_residual_kernel<FINISH_GN, 4> : rgb_residual_kernel<FINISH_GN, 1>, dim3(res_records),
-                             dim3(kBlock), o->state, ra, o->gn_partials_res);
-                if (tm.icp) {  // :403-410
-                    icp_records = launch_icp<FINISH_GN>(q, o->state, ia, o->gn_partials_icp);
-                    if (!tm.rgb)  // ICP-only tracking: one workgroup sums the records, solves, updates the pose
-                        q.launch(icp_finish_kernel<FINISH_GN>, dim3(1), dim3(256), o->state, o->gn_partials_icp,
-                                 (unsigned)icp_records, in);
-                }
-            }
-            if (!tm.rgb) continue;
-            RgbStepArgs a = step;
-            a.residual_records = (unsigned)res_records;
-            a.icp_records = (unsigned)icp_records;
-            a.intr = in;
-            // the last step of a level also does the next level's gn_level_begin (one launch less per
-            // level).  Not with rgbOnly: its divergence `break` skips the finishing lane.
-            a.next_level = 0;
-            a.final_step = (last_l0 && !tm.rgb_only) ? 1 : 0;  // odom_end in the finishing lane (which rgbOnly's `break` skips)
-            tail->end_folded = a.final_step != 0;
-            if (j == tm.iterations[i] - 1 && i > 0 && tm.iterations[i - 1] > 0 && !tm.rgb_only) {
-                a.next_level = 1;
-                a.intr = level_intr(o->fx, o->fy, o->cx, o->cy, i - 1);  // only read by the finishing lane's rgb_prepare
-                begin_folded = true;
-            }
-            int grid = reduce_grid(cols * rows, kBlock * 4);  // width, height are multiples of 4
-            if (fuse_producers && x.lead_sparse)
-                grid = quarter(grid);
-            else if (fuse_producers && x.foll_sparse)
-                geom.step_f = (unsigned)quarter(grid);
-            // (the 4-pixel correspondence pass wrote compact records)
-            q.launch(odom_timed_slot(o, i * 2 + 1), res_vec4 ? rgb_step_kernel<FINISH_GN, 4, true> : rgb_step_kernel<FINISH_GN, 4, false>,
-                     dim3(grid, x.ny), dim3(kBlock), o->state, a, o->gn_partials_f, o->gn_ticket, x.bd, geom);
-        }
-    }
-    return MMF_OK;
-}
-
-// publish: the end kernel, every model's result towards the host on the chain's stream, the image ring
-static int odom_chain_publish(const ChainCall& x, Enqueuer& q, const ChainTail& tail) {
-    mmf_odom* o = x.o;
-    if (!tail.end_folded) q.launch(odom_end_kernel, dim3(x.ny), dim3(64), o->state, x.bd);
-    MMF_HIP_TRY(q.flush());
-    if (o->timing) MMF_HIP_TRY(hipEventRecord(o->ev_chain[1], o->ctx->stream));
-    PublishTargets to;
-    std::memset(&to, 0, sizeof(to));
-    const unsigned seq = ++o->publish_seq;
-    for (unsigned m = 0; m < x.ny; ++m) {
-        mmf_odom* om = x.model(m);
-        to.host[m] = om->host_result_dev;
-        om->publish_seq = seq;
-        // a follower of a batch takes the LEADER's counter: whatever its own earlier chains left in the pinned flag, it is not
-        // this chain's number before this chain has written it
-        om->host_result->publish_seq = ~seq;
-        om->pending_icp = x.tm.icp, om->pending_so3 = x.tm.so3;
-        om->track_stream = o->ctx->stream;
-        om->result_of = o;
-        if (om != o) om->so3_prefetched = false;
-        // the image ring (:469-473).  Host bookkeeping only -- the launches above hold their pointers by value -- and
-        // done here rather than when the result is picked up, so that the next frame's sensor-side preparation can be
-        // enqueued while this chain runs
-        if (x.tm.so3)
-            for (int i = 0; i < MMF_NUM_PYRS; ++i) std::swap(om->last_next_image[i], om->next_image[i]);
-    }
-    o->rider = FrameRider();
-    if (tail.final_pending && o->defer_publish && x.ny == 1) {
-        q.launch(gn_final_kernel, dim3(x.ny), dim3(kBlock), o->state, tail.final_args, x.bd);
-        o->rider.st = o->state, o->rider.host = o->host_result_dev, o->rider.seq = seq;
-    } else if (tail.final_pending) {
-        q.launch(gn_final_publish_kernel, dim3(x.ny), dim3(kBlock), o->state, tail.final_args, x.bd, to, seq);
-    } else {
-        q.launch(odom_publish_kernel, dim3(x.ny), dim3(128), o->state, to, seq, x.bd);
-    }
-    MMF_HIP_TRY(q.flush());
-    return MMF_OK;
-}
-
-static int odom_enqueue_tracking(mmf_odom* o, const float trans[3], const float rot[9], const TrackMode& tm, float* icp_err_dev,
-                                 float* rgb_err_dev, const TrackBatch* batch = nullptr) {
-    MMF_HIP_TRY(hipSetDevice(o->ctx->device));
-#ifdef MMF_STAMPS  // (diagnostic builds: MMF_DBG_NO_ERR=1 leaves the error images out, so that a chain's last launch is an ordinary one)
-    if (std::getenv("MMF_DBG_NO_ERR")) icp_err_dev = rgb_err_dev = nullptr;
-#endif
-    MMF_REQUIRE(!batch || batch->n == 1 || odom_batchable(o, tm), "odom_enqueue_tracking: not batchable");
-    TrackMode tmx = tm;
-    const int truncate = g_gn_truncate.exchange(0);
-    if (truncate) {  // (mmf_debug_gn_truncate) n launches at one level
-        for (int i = 0; i < MMF_NUM_PYRS; ++i) tmx.iterations[i] = 0;
-        tmx.first_iter_level = truncate & 0xFF;
-        tmx.iterations[tmx.first_iter_level] = truncate >> 8;
-    }
-    const ChainCall x = odom_chain_call(o, tmx, batch, icp_err_dev, rgb_err_dev);
-    const GnChainPlan plan = x.two_launch_once ? GnChainPlan() : odom_plan_chain(o, tmx, batch, x.sparse_on);
-    MMF_REQUIRE(!truncate || (plan.one_launch && x.ny == 1), "odom_enqueue_tracking: a truncated chain needs the one-launch chain of one model");
-    if (truncate && !o->gn_truncated) {
-        MMF_HIP_TRY(hipMalloc(&o->gn_truncated, sizeof(GnTruncated)));
-        MMF_HIP_TRY(hipMemset(o->gn_truncated, 0, sizeof(GnTruncated)));
-    }
-    for (unsigned m = 0; m < x.ny; ++m) x.model(m)->walked_by_extent = plan.one_launch && ((plan.sparse_mask >> m) & 1u) != 0;
-    Enqueuer q(o->ctx->stream);
-    ChainTail tail;
-    int rc = odom_chain_begin(x, trans, rot, plan.one_launch, q);
-    if (rc == MMF_OK) rc = plan.one_launch ? odom_one_launch_chain(x, plan, q, &tail, truncate != 0) : odom_two_launch_chain(x, q, &tail);
-    return rc == MMF_OK ? odom_chain_publish(x, q, tail) : rc;
-}
-
-// The beginning of the NEXT tracking of one model, to ride the last launch of the preparation that is being enqueued ahead of
-// it (track_kernels.hpp: prep_batch_begin_kernel): `pose` = where that tracking will start (the model's pose now), so3_stage =
-// the staged pre-alignment of that frame (null: none, the tracking runs it itself).  odom_enqueue_tracking skips its own
-// odom_begin_kernel when it is about to pass these very arguments and the caller says the state was left alone (begin_spec_ok).
-static std::atomic<int> g_begin_rider{-1};      // -1: MMF_BEGIN_RIDER decides (default on); 0 / 1: mmf_debug_set_begin_rider
-static std::atomic<int> g_begin_riders_used{0};  // chains that found their beginning done (mmf_debug_begin_rider_count)
-extern "C" int mmf_debug_set_begin_rider(int on) {
-    g_begin_rider.store(on < 0 ? -1 : (on ? 1 : 0));
-    return MMF_OK;
-}
-extern "C" int mmf_debug_begin_rider_count(void) { return g_begin_riders_used.load(); }
-static void odom_begin_rider_used() { g_begin_riders_used.fetch_add(1); }
-static bool odom_begin_rider(mmf_odom* o, const float pose[16], const TrackMode& tm, const OdomState* so3_stage, BeginRider* out) {
-    o->begin_spec_valid = o->begin_spec_ok = false;
-    const int forced = g_begin_rider.load();
-    if (!(forced < 0 ? tunables().begin_rider : forced != 0) || o->two_launch_once) return false;
-    const bool one_launch = odom_plan_chain(o, tm, nullptr, odom_sparse_on()).one_launch;
-    const float trans[3] = {pose[3], pose[7], pose[11]};
-    const float rot[9] = {pose[0], pose[1], pose[2], pose[4], pose[5], pose[6], pose[8], pose[9], pose[10]};
-    std::memset(out, 0, sizeof(*out));
-    out->st = o->state;
-    out->a = odom_begin_args(o, trans, rot, tm, so3_stage != nullptr, so3_stage, one_launch);
-    o->begin_spec = out->a;
-    o->begin_spec_valid = true;
-    return true;
-}
-
-// second half: wait for the stream, hand the result out
-static int odom_finish_tracking(mmf_odom* o, float trans[3], float rot[9]) {
-    mmf_ctx* c = o->ctx;
-    MMF_HIP_TRY(hipSetDevice(c->device));
-    // the chain it rode on publishes into this odometry's pinned state and then stores the sequence number
-    if (o->result_of) {
-        const volatile unsigned* flag = &o->host_result->publish_seq;
-        bool seen = false;
-        const auto t_poll = std::chrono::steady_clock::now();
-        while (!seen) {  // a few seconds of polling at most, then the stream says why
-            for (int i = 0; i < 4096 && !seen; ++i) seen = *flag == o->publish_seq;
-            if (seen || std::chrono::steady_clock::now() - t_poll > std::chrono::seconds(5)) break;
-        }
-        if (!seen) {
-            MMF_HIP_TRY(hipStreamSynchronize(o->track_stream));
-            MMF_REQUIRE(*flag == o->publish_seq, "odometry: the tracking result did not reach the host");
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-    } else {
-        MMF_HIP_TRY(wait_stream(c->stream));
-    }
-    o->track_stream = nullptr, o->result_of = nullptr;
-    const bool icp = o->pending_icp, so3 = o->pending_so3;
-    if (o->timing) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, o->ev_chain[0], o->ev_chain[1]) == hipSuccess) {
-            o->timing_acc.chain_us_sum += ms * 1e3;
-            o->timing_acc.chains += 1;
-        }
-        for (int k = 0; k < o->n_timed; ++k)
-            if (hipEventElapsedTime(&ms, o->ev_kernel[2 * k], o->ev_kernel[2 * k + 1]) == hipSuccess) {
-                const int lvl = o->timed_kind[k] >> 1, step = o->timed_kind[k] & 1;
-                double* sum = step ? o->timing_acc.rgb_step_us_sum : o->timing_acc.producer_us_sum;
-                double* mn = step ? o->timing_acc.rgb_step_us_min : o->timing_acc.producer_us_min;
-                int* n = step ? o->timing_acc.rgb_step_launches : o->timing_acc.producer_launches;
-                sum[lvl] += ms * 1e3;
-                if (n[lvl] == 0 || ms * 1e3 < mn[lvl]) mn[lvl] = ms * 1e3;
-                n[lvl] += 1;
-            }
-        o->n_timed = 0;
-    }
-
-    const OdomState* r = o->host_result;
-    if (o->walked_by_extent) std::memcpy(o->gn_need, r->gn_need, sizeof(o->gn_need));  // (valid also when the chain gave up)
-    if (r->gn_fault) {  // the one-launch chain gave up: nothing of its result is valid
-        o->last_gn_fault = r->gn_fault;
-        return kGnRetry;
-    }
-    o->last_gn_fault = 0;
-    std::memcpy(trans, r->trans_out, sizeof(float) * 3);
-    std::memcpy(rot, r->rot_out, sizeof(float) * 9);
-    // members the reference leaves untouched in a given mode keep their previous values
-    if (icp) {
-        o->stats.lastICPError = r->st.lastICPError;
-        o->stats.lastICPCount = r->st.lastICPCount;
-    }
-    o->stats.lastRGBError = r->st.lastRGBError;
-    o->stats.lastRGBCount = r->st.lastRGBCount;
-    if (so3) {
-        o->stats.lastSO3Error = r->st.lastSO3Error;
-        o->stats.lastSO3Count = r->st.lastSO3Count;
-    }
-    if (r->st.iterations_run > 0) {
-        std::memcpy(o->stats.lastA, r->st.lastA, sizeof(double) * 36);
-        std::memcpy(o->stats.lastb, r->st.lastb, sizeof(double) * 6);
-    }
-    o->stats.iterations_run = r->st.iterations_run;
-    o->stats.so3_iterations_run = r->st.so3_iterations_run;
-    return MMF_OK;
-}
-
-// A one-launch chain gave up (odom_finish_tracking returned kGnRetry for a model it tracked): the process stops using that
-// chain, and every odometry the chain drove is put back to where odom_enqueue_tracking found it -- the image ring (:469-473)
-// and the prefetched SO3 pre-alignment it consumed -- so that the same call can be enqueued again and take the two-launch
-// chain from the pose the frame started with.  RGBDOdometry.cpp:464-467: the call returns a pose or reverts, it never aborts.
-static void odom_retrack_prepare(mmf_odom* const* odoms, int n, int so3) {
-    // An object model whose extent did not fit its workgroups (kGnFaultExtent) says nothing about the GPU: this frame is tracked
-    // again on the two-launch chain, the model's next chain is sized by what the box needed (odom_finish_tracking has taken
-    // OdomState::gn_need over), and the one-launch chain stays in use.
-    bool extent_only = true;
-    for (int k = 0; k < n; ++k) {
-        const int fault = odoms[k]->host_result ? odoms[k]->host_result->gn_fault : 0;
-        if (fault != 0 && fault != kGnFaultExtent) extent_only = false;
-    }
-    if (!extent_only) g_gn_latched_off.store(true);
-    g_gn_recoveries.fetch_add(1);
-    for (int k = 0; k < n; ++k) {
-        mmf_odom* o = odoms[k];
-        o->two_launch_once = true;
-        if (so3)
-            for (int i = 0; i < MMF_NUM_PYRS; ++i) std::swap(o->last_next_image[i], o->next_image[i]);
-        o->so3_prefetched = odoms[0]->retry_so3_prefetched, o->so3_stage = odoms[0]->retry_so3_stage;
-        o->track_stream = nullptr, o->result_of = nullptr;
-    }
-}
-
-extern "C" int mmf_odom_get_incremental_transformation(mmf_odom* o, float trans[3], float rot[9], int rgb_only,
-                                                       float icp_weight, int pyramid, int fast_odom, int so3,
-                                                       float* icp_err_dev, float* rgb_err_dev) {
-    MMF_REQUIRE(o && trans && rot, "mmf_odom_get_incremental_transformation: null argument");
-    const float trans0[3] = {trans[0], trans[1], trans[2]};
-    float rot0[9];
-    std::memcpy(rot0, rot, sizeof(rot0));
-    const TrackMode tm = track_mode(rgb_only, icp_weight, pyramid, fast_odom, so3);
-    int rc = odom_enqueue_tracking(o, trans, rot, tm, icp_err_dev, rgb_err_dev);
-    if (rc) return rc;
-    rc = odom_finish_tracking(o, trans, rot);
-    if (rc != kGnRetry) return rc;
-    odom_retrack_prepare(&o, 1, so3);
-    rc = odom_enqueue_tracking(o, trans0, rot0, tm, icp_err_dev, rgb_err_dev);
-    if (rc) return rc;
-    rc = odom_finish_tracking(o, trans, rot);
-    return rc == kGnRetry ? gn_retry_twice() : rc;
-}
-
-// measurement mode: per-launch durations of the Gauss-Newton kernels from the dispatches' own timestamps
-extern "C" int mmf_odom_enable_timing(mmf_odom* o, int on) {
-    MMF_REQUIRE(o != nullptr, "mmf_odom_enable_timing: null odometry");
-    MMF_HIP_TRY(hipSetDevice(o->ctx->device));
-    if (on && !o->ev_chain[0]) {
-        for (hipEvent_t& e : o->ev_kernel) MMF_HIP_TRY(hipEventCreate(&e));
-        for (hipEvent_t& e : o->ev_chain) MMF_HIP_TRY(hipEventCreate(&e));
-    }
-    o->timing = on < 0 ? 0 : (on > 2 ? 2 : on);
-    std::memset(&o->timing_acc, 0, sizeof(o->timing_acc));
-    return MMF_OK;
-}
-extern "C" int mmf_odom_get_timing(mmf_odom* o, mmf_odom_timing* out) {
-    MMF_REQUIRE(o && out, "mmf_odom_get_timing: null argument");
-    *out = o->timing_acc;
-    return MMF_OK;
-}
-
-extern "C" int mmf_odom_get_stats(mmf_odom* o, mmf_odom_stats* out) {
-    MMF_REQUIRE(o && out, "mmf_odom_get_stats: null argument");
-    *out = o->stats;
-    return MMF_OK;
-}
-
-// RGBDOdometry.cpp:479 -- lastA.lu().inverse(); Gauss-Jordan with partial pivoting on the host
-extern "C" int mmf_odom_get_covariance(mmf_odom* o, double cov[36]) {
-    MMF_REQUIRE(o && cov, "mmf_odom_get_covariance: null argument");
-    double a[6][12];
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) {
-            a[i][j] = o->stats.lastA[i * 6 + j];
-            a[i][6 + j] = (i == j) ? 1.0 : 0.0;
-        }
-    for (int col = 0; col < 6; ++col) {
-        int piv = col;
-        for (int r = col + 1; r < 6; ++r)
-            if (std::fabs(a[r][col]) > std::fabs(a[piv][col])) piv = r;
-        if (piv != col)
-            for (int k = 0; k < 12; ++k) std::swap(a[piv][k], a[col][k]);
-        const double d = a[col][col];
-        for (int k = 0; k < 12; ++k) a[col][k] /= d;
-        for (int r = 0; r < 6; ++r)
-            if (r != col) {
-                const double f = a[r][col];
-                for (int k = 0; k < 12; ++k) a[r][k] -= f * a[col][k];
-            }
-    }
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) cov[i * 6 + j] = a[i][6 + j];
-    return MMF_OK;
-}
-
-extern "C" int mmf_odom_buffer(mmf_odom* o, const char* name, int level, void** dev_ptr, size_t* bytes) {
-    MMF_REQUIRE(o && name && dev_ptr && bytes && level >= 0 && level < MMF_NUM_PYRS, "mmf_odom_buffer: bad argument");
-    const size_t n = (size_t)(o->width >> level) * (o->height >> level);
-    const std::string s(name);
-    void* p = nullptr;
-    size_t b = 0;
-    if (s == "vmaps_curr") p = o->vmaps_curr[level], b = 3 * n * 4;
-    else if (s == "nmaps_curr") p = o->nmaps_curr[level], b = 3 * n * 4;
-    else if (s == "vmaps_g_prev") p = o->vmaps_g_prev[level], b = 3 * n * 4;
-    else if (s == "nmaps_g_prev") p = o->nmaps_g_prev[level], b = 3 * n * 4;
-    else if (s == "last_depth") p = o->last_depth[level], b = n * 4;
-    else if (s == "next_depth") p = o->next_depth[level], b = n * 4;
-    else if (s == "depth_pyr") p = o->depth_pyr[level], b = n * 4;
-    else if (s == "cloud") p = o->cloud[level], b = 3 * n * 4;
-    else if (s == "cloud4") p = o->cloud4[level], b = 4 * n * 4;         // {X, Y, Z, 1/Z} per pixel
-    else if (s == "prev_packed") p = o->prev_packed[level], b = 6 * n * 4;  // {vertex, normal} per pixel
-    else if (s == "last_image") p = o->last_image[level], b = n;
-    else if (s == "next_image") p = o->next_image[level], b = n;
-    else if (s == "last_next_image") p = o->last_next_image[level], b = n;
-    else if (s == "dIdx") p = o->dIdx[level], b = n * 2;
-    else if (s == "dIdy") p = o->dIdy[level], b = n * 2;
-    else if (s == "corres") p = o->corres[level], b = n * sizeof(mmf_dataterm);
-    else if (s == "icp_error") p = o->icp_err, b = (size_t)o->width * o->height * 4;  // Model::icpError / rgbError (R32F, full size;
-    else if (s == "rgb_error") p = o->rgb_err, b = (size_t)o->width * o->height * 4;  // `level` is ignored)
-    else if (s == "extent") p = o->extent, b = kExtentWords * sizeof(unsigned long long);  // extent.hpp's words (tests; `level` is ignored)
-    else if (s == "prep_box") p = o->prep_box, b = 8 * sizeof(int);                        // PrepJob::rect_store's two slots
-    else return fail(MMF_ERR_INVALID, "mmf_odom_buffer: unknown buffer name '" + s + "'");
-    *dev_ptr = p;
-    *bytes = b;
-    return MMF_OK;
-}
-
-extern "C" int mmf_odom_download(mmf_odom* o, const char* name, int level, void* host_dst, size_t host_bytes) {
-    MMF_REQUIRE(host_dst != nullptr, "mmf_odom_download: null destination");
-    void* p = nullptr;
-    size_t b = 0;
-    int rc = mmf_odom_buffer(o, name, level, &p, &b);
-    if (rc) return rc;
-    MMF_REQUIRE(b == host_bytes, "mmf_odom_download: size mismatch");
-    MMF_HIP_TRY(hipSetDevice(o->ctx->device));
-    MMF_HIP_TRY(hipMemcpyAsync(host_dst, p, b, hipMemcpyDeviceToHost, o->ctx->stream));
-    MMF_HIP_TRY(hipStreamSynchronize(o->ctx->stream));
-    return MMF_OK;
-}
-
-extern "C" int mmf_odom_time_icp_kernel(mmf_odom* o, int level, int reps, int variant, float* mean_us_out) {
-    MMF_REQUIRE(o && mean_us_out && level >= 0 && level < MMF_NUM_PYRS && reps > 0, "mmf_odom_time_icp_kernel: bad argument");
-    MMF_REQUIRE(variant == 0, "mmf_odom_time_icp_kernel: variant must be 0 (the shipped launch geometry)");
-    mmf_ctx* c = o->ctx;
-    MMF_HIP_TRY(hipSetDevice(c->device));
-    const IcpArgs a = odom_icp_args(o, level, nullptr);
-    Enqueuer q(c->stream);
-    // the state's pose fields are whatever the last getIncrementalTransformation left (or zero);
-    // FINISH_RAW only writes out_f
-    for (int w = 0; w < 3; ++w) launch_icp<FINISH_RAW>(q, o->state, a, c->partials_icp);
-    MMF_HIP_TRY(q.flush());
-    MMF_HIP_TRY(hipEventRecord(c->ev0, c->stream));
-    for (int r = 0; r < reps; ++r) launch_icp<FINISH_RAW>(q, o->state, a, c->partials_icp);
-    MMF_HIP_TRY(q.flush());
-    MMF_HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    MMF_HIP_TRY(hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    MMF_HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *mean_us_out = ms * 1000.0f / reps;
-    return MMF_OK;
-}
+#include "odom_host.hpp"
+#include "prep_host.hpp"
+#include "chain_host.hpp"
 
 // =============================================================================================
 // Surfel model (Core/Model/Model.{h,cpp} + Core/Model/ModelProjection.{h,cpp}), pure HIP

@@ -388,9 +388,9 @@ extern "C" int mmf_debug_depth_keys(mmf_ctx* c, const float* z_dev, int n, float
     MMF_HIP_TRY(hipGetLastError());
     return MMF_OK;
 }
-static std::atomic<int> g_splat_bound{-2};  // the early depth test of a deep store; -2: what the environment says (MMF_SPLAT_BOUND), else by the surfel count; -1 / 0 / 1: mmf_debug_set_splat_bound
+static Override g_splat_bound;  // the early depth test of a deep store; unset: what the environment says (MMF_SPLAT_BOUND), else by the surfel count; -1 / 0 / 1: mmf_debug_set_splat_bound
 extern "C" int mmf_debug_set_splat_bound(int mode) {
-    g_splat_bound.store(mode < 0 ? -1 : (mode ? 1 : 0));
+    g_splat_bound.set(mode < 0 ? -1 : (mode ? 1 : 0));
     return MMF_OK;
 }
 // the arguments of the rasterising and resolving passes of combinedPredict / synthesizeDepth; early_z = 0 until the caller of a deep store sets it
@@ -421,8 +421,7 @@ static SplatPlan model_splat_plan(const mmf_model* m) {
     p.launch_count = m->count_pending ? m->count_bound : m->count;
     // a DEEP store (two surfels per pixel and more: occluded layers) looks at the key image before it evaluates a fragment
     // (surfel_kernels.hpp, splat_kernel<true>): a fraction of the fragments and of their atomics.  Same images either way.
-    const int hook = g_splat_bound.load();
-    const int bound_mode = hook == -2 ? tunables().splat_bound : hook;
+    const int bound_mode = (int)g_splat_bound.get(tunables().splat_bound);
     const size_t npix =(size_t)m->width * m->height;
     p.deep = bound_mode < 0 ? (size_t)p.launch_count >= 2 * npix : bound_mode != 0;
     // The bound right after clean() is count + every pixel; the waves deal the surfels out whatever the grid is, and every

@@ -12,7 +12,7 @@
 // model side (prediction -> pyramids, global-frame maps, point clouds) is TWO dependent launches (PREP_TEX_*, PREP_RESIZE_TP,
 // PREP_PYR_PROJECT), the depth side of the sensor frame THREE (PREP_VMAP_NMAP), its image side four; a launch on the
 // model's stream costs ~4.5 us before it does anything, which is most of what a small stage takes.
-// This is the ONE arrangement of the jobs (mmf_hip.hip: prep_collect_sensor, prep_collect_model); the earlier ones -- four and
+// This is the ONE arrangement of the jobs (prep_host.hpp: prep_collect_sensor, prep_collect_model); the earlier ones -- four and
 // three model-side stages, vertex and normal maps as two jobs, planar model maps and an AoS cloud beside the records -- were
 // measured against it in LABNOTES rounds 3 to 5 and are gone.  The model maps in the global frame go out as the packed
 // records and the {X, Y, Z, 1/Z} point records the chains gather from, nothing else.

@@ -1,7 +1,10 @@
 // tunables.hpp -- every environment switch of the library, read ONCE (the first mmf_ctx_create) into one struct.
 // None changes a result: they select between bit-identical ways of scheduling the same work (A/B aids, measured in
-// LABNOTES.md) or size a launch.  Defaults are the shipped configuration.
+// LABNOTES.md) or size a launch.  Defaults are the shipped configuration.  Also here: Override, the one form of a switch
+// that a mmf_debug_set_* hook can force over its environment value.
 #pragma once
+#include <atomic>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -9,7 +12,7 @@
 namespace mmf {
 
 struct Tunables {
-    // ---- Gauss-Newton chain (gn_fused.hpp, mmf_hip.hip: gn_geometry, odom_plan_chain) ----
+    // ---- Gauss-Newton chain (gn_fused.hpp, chain_host.hpp: gn_geometry, odom_plan_chain) ----
     bool gn_fused = true;     // MMF_GN_FUSED=0: always the two-launch chain (producer + step)
     int gn_fused_max = 8;     // MMF_GN_FUSED_MAX: models one one-launch chain carries at most (the residency check decides below that)
     int gn_px[3] = {0, 0, 0}; // MMF_GN_PX="p0,p1,p2": pixels per lane of a level (0 = by geometry)
@@ -72,5 +75,23 @@ inline const Tunables& tunables() {
     }();
     return t;
 }
+
+// A switch that a test or an A/B run can force from inside the process (the mmf_debug_set_* hooks): unset -- the caller's
+// default decides, usually a member of tunables() -- or forced to a value.  One atomic word: a read on the per-frame path
+// is one load.
+struct Override {
+    void set(long v) { v_.store(v); }
+    void clear() { v_.store(kUnset); }
+    long get(long env_default) const {
+        const long v = v_.load();
+        return v == kUnset ? env_default : v;
+    }
+
+private:
+    static constexpr long kUnset = LONG_MIN;
+    std::atomic<long> v_{kUnset};
+};
+// the hooks' common argument: < 0 back to the default, else off / on
+inline void override_flag(Override& o, int on) { on < 0 ? o.clear() : o.set(on ? 1 : 0); }
 
 }  // namespace mmf
