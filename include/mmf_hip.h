@@ -1327,6 +1327,11 @@ int mmf_flowcrf_result(mmf_flowcrf *fc, const uint8_t **ids_dev, const uint8_t *
                        const float **q_dev, int *w, int *h, int *n_labels);
 int mmf_flowcrf_download(mmf_flowcrf *fc, const char *name, void *host_dst, size_t bytes);
 int mmf_flowcrf_last_launches(mmf_flowcrf *fc);
+/* test hook: how the pair pass of (d) splits a cell's sum over j for an image of n_cells cells at a padded label width (1, 2,
+ * 4, 8, 16 or 32): *nsplit ranges (the launch's grid.y), *nchunk chunks of 256 cells j, *per = ceil(nchunk / nsplit) chunks per
+ * range; range s takes the chunks [s per, min(nchunk, (s + 1) per)) and is empty from s per >= nchunk on.  The launch's own
+ * policy, not a copy of it; a host function: needs no device.  MMF_ERR_INVALID for any other width or n_cells < 1. */
+int mmf_debug_flowcrf_pair_geometry(int n_cells, int padded_labels, int *nsplit, int *nchunk, int *per);
 int mmf_fusion_set_flow_inference(mmf_fusion *f, const mmf_flowcrf_config *cfg);
 int mmf_fusion_last_flow_inference(mmf_fusion *f, const uint8_t **ids_dev, const uint8_t **ids_full_dev, int *w, int *h,
                                    int *n_labels, int *has_result);

@@ -410,6 +410,7 @@ SIGNATURES = {
     "mmf_flowcrf_result": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _ip, _ip, _ip]),
     "mmf_flowcrf_download": (_i, [_vp, C.c_char_p, _vp, _sz]),
     "mmf_flowcrf_last_launches": (_i, [_vp]),
+    "mmf_debug_flowcrf_pair_geometry": (_i, [_i, _i, _ip, _ip, _ip]),
     "mmf_fusion_set_flow_inference": (_i, [_vp, C.POINTER(mmf_flowcrf_config)]),
     "mmf_fusion_last_flow_inference": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _ip, _ip, _ip, _ip]),
     "mmf_fusion_flow_inference_download": (_i, [_vp, C.c_char_p, _vp, _sz]),

@@ -36,6 +36,17 @@ static int flowcrf_nsplit(int N, int LP) {
     return std::max(1, std::min(nchunk, (768 + tiles - 1) / tiles));
 }
 
+// the split of fcrf_pair_kernel's sum over j as flowcrf_launch_pair launches it and the kernel walks it (host: no device needed)
+extern "C" int mmf_debug_flowcrf_pair_geometry(int n_cells, int padded_labels, int* nsplit, int* nchunk, int* per) {
+    MMF_REQUIRE(n_cells >= 1 && padded_labels >= 1 && padded_labels <= mmf::kCrfMaxLabels && flowcrf_pad_labels(padded_labels) == padded_labels,
+                "mmf_debug_flowcrf_pair_geometry: cells >= 1 and a padded label width of 1, 2, 4, 8, 16 or 32");
+    MMF_REQUIRE(nsplit && nchunk && per, "mmf_debug_flowcrf_pair_geometry: null argument");
+    *nsplit = flowcrf_nsplit(n_cells, padded_labels);
+    *nchunk = (n_cells + mmf::kFcrfTJ - 1) / mmf::kFcrfTJ;
+    *per = (*nchunk + *nsplit - 1) / *nsplit;
+    return MMF_OK;
+}
+
 static int flowcrf_check_config(int width, int height, int max_labels, int max_tracks, const mmf_flowcrf_config* cfg, const char* who) {
     const std::string w(who);
     MMF_REQUIRE(cfg != nullptr, w + ": null configuration");

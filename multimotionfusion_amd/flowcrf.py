@@ -33,6 +33,22 @@ class FlowCrfConfig:
         raise AttributeError(k)
 
 
+def pad_labels(n_labels):
+    """the label width an inference of n_labels labels runs at: the next power of two"""
+    p = 1
+    while p < n_labels:
+        p *= 2
+    return p
+
+
+def pair_geometry(n_cells, padded_labels):
+    """(nsplit, nchunk, per) of the pair pass for an image of n_cells cells at a padded label width (mmf_debug_flowcrf_pair_geometry,
+    a host function): nsplit ranges of `per` chunks of 256 cells j, nchunk chunks in all"""
+    nsplit, nchunk, per = C.c_int(), C.c_int(), C.c_int()
+    check(_capi.load().mmf_debug_flowcrf_pair_geometry(int(n_cells), int(padded_labels), C.byref(nsplit), C.byref(nchunk), C.byref(per)))
+    return nsplit.value, nchunk.value, per.value
+
+
 def _torch():
     import torch
     return torch

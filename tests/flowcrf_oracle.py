@@ -270,7 +270,7 @@ def make_scene(w, h, L, allow_new, seed, edge_tracks=True):
     st = np.minimum(ex * M // W, M - 1)
     n0 = len(ex)
     co_cur = back_project(ex.astype(F64), ey.astype(F64), np.full(n0, Z0), cam)
-    sh = np.array([shift_of(s) for s in st], F64)
+    sh = np.array([shift_of(s) for s in st], F64).reshape(-1, 2)  # (an image too small for the grid has no such track)
     co_prev = (co_cur.astype(F64) - np.concatenate([sh * unit, np.zeros((n0, 1))], 1)).astype(F32)
     # model m: T_start = identity, T_end takes the model's own motion out again
     T_start = [np.eye(4, dtype=F32) for _ in range(M)]

@@ -1,8 +1,9 @@
 """-m gpu: the flow-CRF inference engine (csrc/flowcrf_kernels.hpp) against tests/flowcrf_oracle.py on the scenes
 of flowcrf_oracle.GPU_CASES (CRF images 8 x 8, 44 x 12, 43 x 25, 80 x 60; 1, 2, 3, 9 and 32 labels, with and without the new
 label): the track errors, the tracks' cells and `invalid` bit for bit; unaries and projection probabilities up to the library
-functions; Q, prob and the labels with the tolerances of test_gpu_crf.py.  Then the structure of the result, determinism, the
-launch count, the tracker entry point, the two large sizes and every refusal."""
+functions; Q, prob and the labels with the tolerances of test_gpu_crf.py; stage (e) replayed exactly from the device's own Q and
+proj (flowcrf_edges.check_against_oracle, shared with test_gpu_flowcrf_edges.py).  Then the structure of the result,
+determinism, the launch count, the tracker entry point, the two large sizes and every refusal."""
 import functools
 import os
 import subprocess
@@ -10,14 +11,13 @@ import sys
 
 import numpy as np
 import pytest
-import torch
 
 import flowcrf_oracle as fo
-from helpers import assert_bit_equal, bits
+from flowcrf_edges import STAGES, check_against_oracle, dev, engine, infer, same_bits_nan_as_nan
+from helpers import assert_bit_equal
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-STAGES = ("E", "U", "proj", "Q", "prob", "label", "ids", "ids_full", "invalid")
 
 
 @functools.lru_cache(maxsize=None)
@@ -26,88 +26,12 @@ def reference(w, h, L, allow_new):
     return sc, cfg, fo.run_scene(sc, cfg)
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def vertex_images(vz, seed=0):
-    """[H][W][4] per model: channel 2 is z; the others hold numbers the engine must not read"""
-    rng = np.random.default_rng(seed)
-    out = []
-    for z in vz:
-        v = rng.normal(0, 100, z.shape + (4,)).astype(F32)
-        v[..., 2] = z
-        out.append(dev(v))
-    return out
-
-
-def engine(gpu_ctx, sc, cfg, **kw):
-    from multimotionfusion_amd.flowcrf import FlowCrf
-    n = len(sc["tracks"]["ts_cur"]) if sc["tracks"] is not None else 0
-    kw.setdefault("max_tracks", n + 7)
-    kw.setdefault("max_labels", len(sc["ids"]) + int(sc["allow_new"]))
-    return FlowCrf(gpu_ctx, sc["W"], sc["H"], sc["cam"], **kw, **{k: v for k, v in cfg.items()})
-
-
-def infer(e, sc, tracks="scene"):
-    tr = sc["tracks"] if tracks == "scene" else tracks
-    if isinstance(tr, dict):
-        tr = {k: dev(v) for k, v in tr.items()}
-    return e.infer(sc["ids"], sc["T_start"], sc["T_end"], vertex_images(sc["vertex_z"]), dev(sc["depth"]), dev(sc["flow"]),
-                   dev(sc["motion"]), tracks=tr, allow_new=sc["allow_new"], new_id=sc["new_id"])
-
-
-def same_bits_nan_as_nan(got, want, what):
-    """bit for bit; a NaN equals a NaN (the sign of 0 / 0 is the processor's choice)"""
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape)
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), what
-    ne = (bits(got) != bits(want)) & ~nan
-    assert not ne.any(), f"{what}: {int(ne.sum())} of {ne.size} differ, first at {np.argwhere(ne)[:4].tolist()}"
-
-
 @pytest.mark.parametrize("w,h,L,allow_new", fo.GPU_CASES)
 def test_every_stage_against_the_oracle(gpu_ctx, w, h, L, allow_new):
+    """flowcrf_edges.check_against_oracle: stages (a) to (e), the replay of (e) from the device's own Q and proj, the structure,
+    the launch count and a second run with the same bits"""
     sc, cfg, want = reference(w, h, L, allow_new)
-    e = engine(gpu_ctx, sc, cfg)
-    ids_t, full_t = infer(e, sc)
-    got = {name: e.download(name) for name in STAGES}
-    n = len(sc["tracks"]["ts_cur"])
-    what = f"{w}x{h} L={L} new={allow_new}"
-    # (a): bit for bit
-    same_bits_nan_as_nan(got["E"], want["E"], what + ": E")
-    cell = e.download("cell")
-    assert np.array_equal(cell[:, :n], want["cell"]) and (cell[:, n:] == -1).all(), what  # (rows past the table: no sample)
-    assert np.array_equal(got["invalid"].astype(bool), want["invalid"]), what
-    # (b), (c): a few ulp of expf / logf / a division over at most 32 terms
-    U, Uo = got["U"], want["U"]
-    assert np.array_equal(np.isposinf(U), np.isposinf(Uo)) and not np.isnan(U).any(), what
-    fin = np.isfinite(Uo)
-    errU = np.abs(U[fin] - Uo[fin]) / np.maximum(1, np.abs(Uo[fin]))
-    near = np.abs(want["proj64"] - 0.3) < 1e-5
-    assert near.mean() < 0.01
-    errP = np.abs(got["proj"] - want["proj"])[~near]
-    # (d), (e)
-    errQ = np.abs(got["Q"].astype(np.float64) - want["Q"])
-    errProb = np.abs(got["prob"].astype(np.float64) - want["prob"])
-    print(f"{what}: max |dU| {errU.max():.3g}  |dproj| {errP.max():.3g}  |dQ| {errQ.max():.3g}  |dprob| {errProb.max():.3g}")
-    assert errU.max() <= 1e-5 and errP.max() <= 1e-5, what
-    assert errQ.max() <= 1e-4 and errProb.max() <= 1e-4, what
-    clear = want["margin"] >= 1e-3
-    assert L == 1 or clear.mean() >= 0.9
-    assert np.array_equal(got["label"][clear], want["label"][clear]) and np.array_equal(got["ids"][clear], want["ids"][clear]), what
-    # structure: the ids follow the labels, the large image is the nearest x4 of the small one, the tensors are the images
-    all_ids = np.array(sc["ids"] + ([sc["new_id"]] if allow_new else []), np.uint8)
-    assert np.array_equal(got["ids"], all_ids[got["label"]])
-    assert np.array_equal(got["ids_full"], fo.upscale4(got["ids"]))
-    assert np.array_equal(ids_t.cpu().numpy(), got["ids"]) and np.array_equal(full_t.cpu().numpy(), got["ids_full"])
-    assert np.abs(got["Q"].sum(0) - 1).max() <= 1e-5 and got["prob"].min() >= 0 and got["prob"].max() <= 1
-    assert e.last_launches() == (5 + 3 * cfg["iterations"])
-    # a second run on the same input: the same bits in every stage
-    infer(e, sc)
-    for name in STAGES:
-        assert_bit_equal(e.download(name), got[name], f"{what}: second run, {name}")
-    e.close()
+    check_against_oracle(gpu_ctx, sc, cfg, want)
 
 
 def test_the_launch_count_does_not_depend_on_size_labels_or_tracks(gpu_ctx):
