@@ -72,16 +72,10 @@ static void odom_alias_sensor_side(mmf_odom* o, const mmf_odom* primary) {
     o->in.depth_l0 = primary->in.depth_l0;
 }
 
-// where an OBJECT model's latest prediction is non-zero (device, PassBoxes::spl_nz of its last resolve), for a model-side
-// preparation that may then leave the rest of the frame alone; null: unknown, or not such a model
+// where an OBJECT model's latest prediction is non-zero (model_pred_box), for a model-side preparation that may then leave
+// the rest of the frame alone; null: unknown, or not such a model
 static const int* fusion_pred_box(const FusionModel* fm) {
-    const mmf_model* m = fm->model;
-    if (fm->fill_in || !fm->odom->sparse || !m->boxes || !m->spl_nz_known) return nullptr;
-    return m->boxes->spl_nz[m->sgen & 1u];
-}
-// the covered thumbnail samples of a model's latest prediction (thumbnail_count_px)
-static const int* fusion_thumb_count(const mmf_model* m) {
-    return reinterpret_cast<const int*>(&m->totals[4 + (m->thumb_gen & 1)]);
+    return fm->fill_in || !fm->odom->sparse ? nullptr : model_pred_box(fm->model);
 }
 
 // Model::combinedPredict(ACTIVE) + Model::performFillIn of one model (the body of predict(), :863-875)
@@ -260,7 +254,7 @@ static void fusion_collect_prep(mmf_fusion* f, PrepStages& stages, FusionModel* 
     p.channels = 4;
     p.pose = pose;
     p.depth_l0 = f->depth_filtered;
-    p.sel = fm->fill_in ? fusion_thumb_count(m) : nullptr;
+    p.sel = fm->fill_in ? reinterpret_cast<const int*>(model_latest_thumb_count(m)) : nullptr;
     p.alt_vertex = (const float*)m->fill_vertex, p.alt_normal = (const float*)m->fill_normal, p.alt_image = (const uint8_t*)m->fill_image;
     p.sel_total = (m->width / 20) * (m->height / 20), p.sel_ratio = 0.75f;
     p.ext_gen = boxed && fm->odom->sparse ? ext_gen : 0u;
@@ -303,7 +297,7 @@ static int fusion_enqueue_chains(mmf_fusion* f, FusionModel* const* fms, size_t 
     std::memset(&tb.bd, 0, sizeof(tb.bd));
     for (int k = 0; k < tb.n; ++k) {
         tb.o[k] = fms[k]->odom;
-        tb.bd.d[k] = (long long)(reinterpret_cast<char*>(fms[k]->odom->slab) - reinterpret_cast<char*>(lead->odom->slab));
+        tb.bd.d[k] = odom_slab_delta(fms[k]->odom, lead->odom);
         pose_trans_rot(start_pose(fms[k]), tb.poses.trans[k], tb.poses.rot[k]);
     }
     int rc = odom_enqueue_tracking(lead->odom, tb.poses.trans[0], tb.poses.rot[0], tm, lead->icp_error, lead->rgb_error, &tb);
@@ -386,7 +380,7 @@ static int frame_track_sensor_side(mmf_fusion* f, FrameRun& r) {
         float pose_now[16];
         mmf_model_get_pose(fm->model, pose_now);
         fm->spec_hit = fm->spec_valid && fusion_owns(f, k) && !r.have_init && std::memcmp(pose_now, fm->spec_pose, sizeof(pose_now)) == 0 &&
-                       fm->model->tex_gen == fm->spec_tex_gen && fm->spec_f2f == g.frame_to_frame_rgb && fm->odom->in.prep_batched;
+                       fm->model->gen.tex == fm->spec_tex_gen && fm->spec_f2f == g.frame_to_frame_rgb && fm->odom->in.prep_batched;
         fm->spec_valid = false;
         fm->odom->spec.ok = fm->spec_hit;  // (the tracking's beginning rode that preparation: odom_begin_rider)
         fm->early_done = fm->early_fused = false;
@@ -578,28 +572,27 @@ static int frame_enqueue_ahead(mmf_fusion* f, FrameRun& r) {
     FusionModel* fm = r.tracked[0];
     mmf_model* m = fm->model;
     r.early_snapshot = *m, r.early_snapshot_valid = true;
-    m->abort_dev = &fm->odom->state->gn_fault;
+    m->dev.abort = &fm->odom->state->gn_fault;
     // "nothing enqueued so far reads the odometries' sensor-side buffers or the other filtered-depth buffer" holds
     // HERE, behind the one chain of this process; the passes enqueued next do not read them either.  No event
     // says so any more (see frame_track: the host knows when it has the pose; a marker behind the chain cost the
     // model's stream ~4 us in front of the frame's first projection).
-    m->t_inv_dev = fm->odom->state->pose_inv;
-    m->rider = fm->odom->rider;
+    m->dev.t_inv = fm->odom->state->pose_inv;
+    m->dev.rider = fm->odom->rider;
     fm->odom->rider = FrameRider();
     int rc = fusion_mid_predict() ? fusion_predict_model(f, fm) : MMF_OK;
     if (rc == MMF_OK) rc = mmf_model_predict_indices(m, f->tick, g.max_depth_processed, g.time_delta);
-    MMF_REQUIRE(rc != MMF_OK || m->rider.st == nullptr, "mmf_fusion_process_frame: the tracking result was not handed over");
+    MMF_REQUIRE(rc != MMF_OK || m->dev.rider.st == nullptr, "mmf_fusion_process_frame: the tracking result was not handed over");
     fm->early_done = rc == MMF_OK;
     // Without a segmentation the mask of the frame is known (all zeros) and nothing the host decides lies
     // between tracking and fusion: fuse -> predictIndices -> clean (:791-816) follow at once, with the pose and
     // Model::computeFusionWeight taken from the device state (odom_end, odom_fusion_weight_kernel).
     if (rc == MMF_OK && !g.enable_multiple_models) {
-        m->pose_dev = fm->odom->state->pose_out, m->weight_dev = &fm->odom->state->fusion_weight;
+        m->dev.pose = fm->odom->state->pose_out, m->dev.weight = &fm->odom->state->fusion_weight;
         rc = fusion_fuse_clean_model(f, fm, r.fr->weight_multiplier, true);
         fm->early_fused = rc == MMF_OK;
     }
-    m->t_inv_dev = m->pose_dev = m->weight_dev = nullptr;
-    m->abort_dev = nullptr;
+    m->dev.reset();
     return rc;
 }
 
@@ -991,7 +984,7 @@ static int frame_prepare_next(mmf_fusion* f, const FrameRun& r) {
         if (!ride) only->odom->spec.valid = false;
         int rc = stages.launch(st, ride ? &rider : nullptr);
         if (rc) return rc;
-        only->spec_tex_gen = m->tex_gen;
+        only->spec_tex_gen = m->gen.tex;
         only->spec_f2f = g.frame_to_frame_rgb;
         only->spec_valid = true;
     } else if (owned >= std::max(2, tunables().spec_prep_all) && f->shard_world <= 1 && g.batch_tracking && owned <= kMaxBatch && tunables().spec_prep_all) {
@@ -1011,7 +1004,7 @@ static int frame_prepare_next(mmf_fusion* f, const FrameRun& r) {
             fm->odom->sparse = fm != global && !fm->fill_in;
             mmf_model_get_pose(fm->model, fm->spec_pose);
             fusion_collect_prep(f, stages, fm, fm->spec_pose, PREP_MODEL_SIDE, true, ext_gen);
-            fm->spec_tex_gen = fm->model->tex_gen;
+            fm->spec_tex_gen = fm->model->gen.tex;
             fm->spec_f2f = g.frame_to_frame_rgb;
             fm->spec_valid = true;
         }

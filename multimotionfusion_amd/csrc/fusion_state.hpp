@@ -291,10 +291,6 @@ struct mmf_fusion {
     HostRing up;           // the host-frame ring and its staging thread
 };
 
-static void identity16(float* m) {
-    for (int i = 0; i < 16; ++i) m[i] = (i % 5 == 0) ? 1.f : 0.f;
-}
-
 extern "C" int mmf_fusion_default_config(mmf_fusion_config* cfg) {
     MMF_REQUIRE(cfg != nullptr, "mmf_fusion_default_config: null argument");
     cfg->time_delta = 200;          // GUI/MainController.cpp:333 (timeDelta flag default)
@@ -504,7 +500,7 @@ extern "C" int mmf_fusion_set_shard(mmf_fusion* f, int rank, int world) {
     // models created ahead of their use (preallocateModels): the ones this rank will not own shrink to bookkeeping
     for (FusionModel*& fm : f->preallocated) {
         const int id = (int)fm->model->id;
-        const bool is_light = fm->model->slab == nullptr, want_light = world > 1 && id % world != rank;
+        const bool is_light = model_is_bookkeeping(fm->model), want_light = world > 1 && id % world != rank;
         if (is_light == want_light) continue;
         FusionModel* again = nullptr;
         const float conf = fm->model->conf_threshold;
@@ -612,15 +608,6 @@ static int lane_wait(FusionModel* fm, hipEvent_t ev) {
 extern "C" int mmf_fusion_get_pose(mmf_fusion* f, float pose[16]) {
     MMF_REQUIRE(f && pose, "mmf_fusion_get_pose: null argument");
     return mmf_model_get_pose(f->models[0]->model, pose);
-}
-
-static int model_reset_store(mmf_model* m) {
-    if (int rc = model_resolve_count(m)) return rc;  // lets an in-flight count land before it is dropped
-    m->count = 0, m->count_pending = false, m->count_bound = 0;
-    if (m->slab) MMF_HIP_TRY(hipMemsetAsync(m->totals, 0, 16, m->ctx->stream));  // (no slab: another rank's model)
-    identity16(m->pose);
-    m->max_depth = FLT_MAX;
-    return MMF_OK;
 }
 
 // start a new map: empty surfel stores, identity poses, tick = 1, only the global model active (what

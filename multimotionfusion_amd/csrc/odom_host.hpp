@@ -233,6 +233,11 @@ static void* odom_buffer_ptr(const mmf_odom* o, const OdomBuffer& b, int level) 
     return p;
 }
 
+// where a batched chain finds odometry o's buffers from the lead's: slab(o) - slab(lead) in bytes (BatchDelta)
+static inline long long odom_slab_delta(const mmf_odom* o, const mmf_odom* lead) {
+    return (long long)(static_cast<const char*>(o->slab) - static_cast<const char*>(lead->slab));
+}
+
 // The host side of an odometry, whole: what mmf_odom_create and odom_create_bookkeeping share.  Null: out of host memory.
 static mmf_odom* odom_new_host(mmf_ctx* c, int width, int height, float cx, float cy, float fx, float fy) {
     mmf_odom* o = new (std::nothrow) mmf_odom();

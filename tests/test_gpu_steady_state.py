@@ -12,7 +12,7 @@ pass silently.
   the previous frame's predictions again -- they must be the GPU's bits; it then tracks (pose within 1e-5, same iteration
   count) and goes on with the GPU's pose (substitute_poses): the map after the frame must be the GPU's bits.  With one model
   and no segmentation the device fuses with the inverse pose and fusion weight it computes itself
-  (csrc/fusion_orchestrator.hpp: t_inv_dev, pose_dev, weight_dev); this pins them to the host formulas.
+  (csrc/fusion_orchestrator.hpp: the model's dev.t_inv, dev.pose, dev.weight); this pins them to the host formulas.
 - Tracked poses, free-running: bounded, not bit-exact (see test_free_running_stays_within_the_oracles_envelope)."""
 import time
 
