@@ -516,6 +516,10 @@ int mmf_debug_expf(mmf_ctx *ctx, const float *x_dev, int n, float *out_mmf_dev, 
 /* test / A-B hook: 1 = run the Gauss-Newton chain as one launch per iteration where it applies (the default), 0 = always as
  * producer + step launches, -1 = what the environment says (MMF_GN_FUSED=0 turns it off).  Process wide. */
 int mmf_debug_set_gn_fused(int on);
+/* test hook: the pixels per lane (1, 2, 4 or 5) of the one-launch chain's launches at pyramid levels 0, 1 and 2; 0 leaves a
+ * level to the launch geometry's own choice.  A value the level's width does not allow (cols % px != 0) keeps that chain from
+ * running.  Any negative argument clears all three: what the environment says (MMF_GN_PX), else by geometry.  Process wide. */
+int mmf_debug_set_gn_px(int p0, int p1, int p2);
 /* The one-launch chain spins on its own workgroups (a count barrier inside every launch); the library checks the launch's
  * occupancy before it uses that chain, but another process on the same GPU can still keep a launch from becoming resident as
  * a whole.  A launch that gives up marks the chain's result void; the call that waits for it tracks the frame again on the

@@ -307,6 +307,7 @@ SIGNATURES = {
     "mmf_debug_expf": (_i, [_vp, _vp, _i, _vp, _vp]),
     "mmf_model_surfel_arrays": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_uint)]),
     "mmf_debug_set_gn_fused": (_i, [_i]),
+    "mmf_debug_set_gn_px": (_i, [_i, _i, _i]),
     "mmf_debug_set_mid_predict": (_i, [_i]),
     "mmf_debug_force_gn_fault": (_i, [_i]),
     "mmf_debug_gn_truncate": (_i, [_i, _i]),

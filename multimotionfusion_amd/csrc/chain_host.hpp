@@ -108,6 +108,13 @@ struct GnGeometry {
 constexpr int kGnMixedLanes = 192;
 static_assert(kGnMixedLanes % 64 == 0 && kGnMixedLanes <= kGnSparseLanes,
               "the sparse walk keeps a workgroup's correspondences in LDS, sized for kGnSparseLanes lanes");
+static Override g_gn_px[MMF_NUM_PYRS];  // unset: MMF_GN_PX decides (default: by geometry); else mmf_debug_set_gn_px
+extern "C" int mmf_debug_set_gn_px(int p0, int p1, int p2) {
+    const int p[MMF_NUM_PYRS] = {p0, p1, p2};
+    const bool clear = p0 < 0 || p1 < 0 || p2 < 0;
+    for (int i = 0; i < MMF_NUM_PYRS; ++i) clear ? g_gn_px[i].clear() : g_gn_px[i].set(p[i]);
+    return MMF_OK;
+}
 static bool gn_geometry(int level, int cols, int rows, GnGeometry* out, bool mixed = false) {
     if (mixed) {
         GnGeometry base;
@@ -120,7 +127,7 @@ static bool gn_geometry(int level, int cols, int rows, GnGeometry* out, bool mix
     const int* forced = tunables().gn_px;
     const int max_groups = tunables().gn_groups;
     const int n = cols * rows;
-    const int want = (level >= 0 && level < 3) ? forced[level] : 0;
+    const int want = (level >= 0 && level < 3) ? (int)g_gn_px[level].get(forced[level]) : 0;
     // a lane's pixels lie in one row; the window words are 4-byte aligned columns
     auto allowed = [&](int px) { return cols % px == 0 && cols % 4 == 0 && (!(want == 1 || want == 2 || want == 4 || want == 5) || px == want); };
     static const int kPx[4] = {1, 2, 4, 5};
