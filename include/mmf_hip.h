@@ -1413,6 +1413,52 @@ int mmf_flowseg_last_launches(mmf_flowseg *fs);
 int mmf_fusion_set_flow_segmentation(mmf_fusion *f, const mmf_flowseg_config *cfg);
 int mmf_fusion_last_flow_segmentation(mmf_fusion *f, mmf_flowseg_summary *summary, int *has_result);
 
+/* ---- the model database: savePly, cloud.ply / tracks.ply, -restore ----
+ * Nothing here runs inside processFrame; every call is synchronous.
+ *   mmf_model_export_cloud   Model::exportModelPLY's loop (Core/Model/Model.cpp:1547-1594) on the device: the surfels with
+ *                         conf > conf_threshold (strict: NaN is dropped) in ascending index, each one packed little-endian
+ *                         31-byte record {x y z f32 | r g b u8 | nx ny nz f32 | radius f32} in HOST memory.  Position =
+ *                         ((p0 x + p1 y) + p2 z) + p3 per row p of the row-major pose, f32, no fused multiply-add; colour
+ *                         c = (int)colour24, r = c >> 16 & 255, g = c >> 8 & 255, b = c & 255; normal =
+ *                         -((r0 nx + r1 ny) + r2 nz) per row r of the pose's 3 x 3; radius copied.  *n_valid is always
+ *                         written; capacity < *n_valid: MMF_ERR_INVALID and nothing is copied (mmf_model_count bounds
+ *                         n_valid).  Reads the store only.  Three launches whatever the count:
+ *   mmf_model_export_last_launches   the launches of the model's last export.
+ *   mmf_model_export_ply     the same records, with the model's own confidence threshold, as a PLY file at `path`.
+ *   mmf_ply_write_cloud / mmf_ply_read_cloud   the file: the reference's header byte for byte (:1516-1537), then n records.
+ *                         The reader takes exactly that: any other header, a body that is not n records long, or
+ *                         capacity < n is MMF_ERR_INVALID (*n is the file's count once the header has parsed).
+ *   mmf_tracks_ply_write     a model's keypoint views (the mmf_viewstore_store layout) in the reference's binary tracks layout
+ *                         with descriptors (:1386-1498), which Model::load reads (:1658-1691): track t = row t of every view
+ *                         (entry i = the vertex of view i's row t, or 0xFFFFFFFF), vertices numbered track by track, then by
+ *                         time index, each pose * coordinate in the arithmetic above, uint16 256, 256 f32; no edges.
+ *   mmf_tracks_ply_read      what Model::load rebuilds: view i = the tracks with a keypoint at i, in track order.  *n_views
+ *                         and *n_rows are always written for a well-formed file (a file without tracks has no views); NULL
+ *                         destinations give the sizes only; too small a capacity, a list length other than 256 / n_views, a
+ *                         vertex index >= the vertex count, a short file or trailing bytes: MMF_ERR_INVALID.
+ *   mmf_viewstore_download_view   a view's rows back: HOST [rows][256] and [rows][3] (either may be NULL), without padding;
+ *                         a bad index or capacity_rows < rows: MMF_ERR_INVALID.
+ *   mmf_fusion_save_models   savePly (Core/MultiMotionFusion.cpp:1001-1018): for every active, then every inactive model,
+ *                         with P = global pose * pose^-1: export_dir/cloud-<id>.ply, export_dir/model_db/model-<id>/cloud.ply
+ *                         and, for a model with views in the fusion's store, .../tracks.ply.  Directories are created.
+ *   mmf_fusion_load_models   loadModels (:131-145): for id = 1..255 ascending with a model_db/model-<id>/tracks.ply, an object
+ *                         model with the next model id and conf_object_init, the file's views stored under that id, unseen
+ *                         count -5, appended to the inactive list; no dense surfels.  A file that does not parse is skipped
+ *                         and named by mmf_last_error.  MMF_ERR_STATE with world > 1. */
+int mmf_model_export_cloud(mmf_model *m, const float pose[16], float conf_threshold, void *host_records, unsigned capacity,
+                           unsigned *n_valid);
+int mmf_model_export_last_launches(mmf_model *m);
+int mmf_model_export_ply(mmf_model *m, const char *path, const float pose[16]);
+int mmf_ply_write_cloud(const char *path, const void *records, unsigned n);
+int mmf_ply_read_cloud(const char *path, void *records, unsigned capacity, unsigned *n);
+int mmf_tracks_ply_write(const char *path, int n_views, const int *counts, const float *descriptor, const float *coordinate,
+                         const float pose[16]);
+int mmf_tracks_ply_read(const char *path, int cap_views, int *n_views, int *counts, int cap_rows, int *n_rows, float *descriptor,
+                        float *coordinate);
+int mmf_viewstore_download_view(mmf_viewstore *vs, int view, int capacity_rows, float *descriptor, float *coordinate);
+int mmf_fusion_save_models(mmf_fusion *f, const char *export_dir);
+int mmf_fusion_load_models(mmf_fusion *f, const char *export_dir, int *n_loaded);
+
 #ifdef __cplusplus
 }
 #endif

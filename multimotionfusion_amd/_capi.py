@@ -424,6 +424,16 @@ SIGNATURES = {
     "mmf_flowseg_last_launches": (_i, [_vp]),
     "mmf_fusion_set_flow_segmentation": (_i, [_vp, C.POINTER(mmf_flowseg_config)]),
     "mmf_fusion_last_flow_segmentation": (_i, [_vp, C.POINTER(mmf_flowseg_summary), _ip]),
+    "mmf_model_export_cloud": (_i, [_vp, _fp, _f, _vp, C.c_uint, C.POINTER(C.c_uint)]),
+    "mmf_model_export_last_launches": (_i, [_vp]),
+    "mmf_model_export_ply": (_i, [_vp, C.c_char_p, _fp]),
+    "mmf_ply_write_cloud": (_i, [C.c_char_p, _vp, C.c_uint]),
+    "mmf_ply_read_cloud": (_i, [C.c_char_p, _vp, C.c_uint, C.POINTER(C.c_uint)]),
+    "mmf_tracks_ply_write": (_i, [C.c_char_p, _i, _vp, _vp, _vp, _fp]),
+    "mmf_tracks_ply_read": (_i, [C.c_char_p, _i, _ip, _vp, _i, _ip, _vp, _vp]),
+    "mmf_viewstore_download_view": (_i, [_vp, _i, _i, _vp, _vp]),
+    "mmf_fusion_save_models": (_i, [_vp, C.c_char_p]),
+    "mmf_fusion_load_models": (_i, [_vp, C.c_char_p, _ip]),
 }
 
 _lib = None

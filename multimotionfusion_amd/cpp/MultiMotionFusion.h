@@ -291,6 +291,24 @@ class Model {
         out.resize(got);
         return out;
     }
+    // Model::exportModelPLY(export_dir, global_pose) (Model.cpp:1600-1605): the stable surfels under global_pose * pose^-1 as
+    // `<export_dir>cloud-<id>.ply` (export_dir ends in '/', as the reference's).  The inverse is the rigid one, [R^T | -R^T t]
+    // (MultiMotionFusion::savePly computes the product inside the library).
+    void exportModelPLY(const std::string& export_dir, const float global_pose[16]) const {
+        float p[16], inv[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1}, P[16];
+        getPose(p);
+        for (int r = 0; r < 3; ++r) {
+            for (int q = 0; q < 3; ++q) inv[4 * r + q] = p[4 * q + r];
+            inv[4 * r + 3] = -((p[r] * p[3] + p[4 + r] * p[7]) + p[8 + r] * p[11]);
+        }
+        for (int r = 0; r < 4; ++r)
+            for (int q = 0; q < 4; ++q) {
+                float acc = global_pose[4 * r] * inv[q];
+                for (int k = 1; k < 4; ++k) acc = acc + global_pose[4 * r + k] * inv[4 * k + q];
+                P[4 * r + q] = acc;
+            }
+        mmf::check(mmf_model_export_ply(m_, (export_dir + "cloud-" + std::to_string(getID()) + ".ply").c_str(), P), "mmf_model_export_ply");
+    }
     // Model.h:297: the surfel store the last fuse / clean left, in place (valid until this model's next fuse / clean)
     const OutputBuffer& getModel() {
         mmf::check(mmf_model_surfel_arrays(m_, &vbo_.positionConfidence, &vbo_.colourTime, &vbo_.normalRadius, &vbo_.count),
@@ -823,6 +841,14 @@ class MultiMotionFusion {
     void getCurrPose(float pose[16]) const { mmf::check(mmf_fusion_get_pose(f_, pose), "mmf_fusion_get_pose"); }
     void exportPoses(const std::string& exportDir = "") {  // (the reference writes into the constructor's exportDirectory)
         mmf::check(mmf_fusion_export_poses(f_, (exportDir.empty() ? exportDirectory_ : exportDir).c_str()), "mmf_fusion_export_poses");
+    }
+    // savePly() (:1001-1018) into the constructor's exportDirectory: cloud-<id>.ply per model and the model database under
+    // model_db/ (mmf_fusion_save_models); loadModels() (:131-145, -restore) from the same place -> the models restored
+    void savePly() { mmf::check(mmf_fusion_save_models(f_, exportDirectory_.c_str()), "mmf_fusion_save_models"); }
+    int loadModels() {
+        int n = 0;
+        mmf::check(mmf_fusion_load_models(f_, exportDirectory_.c_str(), &n), "mmf_fusion_load_models");
+        return n;
     }
     mmf_odom* getFrameOdometryHandle() { return mmf_fusion_odometry(f_); }
     mmf_fusion* handle() const { return f_; }

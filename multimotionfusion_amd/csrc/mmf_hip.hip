@@ -771,6 +771,7 @@ extern "C" int mmf_compute_derivative_images(mmf_ctx* c, const uint8_t* src, siz
 #include "pass_rect.hpp"
 
 #include "model_host.hpp"
+#include "export_host.hpp"
 
 // =============================================================================================
 // Keypoint descriptor matching (Core/Utils/PointTracker.cpp:100-114) on the f32 matrix cores
@@ -1646,6 +1647,7 @@ extern "C" int mmf_debug_set_stamps(void* dev_buf) {
 #include "fusion_keypoints.hpp"
 #include "fusion_ingest.hpp"
 #include "fusion_orchestrator.hpp"
+#include "modeldb_host.hpp"
 
 // =============================================================================================
 // Per-rigid-body shard across GPUs: frame broadcast + pose all-gather over RCCL

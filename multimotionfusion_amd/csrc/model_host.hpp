@@ -126,6 +126,11 @@ struct mmf_model {
     uchar4* fill_image = nullptr;
     // pass_rect.hpp: where this model's key image was written and where its images are non-zero (device; ModelGenerations)
     PassBoxes* boxes = nullptr;
+    // export_host.hpp: the workspace of mmf_model_export_cloud (an allocation of its own, made by the first export) and the
+    // launches of the last one
+    void* export_ws = nullptr;
+    size_t export_ws_bytes = 0;
+    int export_launches = 0;
 };
 
 // Every buffer of the slab, ONCE, in the order it is carved.  The slab's size, the pointers and mmf_model_texture's answers
@@ -296,6 +301,7 @@ extern "C" void mmf_model_destroy(mmf_model* m) {
     (void)hipStreamSynchronize(m->ctx->stream);
     (void)hipFree(m->slab);
     (void)hipFree(m->boxes);
+    (void)hipFree(m->export_ws);
     (void)hipHostFree(m->count.host_totals);
     delete m;
 }

@@ -1,0 +1,118 @@
+// modeldb_host.hpp -- the model database on the fusion: MultiMotionFusion::savePly (Core/MultiMotionFusion.cpp:1001-1018) and
+// loadModels (:131-145, `-restore`).  Textually included by mmf_hip.hip behind fusion_orchestrator.hpp.  Neither call is made by
+// a frame; both are synchronous and leave nothing enqueued.
+#pragma once
+
+#include <filesystem>
+
+static std::string modeldb_join(const std::string& dir, const std::string& name) {
+    return (dir.empty() || dir.back() == '/') ? dir + name : dir + "/" + name;
+}
+static int modeldb_make_dirs(const std::string& dir) {
+    std::error_code ec;
+    std::filesystem::create_directories(dir, ec);
+    if (ec && !std::filesystem::is_directory(dir)) return fail(MMF_ERR_INVALID, "mmf_fusion_save_models: cannot create " + dir + ": " + ec.message());
+    return MMF_OK;
+}
+
+// the views of model `id` in the store, ascending, in the mmf_viewstore_store layout; false: the model has none
+static int modeldb_model_views(mmf_viewstore* vs, int id, std::vector<int>* counts, std::vector<float>* desc, std::vector<float>* coord, bool* any) {
+    counts->clear(), desc->clear(), coord->clear();
+    *any = false;
+    if (!vs) return MMF_OK;
+    std::vector<int> which;
+    size_t rows = 0;
+    for (size_t v = 0; v < vs->views.size(); ++v)
+        if (vs->views[v].model == id) which.push_back((int)v), rows += (size_t)vs->views[v].rows;
+    if (which.empty()) return MMF_OK;
+    *any = true;
+    desc->resize(rows * kRdDim), coord->resize(rows * 3);
+    size_t at = 0;
+    for (int v : which) {
+        const int n = vs->views[(size_t)v].rows;
+        counts->push_back(n);
+        if (int rc = mmf_viewstore_download_view(vs, v, n, desc->data() + at * kRdDim, coord->data() + at * 3)) return rc;
+        at += (size_t)n;
+    }
+    return MMF_OK;
+}
+
+// savePly: every active model, then every inactive one (a model another rank owns has no store here and is left to its
+// owner).  Per model P = global pose * pose^-1: `cloud-<id>.ply` under export_dir, `model_db/model-<id>/cloud.ply` with the
+// same P and -- for a model with views in the fusion's store -- `model_db/model-<id>/tracks.ply` with P.  Observational.
+extern "C" int mmf_fusion_save_models(mmf_fusion* f, const char* export_dir) {
+    MMF_REQUIRE(f && export_dir, "mmf_fusion_save_models: null argument");
+    MMF_HIP_TRY(hipSetDevice(f->ctx->device));
+    // the stores are written on the models' own streams and on those of batched passes: all of it has landed
+    MMF_HIP_TRY(hipDeviceSynchronize());
+    const std::string dir(export_dir), db = modeldb_join(dir, "model_db");
+    if (int rc = modeldb_make_dirs(db)) return rc;
+    float global_pose[16];
+    mmf_model_get_pose(f->models[0]->model, global_pose);
+    std::vector<int> counts;
+    std::vector<float> desc, coord;
+    for (auto* list : {&f->models, &f->inactive})
+        for (FusionModel* fm : *list) {
+            mmf_model* m = fm->model;
+            if (model_is_bookkeeping(m)) continue;
+            const std::string id = std::to_string((int)m->id), model_dir = modeldb_join(db, "model-" + id);
+            float inv[16], P[16];
+            inverse4f_host(m->pose, inv);
+            mmf::host::matmul4(global_pose, inv, P);
+            if (int rc = modeldb_make_dirs(model_dir)) return rc;
+            if (int rc = mmf_model_export_ply(m, modeldb_join(dir, "cloud-" + id + ".ply").c_str(), P)) return rc;
+            if (int rc = mmf_model_export_ply(m, modeldb_join(model_dir, "cloud.ply").c_str(), P)) return rc;
+            bool any = false;
+            if (int rc = modeldb_model_views(f->rd.views, (int)m->id, &counts, &desc, &coord, &any)) return rc;
+            if (!any) continue;
+            if (int rc = mmf_tracks_ply_write(modeldb_join(model_dir, "tracks.ply").c_str(), (int)counts.size(), counts.data(), desc.data(),
+                                              coord.data(), P))
+                return rc;
+        }
+    return MMF_OK;
+}
+
+// loadModels: for id = 1 .. 255 ascending with a `model_db/model-<id>/tracks.ply`, an object model with the NEXT model id and
+// conf_object_init, the file's views stored for that id, unseen count -5 (:141), at the end of the inactive list.  No dense
+// surfels (as in the reference).  A file that does not parse is skipped: mmf_last_error names the last such file, the models
+// before and behind it are loaded.
+extern "C" int mmf_fusion_load_models(mmf_fusion* f, const char* export_dir, int* n_loaded) {
+    MMF_REQUIRE(f && export_dir, "mmf_fusion_load_models: null argument");
+    if (n_loaded) *n_loaded = 0;
+    if (f->shard_world > 1) return fail(MMF_ERR_STATE, "mmf_fusion_load_models: not supported on a shard (world > 1)");
+    MMF_HIP_TRY(hipSetDevice(f->ctx->device));
+    if (int rc = fusion_viewstore(f)) return rc;
+    const std::string db = modeldb_join(export_dir, "model_db");
+    std::string skipped;
+    std::vector<int> counts;
+    std::vector<float> desc, coord;
+    for (int id = 1; id < 256; ++id) {
+        const std::string path = modeldb_join(modeldb_join(db, "model-" + std::to_string(id)), "tracks.ply");
+        std::error_code ec;
+        if (!std::filesystem::exists(path, ec)) continue;
+        int n_views = 0, n_rows = 0;
+        int rc = mmf_tracks_ply_read(path.c_str(), 0, &n_views, nullptr, 0, &n_rows, nullptr, nullptr);
+        if (rc == MMF_OK) {
+            counts.assign((size_t)n_views, 0), desc.assign((size_t)n_rows * kRdDim, 0.f), coord.assign((size_t)n_rows * 3, 0.f);
+            rc = mmf_tracks_ply_read(path.c_str(), n_views, &n_views, counts.data(), n_rows, &n_rows, desc.data(), coord.data());
+        }
+        if (rc != MMF_OK) {
+            skipped = path + ": " + g_last_error;
+            continue;
+        }
+        FusionModel* fm = nullptr;
+        if (int rc_new = fusion_model_create(f, fusion_next_model_id(f, true), f->cfg.conf_object_init, 0, true, &fm)) return rc_new;
+        int stored = 0;
+        rc = mmf_viewstore_store(f->rd.views, (int)fm->model->id, n_views, counts.data(), desc.data(), coord.data(), &stored);
+        if (rc != MMF_OK) {
+            const std::string keep = g_last_error;
+            fusion_model_destroy(fm);
+            return fail(rc, keep);
+        }
+        fm->unseen = -5;
+        f->inactive.push_back(fm);
+        if (n_loaded) ++*n_loaded;
+    }
+    g_last_error = skipped.empty() ? std::string() : "mmf_fusion_load_models: skipped " + skipped;
+    return MMF_OK;
+}

@@ -331,6 +331,22 @@ extern "C" int mmf_viewstore_view(mmf_viewstore* vs, int view, int* model_id, in
     if (rows) *rows = vs->views[(size_t)view].rows;
     return MMF_OK;
 }
+// a view's rows back on the HOST, [rows][256] and [rows][3], without the zero rows that pad it to a tile (either destination
+// may be NULL).  Synchronous.
+extern "C" int mmf_viewstore_download_view(mmf_viewstore* vs, int view, int capacity_rows, float* descriptor, float* coordinate) {
+    MMF_REQUIRE(vs && view >= 0 && view < (int)vs->views.size(), "mmf_viewstore_download_view: bad argument");
+    const RdView& v = vs->views[(size_t)view];
+    MMF_REQUIRE(capacity_rows >= v.rows, "mmf_viewstore_download_view: capacity_rows below the view's rows");
+    if (v.rows == 0) return MMF_OK;
+    const size_t n = (size_t)v.rows;
+    if (coordinate) std::memcpy(coordinate, vs->coords.data() + 3 * v.coord0, n * 3 * sizeof(float));
+    if (descriptor) {
+        MMF_HIP_TRY(hipSetDevice(vs->ctx->device));
+        MMF_HIP_TRY(hipMemcpyAsync(descriptor, vs->desc + v.row0 * kRdDim, n * kRdDim * sizeof(float), hipMemcpyDeviceToHost, vs->ctx->stream));
+        MMF_HIP_TRY(hipStreamSynchronize(vs->ctx->stream));
+    }
+    return MMF_OK;
+}
 extern "C" int mmf_viewstore_last_launches(mmf_viewstore* vs) { return vs ? vs->last_launches : -1; }
 
 // the three launches of every set, on `st`; results in out_row / out_dist at [view * nq + i] + V * q0 of the set.

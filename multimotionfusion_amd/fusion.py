@@ -522,6 +522,18 @@ class MultiMotionFusion:
     def exportPoses(self, export_dir):
         check(self.ctx.lib.mmf_fusion_export_poses(self.handle, export_dir.encode()))
 
+    def savePly(self, exportDir):
+        """MultiMotionFusion::savePly (:1001-1018): cloud-<id>.ply per model under exportDir and the model database
+        (model_db/model-<id>/cloud.ply, tracks.ply for models with stored views); modeldb.py reads the files"""
+        check(self.ctx.lib.mmf_fusion_save_models(self.handle, str(exportDir).encode()))
+
+    def loadModels(self, exportDir):
+        """MultiMotionFusion::loadModels (:131-145, -restore): every model_db/model-<id>/tracks.ply under exportDir becomes
+        an inactive object model with the next id and the file's views -> the number of models loaded"""
+        n = C.c_int()
+        check(self.ctx.lib.mmf_fusion_load_models(self.handle, str(exportDir).encode(), C.byref(n)))
+        return n.value
+
     def getPoseLog(self, index=0):
         n = C.c_int()
         check(self.ctx.lib.mmf_fusion_pose_log(self.handle, index, None, None, 0, C.byref(n)))

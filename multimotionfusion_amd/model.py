@@ -105,6 +105,25 @@ class Model:
         check(self.ctx.lib.mmf_model_download_map(self.handle, fptr(out), n, C.byref(got)))
         return out[: got.value]
 
+    def exportCloud(self, pose, confThreshold):
+        """Model::exportModelPLY's loop on the device: the surfels with conf > confThreshold under `pose` as a record array
+        of modeldb.CLOUD_DTYPE (31 bytes each), ascending surfel index."""
+        from .modeldb import CLOUD_DTYPE
+        p = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(16))
+        cap = self.lastCount()
+        out = np.zeros(max(cap, 1), CLOUD_DTYPE)
+        n = C.c_uint(0)
+        check(self.ctx.lib.mmf_model_export_cloud(self.handle, fptr(p), float(confThreshold), out.ctypes.data, cap, C.byref(n)))
+        return out[: n.value]
+
+    def exportLastLaunches(self):
+        return self.ctx.lib.mmf_model_export_last_launches(self.handle)
+
+    def exportModelPLY(self, path, pose):
+        """the stable surfels (the model's own confidence threshold) under `pose` as a binary PLY file"""
+        p = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(16))
+        check(self.ctx.lib.mmf_model_export_ply(self.handle, str(path).encode(), fptr(p)))
+
     def uploadMap(self, surfels):
         s = np.ascontiguousarray(np.asarray(surfels, np.float32).reshape(-1, 12))
         check(self.ctx.lib.mmf_model_upload_map(self.handle, fptr(s), s.shape[0]))

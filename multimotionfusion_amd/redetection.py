@@ -66,6 +66,14 @@ class ViewStore:
             out.append((m.value, i.value, r.value))
         return out
 
+    def downloadView(self, view):
+        """the rows of the view at store position `view` -> (descriptor [rows,256], coordinate [rows,3]) float32, no padding"""
+        rows = C.c_int()
+        check(self.ctx.lib.mmf_viewstore_view(self.handle, int(view), None, None, C.byref(rows)))
+        desc, coord = np.zeros((rows.value, DIM), np.float32), np.zeros((rows.value, 3), np.float32)
+        check(self.ctx.lib.mmf_viewstore_download_view(self.handle, int(view), rows.value, desc.ctypes.data, coord.ctypes.data))
+        return desc, coord
+
     def match(self, query: torch.Tensor):
         """query [nq,256] float32 CUDA tensor against every view -> (trainIdx [views,nq] int32, -1 = unmatched; distance)"""
         assert query.dtype == torch.float32 and query.is_cuda and (query.shape[0] == 0 or query.shape[1] == DIM)
