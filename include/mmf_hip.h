@@ -1004,8 +1004,32 @@ int mmf_ransac_estimate(mmf_ransac *r, const float *p0, const float *p1, int n, 
  *                       its next call.  Two launches whatever n_views is (0 allowed).
  * Differences from the reference: the history is bounded by the log (Model::store has poses.size() views, this the last
  * `frames` of them), and a caller pairs poses with frames BY STAMP (the reference pairs from the end of the lists, which
- * shifts every keypoint against its pose by one frame when a deactivation is scheduled).  refineTrackSubset and the on-disk
- * files are out of scope.
+ * shifts every keypoint against its pose by one frame when a deactivation is scheduled).  The on-disk files are out of
+ * scope.
+ * BACK-DATING (Model::refineTrackSubset, Model.cpp:649-737; csrc/backdate_kernels.hpp): how the tracks of
+ * one segment moved in the frames before it was segmented, as a pose list whose end is the identity.
+ *   mmf_tracker_backdate    waits twice (counts, estimates).  S = the table rows with label[i] == label (after this frame's
+ *                       mmf_tracker_associate), in table order.  len = max(1, min(length, history, the frames newest, newest
+ *                       - 1, ... the ring holds)); entry j = the frame with stamp newest - len + 1 + j.  A track's keypoint in
+ *                       a frame is the entry of that frame's slot with its uid.  ik = 0; for jk = 1 .. len - 1: both = rows of
+ *                       S with a keypoint at ik and at jk, nvalid = those finite at both, from = ik; nvalid < 3: rel[jk] =
+ *                       rel[ik], status TOO_FEW, ik stays; else T = the estimate of a FRESH RigidRANSAC{cfg of `batch`} for
+ *                       the nvalid rows in table order (p0 at ik, p1 at jk), rel[jk] = rel[ik] T, ik = jk.  pose[j] =
+ *                       inverse(rel[len - 1]) rel[j]; pose[len - 1] is exactly the identity.  Three launches whatever len, the
+ *                       tracks and the slots are, then the batch object's one (none without a problem, and then one wait).
+ *                       A problem with more than max_points rows is estimated by the same core on the host and flagged
+ *                       (more than 65535: status TOO_MANY, T identity).  out = HOST [capacity], capacity >= min(history, the
+ *                       frames in the ring) (MMF_ERR_INVALID otherwise); *n_out = len.  2 <= history <= 256 and label 0 .. 255
+ *                       (MMF_ERR_INVALID), a tracker without a view log: MMF_ERR_STATE, a batch object of another context:
+ *                       MMF_ERR_INVALID.  The table and the log are not written.  Frames are paired BY STAMP (the reference
+ *                       indexes the tracks by the camera's pose count, which is wrong once the table was ever empty), every
+ *                       pair gets a fresh engine (the reference runs one on; the same for its only history, 2), and every
+ *                       entry carries its frame's stamp and its add's timestamp, kept on the host (the reference: 0 without
+ *                       a common track)
+ *   mmf_tracker_reserve_backdate   the workspace for windows of up to `history` frames, allocated HERE behind a wait for the
+ *                       stream (0 frees it); a mmf_tracker_backdate that needs more than is reserved reserves it itself
+ *   mmf_tracker_backdate_rows      test accessor: the p0 / p1 rows ([*n][3], HOST arrays of `capacity` rows) the last
+ *                       mmf_tracker_backdate handed the batch object for entry `entry` (none: *n = 0)
  * Inside processFrame (off by default; MMF_ERR_STATE with world > 1; the fusion does not own the tracker, which must share
  * its context and image size):
  *   mmf_fusion_set_tracker      tracker = NULL detaches.  The caller adds and prunes a frame's keypoints BEFORE processFrame
@@ -1123,6 +1147,40 @@ int mmf_ransac_batch_estimate(mmf_ransac_batch *b, const float *p0_dev, const fl
                               mmf_ransac_result *results, unsigned char *inlier);
 int mmf_ransac_batch_max_points(mmf_ransac_batch *b);
 int mmf_ransac_batch_last_launches(mmf_ransac_batch *b);
+/* Back-dating (the tracker section above describes the calls): one entry of the pose list, oldest first.
+ * Inside processFrame (off by default):
+ *   mmf_fusion_set_track_backdating   history = 0 switches it off and frees what the setter made; 2 .. 256: the fusion creates
+ *                         its batch object {10, 0.03, 0.6}, max_points 1024, HERE (never per frame) and, when a tracker is
+ *                         attached, reserves its workspace.  MMF_ERR_STATE with world > 1.  With it on, a tracked frame whose
+ *                         segmentation spawned a model this rank owns, with an attached tracker that keeps a view log, runs
+ *                         mmf_tracker_backdate(new model's id, history) directly behind the frame's association (refineTrack-
+ *                         Subset(segm_tracks[uid], globalModel, 2), MultiMotionFusion.cpp:596-599).  When the models' view-pose
+ *                         lists are kept (redetection on), entries 0 .. len - 2 go in front of the spawn frame's own entry
+ *                         and the list is trimmed to the log's length as before: the views the model stores on deactivation
+ *                         reach back before the spawn.  The model's pose is NOT touched (the reference overrides it with a
+ *                         near-identity; a spawned model's pose is the identity already).  Every other frame: nothing is
+ *                         enqueued or awaited.
+ *   mmf_fusion_last_backdated_poses   what the last mmf_fusion_process_frame* call back-dated: *model_id (-1: nothing) and its
+ *                         entries; cleared at the start of every call */
+typedef struct {
+    int stamp;           /* the frame (mmf_tracker_frame counts them) */
+    long long timestamp; /* of the add that logged it; 0 when the frame is not in the ring */
+    int from;            /* ik: the entry this one is chained to (-1: entry 0) */
+    int both;            /* tracks of the segment with a keypoint in both frames */
+    int nvalid;          /* ... that are finite in both */
+    int status;          /* MMF_RANSAC_* (entry 0: OK) */
+    int host_estimated;  /* 1: more rows than the batch object takes, estimated by the same core on the host */
+    float error;         /* as mmf_ransac_result's; +inf without an estimate */
+    int n_inliers;
+    float T[16];         /* T_01 of (from, this entry), p0 ~ T p1; identity without an estimate */
+    float pose[16];      /* inverse(rel[len - 1]) rel[j]; the last entry's is exactly the identity */
+} mmf_backdated_pose;
+int mmf_tracker_backdate(mmf_tracker *t, int label, int history, mmf_ransac_batch *batch, mmf_backdated_pose *out, int capacity,
+                         int *n_out);
+int mmf_tracker_reserve_backdate(mmf_tracker *t, int history);
+int mmf_tracker_backdate_rows(mmf_tracker *t, int entry, float *p0, float *p1, int capacity, int *n);
+int mmf_fusion_set_track_backdating(mmf_fusion *f, int history);
+int mmf_fusion_last_backdated_poses(mmf_fusion *f, int *model_id, mmf_backdated_pose *out, int capacity, int *n_out);
 /* The view store with a verifier (keypoint redetection, above):
  *   mmf_viewstore_set_verifier   attaches a batch object (NULL detaches it; it belongs to the caller, shares the store's context
  *                         and outlives its attachment).  With one attached the store keeps its coordinates and its view table

@@ -116,6 +116,12 @@ class mmf_ransac_result(C.Structure):
                 ("status", C.c_int)]
 
 
+class mmf_backdated_pose(C.Structure):
+    _fields_ = [("stamp", C.c_int), ("timestamp", C.c_longlong), ("from_", C.c_int), ("both", C.c_int), ("nvalid", C.c_int),
+                ("status", C.c_int), ("host_estimated", C.c_int), ("error", C.c_float), ("n_inliers", C.c_int),
+                ("T", C.c_float * 16), ("pose", C.c_float * 16)]
+
+
 class mmf_flow_config(C.Structure):
     _fields_ = [("div", C.c_int), ("levels", C.c_int), ("winsize", C.c_int), ("iterations", C.c_int), ("poly_n", C.c_int),
                 ("poly_sigma", C.c_float)]
@@ -382,6 +388,11 @@ SIGNATURES = {
     "mmf_ransac_batch_estimate": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "mmf_ransac_batch_max_points": (_i, [_vp]),
     "mmf_ransac_batch_last_launches": (_i, [_vp]),
+    "mmf_tracker_backdate": (_i, [_vp, _i, _i, _vp, C.POINTER(mmf_backdated_pose), _i, _ip]),
+    "mmf_tracker_reserve_backdate": (_i, [_vp, _i]),
+    "mmf_tracker_backdate_rows": (_i, [_vp, _i, _vp, _vp, _i, _ip]),
+    "mmf_fusion_set_track_backdating": (_i, [_vp, _i]),
+    "mmf_fusion_last_backdated_poses": (_i, [_vp, _ip, C.POINTER(mmf_backdated_pose), _i, _ip]),
     "mmf_viewstore_set_verifier": (_i, [_vp, _vp]),
     "mmf_viewstore_best_match_device": (_i, [_vp, _i, _vp, _vp, _i, _vp, _fp, _ip, _ip, _ip, _vp, _ip]),
     "mmf_fusion_set_redetection_verifier": (_i, [_vp, _i]),

@@ -791,6 +791,20 @@ class MultiMotionFusion {
         for (int k = 0; k < n; ++k) out.push_back(StoredViews{ids[(size_t)k], views[(size_t)k], rows[(size_t)k]});
         return out;
     }
+    // refineTrackSubset(segm_tracks[uid], globalModel, 2) (:596-599) inside processFrame: history 0 = off (the default), the
+    // reference's value is 2.  The frame that spawns a model back-dates its poses from the tracks of its segment (an attached
+    // tracker with a view log); with redetection on the views it stores on deactivation reach back before the spawn.  The
+    // model's pose is not overridden.
+    void setTrackBackdating(int history) { mmf::check(mmf_fusion_set_track_backdating(f_, history), "mmf_fusion_set_track_backdating"); }
+    // what the last processFrame back-dated: the model's id (-1: nothing) and its entries, oldest first
+    std::vector<mmf_backdated_pose> getLastBackdatedPoses(int* modelId = nullptr) {
+        int n = 0, id = -1;
+        mmf::check(mmf_fusion_last_backdated_poses(f_, &id, nullptr, 0, &n), "mmf_fusion_last_backdated_poses");
+        std::vector<mmf_backdated_pose> out((size_t)n);
+        if (n) mmf::check(mmf_fusion_last_backdated_poses(f_, &id, out.data(), n, &n), "mmf_fusion_last_backdated_poses");
+        if (modelId) *modelId = id;
+        return out;
+    }
     // ----- keypoint tracks (MultiMotionFusion.h:307-309, 366; .cpp:223-248, 312-335): with a predictor set, processFrame(FrameData)
     // runs getFeatures on the frame, adds its keypoints to the tracker (0.7, 30) and prunes it (30, 1 s) before the library
     // call, which initialises every model from its own tracks when odom_cfg.init == "kp" and keeps the models' track sets

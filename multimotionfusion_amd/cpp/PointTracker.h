@@ -134,6 +134,19 @@ class PointTracker {
         out.counts.assign(counts, counts + frames.size());
         return out;
     }
+    // ----- back-dating: Model::refineTrackSubset(tracks, parent, history) (Model.cpp:649-737) for the tracks that carry
+    // `label` after this frame's association, from the table and the view log.  The entries are the reference's `poses`
+    // (oldest first, the last one exactly the identity) with each pair's counts and estimate beside them.  `batch` is a
+    // mmf_ransac_batch of this context with the reference's {10, 0.03, 0.6} (mmf_ransac_batch_create); frames are paired by
+    // stamp, every pair gets a fresh engine, the window is bounded by the log.
+    void reserveBackdate(int history) { mmf::check(mmf_tracker_reserve_backdate(t_, history), "mmf_tracker_reserve_backdate"); }
+    std::vector<mmf_backdated_pose> backdate(int label, mmf_ransac_batch* batch, int history = 2) {
+        std::vector<mmf_backdated_pose> out((size_t)(history > 0 ? history : 0));
+        int n = 0;
+        mmf::check(mmf_tracker_backdate(t_, label, history, batch, out.data(), (int)out.size(), &n), "mmf_tracker_backdate");
+        out.resize((size_t)n);
+        return out;
+    }
     mmf_tracker* handle() const { return t_; }
 
    private:

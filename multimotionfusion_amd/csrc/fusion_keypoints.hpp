@@ -14,6 +14,7 @@ extern "C" int mmf_fusion_set_tracker(mmf_fusion* f, mmf_tracker* tracker, int o
     f->kp.init_kp = tracker && odom_init_kp != 0, f->kp.icp_refine = icp_refine != 0;
     f->kp.ids.clear(), f->kp.T.clear();
     f->kp.view_poses.clear();  // (the entries carry the stamps of the tracker that leaves)
+    if (tracker && f->kp.backdate_history) return mmf_tracker_reserve_backdate(tracker, f->kp.backdate_history);  // (here, not in a frame)
     return MMF_OK;
 }
 
@@ -168,6 +169,68 @@ static int fusion_store_views(mmf_fusion* f, FusionModel* fm) {
         f->kp.stored_ids.push_back(id), f->kp.stored_views.push_back(n), f->kp.stored_rows.push_back(rows);
     }
     f->kp.view_poses.erase(id);
+    return MMF_OK;
+}
+
+// ---- back-dating a spawned model's poses (MultiMotionFusion.cpp:596-599; Model::refineTrackSubset, Model.cpp:649-737) ---------
+extern "C" int mmf_fusion_set_track_backdating(mmf_fusion* f, int history) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_set_track_backdating: null fusion object");
+    MMF_REQUIRE(history == 0 || (history >= 2 && history <= mmf::kTrkBackdateMax), "mmf_fusion_set_track_backdating: history is 0 (off) or 2 .. 256");
+    if (history && f->shard_world > 1) return fail(MMF_ERR_STATE, "mmf_fusion_set_track_backdating: sharded use is not supported (world > 1)");
+    if (history == 0) {
+        mmf_ransac_batch_destroy(f->kp.backdate_batch);  // (waits for the stream)
+        f->kp.backdate_batch = nullptr, f->kp.backdate_history = 0;
+        f->kp.backdated.clear(), f->kp.backdated_id = -1;
+        return MMF_OK;
+    }
+    if (!f->kp.backdate_batch) {
+        const mmf_ransac_config cfg{kTrackRansac.iterations, kTrackRansac.inlier_threshold, kTrackRansac.inlier_fraction};  // (:665)
+        int rc = mmf_ransac_batch_create(f->ctx, &cfg, mmf::kRansacMaxPoints, &f->kp.backdate_batch);
+        if (rc) return rc;
+    }
+    if (f->kp.tracker) {  // (a tracker attached later gets its workspace in mmf_fusion_set_tracker)
+        int rc = mmf_tracker_reserve_backdate(f->kp.tracker, history);
+        if (rc) return rc;
+    }
+    f->kp.backdate_history = history;
+    return MMF_OK;
+}
+
+extern "C" int mmf_fusion_last_backdated_poses(mmf_fusion* f, int* model_id, mmf_backdated_pose* out, int capacity, int* n_out) {
+    MMF_REQUIRE(f && n_out && capacity >= 0 && (out || capacity == 0), "mmf_fusion_last_backdated_poses: bad argument");
+    if (model_id) *model_id = f->kp.backdated_id;
+    *n_out = (int)f->kp.backdated.size();
+    for (int i = 0; i < *n_out && i < capacity; ++i) out[i] = f->kp.backdated[(size_t)i];
+    return MMF_OK;
+}
+
+// directly behind the frame's association: the tracks that carry the spawned model's label say how it moved before it was
+// segmented.  With the models' view-pose lists kept, entries 0 .. len - 2 go in front of the spawn frame's own entry
+// (fusion_note_view_poses made it), so that fusion_store_views builds the earlier views too; the model's pose stays as it is.
+static int frame_backdate(mmf_fusion* f) {
+    mmf_tracker* t = f->kp.tracker;
+    const int id = f->kp.spawned_id, history = f->kp.backdate_history;
+    if (history < 2 || !f->kp.backdate_batch || !t || t->log.frames <= 0 || id <= 0 || id >= mmf::kTrkMaxModels) return MMF_OK;
+    f->kp.backdated.resize((size_t)history);
+    int n = 0;
+    int rc = mmf_tracker_backdate(t, id, history, f->kp.backdate_batch, f->kp.backdated.data(), history, &n);
+    if (rc) {
+        f->kp.backdated.clear();
+        return rc;
+    }
+    f->kp.backdated.resize((size_t)n), f->kp.backdated_id = id;
+    if (!fusion_view_log_on(f)) return MMF_OK;
+    std::vector<Keypoints::ViewPose>& list = f->kp.view_poses[id];
+    if (list.size() != 1 || list.back().stamp != (int)t->frame) return MMF_OK;  // (only the spawn frame's own entry is expected)
+    std::vector<Keypoints::ViewPose> front;
+    for (int j = 0; j + 1 < n; ++j) {
+        Keypoints::ViewPose e;
+        e.stamp = f->kp.backdated[(size_t)j].stamp;
+        std::memcpy(e.pose, f->kp.backdated[(size_t)j].pose, sizeof(e.pose));
+        front.push_back(e);
+    }
+    list.insert(list.begin(), front.begin(), front.end());
+    if ((int)list.size() > t->log.frames) list.erase(list.begin(), list.end() - t->log.frames);
     return MMF_OK;
 }
 

@@ -798,6 +798,7 @@ static int frame_segment(mmf_fusion* f, const FrameRun& r) {
         rc = mmf_model_clean(fresh->model, f->tick, g.time_delta, g.max_depth_processed, f->depth_filtered, f->mask.get(), g.outlier_coeff);
         if (rc) return rc;
         f->models.push_back(fresh);  // moveNewModelToList (:600)
+        f->kp.spawned_id = (int)fresh->model->id;
     }
     // unseen models leave the list (:606-613); the confidence of object models rises (:616-620)
     std::vector<FusionModel*> lost;
@@ -1062,6 +1063,7 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
     f->t_tracking_s = 0;
     f->rd.last.clear();  // (mmf_fusion_last_redetections speaks of this call)
     f->kp.stored_ids.clear(), f->kp.stored_views.clear(), f->kp.stored_rows.clear();
+    f->kp.spawned_id = -1, f->kp.backdated_id = -1, f->kp.backdated.clear();
     int rc = MMF_OK;
     if (f->flow.engine) {
         f->fi.has = false;
@@ -1103,6 +1105,10 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
         if (r.track && !first) fusion_note_view_poses(f, false);
         rc = frame_associate_tracks(f, first || !f->cfg.enable_multiple_models, r.track);
         if (rc) return rc;
+        if (f->kp.backdate_history && f->kp.spawned_id >= 0 && r.track && !first) {  // refineTrackSubset (:596-599)
+            rc = frame_backdate(f);
+            if (rc) return rc;
+        }
     }
     f->sp.next = false;  // (mmf_fusion_set_superpixels: this call's labels only, whichever segmentation ran)
     f->rd.kp_next = false;  // (mmf_fusion_set_keypoints: this call's keypoints only, whether or not a segmentation ran)

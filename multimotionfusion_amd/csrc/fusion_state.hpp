@@ -166,6 +166,14 @@ struct Keypoints {
     };
     std::map<int, std::vector<ViewPose>> view_poses;
     std::vector<int> stored_ids, stored_views, stored_rows;
+    // back-dating of a spawned model's poses from its tracks (mmf_fusion_set_track_backdating; Model::refineTrackSubset,
+    // Model.cpp:649-737): off unless a history is set.  The batch object is the one thing here that is owned
+    int backdate_history = 0;
+    mmf_ransac_batch* backdate_batch = nullptr;  // created by the setter, never per frame
+    int spawned_id = -1;                         // the model this call's segmentation spawned on this rank, -1: none
+    int backdated_id = -1;                       // what this call back-dated (mmf_fusion_last_backdated_poses)
+    std::vector<mmf_backdated_pose> backdated;
+    ~Keypoints() { mmf_ransac_batch_destroy(backdate_batch); }
 };
 
 // next-frame prefetch (mmf_fusion_prefetch_frame): the filter and the input-side preparation of frame t+1 run on `side` and
@@ -496,6 +504,7 @@ extern "C" int mmf_fusion_set_shard(mmf_fusion* f, int rank, int world) {
     if (world > 1 && f->rd.on) return fail(MMF_ERR_STATE, "mmf_fusion_set_shard: redetection is on (sharded redetection is not supported)");
     if (world > 1 && f->rd.verifier_mode) return fail(MMF_ERR_STATE, "mmf_fusion_set_shard: the redetection verifier is on (not supported on a shard)");
     if (world > 1 && f->flow.engine) return fail(MMF_ERR_STATE, "mmf_fusion_set_shard: the optical-flow hook is on (not supported on a shard)");
+    if (world > 1 && f->kp.backdate_history) return fail(MMF_ERR_STATE, "mmf_fusion_set_shard: track back-dating is on (not supported on a shard)");
     f->shard_rank = rank, f->shard_world = world;
     // models created ahead of their use (preallocateModels): the ones this rank will not own shrink to bookkeeping
     for (FusionModel*& fm : f->preallocated) {

@@ -9,6 +9,7 @@
 #pragma once
 
 #include "tracker_kernels.hpp"
+#include "backdate_kernels.hpp"
 
 struct mmf_tracker {
     mmf_ctx* ctx = nullptr;
@@ -42,6 +43,15 @@ struct mmf_tracker {
     int *view_count_pin = nullptr, *view_count_dev = nullptr, *view_row = nullptr;
     float *view_co = nullptr, *view_out_desc = nullptr, *view_out_co = nullptr;
     size_t view_out_rows = 0;
+    // back-dating (mmf_tracker_backdate, backdate_host.hpp): the workspace of `bd_history` window frames, all null until reserved
+    std::vector<long long> add_ts;  // the timestamp of the add that wrote slot stamp % log.frames (host side; the log's size)
+    int bd_history = 0;
+    int* bd_ent = nullptr;                                  // [bd_history][cap_pad]
+    mmf::TrkBackdate *bd_pin = nullptr, *bd_dev = nullptr;  // the chain kernel's record
+    float *bd_p0 = nullptr, *bd_p1 = nullptr;               // [bd_row_cap][3] the problems' rows
+    int bd_row_cap = 0;
+    mmf::TrkBackdate bd_last{};  // the record of the last call (mmf_tracker_backdate_rows)
+    bool bd_valid = false;
 };
 
 template <typename P>
@@ -61,6 +71,8 @@ static int tracker_clear(mmf_tracker* t) {
     std::memset(t->rec, 0, sizeof(mmf::TrkRecord));
     t->bound = 0, t->cur = 0, t->last_launches = 0;
     t->frame = 0, t->log_first = 1;  // (the stream has been awaited: no slot of the ring is of interest any more)
+    std::fill(t->add_ts.begin(), t->add_ts.end(), 0ll);
+    t->bd_valid = false;
     return MMF_OK;
 }
 
@@ -71,6 +83,16 @@ static void tracker_free_log(mmf_tracker* t) {
     (void)hipFree(t->log.co);
     (void)hipFree(t->log.desc);
     t->log = mmf::TrkLog{};
+}
+
+static void tracker_free_backdate(mmf_tracker* t) {
+    if (t->bd_pin) (void)hipHostFree(t->bd_pin);
+    (void)hipFree(t->bd_dev);
+    (void)hipFree(t->bd_ent);
+    (void)hipFree(t->bd_p0);
+    (void)hipFree(t->bd_p1);
+    t->bd_pin = t->bd_dev = nullptr, t->bd_ent = nullptr, t->bd_p0 = t->bd_p1 = nullptr;
+    t->bd_history = 0, t->bd_row_cap = 0, t->bd_valid = false;
 }
 
 static void tracker_free_views(mmf_tracker* t) {
@@ -91,6 +113,7 @@ extern "C" void mmf_tracker_destroy(mmf_tracker* t) {
     for (void* p : t->device_allocs) (void)hipFree(p);
     tracker_free_log(t);
     tracker_free_views(t);
+    tracker_free_backdate(t);
     (void)hipFree(t->view_out_desc);
     (void)hipFree(t->view_out_co);
     if (t->rec) (void)hipHostFree(t->rec);
@@ -151,14 +174,15 @@ extern "C" int mmf_tracker_last_launches(mmf_tracker* t) { return t ? t->last_la
 static void tracker_refresh(mmf_tracker* t) { t->bound = std::min(t->capacity, std::max(0, t->rec->n_tracks)); }
 
 // the end of an add: the stamp, and with the view log on the frame's visible set into its slot of the ring (two more
-// launches, nothing read back)
-static void tracker_add_tail(mmf_tracker* t) {
+// launches, nothing read back); the add's timestamp stays on the host, beside the slot's stamp
+static void tracker_add_tail(mmf_tracker* t, long long timestamp) {
     using namespace mmf;
     hipStream_t st = t->ctx->stream;
     t->last_launches = 7;
     t->frame += 1;
     if (t->log.frames > 0) {
         const int slot = (int)(t->frame % t->log.frames);
+        t->add_ts[(size_t)slot] = timestamp;
         hipLaunchKernelGGL(trk_log_kernel, dim3(1), dim3(kTrkBlock), 0, st, t->T, t->log, slot, t->frame, t->map);
         hipLaunchKernelGGL(trk_gather_rows_kernel, dim3(tracker_row_blocks(t->max_keypoints)), dim3(256), 0, st,
                            (const float*)t->desc[t->cur], (const int*)t->map, (const int*)(t->log.count + slot),
@@ -197,7 +221,7 @@ extern "C" int mmf_tracker_add_keypoints(mmf_tracker* t, int n, const int* xy, c
                        (const int*)t->train_idx, (const int*)t->active_idx, timestamp, t->dest_row);
     hipLaunchKernelGGL(trk_scatter_rows_kernel, dim3(tracker_row_blocks(std::max(n, 1))), dim3(256), 0, st, descriptor, n,
                        (const int*)t->dest_row, t->desc[t->cur], t->capacity);
-    tracker_add_tail(t);
+    tracker_add_tail(t, timestamp);
     MMF_HIP_TRY(hipGetLastError());
     t->bound = (int)std::min<long long>(t->capacity, (long long)t->bound + n);
     t->caller_adds += 1;
@@ -231,7 +255,7 @@ static int tracker_add_counted(mmf_tracker* t, const int* n_dev, const int* fail
                        (const float*)t->q_co, (const int*)t->train_idx, (const int*)t->active_idx, timestamp, t->dest_row);
     hipLaunchKernelGGL(trk_scatter_rows_counted_kernel, dim3(tracker_row_blocks(K)), dim3(256), 0, st, descriptor, n_dev, fail_dev, K,
                        (const int*)t->dest_row, t->desc[t->cur], t->capacity);
-    tracker_add_tail(t);
+    tracker_add_tail(t, timestamp);
     MMF_HIP_TRY(hipGetLastError());
     t->bound = (int)std::min<long long>(t->capacity, (long long)t->bound + K);
     return MMF_OK;
@@ -276,6 +300,8 @@ extern "C" int mmf_tracker_set_view_log(mmf_tracker* t, int frames) {
     MMF_HIP_TRY(hipStreamSynchronize(st));
     tracker_free_log(t);
     t->log_first = t->frame + 1;
+    t->add_ts.assign((size_t)frames, 0ll);
+    t->bd_valid = false;
     if (frames == 0) return MMF_OK;
     const size_t F = (size_t)frames, K = (size_t)t->max_keypoints;
     mmf::TrkLog L{};
@@ -566,3 +592,5 @@ extern "C" int mmf_tracker_download(mmf_tracker* t, int capacity, int* n_tracks,
     }
     return MMF_OK;
 }
+
+#include "backdate_host.hpp"

@@ -496,6 +496,22 @@ class MultiMotionFusion:
         check(self.ctx.lib.mmf_fusion_last_track_transforms(self.handle, T.ctypes.data, n.value, C.byref(n)))
         return T[:n.value]
 
+    def setTrackBackdating(self, history):
+        """back-date a spawned model's poses from its keypoint tracks (Model::refineTrackSubset; the reference passes
+        history 2).  0 switches it off (the default).  Needs an attached tracker with a view log to do anything; with
+        redetection on, the views the model stores on deactivation then reach back before its spawn."""
+        check(self.ctx.lib.mmf_fusion_set_track_backdating(self.handle, int(history)))
+
+    def getLastBackdatedPoses(self):
+        """(model id, [entry dicts, oldest first]) of what the last processFrame back-dated; (-1, []) when nothing"""
+        from ._capi import mmf_backdated_pose
+        from .tracker import backdated_pose_dict
+        n, mid = C.c_int(), C.c_int()
+        check(self.ctx.lib.mmf_fusion_last_backdated_poses(self.handle, C.byref(mid), None, 0, C.byref(n)))
+        out = (mmf_backdated_pose * max(n.value, 1))()
+        check(self.ctx.lib.mmf_fusion_last_backdated_poses(self.handle, C.byref(mid), out, n.value, C.byref(n)))
+        return mid.value, [backdated_pose_dict(out[j]) for j in range(n.value)]
+
     def getConfig(self):
         cfg = mmf_fusion_config()
         check(self.ctx.lib.mmf_fusion_get_config(self.handle, C.byref(cfg)))

@@ -10,8 +10,15 @@ import weakref
 import numpy as np
 import torch
 
-from ._capi import check, mmf_ransac_config
+from ._capi import check, mmf_backdated_pose, mmf_ransac_config
 from .cudafuncs import Context, _p
+
+
+def backdated_pose_dict(e):
+    """one mmf_backdated_pose as a dict of plain values and float32 [4,4] arrays"""
+    return dict(stamp=e.stamp, timestamp=e.timestamp, **{"from": e.from_}, both=e.both, nvalid=e.nvalid, status=e.status,
+                host_estimated=e.host_estimated, error=np.float32(e.error), n_inliers=e.n_inliers,
+                T=np.array(e.T, np.float32).reshape(4, 4), pose=np.array(e.pose, np.float32).reshape(4, 4))
 
 
 class DevicePointTracker:
@@ -132,6 +139,27 @@ class DevicePointTracker:
             out.append((d[o:o + n].copy(), c[o:o + n].copy()))
             o += int(n)
         return out, missing
+
+    # ----- back-dating: Model::refineTrackSubset (Model.cpp:649-737) from the table and the log
+    def reserveBackdate(self, history):
+        """the workspace for windows of up to `history` frames (0 frees it); allocated here, never per frame"""
+        check(self.ctx.lib.mmf_tracker_reserve_backdate(self.handle, int(history)))
+
+    def backdate(self, label, history, batch):
+        """how the tracks labelled `label` (after this frame's associate) moved over the last min(length, history, logged)
+        frames -> a list of dicts, oldest first, the last one's pose exactly the identity.  batch: ransac.RansacBatch of the
+        same context ({10, 0.03, 0.6} is the reference's).  Waits twice."""
+        out = (mmf_backdated_pose * int(history))()
+        n = C.c_int()
+        check(self.ctx.lib.mmf_tracker_backdate(self.handle, int(label), int(history), batch.handle, out, int(history), C.byref(n)))
+        return [backdated_pose_dict(out[j]) for j in range(n.value)]
+
+    def backdateRows(self, entry):
+        """test accessor: the (p0 [n,3], p1 [n,3]) rows the last backdate() handed the batch object for entry `entry`"""
+        k = min(self.capacity, self.max_keypoints)
+        p0, p1, n = np.zeros((k, 3), np.float32), np.zeros((k, 3), np.float32), C.c_int()
+        check(self.ctx.lib.mmf_tracker_backdate_rows(self.handle, int(entry), p0.ctypes.data, p1.ctypes.data, k, C.byref(n)))
+        return p0[:n.value].copy(), p1[:n.value].copy()
 
     # ----- the models' track sets
     @staticmethod
