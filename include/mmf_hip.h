@@ -696,6 +696,23 @@ int mmf_superpoint_last_launches(mmf_superpoint *sp);
  * cin a multiple of 32; nt = output-channel tiles of 32 per workgroup (1, 2, 4; 0 = automatic). Synchronous. */
 int mmf_superpoint_conv(mmf_ctx *ctx, const float *in, int height, int width, int cin, const float *w,
                         const float *bias, int cout, int taps, int relu, int pool, int nt, float *out);
+/* the post-processing by itself (tests / tools): the code behind the two feature calls above, on maps given from outside.
+ *   mmf_superpoint_set_maps       installs maps as if a forward pass of width x height had produced them.  Exactly one of
+ *                       semi_dev (logits [H/8][W/8][65]; the heat map is then computed from them) and heat_dev ([H][W]);
+ *                       desc_dev [H/8][W/8][256] or NULL (a zero map), L2-normalised per cell when normalize_desc != 0.  DEVICE
+ *                       pointers, copied into the object's own buffers on the context's stream.  Sizes as mmf_superpoint_forward.
+ *                       With heat_dev the logits mmf_superpoint_download(0) returns are unspecified.
+ *   mmf_superpoint_select         mmf_superpoint_get_features without its forward pass (HOST outputs, synchronous).
+ *   mmf_superpoint_select_device  mmf_superpoint_get_features_device without its forward pass; results by
+ *                       mmf_superpoint_last_features, mmf_superpoint_last_launches counts the selection's kernels alone.
+ * Both selections: MMF_ERR_STATE before any maps or forward pass exist.
+ * Contract of a heat map: its values are softmax outputs, that is in [0, 1], +inf or NaN (NaN is never a candidate and never
+ * suppresses).  Negative values and -0.0 are outside it: the ranking (sp_rank_key) orders confidences by bit pattern. */
+int mmf_superpoint_set_maps(mmf_superpoint *sp, int width, int height, const float *semi_dev, const float *heat_dev,
+                            const float *desc_dev, int normalize_desc);
+int mmf_superpoint_select(mmf_superpoint *sp, float conf_thresh, int nms_dist, int border, int *xy, float *conf, float *desc,
+                          int *count);
+int mmf_superpoint_select_device(mmf_superpoint *sp, float conf_thresh, int nms_dist, int border);
 
 /* ---- super-pixel resampling for the segmentation ------------------------------
  * Slic::downsample<float>(image, channel) (Core/Segmentation/Slic.h:48-83), Slic::downsampleThresholded<float>

@@ -226,6 +226,9 @@ SIGNATURES = {
     "mmf_superpoint_last_features": (_i, [_vp, _ip, _ip, _vp, _vp, _vp]),
     "mmf_superpoint_last_launches": (_i, [_vp]),
     "mmf_superpoint_conv": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "mmf_superpoint_set_maps": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i]),
+    "mmf_superpoint_select": (_i, [_vp, _f, _i, _i, _vp, _vp, _vp, _ip]),
+    "mmf_superpoint_select_device": (_i, [_vp, _f, _i, _i]),
     "mmf_slic_downsample": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp]),
     "mmf_slic_downsample_rgb": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "mmf_slic_upsample_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp]),

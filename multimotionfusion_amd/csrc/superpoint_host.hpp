@@ -276,21 +276,15 @@ extern "C" int mmf_superpoint_download(mmf_superpoint* sp, int which, float* hos
     return MMF_OK;
 }
 
-// SuperPoint::getFeatures (Core/MultiMotionFusion.cpp:233).  `image` is a DEVICE pointer (interleaved u8).
-// xy [max_keypoints][2] pixel coordinates, conf [max_keypoints], desc [max_keypoints][256]: HOST arrays,
-// strongest keypoint first; *count = number written.  The caller normalises xy by (width, height)
-// (PointTracker.cpp:40-41).  Synchronous.
-extern "C" int mmf_superpoint_get_features(mmf_superpoint* sp, const uint8_t* image, int width, int height, int channels,
-                                           float conf_thresh, int nms_dist, int border, int* xy, float* conf, float* desc,
-                                           int* count) {
-    MMF_REQUIRE(sp && xy && conf && desc && count, "mmf_superpoint_get_features: null argument");
-    MMF_REQUIRE(nms_dist >= 0 && border >= 0, "mmf_superpoint_get_features: negative radius");
-    int rc = mmf_superpoint_forward(sp, image, width, height, channels);
-    if (rc) return rc;
+// everything of mmf_superpoint_get_features after the forward pass: the host-looped selection on the object's heat and
+// descriptor maps of cur_w x cur_h (mmf_superpoint_get_features and mmf_superpoint_select both run this)
+static int sp_select_host(mmf_superpoint* sp, float conf_thresh, int nms_dist, int border, int* xy, float* conf, float* desc,
+                          int* count) {
     mmf_ctx* c = sp->ctx;
     hipStream_t s = c->stream;
-    const int H = height, W = width, npix = H * W;
+    const int H = sp->cur_h, W = sp->cur_w, npix = H * W;
     using namespace mmf;
+    int rc = MMF_OK;
     hipLaunchKernelGGL(sp_nms_init_kernel, grid1d(npix), dim3(256), 0, s, sp->heat, npix, conf_thresh, sp->state);
     // passes until no candidate is undecided; the strongest undecided candidate always decides, so the loop
     // ends after at most npix passes (a handful on real heat maps); checked every 4 passes
@@ -339,6 +333,20 @@ extern "C" int mmf_superpoint_get_features(mmf_superpoint* sp, const uint8_t* im
     return MMF_OK;
 }
 
+// SuperPoint::getFeatures (Core/MultiMotionFusion.cpp:233).  `image` is a DEVICE pointer (interleaved u8).
+// xy [max_keypoints][2] pixel coordinates, conf [max_keypoints], desc [max_keypoints][256]: HOST arrays,
+// strongest keypoint first; *count = number written.  The caller normalises xy by (width, height)
+// (PointTracker.cpp:40-41).  Synchronous.
+extern "C" int mmf_superpoint_get_features(mmf_superpoint* sp, const uint8_t* image, int width, int height, int channels,
+                                           float conf_thresh, int nms_dist, int border, int* xy, float* conf, float* desc,
+                                           int* count) {
+    MMF_REQUIRE(sp && xy && conf && desc && count, "mmf_superpoint_get_features: null argument");
+    MMF_REQUIRE(nms_dist >= 0 && border >= 0, "mmf_superpoint_get_features: negative radius");
+    int rc = mmf_superpoint_forward(sp, image, width, height, channels);
+    if (rc) return rc;
+    return sp_select_host(sp, conf_thresh, nms_dist, border, xy, conf, desc, count);
+}
+
 // ---- the same without the host: mmf_superpoint_get_features_device -------------------------------------------------
 // Enqueues on the context's stream and returns: no wait, nothing read back, no host memory a second call could overwrite.
 // The launches depend on (width, height) alone: the forward pass, the initialisation, the compaction of the candidates
@@ -347,19 +355,17 @@ extern "C" int mmf_superpoint_get_features(mmf_superpoint* sp, const uint8_t* im
 // overwrites only after the finisher has run.
 static constexpr int kSpFixedPasses = 8;
 
-extern "C" int mmf_superpoint_get_features_device(mmf_superpoint* sp, const uint8_t* image, int width, int height, int channels,
-                                                  float conf_thresh, int nms_dist, int border) {
-    MMF_REQUIRE(sp != nullptr, "mmf_superpoint_get_features_device: null argument");
-    MMF_REQUIRE(nms_dist >= 0 && border >= 0, "mmf_superpoint_get_features_device: negative radius");
-    int rc = mmf_superpoint_forward(sp, image, width, height, channels);
-    if (rc) return rc;
+// everything of mmf_superpoint_get_features_device after the forward pass, on the object's maps of cur_w x cur_h;
+// *launches = the kernels enqueued here (mmf_superpoint_get_features_device and mmf_superpoint_select_device both run this)
+static int sp_select_device(mmf_superpoint* sp, float conf_thresh, int nms_dist, int border, int* launches_out) {
     mmf_ctx* c = sp->ctx;
     hipStream_t s = c->stream;
-    const int H = height, W = width, npix = H * W;
+    const int H = sp->cur_h, W = sp->cur_w, npix = H * W;
     using namespace mmf;
+    int rc = MMF_OK;
     int* count = reinterpret_cast<int*>(&sp->counters[4]);
     int* status = reinterpret_cast<int*>(&sp->counters[5]);
-    int launches = sp->fwd_launches;
+    int launches = 0;
     hipLaunchKernelGGL(sp_nms_init_kernel, grid1d(npix), dim3(256), 0, s, sp->heat, npix, conf_thresh, sp->state);
     hipLaunchKernelGGL(sp_undecided_flag_kernel, grid1d(npix), dim3(256), 0, s, sp->state, npix, sp->flags);
     rc = device_scan(c, sp->flags, (unsigned)npix, sp->prefix, sp->block_sums, &sp->counters[3]);
@@ -382,7 +388,20 @@ extern "C" int mmf_superpoint_get_features_device(mmf_superpoint* sp, const uint
                        (const int*)count, H, W, sp->kp_desc);
     launches += 5 + 2;
     MMF_HIP_TRY(hipGetLastError());
-    sp->last_launches = launches;
+    *launches_out = launches;
+    return MMF_OK;
+}
+
+extern "C" int mmf_superpoint_get_features_device(mmf_superpoint* sp, const uint8_t* image, int width, int height, int channels,
+                                                  float conf_thresh, int nms_dist, int border) {
+    MMF_REQUIRE(sp != nullptr, "mmf_superpoint_get_features_device: null argument");
+    MMF_REQUIRE(nms_dist >= 0 && border >= 0, "mmf_superpoint_get_features_device: negative radius");
+    int rc = mmf_superpoint_forward(sp, image, width, height, channels);
+    if (rc) return rc;
+    int launches = 0;
+    rc = sp_select_device(sp, conf_thresh, nms_dist, border, &launches);
+    if (rc) return rc;
+    sp->last_launches = sp->fwd_launches + launches;
     return MMF_OK;
 }
 
@@ -452,4 +471,54 @@ extern "C" int mmf_superpoint_conv(mmf_ctx* c, const float* in, int height, int 
     }
     (void)hipFree(L.wpack), (void)hipFree(L.bias);
     return rc;
+}
+
+// the post-processing by itself (tests, tools): maps installed as if a forward pass of that size had produced them, then the
+// two selections of mmf_superpoint_get_features / _get_features_device on them.  Exactly one of semi_dev [H/8][W/8][65]
+// (the heat map is then sp_heatmap_kernel's) and heat_dev [H][W]; desc_dev [H/8][W/8][256] or null (a zero map), normalised
+// here when normalize_desc is set.  All DEVICE pointers, copied into the object's own buffers on the context's stream.
+extern "C" int mmf_superpoint_set_maps(mmf_superpoint* sp, int width, int height, const float* semi_dev, const float* heat_dev,
+                                       const float* desc_dev, int normalize_desc) {
+    MMF_REQUIRE(sp != nullptr, "mmf_superpoint_set_maps: null argument");
+    MMF_REQUIRE((semi_dev != nullptr) != (heat_dev != nullptr), "mmf_superpoint_set_maps: exactly one of the logits and the heat map");
+    MMF_REQUIRE(width >= 8 && height >= 8 && width % 8 == 0 && height % 8 == 0,
+                "mmf_superpoint_set_maps: image sides must be multiples of 8");
+    MMF_REQUIRE(width <= sp->max_w && height <= sp->max_h && (size_t)width * height <= (size_t)sp->max_w * sp->max_h,
+                "mmf_superpoint_set_maps: image larger than the object was created for");
+    MMF_HIP_TRY(hipSetDevice(sp->ctx->device));
+    hipStream_t s = sp->ctx->stream;
+    const size_t npix = (size_t)width * height, ncell = npix / 64;
+    if (desc_dev)
+        MMF_HIP_TRY(hipMemcpyAsync(sp->desc, desc_dev, ncell * 256 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    else
+        MMF_HIP_TRY(hipMemsetAsync(sp->desc, 0, ncell * 256 * sizeof(float), s));
+    if (normalize_desc)
+        hipLaunchKernelGGL((mmf::sp_l2_normalize_kernel<256>), dim3(((int)ncell + 3) / 4), dim3(256), 0, s, sp->desc, (int)ncell);
+    if (semi_dev) {
+        MMF_HIP_TRY(hipMemcpyAsync(sp->semi, semi_dev, ncell * 65 * sizeof(float), hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(mmf::sp_heatmap_kernel, dim3(((int)ncell + 3) / 4), dim3(256), 0, s, sp->semi, height / 8, width / 8,
+                           sp->heat);
+    } else {
+        MMF_HIP_TRY(hipMemcpyAsync(sp->heat, heat_dev, npix * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    MMF_HIP_TRY(hipGetLastError());
+    sp->cur_w = width, sp->cur_h = height;
+    return MMF_OK;
+}
+
+extern "C" int mmf_superpoint_select(mmf_superpoint* sp, float conf_thresh, int nms_dist, int border, int* xy, float* conf,
+                                     float* desc, int* count) {
+    MMF_REQUIRE(sp && xy && conf && desc && count, "mmf_superpoint_select: null argument");
+    MMF_REQUIRE(nms_dist >= 0 && border >= 0, "mmf_superpoint_select: negative radius");
+    if (sp->cur_w == 0) return fail(MMF_ERR_STATE, "mmf_superpoint_select: no maps yet");
+    MMF_HIP_TRY(hipSetDevice(sp->ctx->device));
+    return sp_select_host(sp, conf_thresh, nms_dist, border, xy, conf, desc, count);
+}
+
+extern "C" int mmf_superpoint_select_device(mmf_superpoint* sp, float conf_thresh, int nms_dist, int border) {
+    MMF_REQUIRE(sp != nullptr, "mmf_superpoint_select_device: null argument");
+    MMF_REQUIRE(nms_dist >= 0 && border >= 0, "mmf_superpoint_select_device: negative radius");
+    if (sp->cur_w == 0) return fail(MMF_ERR_STATE, "mmf_superpoint_select_device: no maps yet");
+    MMF_HIP_TRY(hipSetDevice(sp->ctx->device));
+    return sp_select_device(sp, conf_thresh, nms_dist, border, &sp->last_launches);
 }

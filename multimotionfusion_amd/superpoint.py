@@ -129,8 +129,52 @@ class SuperPoint:
         return xy[:n.value].copy(), conf[:n.value].copy(), desc[:n.value].copy(), status.value
 
     def lastLaunches(self):
-        """kernel launches of the last getFeaturesDevice"""
+        """kernel launches of the last getFeaturesDevice (of the last selectDevice: the selection's alone)"""
         return self.lib.mmf_superpoint_last_launches(self.handle)
+
+    def _map(self, a, shape):
+        if a is None:
+            return None
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.array(a, np.float32, order="C")).cuda(self.ctx.device)  # (a copy: a may be read-only)
+        assert a.dtype == torch.float32 and a.is_cuda and tuple(a.shape) == shape, (tuple(a.shape), shape)
+        return a.contiguous()
+
+    def setMaps(self, width, height, semi=None, heat=None, desc=None, normalize_desc=False):
+        """(tests, tools) installs maps as if a forward pass of width x height had produced them: exactly one of semi
+        [H/8,W/8,65] and heat [H,W]; desc [H/8,W/8,256] or None (zeros), normalised per cell on request"""
+        W, H = int(width), int(height)
+        semi, heat = self._map(semi, (H // 8, W // 8, 65)), self._map(heat, (H, W))
+        desc = self._map(desc, (H // 8, W // 8, 256))
+        check(self.lib.mmf_superpoint_set_maps(self.handle, W, H, _p(semi) if semi is not None else None,
+                                               _p(heat) if heat is not None else None, _p(desc) if desc is not None else None,
+                                               int(bool(normalize_desc))))
+        self.ctx.synchronize()  # the sources may go now
+
+    def download(self, which, width, height):
+        """0 logits, 1 coarse descriptors, 2 heat map of the installed maps or the last forward pass"""
+        H, W = int(height), int(width)
+        a = np.empty(((H // 8, W // 8, 65), (H // 8, W // 8, 256), (H, W))[which], np.float32)
+        check(self.lib.mmf_superpoint_download(self.handle, which, a.ctypes.data, a.size))
+        return a
+
+    def select(self, conf_thresh=None, nms_dist=None, border=None):
+        """keypoints() without the network, on the installed maps"""
+        xy = np.empty((self.max_keypoints, 2), np.int32)
+        conf = np.empty(self.max_keypoints, np.float32)
+        desc = np.empty((self.max_keypoints, 256), np.float32)
+        n = C.c_int(0)
+        check(self.lib.mmf_superpoint_select(self.handle, self.conf_thresh if conf_thresh is None else float(conf_thresh),
+                                             self.nms_dist if nms_dist is None else int(nms_dist),
+                                             self.border if border is None else int(border), xy.ctypes.data, conf.ctypes.data,
+                                             desc.ctypes.data, C.byref(n)))
+        return xy[:n.value].copy(), conf[:n.value].copy(), desc[:n.value].copy()
+
+    def selectDevice(self, conf_thresh=None, nms_dist=None, border=None):
+        """getFeaturesDevice() without the network, on the installed maps; lastFeatures() fetches the results"""
+        check(self.lib.mmf_superpoint_select_device(self.handle, self.conf_thresh if conf_thresh is None else float(conf_thresh),
+                                                    self.nms_dist if nms_dist is None else int(nms_dist),
+                                                    self.border if border is None else int(border)))
 
     def getFeatures(self, img):
         """SuperPoint::getFeatures as MultiMotionFusion.cpp:233 consumes it: (coordinates [n,2] float64 normalised

@@ -618,6 +618,15 @@ def sp_heatmap(semi):
     return heat
 
 
+def sp_l2_normalize(desc):
+    """desc [..., C] -> a normalised copy (norm = sqrtf of the fmaf chain of squares, x / norm: a zero norm gives NaN)"""
+    out = np.array(desc, np.float32, order="C")
+    C_ = out.shape[-1]
+    lib().orc_sp_l2_normalize.restype = None
+    lib().orc_sp_l2_normalize(_pf(out), out.size // C_, C_)
+    return out
+
+
 def sp_keypoints(heat, conf_thresh=0.015, nms_dist=4, border=4):
     heat = _f(heat)
     H, W = heat.shape
