@@ -353,7 +353,7 @@ static int redetect_activate(mmf_fusion* f, FusionModel* fm, const float pose[16
 static int frame_redetect(mmf_fusion* f, bool* has_new) {
     const bool have_kp = f->rd.kp_next;
     f->rd.kp_next = false;  // (for this frame only)
-    if (!f->rd.on || !(have_kp || f->kp.tracker) || f->inactive.empty() || !f->rd.views || f->rd.views->views.empty()) return MMF_OK;
+    if (!f->rd.on || !(have_kp || f->kp.tracker) || f->inactive.empty() || !f->rd.views || f->rd.views->books.views.empty()) return MMF_OK;
     if (!have_kp) {  // no mmf_fusion_set_keypoints for this frame: the attached tracker's visible set (:428-431)
         int nv = 0;
         int rc = tracker_visible_device(f->kp.tracker, &nv);
@@ -400,41 +400,31 @@ static int frame_redetect(mmf_fusion* f, bool* has_new) {
         total_q += by_label[(size_t)l].size();
     }
     if (sets.empty()) return MMF_OK;
-    int rc = viewstore_stage(vs, total_q);
+    const bool on_device = f->rd.verifier_mode == 1 && vs->ver.verifier;  // the segments' coordinates travel with their descriptors
+    float *q_fill = nullptr, *qc_fill = nullptr;
+    int rc = viewstore_stage(vs, total_q, on_device, &q_fill, &qc_fill);
     if (rc) return rc;
     std::vector<float> coords(total_q * 3);
     for (size_t s = 0; s < sets.size(); ++s) {
-        sets[s].q = vs->q_dev + sets[s].q0 * kRdDim;
+        sets[s].q = vs->query.q.dev.get() + sets[s].q0 * kRdDim;
         const std::vector<int>& idx = by_label[(size_t)set_label[s]];
         for (size_t k = 0; k < idx.size(); ++k) {
-            std::memcpy(vs->q_pin + (sets[s].q0 + k) * kRdDim, f->rd.kp_desc.data() + (size_t)idx[k] * kRdDim, kRdDim * sizeof(float));
+            std::memcpy(q_fill + (sets[s].q0 + k) * kRdDim, f->rd.kp_desc.data() + (size_t)idx[k] * kRdDim, kRdDim * sizeof(float));
             std::memcpy(coords.data() + (sets[s].q0 + k) * 3, f->rd.kp_coord.data() + (size_t)idx[k] * 3, 3 * sizeof(float));
         }
     }
-    MMF_HIP_TRY(hipMemcpyAsync(vs->q_dev, vs->q_pin, total_q * kRdDim * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    const bool on_device = f->rd.verifier_mode == 1 && vs->verifier;
-    if (on_device) {  // the segments' coordinates travel with their descriptors
-        if (total_q * 3 > vs->qc_cap) {  // (every earlier verification has been awaited)
-            if (vs->qc_pin) (void)hipHostFree(vs->qc_pin);
-            (void)hipFree(vs->qc_dev);
-            vs->qc_pin = vs->qc_dev = nullptr, vs->qc_cap = 0;
-            const size_t cap = total_q * 3 + total_q * 3 / 2 + 192;
-            MMF_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&vs->qc_pin), cap * sizeof(float), hipHostMallocDefault));
-            MMF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&vs->qc_dev), cap * sizeof(float)));
-            vs->qc_cap = cap;
-        }
-        std::memcpy(vs->qc_pin, coords.data(), total_q * 3 * sizeof(float));
-        MMF_HIP_TRY(hipMemcpyAsync(vs->qc_dev, vs->qc_pin, total_q * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    }
+    if (on_device) std::memcpy(qc_fill, coords.data(), total_q * 3 * sizeof(float));
+    rc = viewstore_upload_staged(vs, total_q, on_device, c->stream);
+    if (rc) return rc;
     rc = viewstore_enqueue(vs, c->stream, sets.data(), (int)sets.size());
     if (rc) return rc;
     // device verifier: behind the matches of all segments the two verification launches for ALL (segment, inactive model)
     // pairs of the frame, before the one wait.  (No match launched -- a store of empty views: nothing can be found.)
     std::vector<int> asked;
-    const bool verified = on_device && vs->last_launches > 0;
+    const bool verified = on_device && vs->match.last_launches > 0;
     if (verified) {
         std::vector<mmf::RdVerifySet> vsets(sets.size());
-        for (size_t s = 0; s < sets.size(); ++s) vsets[s] = mmf::RdVerifySet{vs->qc_dev + sets[s].q0 * 3, sets[s].nq, (int)sets[s].q0};
+        for (size_t s = 0; s < sets.size(); ++s) vsets[s] = mmf::RdVerifySet{vs->query.qc.dev.get() + sets[s].q0 * 3, sets[s].nq, (int)sets[s].q0};
         for (const FusionModel* im : f->inactive) asked.push_back((int)im->model->id);
         rc = viewstore_enqueue_verify(vs, c->stream, vsets.data(), (int)vsets.size(), asked.data(), (int)asked.size());
         if (rc) return rc;
@@ -442,7 +432,7 @@ static int frame_redetect(mmf_fusion* f, bool* has_new) {
     MMF_HIP_TRY(wait_stream(c->stream));  // wait 2: the matches of every segment against every view (and their verification)
     for (size_t s = 0; s < sets.size(); ++s) {
         const int label = set_label[s];
-        const bool too_large = on_device && sets[s].nq > vs->verifier->max_points;  // verified here, under the verifier's rule
+        const bool too_large = on_device && sets[s].nq > vs->ver.verifier->max_points;  // verified here, under the verifier's rule
         if (too_large) ++f->rd.host_verified;
         for (size_t mi = 0; mi < f->inactive.size();) {
             FusionModel* im = f->inactive[mi];
@@ -450,15 +440,10 @@ static int frame_redetect(mmf_fusion* f, bool* has_new) {
             if (!on_device) {
                 best = viewstore_best(vs, (int)im->model->id, sets[s], coords.data() + sets[s].q0 * 3, kRedetectRansac);
             } else if (too_large) {
-                best = viewstore_best_fresh(vs, (int)im->model->id, sets[s], coords.data() + sets[s].q0 * 3, vs->verifier->cfg);
+                best = viewstore_best_fresh(vs, (int)im->model->id, sets[s], coords.data() + sets[s].q0 * 3, vs->ver.verifier->cfg);
             } else if (verified) {  // the record of (segment, model): a model an earlier segment activated has left the list
                 const size_t a = (size_t)(std::find(asked.begin(), asked.end(), (int)im->model->id) - asked.begin());
-                const mmf::RdRecord& rec = vs->rec_pin[s * asked.size() + a];
-                best.found = rec.found != 0, best.error = rec.error, best.inliers = rec.inliers, best.view = rec.view, best.n_matches = rec.n_matches;
-                for (int r = 0; r < 3; ++r) {
-                    for (int q = 0; q < 3; ++q) best.transformation.R[r * 3 + q] = rec.T[r * 4 + q];
-                    best.transformation.t[r] = rec.T[r * 4 + 3];
-                }
+                best = viewstore_best_of_record(vs->ver.rec.get()[s * asked.size() + a]);
             }
             if (!(best.found && (double)best.error < 0.01 && best.inliers > 5)) {  // :516
                 ++mi;

@@ -636,7 +636,7 @@ extern "C" int mmf_fusion_reset(mmf_fusion* f) {
     f->inactive.clear();
     f->scheduled_deactivation.clear();
     if (f->rd.views)  // the stored views belonged to the models of the map that ends here
-        for (RdView& v : f->rd.views->views) v.model = -1;
+        for (RdView& v : f->rd.views->books.views) v.model = -1;
     f->rd.kp_next = false;
     f->rd.last.clear();
     f->kp.ids.clear(), f->kp.T.clear();

@@ -1035,6 +1035,7 @@ extern "C" int mmf_ransac_batch_estimate(mmf_ransac_batch* b, const float* p0_de
 // ---------------------------------------------------------------------------------------------
 // Keypoint redetection: the view store and Model::getBestMatch (Core/Model/Model.cpp:781-874)
 // ---------------------------------------------------------------------------------------------
+#include "stream_lane.hpp"
 #include "redetect_host.hpp"
 
 // ---------------------------------------------------------------------------------------------
@@ -1641,7 +1642,6 @@ extern "C" int mmf_debug_set_stamps(void* dev_buf) {
 // =============================================================================================
 // Orchestrator: MultiMotionFusion::processFrame / predict (Core/MultiMotionFusion.cpp:207-854, 863-875)
 // =============================================================================================
-#include "stream_lane.hpp"
 #include "fusion_state.hpp"
 #include "fusion_hooks.hpp"
 #include "fusion_keypoints.hpp"

@@ -22,14 +22,14 @@ static int modeldb_model_views(mmf_viewstore* vs, int id, std::vector<int>* coun
     if (!vs) return MMF_OK;
     std::vector<int> which;
     size_t rows = 0;
-    for (size_t v = 0; v < vs->views.size(); ++v)
-        if (vs->views[v].model == id) which.push_back((int)v), rows += (size_t)vs->views[v].rows;
+    for (size_t v = 0; v < vs->books.views.size(); ++v)
+        if (vs->books.views[v].model == id) which.push_back((int)v), rows += (size_t)vs->books.views[v].rows;
     if (which.empty()) return MMF_OK;
     *any = true;
     desc->resize(rows * kRdDim), coord->resize(rows * 3);
     size_t at = 0;
     for (int v : which) {
-        const int n = vs->views[(size_t)v].rows;
+        const int n = vs->books.views[(size_t)v].rows;
         counts->push_back(n);
         if (int rc = mmf_viewstore_download_view(vs, v, n, desc->data() + at * kRdDim, coord->data() + at * 3)) return rc;
         at += (size_t)n;

@@ -1,6 +1,6 @@
 // stream_lane.hpp -- the owners of what the orchestrator creates on the device (events, streams, buffers) and the fork /
 // join protocol of a hook that runs on a stream of its own beside the frame.  Host code only; textually included by
-// mmf_hip.hip in front of fusion_state.hpp.
+// mmf_hip.hip in front of redetect_host.hpp, the first file that uses the owners (the view store's buffers).
 #pragma once
 
 // What the owners share: one handle, move-only, released through Free when it goes.  An empty one owns nothing.
@@ -34,8 +34,9 @@ struct Stream : Owned<hipStream_t, hipStreamDestroy> {  // non-blocking
         if (h_) (void)hipStreamSynchronize(h_);
     }
 };
+using DeviceMem = Owned<void*, hipFree>;  // device memory, whatever it holds
 template <typename T>
-struct DeviceBuf : Owned<void*, hipFree> {  // `count` elements of device memory
+struct DeviceBuf : DeviceMem {  // `count` elements of device memory
     hipError_t create(size_t count) { return reset(), hipMalloc(&h_, count * sizeof(T)); }
     T* get() const { return static_cast<T*>(h_); }
 };

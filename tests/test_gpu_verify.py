@@ -170,3 +170,80 @@ def test_more_query_rows_than_the_verifier_takes(gpu_ctx):
         vs.bestMatchDevice(1, dev(qd), dev(qc))
     assert vs.bestMatchDevice(1, dev(qd[:40]), dev(qc[:40]))["found"]
     vs.close(), small.close()
+
+
+def test_scratch_regrows_and_shrinks_between_calls(gpu_ctx, batch):
+    """3 query rows, then as many as the object gives (every scratch and staging buffer is released and allocated anew,
+    larger), then 3 again (the buffers are reused oversized): each answer equals, bit for bit, the answer of a fresh store
+    that was asked only that"""
+    from multimotionfusion_amd.redetection import ViewStore
+    objs, models = build(7, 3, 511)
+
+    def fresh():
+        vs = ViewStore(gpu_ctx)
+        vs.setVerifier(batch)
+        for mid, views in models.items():
+            assert vs.store(mid, views) is True
+        return vs
+
+    big = min(200, len(ro.make_query(objs[1], 951, subset=0.9)[0]))  # (make_query gives fewer than 200 rows for these objects)
+    assert big >= 4 * 3
+    vs = fresh()
+    for nq in (3, big, 3):
+        qd, qc = query(objs[1], 951, nq)
+        got = vs.bestMatchDevice(1, dev(qd), dev(qc))
+        assert vs.lastLaunches() == 5
+        idx, dist = vs.match(dev(qd))
+        one = fresh()
+        same(got, one.bestMatchDevice(1, dev(qd), dev(qc)), ("bestMatchDevice", nq))
+        one.close()
+        one = fresh()
+        want_idx, want_dist = one.match(dev(qd))
+        one.close()
+        assert idx.shape == (7, nq) and np.array_equal(idx, want_idx), nq
+        assert np.array_equal(dist.view(np.uint32), want_dist.view(np.uint32)), nq
+        if nq == big:
+            assert got["found"] and (idx >= 0).any()
+    vs.close()
+
+
+def test_device_store_across_a_doubling_equals_the_host_store(gpu_ctx, batch):
+    """store, then storeDevice of a model that takes the store past its first 4096 rows (descriptors and coordinates double,
+    the old rows are copied), then storeDevice of a small one: the store equals one that took all three through store"""
+    from multimotionfusion_amd.redetection import ViewStore
+    rng = np.random.default_rng(80)
+    obj1, views1 = object_views(81, 4)
+    filler = [(ro.unit_rows(rng, 100), rng.normal(size=(100, 3)).astype(np.float32)) for _ in range(40)]  # 40 x 128 padded rows
+    obj3, views3 = object_views(83, 5)
+
+    def packed(views):
+        return ([len(d) for d, _ in views], dev(np.concatenate([d for d, _ in views])), dev(np.concatenate([c for _, c in views])))
+
+    mixed, host = ViewStore(gpu_ctx), ViewStore(gpu_ctx)
+    mixed.setVerifier(batch), host.setVerifier(batch)
+    assert mixed.store(1, views1) is True
+    assert mixed.storeDevice(2, *packed(filler)) is True
+    assert mixed.storeDevice(3, *packed(views3)) is True
+    for mid, views in ((1, views1), (2, filler), (3, views3)):
+        assert host.store(mid, views) is True
+
+    def equal_stores():
+        assert mixed.views() == host.views() and len(host.views()) == 4 + 40 + 5
+        for v in range(len(host.views())):
+            (dm, cm), (dh, ch) = mixed.downloadView(v), host.downloadView(v)
+            assert np.array_equal(dm.view(np.uint32), dh.view(np.uint32)) and np.array_equal(cm.view(np.uint32), ch.view(np.uint32)), v
+
+    def equal_answers():
+        for mid, obj in ((1, obj1), (3, obj3)):
+            qd, qc = query(obj, 980 + mid, 64)
+            got = mixed.bestMatchDevice(mid, dev(qd), dev(qc))
+            same(got, host.bestMatchDevice(mid, dev(qd), dev(qc)), mid)
+            if mid == 3:
+                assert got["found"] and got["error"] < 0.01 and got["inliers"] > 5
+
+    equal_stores()
+    equal_answers()
+    assert mixed.storeDevice(2, *packed(filler)) is False  # (Model.cpp:1618-1621) ... and nothing changed
+    equal_stores()
+    equal_answers()
+    mixed.close(), host.close()
