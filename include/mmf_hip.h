@@ -1229,6 +1229,22 @@ int mmf_viewstore_best_match_device(mmf_viewstore *vs, int model_id, const float
 int mmf_fusion_set_redetection_verifier(mmf_fusion *f, int mode);
 int mmf_fusion_redetection_host_verified(mmf_fusion *f);
 int mmf_debug_set_redetect_max_points(int max_points); /* the max_points of verifiers created from now on by the setter above (tests) */
+/* The batch a frame's redetection runs (csrc/redetect_host.hpp: viewstore_batch_run, viewstore_batch_best), for the tests:
+ * n_sets query sets of nq[s] rows, descriptor HOST [sum nq][256] / coordinate HOST [sum nq][3] with the sets behind one
+ * another, against the n_asked models asked[].  rule 0 = host, one engine per (set, model); 1 = the device verifier
+ * (MMF_ERR_STATE without one; a set beyond its max_points is verified by the host core and counted in *host_verified).
+ * records OUT [n_sets * n_asked], pair (s, a) at s * n_asked + a, model_id = asked[a]; inlier OUT (optional)
+ * [n_sets * n_asked][inlier_stride] over the hash-sorted matches, inlier_stride >= the largest set.  Launches as a frame's:
+ * 3 per set, and 2 more under rule 1.  Synchronous. */
+typedef struct {
+    float T[16];
+    float error;
+    int inliers, view, n_matches, found, model_id;
+} mmf_debug_redetect_record;
+int mmf_debug_viewstore_best_match_batch(mmf_viewstore *vs, int n_sets, const int *nq, const float *descriptor,
+                                         const float *coordinate, int n_asked, const int *asked, int rule,
+                                         mmf_debug_redetect_record *records, unsigned char *inlier, int inlier_stride,
+                                         int *host_verified);
 int mmf_debug_hash_float(const float *x, int n, unsigned long long *restated, unsigned long long *libstdcxx);
 int mmf_debug_ransac_core_host(const mmf_ransac_config *cfg, const float *p0, const float *p1, int n, float T[16], float *error,
                                unsigned char *inlier, int *has_inlier);

@@ -102,6 +102,11 @@ class mmf_redetection(C.Structure):
                 ("error", C.c_float), ("inliers", C.c_int), ("view", C.c_int), ("transformation", C.c_float * 16)]
 
 
+class mmf_debug_redetect_record(C.Structure):
+    _fields_ = [("T", C.c_float * 16), ("error", C.c_float), ("inliers", C.c_int), ("view", C.c_int), ("n_matches", C.c_int),
+                ("found", C.c_int), ("model_id", C.c_int)]
+
+
 class mmf_ransac_config(C.Structure):
     _fields_ = [("iterations", C.c_int), ("inlier_threshold", C.c_float), ("inlier_fraction", C.c_float)]
 
@@ -401,6 +406,7 @@ SIGNATURES = {
     "mmf_fusion_set_redetection_verifier": (_i, [_vp, _i]),
     "mmf_fusion_redetection_host_verified": (_i, [_vp]),
     "mmf_debug_set_redetect_max_points": (_i, [_i]),
+    "mmf_debug_viewstore_best_match_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _ip]),
     "mmf_debug_hash_float": (_i, [_vp, _i, _vp, _vp]),
     "mmf_debug_ransac_core_host": (_i, [C.POINTER(mmf_ransac_config), _vp, _vp, _i, _vp, _fp, _vp, _ip]),
     "mmf_debug_rounded_ops": (_i, [_vp, _i, _vp, _vp, _sz, _vp]),

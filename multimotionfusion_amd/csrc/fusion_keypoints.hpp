@@ -390,61 +390,38 @@ static int frame_redetect(mmf_fusion* f, bool* has_new) {
         if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]))) continue;
         by_label[(size_t)l].push_back((int)i);
     }
-    std::vector<RdSet> sets;
+    RdBatch batch;
     std::vector<int> set_label;
     size_t total_q = 0;
     for (int l = 1; l < 255; ++l) {
         if (by_label[(size_t)l].size() < 3) continue;  // min_tracks (:493, :507)
-        sets.push_back(RdSet{nullptr, (int)by_label[(size_t)l].size(), total_q});
+        batch.sets.push_back(RdSet{nullptr, (int)by_label[(size_t)l].size(), total_q});
         set_label.push_back(l);
         total_q += by_label[(size_t)l].size();
     }
-    if (sets.empty()) return MMF_OK;
+    if (batch.sets.empty()) return MMF_OK;
     const bool on_device = f->rd.verifier_mode == 1 && vs->ver.verifier;  // the segments' coordinates travel with their descriptors
-    float *q_fill = nullptr, *qc_fill = nullptr;
-    int rc = viewstore_stage(vs, total_q, on_device, &q_fill, &qc_fill);
-    if (rc) return rc;
-    std::vector<float> coords(total_q * 3);
-    for (size_t s = 0; s < sets.size(); ++s) {
-        sets[s].q = vs->query.q.dev.get() + sets[s].q0 * kRdDim;
-        const std::vector<int>& idx = by_label[(size_t)set_label[s]];
-        for (size_t k = 0; k < idx.size(); ++k) {
-            std::memcpy(q_fill + (sets[s].q0 + k) * kRdDim, f->rd.kp_desc.data() + (size_t)idx[k] * kRdDim, kRdDim * sizeof(float));
-            std::memcpy(coords.data() + (sets[s].q0 + k) * 3, f->rd.kp_coord.data() + (size_t)idx[k] * 3, 3 * sizeof(float));
-        }
-    }
-    if (on_device) std::memcpy(qc_fill, coords.data(), total_q * 3 * sizeof(float));
-    rc = viewstore_upload_staged(vs, total_q, on_device, c->stream);
-    if (rc) return rc;
-    rc = viewstore_enqueue(vs, c->stream, sets.data(), (int)sets.size());
-    if (rc) return rc;
     // device verifier: behind the matches of all segments the two verification launches for ALL (segment, inactive model)
-    // pairs of the frame, before the one wait.  (No match launched -- a store of empty views: nothing can be found.)
-    std::vector<int> asked;
-    const bool verified = on_device && vs->match.last_launches > 0;
-    if (verified) {
-        std::vector<mmf::RdVerifySet> vsets(sets.size());
-        for (size_t s = 0; s < sets.size(); ++s) vsets[s] = mmf::RdVerifySet{vs->query.qc.dev.get() + sets[s].q0 * 3, sets[s].nq, (int)sets[s].q0};
-        for (const FusionModel* im : f->inactive) asked.push_back((int)im->model->id);
-        rc = viewstore_enqueue_verify(vs, c->stream, vsets.data(), (int)vsets.size(), asked.data(), (int)asked.size());
-        if (rc) return rc;
-    }
-    MMF_HIP_TRY(wait_stream(c->stream));  // wait 2: the matches of every segment against every view (and their verification)
-    for (size_t s = 0; s < sets.size(); ++s) {
+    // pairs of the frame, before the one wait (viewstore_batch_run, redetect_host.hpp)
+    if (on_device)
+        for (const FusionModel* im : f->inactive) batch.asked.push_back((int)im->model->id);
+    int rc = viewstore_batch_run(vs, c->stream, &batch, on_device, [&](float* desc, float* coord) {
+        for (size_t s = 0; s < batch.sets.size(); ++s) {
+            const std::vector<int>& idx = by_label[(size_t)set_label[s]];
+            for (size_t k = 0; k < idx.size(); ++k) {
+                std::memcpy(desc + (batch.sets[s].q0 + k) * kRdDim, f->rd.kp_desc.data() + (size_t)idx[k] * kRdDim, kRdDim * sizeof(float));
+                std::memcpy(coord + (batch.sets[s].q0 + k) * 3, f->rd.kp_coord.data() + (size_t)idx[k] * 3, 3 * sizeof(float));
+            }
+        }
+    });  // wait 2: the matches of every segment against every view (and their verification)
+    if (rc) return rc;
+    for (size_t s = 0; s < batch.sets.size(); ++s) {
         const int label = set_label[s];
-        const bool too_large = on_device && sets[s].nq > vs->ver.verifier->max_points;  // verified here, under the verifier's rule
-        if (too_large) ++f->rd.host_verified;
+        if (viewstore_batch_too_large(vs, batch, s)) ++f->rd.host_verified;  // verified here, under the verifier's rule
         for (size_t mi = 0; mi < f->inactive.size();) {
             FusionModel* im = f->inactive[mi];
-            RdBest best;
-            if (!on_device) {
-                best = viewstore_best(vs, (int)im->model->id, sets[s], coords.data() + sets[s].q0 * 3, kRedetectRansac);
-            } else if (too_large) {
-                best = viewstore_best_fresh(vs, (int)im->model->id, sets[s], coords.data() + sets[s].q0 * 3, vs->ver.verifier->cfg);
-            } else if (verified) {  // the record of (segment, model): a model an earlier segment activated has left the list
-                const size_t a = (size_t)(std::find(asked.begin(), asked.end(), (int)im->model->id) - asked.begin());
-                best = viewstore_best_of_record(vs->ver.rec.get()[s * asked.size() + a]);
-            }
+            // (with the device verifier the record of (segment, model): a model an earlier segment activated has left the list)
+            const RdBest best = viewstore_batch_best(vs, batch, s, (int)im->model->id, false);
             if (!(best.found && (double)best.error < 0.01 && best.inliers > 5)) {  // :516
                 ++mi;
                 continue;

@@ -647,3 +647,119 @@ static int viewstore_upload_staged(mmf_viewstore* vs, size_t rows, bool with_coo
     if (with_coords) MMF_HIP_TRY(vs->query.qc.upload(rows * 3, st));
     return MMF_OK;
 }
+
+// ---- a frame's batch: several query sets handed in on the host against several models (frame_redetect) --------
+struct RdBatch {
+    std::vector<RdSet> sets;    // the caller gives nq and q0 (the rows of the sets before it); viewstore_batch_run gives q
+    std::vector<int> asked;     // the models the device verifier picks for, in the caller's order
+    std::vector<float> coords;  // HOST [rows][3], the sets behind one another
+    bool on_device = false;     // the device rule: the coordinates travel too, a set beyond max_points goes to the host core
+    bool verified = false;      // the two verification launches were enqueued: the records are this batch's
+};
+
+// Stages the sets, has fill(desc HOST [rows][256], coord HOST [rows][3]) write their rows, uploads, enqueues the three match
+// launches per set and -- on_device (needs a verifier attached) with models asked for and a match launched -- the two
+// verification launches for all (set, asked model) pairs, and waits for `st`: the one wait of the batch.
+template <class Fill>
+static int viewstore_batch_run(mmf_viewstore* vs, hipStream_t st, RdBatch* b, bool on_device, Fill fill) {
+    size_t rows = 0;
+    for (const RdSet& s : b->sets) rows += (size_t)s.nq;
+    b->on_device = on_device, b->verified = false;
+    b->coords.assign(rows * 3, 0.f);
+    float *q_fill = nullptr, *qc_fill = nullptr;
+    int rc = viewstore_stage(vs, rows, on_device, &q_fill, &qc_fill);
+    if (rc) return rc;
+    for (RdSet& s : b->sets) s.q = vs->query.q.dev.get() + s.q0 * kRdDim;
+    if (rows) {
+        fill(q_fill, b->coords.data());
+        if (on_device) std::memcpy(qc_fill, b->coords.data(), rows * 3 * sizeof(float));
+        rc = viewstore_upload_staged(vs, rows, on_device, st);
+        if (rc) return rc;
+    }
+    rc = viewstore_enqueue(vs, st, b->sets.data(), (int)b->sets.size());
+    if (rc) return rc;
+    // (no match launched -- a store without rows: nothing can be found)
+    if (on_device && vs->match.last_launches > 0 && !b->asked.empty()) {
+        std::vector<mmf::RdVerifySet> vsets(b->sets.size());
+        for (size_t s = 0; s < vsets.size(); ++s)
+            vsets[s] = mmf::RdVerifySet{vs->query.qc.dev.get() + b->sets[s].q0 * 3, b->sets[s].nq, (int)b->sets[s].q0};
+        rc = viewstore_enqueue_verify(vs, st, vsets.data(), (int)vsets.size(), b->asked.data(), (int)b->asked.size());
+        if (rc) return rc;
+        b->verified = true;
+    }
+    MMF_HIP_TRY(wait_stream(st));
+    return MMF_OK;
+}
+
+// set s is verified on the host under the verifier's rule: it has more rows than the verifier takes
+static bool viewstore_batch_too_large(const mmf_viewstore* vs, const RdBatch& b, size_t s) {
+    return b.on_device && b.sets[s].nq > vs->ver.verifier->max_points;
+}
+
+// Model::getBestMatch of `model` for set s of a batch that has run.  The host rule: one engine for the pair.  The device rule:
+// the record of (s, model) -- looked up by the model's id among `asked`, wherever the caller's own list has it by now -- or,
+// for a set too large, the host core per view.  with_flags: the inlier flags of a record too (the host rules always give them).
+static RdBest viewstore_batch_best(const mmf_viewstore* vs, const RdBatch& b, size_t s, int model, bool with_flags) {
+    const float* coordinate = b.coords.data() + b.sets[s].q0 * 3;
+    if (model < 0) return RdBest();  // (forgotten views carry -1: they belong to nobody)
+    if (!b.on_device) return viewstore_best(vs, model, b.sets[s], coordinate, kRedetectRansac);
+    if (viewstore_batch_too_large(vs, b, s)) return viewstore_best_fresh(vs, model, b.sets[s], coordinate, vs->ver.verifier->cfg);
+    const size_t a = (size_t)(std::find(b.asked.begin(), b.asked.end(), model) - b.asked.begin());
+    if (!b.verified || a == b.asked.size()) return RdBest();
+    const size_t r = s * b.asked.size() + a;
+    RdBest best = viewstore_best_of_record(vs->ver.rec.get()[r]);
+    if (with_flags && best.found) {
+        const unsigned char* flags = vs->ver.rec_inlier.get() + r * (size_t)vs->ver.rec_stride;
+        best.inlier.assign(flags, flags + best.n_matches);
+    }
+    return best;
+}
+
+// The batch above through the C ABI, for the tests: every (set, asked model) pair's estimate.  descriptor / coordinate = HOST,
+// the sets behind one another.  rule 0 = the host rule, 1 = the device verifier's (MMF_ERR_STATE without one attached; sets
+// beyond its max_points are verified by the host core and counted in *host_verified).  records [n_sets * n_asked], model_id =
+// the asked id; inlier (optional) [n_sets * n_asked][inlier_stride], inlier_stride >= the largest set.  Synchronous.
+extern "C" int mmf_debug_viewstore_best_match_batch(mmf_viewstore* vs, int n_sets, const int* nq, const float* descriptor,
+                                                    const float* coordinate, int n_asked, const int* asked, int rule,
+                                                    mmf_debug_redetect_record* records, unsigned char* inlier, int inlier_stride,
+                                                    int* host_verified) {
+    MMF_REQUIRE(vs && n_sets >= 0 && n_asked >= 0 && (rule == 0 || rule == 1), "mmf_debug_viewstore_best_match_batch: bad argument");
+    MMF_REQUIRE((nq || n_sets == 0) && (asked || n_asked == 0), "mmf_debug_viewstore_best_match_batch: null table");
+    MMF_REQUIRE(records || n_sets == 0 || n_asked == 0, "mmf_debug_viewstore_best_match_batch: null records");
+    if (rule == 1 && !vs->ver.verifier)
+        return fail(MMF_ERR_STATE, "mmf_debug_viewstore_best_match_batch: no verifier attached (mmf_viewstore_set_verifier)");
+    RdBatch b;
+    size_t rows = 0;
+    int largest = 0;
+    for (int s = 0; s < n_sets; ++s) {
+        MMF_REQUIRE(nq[s] >= 0, "mmf_debug_viewstore_best_match_batch: negative set size");
+        b.sets.push_back(RdSet{nullptr, nq[s], rows});
+        rows += (size_t)nq[s], largest = std::max(largest, nq[s]);
+    }
+    MMF_REQUIRE(rows == 0 || (descriptor && coordinate), "mmf_debug_viewstore_best_match_batch: null descriptors or coordinates");
+    MMF_REQUIRE(!inlier || inlier_stride >= largest, "mmf_debug_viewstore_best_match_batch: inlier_stride below the largest set");
+    b.asked.assign(asked, asked + n_asked);
+    MMF_HIP_TRY(hipSetDevice(vs->ctx->device));
+    int rc = viewstore_batch_run(vs, vs->ctx->stream, &b, rule == 1, [&](float* desc, float* coord) {
+        std::memcpy(desc, descriptor, rows * kRdDim * sizeof(float));
+        std::memcpy(coord, coordinate, rows * 3 * sizeof(float));
+    });
+    if (rc) return rc;
+    if (host_verified) *host_verified = 0;
+    for (size_t s = 0; s < b.sets.size(); ++s) {
+        if (host_verified && viewstore_batch_too_large(vs, b, s)) ++*host_verified;
+        for (size_t a = 0; a < b.asked.size(); ++a) {
+            const RdBest best = viewstore_batch_best(vs, b, s, b.asked[a], true);
+            const size_t r = s * b.asked.size() + a;
+            mmf_debug_redetect_record& rec = records[r];
+            isometry_to_4x4(best.transformation, rec.T);
+            rec.error = best.error, rec.inliers = best.inliers, rec.view = best.view, rec.n_matches = best.n_matches;
+            rec.found = best.found ? 1 : 0, rec.model_id = b.asked[a];
+            if (!inlier) continue;
+            unsigned char* flags = inlier + r * (size_t)inlier_stride;
+            std::memset(flags, 0, (size_t)inlier_stride);
+            for (size_t i = 0; i < best.inlier.size() && (int)i < best.n_matches; ++i) flags[i] = best.inlier[i];
+        }
+    }
+    return MMF_OK;
+}

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._capi import check, fptr, mmf_redetection
+from ._capi import check, fptr, mmf_debug_redetect_record, mmf_redetection
 from .cudafuncs import Context, _p
 
 DIM = 256
@@ -123,6 +123,39 @@ class ViewStore:
                                                            C.byref(view), C.byref(nm), mask.ctypes.data, C.byref(found)))
         return dict(found=bool(found.value), transformation=T, error=err.value, inliers=inl.value, view=view.value,
                     n_matches=nm.value, inlier=mask[:nm.value].astype(bool))
+
+    def bestMatchBatch(self, sets, asked, rule):
+        """the batch a frame's redetection runs (mmf_debug_viewstore_best_match_batch): sets = [(descriptor [n,256],
+        coordinate [n,3])] host arrays, asked = model ids, rule 0 = host (one engine per pair) / 1 = the attached device
+        verifier -> (records[s][a] = the dict of bestMatch with model_id, sets verified by the host core under rule 1)"""
+        nq = np.array([len(d) for d, _ in sets], np.int32)
+        rows = int(nq.sum())
+        desc, coord = np.zeros((rows, DIM), np.float32), np.zeros((rows, 3), np.float32)
+        o = 0
+        for d, c in sets:
+            n = len(d)
+            if n:
+                desc[o:o + n], coord[o:o + n] = np.asarray(d, np.float32).reshape(n, DIM), np.asarray(c, np.float32).reshape(n, 3)
+            o += n
+        ids = np.ascontiguousarray(np.asarray(asked, np.int32).reshape(-1))
+        stride = max(int(nq.max()) if len(nq) else 0, 1)
+        pairs = len(nq) * len(ids)
+        rec = (mmf_debug_redetect_record * max(pairs, 1))()
+        flags = np.zeros((max(pairs, 1), stride), np.uint8)
+        host = C.c_int()
+        check(self.ctx.lib.mmf_debug_viewstore_best_match_batch(self.handle, len(nq), nq.ctypes.data, desc.ctypes.data, coord.ctypes.data,
+                                                                len(ids), ids.ctypes.data, int(rule), C.addressof(rec),
+                                                                flags.ctypes.data, stride, C.byref(host)))
+        out = []
+        for s in range(len(nq)):
+            row = []
+            for a in range(len(ids)):
+                r = rec[s * len(ids) + a]
+                row.append(dict(found=bool(r.found), transformation=np.array(r.T, np.float32).reshape(4, 4), error=r.error,
+                                inliers=r.inliers, view=r.view, n_matches=r.n_matches, model_id=r.model_id,
+                                inlier=flags[s * len(ids) + a, :r.n_matches].astype(bool)))
+            out.append(row)
+        return out, host.value
 
     def close(self):
         if self._own and self.handle and self.ctx.handle:

@@ -1,6 +1,8 @@
 """-m gpu: keypoint redetection inside MultiMotionFusion::processFrame (Core/MultiMotionFusion.cpp:425-436, 489-559) with
 dictated segmentation masks (ground-truth ids of synth.py) and synthetic keypoints: physical points of the object with one
 unit descriptor each (the generator of tests/redetect_oracle.py), their camera-frame coordinates analytic."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -258,6 +260,98 @@ def test_older_newer_rule_and_small_segments(gpu_ctx, orc):
     assert g.getNextModelID() == 4
     del ids
     g.close()
+
+
+N_A = 30  # two_segment_inputs: the keypoints on label 3; label 4 gets every row of its query, more than N_A
+
+
+@functools.lru_cache(maxsize=None)
+def two_segment_inputs():
+    """CPU.  Three objects, models 1, 2 and 3 spawned over frames 1..3; frame 4 carries label 3 only (active [0, 3], inactive
+    [1, 2]); frame 5 carries label 3 on object 3 and the NEW label 4 on object 1.  Models 1 and 2 get the stored views of two
+    objects of tests/redetect_oracle.py, A and B; in frame 5 the keypoints of a query of A lie on label-3 pixels, those of a
+    query of B on label-4 pixels, interleaved.  -> frames, masks [6], new-label flags [6], views A, views B, (xy, coordinate,
+    descriptor) of frame 5"""
+    poses = synth.trajectory(6, seed=21)
+    objs = synth.make_objects(3, seed=21)
+    traj = synth.object_trajectories(objs, 6, seed=21)
+    frames = [synth.render(p, W, H, seed=i, objects=objs, object_poses=[t[i] for t in traj]) for i, p in enumerate(poses)]
+    ids = [f["ids"] for f in frames]
+    masks = [np.zeros((H, W), np.uint8), np.where(ids[1] == 1, 1, 0), np.where(np.isin(ids[2], [1, 2]), ids[2], 0),
+             np.where(np.isin(ids[3], [1, 2, 3]), ids[3], 0), np.where(ids[4] == 3, 3, 0),
+             np.where(ids[5] == 3, 3, np.where(ids[5] == 1, 4, 0))]
+    masks = [m.astype(np.uint8) for m in masks]
+    views, queries = [], []
+    for seed in (3, 11):
+        obj = ro.make_object(seed)
+        tr, po = ro.make_tracks(obj, 7, seed + 100)
+        views.append(ro.views_of(ro.project_first_frame(tr, po)))
+        qd, qc, _, _ = ro.make_query(obj, seed + 200)
+        queries.append((qd, qc))
+    (qd_a, qc_a), (qd_b, qc_b) = (queries[0][0][:N_A], queries[0][1][:N_A]), queries[1]
+    assert len(qd_a) == N_A < len(qd_b)
+    rng = np.random.default_rng(5)
+    xy = []
+    for label, count in ((3, len(qd_a)), (4, len(qd_b))):
+        ys, xs = np.nonzero(masks[5] == label)
+        sel = rng.choice(len(ys), count, replace=False)
+        xy.append(np.stack([xs[sel], ys[sel]], 1).astype(np.int32))
+    order = rng.permutation(len(qd_a) + len(qd_b))
+    kp = (np.concatenate(xy)[order], np.concatenate([qc_a, qc_b])[order], np.concatenate([qd_a, qd_b])[order])
+    return frames, masks, [False, True, True, True, False, True], views[0], views[1], kp
+
+
+def run_two_segments(gpu_ctx, orc, oracle, verifier, max_points=None):
+    """two_segment_inputs through processFrame, against `oracle`.redetect (redetect_oracle: the host rule; verify_oracle: the
+    device verifier's) on frame 5's mask and keypoints.  Segment 3 is served first: it drops the newer model 3 and activates
+    model 1; segment 4 then asks for model 2, by now the first of the inactive list.  -> the store's launches, host-verified"""
+    from multimotionfusion_amd.fusion import MultiMotionFusion
+    frames, masks, new, views_a, views_b, kp = two_segment_inputs()
+    want = oracle.redetect(orc, masks[5], *kp, [0, 3], [(1, views_a), (2, views_b)], True)
+    assert [(e["label"], e["model_id"], e["removed_id"], e["activated"]) for e in want["events"]] == [(3, 1, 3, True), (4, 2, -1, True)]
+    assert want["active_ids"] == [0, 1, 2] and want["inactive_ids"] == [] and want["has_new_label"] is False
+    K = synth.intrinsics(W, H)
+    g = MultiMotionFusion(gpu_ctx, W, H, K["cx"], K["cy"], K["fx"], K["fy"], enable_multiple_models=1)
+    g.setEnableRedetection(True)
+    if verifier:
+        if max_points is not None:
+            assert gpu_ctx.lib.mmf_debug_set_redetect_max_points(max_points) == 0
+        try:
+            g.setRedetectionVerifier(1)
+        finally:
+            gpu_ctx.lib.mmf_debug_set_redetect_max_points(1024)
+    keep = []
+    expect = [([0], []), ([0, 1], []), ([0, 1, 2], []), ([0, 1, 2, 3], []), ([0, 3], [1, 2]), ([0, 1, 2], [])]
+    for i in range(6):
+        ids_now = [m.id for m in g.getModels()]
+        data = model_data(masks[i], frames[i]["depth"], ids_now + ([g.getNextModelID()] if new[i] else [])) if i > 0 else None
+        if i == 5:
+            assert g.storeViews(1, views_a) is True and g.storeViews(2, views_b) is True
+            assert g.getNextModelID() == 4
+            g.setKeypoints(*kp)
+        keep.append((dev(frames[i]["rgb"]), dev(frames[i]["depth"]), dev(masks[i])))
+        g.processFrame(*keep[-1][:2], timestamp=1000 + i, mask=keep[-1][2], hasNewLabel=new[i], modelData=data)
+        assert ([m.id for m in g.getModels()], [m.id for m in g.getInactiveModels()]) == expect[i], i
+    events = g.getLastRedetections()
+    assert len(events) == 2
+    for ev, w in zip(events, want["events"]):
+        best = w["best"]
+        assert (ev["label"], ev["model_id"], ev["removed_id"], ev["activated"]) == (w["label"], w["model_id"], w["removed_id"], w["activated"])
+        assert ev["view"] == best["view"] and ev["inliers"] == best["inliers"], (ev, best)
+        assert np.float32(ev["error"]).view(np.uint32) == np.float32(best["error"]).view(np.uint32), (ev["error"], best["error"])
+        assert np.array_equal(ev["transformation"].view(np.uint32), np.asarray(best["transformation"], np.float32).view(np.uint32))
+    assert g.getNextModelID() == 4  # the new label was cancelled: no model 4
+    models = g.getModels()
+    for m, w in zip(models[1:], want["events"]):
+        assert m.id == w["model_id"] and np.array_equal(m.getPose().view(np.uint32), w["pose"].view(np.uint32)), m.id
+    out = g.getViewStore().lastLaunches(), g.redetectionHostVerified()
+    g.close()
+    return out
+
+
+def test_two_segments_and_two_inactive_models_in_one_frame(gpu_ctx, orc):
+    """the host rule: events, lists, poses and the cancelled label equal the one-engine oracle; 3 launches per segment"""
+    assert run_two_segments(gpu_ctx, orc, ro, False) == (3 * 2, 0)
 
 
 def test_redetection_is_refused_on_a_shard_and_off_by_default(gpu_ctx):

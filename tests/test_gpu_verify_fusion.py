@@ -166,6 +166,19 @@ def test_older_newer_rule_on_the_device(gpu_ctx, orc):
     g.close()
 
 
+def test_two_segments_and_two_inactive_models_in_one_frame_on_the_device(gpu_ctx, orc):
+    """test_gpu_redetect_fusion.run_two_segments with the device verifier: segment 3 activates model 1 -- asked[0] -- and
+    segment 4 then reads model 2's record at asked[1] although model 2 is inactive[0] by then.  Events, lists, poses and the
+    cancelled label equal the per-view oracle; two segments are 3 * 2 match launches and 2 for the verification of all pairs."""
+    assert rf.run_two_segments(gpu_ctx, orc, vo, True) == (3 * 2 + 2, 0)
+
+
+def test_one_segment_on_the_host_core_and_one_on_the_device_in_one_frame(gpu_ctx, orc):
+    """a verifier of 32 points: segment 3 (30 keypoints) is verified on the device, segment 4 (35) by the host core"""
+    assert rf.N_A <= 32 < len(rf.two_segment_inputs()[5][0]) - rf.N_A
+    assert rf.run_two_segments(gpu_ctx, orc, vo, True, max_points=32) == (3 * 2 + 2, 1)
+
+
 def test_the_verifier_is_refused_on_a_shard_and_off_by_default(gpu_ctx):
     from multimotionfusion_amd._capi import MmfError
     from multimotionfusion_amd.fusion import MultiMotionFusion

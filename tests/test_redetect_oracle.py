@@ -96,6 +96,64 @@ def test_decision_block(orc, seed):
         assert not r["events"] and r["has_new_label"] is True
 
 
+def two_label_inputs(seed_a, seed_b, second_shows_a):
+    """labels 3 and 4 side by side; the keypoints on label 3 show object A, those on label 4 object B (or A once more)"""
+    _, _, _, views_a, qd_a, qc_a, _, _ = fixture(seed_a)
+    _, _, _, views_b, qd_b, qc_b, _, _ = fixture(seed_b)
+    if second_shows_a:
+        qd_b, qc_b, _, _ = ro.make_query(ro.make_object(seed_a), seed_a + 250)
+    mask = np.zeros((48, 64), np.uint8)
+    mask[10:40, 5:30], mask[10:40, 35:60] = 3, 4
+    rng = np.random.default_rng(seed_a)
+    xy = np.concatenate([np.stack([rng.integers(5, 30, len(qd_a)), rng.integers(10, 40, len(qd_a))], 1),
+                         np.stack([rng.integers(35, 60, len(qd_b)), rng.integers(10, 40, len(qd_b))], 1)])
+    order = rng.permutation(len(xy))  # the two segments' keypoints interleaved, as a tracker hands them over
+    on_a = (np.arange(len(xy)) < len(qd_a))[order]
+    return mask, xy[order], np.concatenate([qc_a, qc_b])[order], np.concatenate([qd_a, qd_b])[order], views_a, views_b, on_a
+
+
+@pytest.mark.parametrize("rule", ["one engine", "per view"])
+def test_decision_block_two_labels_two_inactive_models(orc, rule):
+    """Active [0, 3], inactive [1, 2] (views of A, views of B), a new label 4.  Expectations written out by hand, for the
+    one-engine oracle and for the per-view one (tests/verify_oracle.py) the device tests lean on."""
+    import verify_oracle as vo
+    oracle = ro if rule == "one engine" else vo
+    # label 3 shows A, label 4 shows B: label 3 drops the newer model 3 for model 1; label 4, not carried by any model,
+    # brings model 2 back although it is by then the FIRST of the inactive list; the new label is cancelled
+    mask, xy, qc, qd, views_a, views_b, on_a = two_label_inputs(3, 11, False)
+    r = oracle.redetect(orc, mask, xy, qc, qd, [0, 3], [(1, views_a), (2, views_b)], True)
+    assert r["active_ids"] == [0, 1, 2] and r["inactive_ids"] == [] and r["has_new_label"] is False
+    assert [(e["label"], e["model_id"], e["removed_id"], e["activated"]) for e in r["events"]] == [(3, 1, 3, True), (4, 2, -1, True)]
+    for ev, sel, views in ((r["events"][0], on_a, views_a), (r["events"][1], ~on_a, views_b)):
+        alone = oracle.get_best_match(orc, qd[sel], qc[sel], views)  # the segment's keypoints in their order, that model's views
+        assert alone["found"] and alone["view"] == ev["best"]["view"] and alone["inliers"] == ev["best"]["inliers"]
+        assert np.array_equal(np.asarray(alone["transformation"], np.float32), np.asarray(ev["best"]["transformation"], np.float32))
+        assert np.array_equal(ev["pose"], ro.inverse_isometry(alone["transformation"]))
+    # the same with the inactive list the other way round: the events keep the labels' order
+    r = oracle.redetect(orc, mask, xy, qc, qd, [0, 3], [(2, views_b), (1, views_a)], True)
+    assert r["active_ids"] == [0, 1, 2] and r["inactive_ids"] == []
+    assert [(e["label"], e["model_id"], e["removed_id"]) for e in r["events"]] == [(3, 1, 3), (4, 2, -1)]
+    # both labels show A: label 3 takes model 1 out of the list label 4 iterates, so label 4 -- whose keypoints would match
+    # model 1 -- has only model 2 left to ask and finds nothing; model 2 stays inactive
+    mask, xy, qc, qd, views_a, views_b, on_a = two_label_inputs(3, 11, True)
+    assert oracle.get_best_match(orc, qd[~on_a], qc[~on_a], views_a)["found"]
+    r = oracle.redetect(orc, mask, xy, qc, qd, [0, 3], [(1, views_a), (2, views_b)], True)
+    assert r["active_ids"] == [0, 1] and r["inactive_ids"] == [2] and r["has_new_label"] is False
+    assert [(e["label"], e["model_id"], e["removed_id"], e["activated"]) for e in r["events"]] == [(3, 1, 3, True)]
+    # ... and with model 1 still there (nothing on label 3) label 4 does take it
+    r = oracle.redetect(orc, mask, xy[~on_a], qc[~on_a], qd[~on_a], [0, 3], [(1, views_a), (2, views_b)], True)
+    assert r["active_ids"] == [0, 3, 1] and r["inactive_ids"] == [2]
+    assert [(e["label"], e["model_id"], e["removed_id"], e["activated"]) for e in r["events"]] == [(4, 1, -1, True)]
+
+
+def test_the_batch_cases_are_what_their_gpu_tests_need(orc):
+    """tests/redetect_batch_cases.py under the oracle alone: found and not-found pairs, both models found, the set too large
+    for a verifier of 40 points found, and the three 70-view layouts won by the view each is built for"""
+    import redetect_batch_cases as bc
+    bc.check_batch_conditions(orc)
+    assert sorted(bc.chunk_layouts(orc)) == ["a", "b", "c"]
+
+
 @pytest.mark.parametrize("seed", SEEDS)
 def test_host_mirror_bookkeeping(seed):
     """ModelTracks: updateTracks, the pose list, computeTrackProjectionFirstFrame, store-once, activate"""
