@@ -655,6 +655,19 @@ typedef struct mmf_superpoint mmf_superpoint;
 int mmf_superpoint_create(mmf_ctx *ctx, const float *const *weights, int max_width, int max_height,
                           int max_keypoints, mmf_superpoint **out);
 void mmf_superpoint_destroy(mmf_superpoint *sp);
+/* The precision of the forward pass is a property of the object.  MMF_SP_F32: the path above, and what
+ * mmf_superpoint_create makes.  MMF_SP_F16: conv1a keeps f32 weights and arithmetic and stores f16; the weights of every
+ * other layer are rounded to f16 (nearest, ties to even) when they are packed, activations between layers are f16, every
+ * output has one f32 accumulator on v_mfma_f32_32x32x16_f16 (csrc/superpoint_f16_kernels.hpp); logits and descriptors
+ * leave the two 1x1 heads as f32, and everything behind them is the same code on the same buffers.  A weight of conv1b ...
+ * convDb that is not finite, or not finite after the rounding (|w| >= 65520), makes an f16 creation MMF_ERR_INVALID.
+ * With precision MMF_SP_F32, mmf_superpoint_create_ex is mmf_superpoint_create. */
+enum { MMF_SP_F32 = 0, MMF_SP_F16 = 1 };
+int mmf_superpoint_create_ex(mmf_ctx *ctx, const float *const *weights, int max_width, int max_height,
+                             int max_keypoints, int precision, mmf_superpoint **out);
+int mmf_superpoint_precision(mmf_superpoint *sp); /* MMF_SP_F32 / MMF_SP_F16; -1 for NULL */
+/* the rounding of that packing: src[n] f32 -> dst[n] f16 bits, nearest-even, |x| >= 65520 to inf, NaN kept.  Host only. */
+int mmf_f16_round(const float *src, size_t n, uint16_t *dst);
 /* the network alone: image = DEVICE pointer to interleaved u8 (1 = grey, 3 / 4 = RGB[A]); leaves the detector
  * logits [H/8][W/8][65], the normalised coarse descriptors [H/8][W/8][256] and the heat map [H][W] on the
  * device.  Asynchronous on the context's stream. */
@@ -696,6 +709,16 @@ int mmf_superpoint_last_launches(mmf_superpoint *sp);
  * cin a multiple of 32; nt = output-channel tiles of 32 per workgroup (1, 2, 4; 0 = automatic). Synchronous. */
 int mmf_superpoint_conv(mmf_ctx *ctx, const float *in, int height, int width, int cin, const float *w,
                         const float *bias, int cout, int taps, int relu, int pool, int nt, float *out);
+/* one layer of the f16 path (tests / tools): in [H][W][cin] f16 bits on the device; w, bias f32 on the HOST, w rounded as an
+ * f16 creation rounds it (and refused like there); out f16 bits or, with out_is_f32, the unrounded f32 value (the two 1x1
+ * heads).  Sizes, taps, nt and refusals as mmf_superpoint_conv.  Synchronous. */
+int mmf_superpoint_conv_f16(mmf_ctx *ctx, const uint16_t *in, int height, int width, int cin, const float *w,
+                            const float *bias, int cout, int taps, int relu, int pool, int nt, int out_is_f32, void *out);
+/* (tests / tools) the first `layers` launches of mmf_superpoint_forward -- 1 = conv1a, 2 = conv1b + pool, 3 = conv2a, 4 = conv2b +
+ * pool, 5 = conv3a, 6 = conv3b + pool, 7 = conv4a, 8 = conv4b, 9 = convPa | convDa -- and that launch's output [h][w][cout] copied
+ * to the HOST: f16 bits on an MMF_SP_F16 object, f32 on an MMF_SP_F32 one; bytes = its exact size.  Synchronous. */
+int mmf_debug_superpoint_forward_prefix(mmf_superpoint *sp, const uint8_t *image, int width, int height, int channels,
+                                        int layers, void *host_out, size_t bytes);
 /* the post-processing by itself (tests / tools): the code behind the two feature calls above, on maps given from outside.
  *   mmf_superpoint_set_maps       installs maps as if a forward pass of width x height had produced them.  Exactly one of
  *                       semi_dev (logits [H/8][W/8][65]; the heat map is then computed from them) and heat_dev ([H][W]);

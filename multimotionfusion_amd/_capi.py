@@ -221,6 +221,11 @@ SIGNATURES = {
     "mmf_model_synthesize_depth": (_i, [_vp, _f, _f, _i, _i, _i]),
     "mmf_match_descriptors": (_i, [_vp, _vp, _i, _vp, _i, _i, _f, _vp, _vp]),
     "mmf_superpoint_create": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_vp)]),
+    "mmf_superpoint_create_ex": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_vp)]),
+    "mmf_superpoint_precision": (_i, [_vp]),
+    "mmf_f16_round": (_i, [_vp, _sz, _vp]),
+    "mmf_superpoint_conv_f16": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "mmf_debug_superpoint_forward_prefix": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz]),
     "mmf_superpoint_destroy": (None, [_vp]),
     "mmf_superpoint_forward": (_i, [_vp, _vp, _i, _i, _i]),
     "mmf_superpoint_download": (_i, [_vp, _i, _vp, _sz]),

@@ -17,10 +17,15 @@
 class SuperPoint {
    public:
     // weights[24]: {w, b} of conv1a conv1b conv2a conv2b conv3a conv3b conv4a conv4b convPa convPb convDa convDb
-    SuperPoint(mmf::Context& ctx, const float* const* weights, int max_width, int max_height, int max_keypoints = 4096) {
-        mmf::check(mmf_superpoint_create(ctx.get(), weights, max_width, max_height, max_keypoints, &sp_), "mmf_superpoint_create");
+    // precision: F32 (the default) or F16 -- f16 operands, f32 accumulation; keypoints and descriptors stay f32
+    enum Precision { F32 = MMF_SP_F32, F16 = MMF_SP_F16 };
+    SuperPoint(mmf::Context& ctx, const float* const* weights, int max_width, int max_height, int max_keypoints = 4096,
+               Precision precision = F32) {
+        mmf::check(mmf_superpoint_create_ex(ctx.get(), weights, max_width, max_height, max_keypoints, (int)precision, &sp_),
+                   "mmf_superpoint_create_ex");
         max_kp_ = max_keypoints;
     }
+    Precision precision() const { return (Precision)mmf_superpoint_precision(sp_); }
     ~SuperPoint() { mmf_superpoint_destroy(sp_); }
     SuperPoint(const SuperPoint&) = delete;
     SuperPoint& operator=(const SuperPoint&) = delete;

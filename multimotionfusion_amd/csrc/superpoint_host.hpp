@@ -33,7 +33,8 @@ static std::vector<float> sp_pack_weights(const float* w, int cin, int cout, int
 struct SpLayer {
     int cin = 0, cout = 0, taps = 9, nt = 1;
     bool pool = false, relu = true;
-    float* wpack = nullptr;
+    float* wpack = nullptr;       // f32 objects
+    uint16_t* wpack16 = nullptr;  // f16 objects (sp_pack_weights_f16)
     float* bias = nullptr;
 };
 
@@ -89,9 +90,12 @@ static void sp_launch_head_pair(hipStream_t s, const SpConvArgs& a, const SpConv
 
 }  // namespace mmf
 
+#include "superpoint_f16_host.hpp"
+
 struct mmf_superpoint {
     mmf_ctx* ctx = nullptr;
     int max_w = 0, max_h = 0, max_kp = 0;
+    int precision = MMF_SP_F32;  // MMF_SP_F16: act0 / act1 / head hold f16, the layers' weights are wpack16
     float *w1a = nullptr, *b1a = nullptr;  // conv1a: [9][64] + [64]
     // conv1b conv2a conv2b conv3a conv3b conv4a conv4b, {convPa | convDa} fused (512 outputs), convPb, convDb
     mmf::SpLayer L[10];
@@ -117,12 +121,32 @@ static int sp_upload(float** dst, const float* src, size_t n, hipStream_t s) {
     return MMF_OK;
 }
 
+static int sp_upload_f16(uint16_t** dst, const uint16_t* src, size_t n, hipStream_t s) {
+    MMF_HIP_TRY(hipMalloc(dst, n * sizeof(uint16_t)));
+    MMF_HIP_TRY(hipMemcpyAsync(*dst, src, n * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    MMF_HIP_TRY(hipStreamSynchronize(s));  // src may be a temporary
+    return MMF_OK;
+}
+
+// the f16 form of a layer's weights: every one of them must be finite after the rounding
+static int sp_upload_weights_f16(mmf::SpLayer& L, const float* w, const char* who, hipStream_t s) {
+    const size_t n = (size_t)L.cout * L.cin * L.taps;
+    for (size_t k = 0; k < n; ++k)
+        if (!mmf::sp_f16_finite(w[k])) return fail(MMF_ERR_INVALID, std::string(who) + ": a weight is not finite in f16");
+    const std::vector<uint16_t> packed = mmf::sp_pack_weights_f16(w, L.cin, L.cout, L.taps, L.nt);
+    return sp_upload_f16(&L.wpack16, packed.data(), packed.size(), s);
+}
+
 static int sp_make_layer(mmf::SpLayer& L, const float* w, const float* b, int cin, int cout, int taps, bool pool, bool relu, int H,
-                         int W, hipStream_t s) {
+                         int W, int precision, hipStream_t s) {
     L.cin = cin, L.cout = cout, L.taps = taps, L.pool = pool, L.relu = relu;
     L.nt = mmf::sp_choose_nt(H, W, cout);
-    const std::vector<float> packed = mmf::sp_pack_weights(w, cin, cout, taps, L.nt);
-    if (int rc = sp_upload(&L.wpack, packed.data(), packed.size(), s)) return rc;
+    if (precision == MMF_SP_F16) {
+        if (int rc = sp_upload_weights_f16(L, w, "mmf_superpoint_create_ex", s)) return rc;
+    } else {
+        const std::vector<float> packed = mmf::sp_pack_weights(w, cin, cout, taps, L.nt);
+        if (int rc = sp_upload(&L.wpack, packed.data(), packed.size(), s)) return rc;
+    }
     return sp_upload(&L.bias, b, (size_t)cout, s);
 }
 
@@ -131,15 +155,16 @@ extern "C" void mmf_superpoint_destroy(mmf_superpoint* sp) {
     (void)hipSetDevice(sp->ctx->device);
     (void)hipStreamSynchronize(sp->ctx->stream);
     (void)hipFree(sp->w1a), (void)hipFree(sp->b1a);
-    for (auto& L : sp->L) (void)hipFree(L.wpack), (void)hipFree(L.bias);
+    for (auto& L : sp->L) (void)hipFree(L.wpack), (void)hipFree(L.wpack16), (void)hipFree(L.bias);
     (void)hipFree(sp->slab);
     (void)hipHostFree(sp->host_counters);
     delete sp;
 }
 
-extern "C" int mmf_superpoint_create(mmf_ctx* c, const float* const* weights, int max_width, int max_height, int max_keypoints,
-                                     mmf_superpoint** out) {
+extern "C" int mmf_superpoint_create_ex(mmf_ctx* c, const float* const* weights, int max_width, int max_height, int max_keypoints,
+                                        int precision, mmf_superpoint** out) {
     MMF_REQUIRE(c && weights && out, "mmf_superpoint_create: null argument");
+    MMF_REQUIRE(precision == MMF_SP_F32 || precision == MMF_SP_F16, "mmf_superpoint_create_ex: precision must be MMF_SP_F32 or MMF_SP_F16");
     for (int i = 0; i < 24; ++i) MMF_REQUIRE(weights[i] != nullptr, "mmf_superpoint_create: 24 weight arrays expected");
     MMF_REQUIRE(max_width >= 8 && max_height >= 8 && max_width % 8 == 0 && max_height % 8 == 0,
                 "mmf_superpoint_create: image sides must be multiples of 8");
@@ -148,6 +173,7 @@ extern "C" int mmf_superpoint_create(mmf_ctx* c, const float* const* weights, in
     mmf_superpoint* sp = new (std::nothrow) mmf_superpoint();
     MMF_REQUIRE(sp != nullptr, "mmf_superpoint_create: out of host memory");
     sp->ctx = c, sp->max_w = max_width, sp->max_h = max_height, sp->max_kp = max_keypoints;
+    sp->precision = precision;
     int rc = MMF_OK;
     auto guard = [&](int r) {
         if (r && !rc) rc = r;
@@ -166,17 +192,17 @@ extern "C" int mmf_superpoint_create(mmf_ctx* c, const float* const* weights, in
     static const bool pool[7] = {true, false, true, false, true, false, false};
     for (int l = 0; l < 7 && !rc; ++l)
         guard(sp_make_layer(sp->L[l], weights[2 * (l + 1)], weights[2 * (l + 1) + 1], cin[l], cout[l], 9, pool[l], true,
-                            H >> shift[l], W >> shift[l], c->stream));
+                            H >> shift[l], W >> shift[l], precision, c->stream));
     if (!rc) {  // detector and descriptor 3x3 heads read the same input: one launch with 512 outputs
         std::vector<float> w((size_t)512 * 128 * 9), b(512);
         std::memcpy(w.data(), weights[16], sizeof(float) * 256 * 128 * 9);
         std::memcpy(w.data() + (size_t)256 * 128 * 9, weights[20], sizeof(float) * 256 * 128 * 9);
         std::memcpy(b.data(), weights[17], sizeof(float) * 256);
         std::memcpy(b.data() + 256, weights[21], sizeof(float) * 256);
-        guard(sp_make_layer(sp->L[7], w.data(), b.data(), 128, 512, 9, false, true, H >> 3, W >> 3, c->stream));
+        guard(sp_make_layer(sp->L[7], w.data(), b.data(), 128, 512, 9, false, true, H >> 3, W >> 3, precision, c->stream));
     }
-    if (!rc) guard(sp_make_layer(sp->L[8], weights[18], weights[19], 256, 65, 1, false, false, H >> 3, W >> 3, c->stream));
-    if (!rc) guard(sp_make_layer(sp->L[9], weights[22], weights[23], 256, 256, 1, false, false, H >> 3, W >> 3, c->stream));
+    if (!rc) guard(sp_make_layer(sp->L[8], weights[18], weights[19], 256, 65, 1, false, false, H >> 3, W >> 3, precision, c->stream));
+    if (!rc) guard(sp_make_layer(sp->L[9], weights[22], weights[23], 256, 256, 1, false, false, H >> 3, W >> 3, precision, c->stream));
 
     const size_t npix = (size_t)H * W, ncell = npix / 64;
     size_t off = 0;
@@ -185,8 +211,9 @@ extern "C" int mmf_superpoint_create(mmf_ctx* c, const float* const* weights, in
         off = align_up(off + bytes, 256);
         return at;
     };
-    const size_t o_act0 = carve(npix * 64 * 4), o_act1 = carve(npix / 4 * 64 * 4);
-    const size_t o_head = carve(ncell * 512 * 4), o_semi = carve(ncell * 65 * 4), o_desc = carve(ncell * 256 * 4);
+    const size_t esz = precision == MMF_SP_F16 ? 2 : 4;  // bytes per activation between the layers
+    const size_t o_act0 = carve(npix * 64 * esz), o_act1 = carve(npix / 4 * 64 * esz);
+    const size_t o_head = carve(ncell * 512 * esz), o_semi = carve(ncell * 65 * 4), o_desc = carve(ncell * 256 * 4);
     const size_t o_heat = carve(npix * 4), o_state = carve(npix);
     const size_t o_flags = carve(npix * 4), o_prefix = carve(npix * 4);
     const size_t o_bsum = carve(((npix + mmf::kScanTile - 1) / mmf::kScanTile + 1) * 4), o_cnt = carve(64);
@@ -223,31 +250,85 @@ extern "C" int mmf_superpoint_create(mmf_ctx* c, const float* const* weights, in
     return MMF_OK;
 }
 
-// the network: image -> semi [H/8][W/8][65], desc [H/8][W/8][256] (normalised), heat [H][W]; all on the device
-extern "C" int mmf_superpoint_forward(mmf_superpoint* sp, const uint8_t* image, int width, int height, int channels) {
+extern "C" int mmf_superpoint_create(mmf_ctx* c, const float* const* weights, int max_width, int max_height, int max_keypoints,
+                                     mmf_superpoint** out) {
+    return mmf_superpoint_create_ex(c, weights, max_width, max_height, max_keypoints, MMF_SP_F32, out);
+}
+
+extern "C" int mmf_superpoint_precision(mmf_superpoint* sp) { return sp ? sp->precision : -1; }
+
+// the nine launches in front of the 1x1 heads.  Launch k (1-based) runs layer `layer` (-1: conv1a) at (H, W) >> shift
+// from buffer `in` into buffer `out` (0 act0, 1 act1, 2 head), whose rows hold `cout` channels
+struct SpStage {
+    int layer, in, out, shift, cin, cout, out_shift;
+};
+static const SpStage kSpStages[9] = {
+    {-1, -1, 0, 0, 1, 64, 0},    // conv1a
+    {0, 0, 1, 0, 64, 64, 1},     // conv1b + pool
+    {1, 1, 0, 1, 64, 64, 1},     // conv2a
+    {2, 0, 1, 1, 64, 64, 2},     // conv2b + pool
+    {3, 1, 0, 2, 64, 128, 2},    // conv3a
+    {4, 0, 1, 2, 128, 128, 3},   // conv3b + pool
+    {5, 1, 0, 3, 128, 128, 3},   // conv4a
+    {6, 0, 1, 3, 128, 128, 3},   // conv4b
+    {7, 1, 2, 3, 128, 512, 3},   // convPa | convDa
+};
+
+static int sp_check_image(const mmf_superpoint* sp, const uint8_t* image, int width, int height, int channels) {
     MMF_REQUIRE(sp && image, "mmf_superpoint_forward: null argument");
     MMF_REQUIRE(channels == 1 || channels == 3 || channels == 4, "mmf_superpoint_forward: 1, 3 or 4 channels");
     MMF_REQUIRE(width >= 8 && height >= 8 && width % 8 == 0 && height % 8 == 0,
                 "mmf_superpoint_forward: image sides must be multiples of 8");
     MMF_REQUIRE(width <= sp->max_w && height <= sp->max_h && (size_t)width * height <= (size_t)sp->max_w * sp->max_h,
                 "mmf_superpoint_forward: image larger than the object was created for");
+    return MMF_OK;
+}
+
+// enqueues the first `layers` of those launches, in the object's precision
+static void sp_enqueue_stages(mmf_superpoint* sp, const uint8_t* image, int W, int H, int channels, int layers) {
+    using namespace mmf;
+    hipStream_t s = sp->ctx->stream;
+    float* const buf[3] = {sp->act0, sp->act1, sp->head};
+    const bool f16 = sp->precision == MMF_SP_F16;
+    for (int k = 0; k < layers; ++k) {
+        const SpStage& g = kSpStages[k];
+        const int h = H >> g.shift, w = W >> g.shift;
+        if (g.layer < 0) {
+            if (f16)
+                hipLaunchKernelGGL(sp_conv1a_f16_kernel, grid1d((size_t)H * W * 4), dim3(256), 0, s, image, channels, H, W, sp->w1a,
+                                   sp->b1a, reinterpret_cast<_Float16*>(buf[g.out]));
+            else
+                hipLaunchKernelGGL(sp_conv1a_kernel, grid1d((size_t)H * W * 4), dim3(256), 0, s, image, channels, H, W, sp->w1a,
+                                   sp->b1a, buf[g.out]);
+        } else if (f16) {
+            sp_launch_conv_f16(s, sp->L[g.layer], reinterpret_cast<const _Float16*>(buf[g.in]), g.cin, buf[g.out], g.cout, h, w, false);
+        } else {
+            sp_launch_conv(s, sp->L[g.layer], buf[g.in], g.cin, buf[g.out], g.cout, h, w);
+        }
+    }
+}
+
+// the network: image -> semi [H/8][W/8][65], desc [H/8][W/8][256] (normalised), heat [H][W]; all on the device
+extern "C" int mmf_superpoint_forward(mmf_superpoint* sp, const uint8_t* image, int width, int height, int channels) {
+    if (int rc = sp_check_image(sp, image, width, height, channels)) return rc;
     mmf_ctx* c = sp->ctx;
     MMF_HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int H = height, W = width, npix = H * W;
     using namespace mmf;
-    hipLaunchKernelGGL(sp_conv1a_kernel, grid1d((size_t)npix * 4), dim3(256), 0, s, image, channels, H, W, sp->w1a, sp->b1a,
-                       sp->act0);
-    sp_launch_conv(s, sp->L[0], sp->act0, 64, sp->act1, 64, H, W);              // conv1b + pool
-    sp_launch_conv(s, sp->L[1], sp->act1, 64, sp->act0, 64, H / 2, W / 2);      // conv2a
-    sp_launch_conv(s, sp->L[2], sp->act0, 64, sp->act1, 64, H / 2, W / 2);      // conv2b + pool
-    sp_launch_conv(s, sp->L[3], sp->act1, 64, sp->act0, 128, H / 4, W / 4);     // conv3a
-    sp_launch_conv(s, sp->L[4], sp->act0, 128, sp->act1, 128, H / 4, W / 4);    // conv3b + pool
-    sp_launch_conv(s, sp->L[5], sp->act1, 128, sp->act0, 128, H / 8, W / 8);    // conv4a
-    sp_launch_conv(s, sp->L[6], sp->act0, 128, sp->act1, 128, H / 8, W / 8);    // conv4b
-    sp_launch_conv(s, sp->L[7], sp->act1, 128, sp->head, 512, H / 8, W / 8);    // convPa | convDa
-    sp->fwd_launches = 11 + ((sp->L[8].nt == 1 && sp->L[9].nt == 1) ? 1 : 2);  // conv1a, these eight, the heads, two below
-    if (sp->L[8].nt == 1 && sp->L[9].nt == 1) {  // convPb + convDb: one launch
+    sp_enqueue_stages(sp, image, W, H, channels, 9);
+    const bool paired = sp->L[8].nt == 1 && sp->L[9].nt == 1;  // convPb + convDb: one launch
+    sp->fwd_launches = 11 + (paired ? 1 : 2);                 // conv1a, the eight 3x3 layers, the heads, two below
+    if (sp->precision == MMF_SP_F16) {  // f16 in, f32 logits and descriptors out
+        const _Float16* head = reinterpret_cast<const _Float16*>(sp->head);
+        if (paired) {
+            sp_launch_head_pair_f16(s, sp_conv_args_f16(sp->L[8], head, 512, sp->semi, 65, H / 8, W / 8),
+                                    sp_conv_args_f16(sp->L[9], head + 256, 512, sp->desc, 256, H / 8, W / 8));
+        } else {
+            sp_launch_conv_f16(s, sp->L[8], head, 512, sp->semi, 65, H / 8, W / 8, true);         // convPb
+            sp_launch_conv_f16(s, sp->L[9], head + 256, 512, sp->desc, 256, H / 8, W / 8, true);  // convDb
+        }
+    } else if (paired) {
         sp_launch_head_pair(s, sp_conv_args(sp->L[8], sp->head, 512, sp->semi, 65, H / 8, W / 8),
                             sp_conv_args(sp->L[9], sp->head + 256, 512, sp->desc, 256, H / 8, W / 8));
     } else {
@@ -259,6 +340,27 @@ extern "C" int mmf_superpoint_forward(mmf_superpoint* sp, const uint8_t* image, 
     hipLaunchKernelGGL(sp_heatmap_kernel, dim3((ncell + 3) / 4), dim3(256), 0, s, sp->semi, H / 8, W / 8, sp->heat);
     MMF_HIP_TRY(hipGetLastError());
     sp->cur_w = W, sp->cur_h = H;
+    return MMF_OK;
+}
+
+// (tests, tools) the first `layers` launches of the forward pass -- 1 = conv1a, 2 = conv1b + pool, ... 9 = the fused 3x3
+// head -- and that launch's output on the host: [h][w][cout] in the object's precision (f16 bits or f32), `bytes` its exact
+// size.  Synchronous; the maps of an earlier forward pass stay as they are
+extern "C" int mmf_debug_superpoint_forward_prefix(mmf_superpoint* sp, const uint8_t* image, int width, int height, int channels,
+                                                   int layers, void* host_out, size_t bytes) {
+    if (int rc = sp_check_image(sp, image, width, height, channels)) return rc;
+    MMF_REQUIRE(host_out != nullptr, "mmf_debug_superpoint_forward_prefix: null argument");
+    MMF_REQUIRE(layers >= 1 && layers <= 9, "mmf_debug_superpoint_forward_prefix: layers must be in 1..9");
+    const SpStage& g = kSpStages[layers - 1];
+    const size_t esz = sp->precision == MMF_SP_F16 ? 2 : 4;
+    const size_t n = (size_t)(height >> g.out_shift) * (size_t)(width >> g.out_shift) * g.cout * esz;
+    MMF_REQUIRE(bytes == n, "mmf_debug_superpoint_forward_prefix: bad size");
+    MMF_HIP_TRY(hipSetDevice(sp->ctx->device));
+    sp_enqueue_stages(sp, image, width, height, channels, layers);
+    MMF_HIP_TRY(hipGetLastError());
+    const float* const buf[3] = {sp->act0, sp->act1, sp->head};
+    MMF_HIP_TRY(hipMemcpyAsync(host_out, buf[g.out], n, hipMemcpyDeviceToHost, sp->ctx->stream));
+    MMF_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
     return MMF_OK;
 }
 
@@ -470,6 +572,32 @@ extern "C" int mmf_superpoint_conv(mmf_ctx* c, const float* in, int height, int 
         if (e != hipSuccess) rc = fail(MMF_ERR_HIP, std::string("mmf_superpoint_conv: ") + hipGetErrorString(e));
     }
     (void)hipFree(L.wpack), (void)hipFree(L.bias);
+    return rc;
+}
+
+// the same for one f16 layer: in [H][W][cin] f16 on the device, w (f32, rounded here as creation rounds it) and bias on the
+// HOST, out f16 or, with out_is_f32, the unrounded f32 value
+extern "C" int mmf_superpoint_conv_f16(mmf_ctx* c, const uint16_t* in, int height, int width, int cin, const float* w,
+                                       const float* bias, int cout, int taps, int relu, int pool, int nt, int out_is_f32, void* out) {
+    MMF_REQUIRE(c && in && w && bias && out, "mmf_superpoint_conv_f16: null argument");
+    MMF_REQUIRE(taps == 9 || taps == 1, "mmf_superpoint_conv_f16: 3x3 or 1x1");
+    MMF_REQUIRE(cin > 0 && cin % 32 == 0 && cout > 0, "mmf_superpoint_conv_f16: cin must be a multiple of 32");
+    MMF_REQUIRE(width > 0 && height > 0 && (!pool || (taps == 9 && width % 2 == 0 && height % 2 == 0)),
+                "mmf_superpoint_conv_f16: bad size");
+    MMF_REQUIRE(nt == 0 || nt == 1 || nt == 2 || nt == 4, "mmf_superpoint_conv_f16: nt must be 0, 1, 2 or 4");
+    MMF_HIP_TRY(hipSetDevice(c->device));
+    mmf::SpLayer L;
+    L.cin = cin, L.cout = cout, L.taps = taps, L.pool = pool != 0, L.relu = relu != 0;
+    L.nt = nt ? nt : mmf::sp_choose_nt(height, width, cout);
+    int rc = sp_upload_weights_f16(L, w, "mmf_superpoint_conv_f16", c->stream);
+    if (!rc) rc = sp_upload(&L.bias, bias, (size_t)cout, c->stream);
+    if (!rc) {
+        mmf::sp_launch_conv_f16(c->stream, L, reinterpret_cast<const _Float16*>(in), cin, out, cout, height, width, out_is_f32 != 0);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(MMF_ERR_HIP, std::string("mmf_superpoint_conv_f16: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(L.wpack16), (void)hipFree(L.bias);
     return rc;
 }
 

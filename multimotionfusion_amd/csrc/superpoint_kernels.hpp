@@ -8,7 +8,8 @@
 //
 // The convolutions are the only dense contractions of the whole project and run on the matrix cores as an
 // implicit GEMM in f32 (v_mfma_f32_32x32x2_f32: f32 operands, f32 accumulate -- the reference computes in
-// fp32, so no reduced-precision operand is introduced):
+// fp32, so no reduced-precision operand is introduced on this path; the optional f16 forward pass is
+// superpoint_f16_kernels.hpp):
 //   * activations are channels-last [H][W][C], so the K dimension (tap, channel) is contiguous per pixel;
 //   * one workgroup (4 waves) owns an 8 x 16 pixel tile and 32*NT output channels; wave w owns rows 2w, 2w+1.
 //     The 32 MFMA rows of a wave are eight 2x2 pixel blocks (row = 4*block + 2*dy + dx), which puts the four

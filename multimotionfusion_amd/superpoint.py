@@ -4,6 +4,8 @@ ABI -- no fallback.
 
     kp = SuperPoint(ctx, weights, max_width=640, max_height=480)
     coordinates, descriptors = kp.getFeatures(img)        # [n,2] float64 in [0,1), [n,256] float64
+
+`precision="f16"` runs the forward pass with f16 operands and f32 accumulation; the default is "f32".
 """
 import ctypes as C
 import weakref
@@ -51,9 +53,24 @@ def load_weights(path):
     return [(sd[f"{n}.weight"].float().numpy(), sd[f"{n}.bias"].float().numpy()) for n in LAYERS]
 
 
+PRECISIONS = {"f32": 0, "f16": 1}  # MMF_SP_F32, MMF_SP_F16
+
+# (cout, shift of the output's sides) of forwardPrefix(img, layers), layers = 1..9
+PREFIX_SHAPES = ((64, 0), (64, 1), (64, 1), (64, 2), (128, 2), (128, 3), (128, 3), (128, 3), (512, 3))
+
+
+def f16_round(a):
+    """the library's f32 -> f16 rounding (mmf_f16_round): the bits as a uint16 array of a's shape"""
+    from . import _capi
+    a = np.ascontiguousarray(a, np.float32)
+    out = np.empty(a.shape, np.uint16)
+    check(_capi.load().mmf_f16_round(a.ctypes.data, a.size, out.ctypes.data))
+    return out
+
+
 class SuperPoint:
     def __init__(self, ctx: Context, weights, max_width=640, max_height=480, max_keypoints=4096, conf_thresh=0.015,
-                 nms_dist=4, border=4):
+                 nms_dist=4, border=4, precision="f32"):
         if isinstance(weights, str):
             weights = load_weights(weights)
         assert len(weights) == 12
@@ -65,7 +82,12 @@ class SuperPoint:
         self.max_keypoints = int(max_keypoints)
         self.conf_thresh, self.nms_dist, self.border = float(conf_thresh), int(nms_dist), int(border)
         h = C.c_void_p()
-        check(self.lib.mmf_superpoint_create(ctx.handle, arr, int(max_width), int(max_height), self.max_keypoints, C.byref(h)))
+        code = PRECISIONS.get(precision, precision)  # (an unknown value goes to the library, which refuses it)
+        if precision == "f32":
+            check(self.lib.mmf_superpoint_create(ctx.handle, arr, int(max_width), int(max_height), self.max_keypoints, C.byref(h)))
+        else:
+            check(self.lib.mmf_superpoint_create_ex(ctx.handle, arr, int(max_width), int(max_height), self.max_keypoints, int(code),
+                                                    C.byref(h)))
         self.handle = h
         self._size = None
         ctx._children.append(weakref.ref(self))
@@ -87,6 +109,19 @@ class SuperPoint:
             check(self.lib.mmf_superpoint_download(self.handle, which, a.ctypes.data, a.size))
             out.append(a)
         return tuple(out)
+
+    @property
+    def precision(self):
+        return {v: k for k, v in PRECISIONS.items()}[self.lib.mmf_superpoint_precision(self.handle)]
+
+    def forwardPrefix(self, img, layers):
+        """(tests, tools) the first `layers` launches of the forward pass (1 = conv1a ... 9 = the fused 3x3 head) and that
+        launch's output [h,w,cout]: float16 on an f16 object, float32 on an f32 one"""
+        img, H, W, ch = self._image(img)
+        cout, shift = PREFIX_SHAPES[int(layers) - 1]
+        a = np.empty((H >> shift, W >> shift, cout), np.float16 if self.precision == "f16" else np.float32)
+        check(self.lib.mmf_debug_superpoint_forward_prefix(self.handle, _p(img), W, H, ch, int(layers), a.ctypes.data, a.nbytes))
+        return a
 
     def enqueue(self, img):
         """forward pass only, asynchronous (bench)"""
@@ -205,4 +240,19 @@ def conv(ctx: Context, x: torch.Tensor, w, b, relu=True, pool=False, nt=0):
     out = torch.empty((H // 2, W // 2, cout) if pool else (H, W, cout), dtype=torch.float32, device=x.device)
     check(ctx.lib.mmf_superpoint_conv(ctx.handle, _p(x), H, W, cin, w.ctypes.data, b.ctypes.data, cout, taps, int(relu),
                                       int(pool), int(nt), _p(out)))
+    return out
+
+
+def conv_f16(ctx: Context, x: torch.Tensor, w, b, relu=True, pool=False, nt=0, out_f32=False):
+    """One layer of the f16 path by itself: x [H,W,Cin] float16 CUDA tensor (channels last), w [Cout,Cin,k,k], b [Cout] float32
+    numpy (w is rounded to f16 as an f16 SuperPoint rounds it).  Returns float16, or the unrounded float32 with out_f32."""
+    assert x.dtype == torch.float16 and x.is_cuda and x.dim() == 3
+    x = x.contiguous()
+    w, b = np.ascontiguousarray(w, np.float32), np.ascontiguousarray(b, np.float32)
+    H, W, cin = x.shape
+    cout, taps = w.shape[0], w.shape[2] * w.shape[3]
+    out = torch.empty((H // 2, W // 2, cout) if pool else (H, W, cout), dtype=torch.float32 if out_f32 else torch.float16,
+                      device=x.device)
+    check(ctx.lib.mmf_superpoint_conv_f16(ctx.handle, _p(x), H, W, cin, w.ctypes.data, b.ctypes.data, cout, taps, int(relu),
+                                          int(pool), int(nt), int(bool(out_f32)), _p(out)))
     return out

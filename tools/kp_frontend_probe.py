@@ -10,7 +10,9 @@ map (random weights put about half of all pixels above 0.015, far denser than a 
 plus the stream time of the features alone (forward pass; forward pass + selection on the device; the host-facing call) and,
 per frame of the sequence, candidates (heat >= threshold), kept (after suppression and border) and count (min(kept, 1024)).
 
-    python tools/kp_frontend_probe.py [--frames 200] [--warmup 20] > profiles/r14_kp_frontend_probe.txt
+    python tools/kp_frontend_probe.py [--frames 200] [--warmup 20] [--precision f32|f16] > profiles/r14_kp_frontend_probe.txt
+
+--precision f16 runs every SuperPoint object of the probe with the f16 forward pass.
 """
 import argparse
 import os
@@ -36,9 +38,9 @@ def pingpong(i, n):
     return p if p < n else 2 * n - 2 - p
 
 
-def run(ctx, K, d_rgb, d_depth, weights, thresh, on_device, warmup, frames):
+def run(ctx, K, d_rgb, d_depth, weights, thresh, on_device, warmup, frames, precision):
     g = MultiMotionFusion(ctx, W, H, K["cx"], K["cy"], K["fx"], K["fy"], icp_weight=ICP_WEIGHT)
-    sp = SuperPoint(ctx, weights, max_width=W, max_height=H, max_keypoints=MAX_KP, conf_thresh=thresh)
+    sp = SuperPoint(ctx, weights, max_width=W, max_height=H, max_keypoints=MAX_KP, conf_thresh=thresh, precision=precision)
     fe = NativeKeypointFrontEnd(ctx, g, sp, (K["fx"], K["fy"], K["cx"], K["cy"]), icp_refine=True, max_keypoints=MAX_KP, on_device=on_device)
     t0 = None
     for i in range(warmup + frames):
@@ -75,6 +77,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--precision", choices=("f32", "f16"), default="f32")
     args = ap.parse_args()
     ctx = Context(0)
     K = synth.intrinsics(W, H)
@@ -83,10 +86,10 @@ def main():
     d_rgb = [torch.from_numpy(f["rgb"]).cuda() for f in seq]
     d_depth = [torch.from_numpy(f["depth"]).cuda() for f in seq]
     weights = random_weights(0)
-    big = SuperPoint(ctx, weights, max_width=W, max_height=H, max_keypoints=16384)
+    big = SuperPoint(ctx, weights, max_width=W, max_height=H, max_keypoints=16384, precision=args.precision)
     heat0 = big.forward(d_rgb[0])[2]
     rows = [("default threshold", 0.015), ("97th percentile of frame 0's heat map", float(np.quantile(heat0, 0.97)))]
-    print(f"device {ctx.device_name()}  {W}x{H}  max_keypoints {MAX_KP}  {args.frames} timed frames after {args.warmup}")
+    print(f"device {ctx.device_name()}  {W}x{H}  SuperPoint precision {args.precision}  max_keypoints {MAX_KP}  {args.frames} timed frames after {args.warmup}")
     for name, thresh in rows:
         print(f"\n== {name}: conf_thresh = {thresh:.6g}")
         big.conf_thresh = thresh
@@ -98,7 +101,7 @@ def main():
         print("frame: candidates kept count")
         for k, s in enumerate(stats):
             print(f"  {k:2d}: {s[0]:6d} {s[1]:5d} {s[2]:4d}")
-        sp = SuperPoint(ctx, weights, max_width=W, max_height=H, max_keypoints=MAX_KP, conf_thresh=thresh)
+        sp = SuperPoint(ctx, weights, max_width=W, max_height=H, max_keypoints=MAX_KP, conf_thresh=thresh, precision=args.precision)
         t_fwd = stream_ms(lambda: sp.enqueue(d_rgb[0]))
         t_dev = stream_ms(lambda: sp.getFeaturesDevice(d_rgb[0]))
         t_host = stream_ms(lambda: sp.keypoints(d_rgb[0]))
@@ -107,7 +110,7 @@ def main():
         sp.close()
         res = {}
         for label, on_device in (("(a) caller-driven", False), ("(b) in-frame, on the device", True)):
-            ms, tracks, dropped, pose, failures = run(ctx, K, d_rgb, d_depth, weights, thresh, on_device, args.warmup, args.frames)
+            ms, tracks, dropped, pose, failures = run(ctx, K, d_rgb, d_depth, weights, thresh, on_device, args.warmup, args.frames, args.precision)
             res[on_device] = (ms, pose)
             print(f"{label}: {ms:.3f} ms per frame  (tracks {tracks}, dropped appends {dropped}, failed adds {failures})")
         same = np.array_equal(res[False][1].view(np.uint32), res[True][1].view(np.uint32))
