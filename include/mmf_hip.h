@@ -1558,7 +1558,40 @@ int mmf_fusion_last_flow_segmentation(mmf_fusion *f, mmf_flowseg_summary *summar
  *   mmf_fusion_load_models   loadModels (:131-145): for id = 1..255 ascending with a model_db/model-<id>/tracks.ply, an object
  *                         model with the next model id and conf_object_init, the file's views stored under that id, unseen
  *                         count -5, appended to the inactive list; no dense surfels.  A file that does not parse is skipped
- *                         and named by mmf_last_error.  MMF_ERR_STATE with world > 1. */
+ *                         and named by mmf_last_error.  MMF_ERR_STATE with world > 1.
+ * Restoring a model's dense surfels (ours: the reference restores none):
+ *   mmf_model_import_cloud   the inverse of mmf_model_export_cloud: record i of `host_records` (n records of 31 bytes, HOST
+ *                         memory) becomes surfel i of the store, in file order.  With the row-major pose Q (NULL = identity,
+ *                         the same arithmetic): position = ((q0 x + q1 y) + q2 z) + q3 per row q, normal =
+ *                         -((r0 nx + r1 ny) + r2 nz) per row r of Q's 3 x 3 (the export negates, the import negates back),
+ *                         f32, no fused multiply-add; radius copied; colour24 = (float)(r << 16 | g << 8 | b), the colour
+ *                         vector's second component 0; confidence = `confidence`; initTime = timestamp = (float)time.
+ *                         REPLACES the store's content (count = n; n = 0 empties it) and leaves the model as
+ *                         mmf_model_upload_map leaves it for the same surfels.  n > the model's capacity: MMF_ERR_INVALID,
+ *                         the store is untouched.  Synchronous (it first lets an in-flight count land); one launch whatever n:
+ *   mmf_model_import_last_launches   the launches of the model's last import.
+ *   mmf_model_import_ply     the file at `path` through mmf_ply_read_cloud, then the above.  A file that does not parse or holds
+ *                         more records than the model holds surfels: MMF_ERR_INVALID, the store is untouched.
+ *   mmf_model_set_timestamps   timestamp = (float)time for every surfel of the store; initTime and everything else stay.
+ *                         Synchronous; one launch.  (combinedPredict / predictIndices drop a surfel with time - timestamp >
+ *                         timeDelta: restored surfels are brought into the window of the frame that uses them; their initTime
+ *                         still says when they were loaded.)
+ *   mmf_fusion_load_models_ex   mmf_fusion_load_models with flags.  MMF_LOAD_DENSE: every model loaded from a tracks.ply also
+ *                         gets the records of model_db/model-<id>/cloud.ply as surfels: Q = identity, confidence = the model's
+ *                         threshold + 1, time = the fusion's tick at the call.  A missing cloud.ply, one that does not parse or
+ *                         one with more records than the model holds leaves the model without surfels; it is loaded all the
+ *                         same and mmf_last_error names the file.  When redetection activates such a model for the first time
+ *                         its timestamps are set to the activating frame's tick: one launch on the model's stream, no wait.
+ *                         mmf_fusion_load_models = flags 0.  Any other flag: MMF_ERR_INVALID.
+ *   mmf_fusion_last_dense_restores   per model of the last load call with MMF_LOAD_DENSE, in load order.  *n is always the
+ *                         number of entries, at most `capacity` are written.  Observational. */
+#define MMF_LOAD_DENSE 1u
+enum { MMF_DENSE_RESTORED = 0, MMF_DENSE_NO_FILE = 1, MMF_DENSE_NO_PARSE = 2, MMF_DENSE_TOO_LARGE = 3 };
+typedef struct mmf_dense_restore {
+    int model_id;      /* the id the model got in this fusion */
+    unsigned surfels;  /* the surfels it got: the file's records, or 0 */
+    int status;        /* MMF_DENSE_* */
+} mmf_dense_restore;
 int mmf_model_export_cloud(mmf_model *m, const float pose[16], float conf_threshold, void *host_records, unsigned capacity,
                            unsigned *n_valid);
 int mmf_model_export_last_launches(mmf_model *m);
@@ -1572,6 +1605,12 @@ int mmf_tracks_ply_read(const char *path, int cap_views, int *n_views, int *coun
 int mmf_viewstore_download_view(mmf_viewstore *vs, int view, int capacity_rows, float *descriptor, float *coordinate);
 int mmf_fusion_save_models(mmf_fusion *f, const char *export_dir);
 int mmf_fusion_load_models(mmf_fusion *f, const char *export_dir, int *n_loaded);
+int mmf_model_import_cloud(mmf_model *m, const float pose[16], const void *host_records, unsigned n, float confidence, int time);
+int mmf_model_import_last_launches(mmf_model *m);
+int mmf_model_import_ply(mmf_model *m, const char *path, const float pose[16], float confidence, int time);
+int mmf_model_set_timestamps(mmf_model *m, int time);
+int mmf_fusion_load_models_ex(mmf_fusion *f, const char *export_dir, unsigned flags, int *n_loaded);
+int mmf_fusion_last_dense_restores(mmf_fusion *f, mmf_dense_restore *out, int capacity, int *n);
 
 #ifdef __cplusplus
 }

@@ -102,6 +102,10 @@ class mmf_redetection(C.Structure):
                 ("error", C.c_float), ("inliers", C.c_int), ("view", C.c_int), ("transformation", C.c_float * 16)]
 
 
+class mmf_dense_restore(C.Structure):
+    _fields_ = [("model_id", C.c_int), ("surfels", C.c_uint), ("status", C.c_int)]
+
+
 class mmf_debug_redetect_record(C.Structure):
     _fields_ = [("T", C.c_float * 16), ("error", C.c_float), ("inliers", C.c_int), ("view", C.c_int), ("n_matches", C.c_int),
                 ("found", C.c_int), ("model_id", C.c_int)]
@@ -459,6 +463,12 @@ SIGNATURES = {
     "mmf_viewstore_download_view": (_i, [_vp, _i, _i, _vp, _vp]),
     "mmf_fusion_save_models": (_i, [_vp, C.c_char_p]),
     "mmf_fusion_load_models": (_i, [_vp, C.c_char_p, _ip]),
+    "mmf_model_import_cloud": (_i, [_vp, _fp, _vp, C.c_uint, _f, _i]),
+    "mmf_model_import_last_launches": (_i, [_vp]),
+    "mmf_model_import_ply": (_i, [_vp, C.c_char_p, _fp, _f, _i]),
+    "mmf_model_set_timestamps": (_i, [_vp, _i]),
+    "mmf_fusion_load_models_ex": (_i, [_vp, C.c_char_p, C.c_uint, _ip]),
+    "mmf_fusion_last_dense_restores": (_i, [_vp, C.POINTER(mmf_dense_restore), _i, _ip]),
 }
 
 _lib = None

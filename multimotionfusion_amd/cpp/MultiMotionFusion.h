@@ -309,6 +309,17 @@ class Model {
             }
         mmf::check(mmf_model_export_ply(m_, (export_dir + "cloud-" + std::to_string(getID()) + ".ply").c_str(), P), "mmf_model_export_ply");
     }
+    // Ours (the reference restores no surfels): n packed 31-byte records {x y z f32 | r g b u8 | nx ny nz f32 | radius f32}
+    // become the store's surfels under `pose` (nullptr: identity) with the given confidence and initTime = timestamp = time
+    // (mmf_model_import_cloud: the store's content is replaced); the same from a PLY cloud; and every surfel's timestamp set
+    // to `time`, into the prediction window of the frame that uses a restored map
+    void importCloud(const void* records, unsigned n, const float* pose, float confidence, int time) {
+        mmf::check(mmf_model_import_cloud(m_, pose, records, n, confidence, time), "mmf_model_import_cloud");
+    }
+    void importPly(const std::string& path, const float* pose, float confidence, int time) {
+        mmf::check(mmf_model_import_ply(m_, path.c_str(), pose, confidence, time), "mmf_model_import_ply");
+    }
+    void setTimestamps(int time) { mmf::check(mmf_model_set_timestamps(m_, time), "mmf_model_set_timestamps"); }
     // Model.h:297: the surfel store the last fuse / clean left, in place (valid until this model's next fuse / clean)
     const OutputBuffer& getModel() {
         mmf::check(mmf_model_surfel_arrays(m_, &vbo_.positionConfidence, &vbo_.colourTime, &vbo_.normalRadius, &vbo_.count),
@@ -859,9 +870,11 @@ class MultiMotionFusion {
     // savePly() (:1001-1018) into the constructor's exportDirectory: cloud-<id>.ply per model and the model database under
     // model_db/ (mmf_fusion_save_models); loadModels() (:131-145, -restore) from the same place -> the models restored
     void savePly() { mmf::check(mmf_fusion_save_models(f_, exportDirectory_.c_str()), "mmf_fusion_save_models"); }
+    // setRestoreDense(true) (ours, default false): loadModels() also restores every model's surfels from its cloud.ply
+    void setRestoreDense(bool val) { restoreDense_ = val; }
     int loadModels() {
         int n = 0;
-        mmf::check(mmf_fusion_load_models(f_, exportDirectory_.c_str(), &n), "mmf_fusion_load_models");
+        mmf::check(mmf_fusion_load_models_ex(f_, exportDirectory_.c_str(), restoreDense_ ? MMF_LOAD_DENSE : 0u, &n), "mmf_fusion_load_models");
         return n;
     }
     mmf_odom* getFrameOdometryHandle() { return mmf_fusion_odometry(f_); }
@@ -941,6 +954,7 @@ class MultiMotionFusion {
     OdometryConfig odom_cfg_;
     SegmentationConfiguration segm_cfg_;
     std::string exportDirectory_;
+    bool restoreDense_ = false;
     ModelList models_, inactive_;
     std::map<std::string, GPUTexture*> textures_;
     std::map<std::string, float> other_;

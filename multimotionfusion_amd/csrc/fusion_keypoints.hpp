@@ -344,7 +344,16 @@ static int redetect_activate(mmf_fusion* f, FusionModel* fm, const float pose[16
         std::memcpy(e.pose, pose, sizeof(e.pose));
         f->kp.view_poses[(int)fm->model->id].assign(1, e);
     }
-    if (fm->lane->stream != f->ctx->stream) return lane_wait(fm, f->ev_frame_ready.get());
+    if (fm->lane->stream != f->ctx->stream) {
+        int rc = lane_wait(fm, f->ev_frame_ready.get());
+        if (rc) return rc;
+    }
+    if (fm->restored_dense) {
+        // surfels restored from a cloud.ply carry the tick of the load: into this frame's prediction window, once, in one
+        // launch on the model's stream ahead of every pass of the frame (its count is exact: no pass has run on it)
+        fm->restored_dense = false;
+        return model_enqueue_timestamps(fm->model, (float)f->tick, fm->lane->stream);
+    }
     return MMF_OK;
 }
 

@@ -21,6 +21,9 @@ struct FusionModel {  // one ModelPointer of the reference's `models` list
     float prev_pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     int fill_in = 0;           // Model::allowsFillIn()
     long long unseen = 0;      // Model::unseenCount
+    // its surfels came from a cloud.ply (mmf_fusion_load_models_ex, MMF_LOAD_DENSE) and it has not been active since: the
+    // frame that activates it sets their timestamps to its tick (redetect_activate), once
+    bool restored_dense = false;
     float* icp_error = nullptr;  // Model::icpError / rgbError (R32F, enableErrorRecording)
     float* rgb_error = nullptr;
     Event ev_done;
@@ -293,6 +296,7 @@ struct mmf_fusion {
     FlowHook flow;         // the optical-flow hook
     FlowInference fi;      // the flow inference.  Behind `flow`: it is released before the flow engine and the flow's stream
     FlowSegmentation fseg; // the flow_crf mode: the blob stage behind the inference
+    std::vector<mmf_dense_restore> dense_restores;  // modeldb_host.hpp: per model of the last load call
     Redetection rd;        // redetection: view store, verifier, keypoint hand-over
     Keypoints kp;          // tracker, keypoint front end, view-pose log
     Prefetch pre;          // the next frame's prefetch on the side streams
@@ -654,6 +658,7 @@ extern "C" int mmf_fusion_reset(mmf_fusion* f) {
         fm->odom->so3.prefetched = false, fm->odom->so3.stage = nullptr;
         fm->odom->in.have_tmp = false;
         fm->unseen = 0;
+        fm->restored_dense = false;  // (its store is empty now)
         fm->pose_log.clear();
     }
     for (FusionModel* fm : all) fm->spec_valid = false;

@@ -772,6 +772,7 @@ extern "C" int mmf_compute_derivative_images(mmf_ctx* c, const uint8_t* src, siz
 
 #include "model_host.hpp"
 #include "export_host.hpp"
+#include "import_host.hpp"
 
 // =============================================================================================
 // Keypoint descriptor matching (Core/Utils/PointTracker.cpp:100-114) on the f32 matrix cores

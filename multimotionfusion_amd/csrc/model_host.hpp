@@ -131,6 +131,7 @@ struct mmf_model {
     void* export_ws = nullptr;
     size_t export_ws_bytes = 0;
     int export_launches = 0;
+    int import_launches = 0;  // import_host.hpp: the launches of the last mmf_model_import_cloud
 };
 
 // Every buffer of the slab, ONCE, in the order it is carved.  The slab's size, the pointers and mmf_model_texture's answers

@@ -72,14 +72,47 @@ extern "C" int mmf_fusion_save_models(mmf_fusion* f, const char* export_dir) {
     return MMF_OK;
 }
 
+// MMF_LOAD_DENSE for one loaded model: its cloud.ply into its store, the outcome into f->dense_restores; a file that cannot be
+// used is named in *skipped and is no error
+static int modeldb_restore_dense(mmf_fusion* f, FusionModel* fm, const std::string& path, std::string* skipped) {
+    mmf_dense_restore r;
+    r.model_id = (int)fm->model->id, r.surfels = 0, r.status = MMF_DENSE_RESTORED;
+    std::error_code ec;
+    if (!std::filesystem::exists(path, ec)) {
+        r.status = MMF_DENSE_NO_FILE;
+        *skipped = path + ": no such file";
+    } else {
+        unsigned n = 0;
+        const int rc = model_import_ply(fm->model, path.c_str(), nullptr, fm->model->conf_threshold + 1.f, f->tick, &n);
+        if (rc == MMF_ERR_INVALID) {
+            r.status = n > (unsigned)fm->model->capacity ? MMF_DENSE_TOO_LARGE : MMF_DENSE_NO_PARSE;
+            *skipped = path + ": " + g_last_error;
+        } else if (rc != MMF_OK) {
+            return rc;
+        } else {
+            r.surfels = n;
+            fm->restored_dense = n > 0;
+        }
+    }
+    f->dense_restores.push_back(r);
+    return MMF_OK;
+}
+
 // loadModels: for id = 1 .. 255 ascending with a `model_db/model-<id>/tracks.ply`, an object model with the NEXT model id and
-// conf_object_init, the file's views stored for that id, unseen count -5 (:141), at the end of the inactive list.  No dense
-// surfels (as in the reference).  A file that does not parse is skipped: mmf_last_error names the last such file, the models
-// before and behind it are loaded.
-extern "C" int mmf_fusion_load_models(mmf_fusion* f, const char* export_dir, int* n_loaded) {
+// conf_object_init, the file's views stored for that id, unseen count -5 (:141), at the end of the inactive list.  A file that
+// does not parse is skipped: mmf_last_error names the last such file, the models before and behind it are loaded.
+// flags 0: no dense surfels (as in the reference).  MMF_LOAD_DENSE (ours): the records of
+// `model_db/model-<id>/cloud.ply` become the model's surfels under the identity (the file's frame is the frame of the
+// restored views' coordinates), confidence = the model's threshold + 1 (strictly stable: drawn and exported again), both
+// times = the tick now; the activating frame moves the timestamps into its window (redetect_activate).  A missing file,
+// one that does not parse or one with more records than the model holds leaves the model without surfels -- it is loaded all
+// the same, mmf_last_error names the file, mmf_fusion_last_dense_restores tells which it was.
+extern "C" int mmf_fusion_load_models_ex(mmf_fusion* f, const char* export_dir, unsigned flags, int* n_loaded) {
     MMF_REQUIRE(f && export_dir, "mmf_fusion_load_models: null argument");
     if (n_loaded) *n_loaded = 0;
+    MMF_REQUIRE((flags & ~(unsigned)MMF_LOAD_DENSE) == 0, "mmf_fusion_load_models: unknown flag");
     if (f->shard_world > 1) return fail(MMF_ERR_STATE, "mmf_fusion_load_models: not supported on a shard (world > 1)");
+    f->dense_restores.clear();
     MMF_HIP_TRY(hipSetDevice(f->ctx->device));
     if (int rc = fusion_viewstore(f)) return rc;
     const std::string db = modeldb_join(export_dir, "model_db");
@@ -87,7 +120,7 @@ extern "C" int mmf_fusion_load_models(mmf_fusion* f, const char* export_dir, int
     std::vector<int> counts;
     std::vector<float> desc, coord;
     for (int id = 1; id < 256; ++id) {
-        const std::string path = modeldb_join(modeldb_join(db, "model-" + std::to_string(id)), "tracks.ply");
+        const std::string model_dir = modeldb_join(db, "model-" + std::to_string(id)), path = modeldb_join(model_dir, "tracks.ply");
         std::error_code ec;
         if (!std::filesystem::exists(path, ec)) continue;
         int n_views = 0, n_rows = 0;
@@ -112,7 +145,21 @@ extern "C" int mmf_fusion_load_models(mmf_fusion* f, const char* export_dir, int
         fm->unseen = -5;
         f->inactive.push_back(fm);
         if (n_loaded) ++*n_loaded;
+        if (flags & MMF_LOAD_DENSE)
+            if (int rc_dense = modeldb_restore_dense(f, fm, modeldb_join(model_dir, "cloud.ply"), &skipped)) return rc_dense;
     }
     g_last_error = skipped.empty() ? std::string() : "mmf_fusion_load_models: skipped " + skipped;
+    return MMF_OK;
+}
+extern "C" int mmf_fusion_load_models(mmf_fusion* f, const char* export_dir, int* n_loaded) {
+    return mmf_fusion_load_models_ex(f, export_dir, 0, n_loaded);
+}
+
+// per model of the last load call with MMF_LOAD_DENSE, in load order: its id, the surfels it got, why it got none.
+// *n is always the number of entries; at most `capacity` are written.  Observational
+extern "C" int mmf_fusion_last_dense_restores(mmf_fusion* f, mmf_dense_restore* out, int capacity, int* n) {
+    MMF_REQUIRE(f && n && (out || capacity <= 0), "mmf_fusion_last_dense_restores: null argument");
+    *n = (int)f->dense_restores.size();
+    for (int i = 0; i < *n && i < capacity; ++i) out[i] = f->dense_restores[(size_t)i];
     return MMF_OK;
 }

@@ -12,6 +12,9 @@ from .cudafuncs import Context, _p
 from .model import Model
 from .odometry import RGBDOdometry
 
+MMF_LOAD_DENSE = 1  # mmf_fusion_load_models_ex's flag
+DENSE_STATUS = ("restored", "no file", "does not parse", "too large")  # MMF_DENSE_*
+
 
 class HostFrame:
     """One frame in host memory (FrameData::rgb / depth as numpy arrays) with the arrays' addresses taken once: numpy's
@@ -543,12 +546,26 @@ class MultiMotionFusion:
         (model_db/model-<id>/cloud.ply, tracks.ply for models with stored views); modeldb.py reads the files"""
         check(self.ctx.lib.mmf_fusion_save_models(self.handle, str(exportDir).encode()))
 
-    def loadModels(self, exportDir):
+    def loadModels(self, exportDir, dense=False):
         """MultiMotionFusion::loadModels (:131-145, -restore): every model_db/model-<id>/tracks.ply under exportDir becomes
-        an inactive object model with the next id and the file's views -> the number of models loaded"""
+        an inactive object model with the next id and the file's views -> the number of models loaded.  dense=True (ours, the
+        reference restores no surfels): the records of model_db/model-<id>/cloud.ply become the model's surfels, stable, with
+        the tick of the load as both times; the frame that activates the model moves their timestamps into its window."""
         n = C.c_int()
-        check(self.ctx.lib.mmf_fusion_load_models(self.handle, str(exportDir).encode(), C.byref(n)))
+        if dense:
+            check(self.ctx.lib.mmf_fusion_load_models_ex(self.handle, str(exportDir).encode(), MMF_LOAD_DENSE, C.byref(n)))
+        else:
+            check(self.ctx.lib.mmf_fusion_load_models(self.handle, str(exportDir).encode(), C.byref(n)))
         return n.value
+
+    def getLastDenseRestores(self):
+        """per model of the last loadModels(dense=True): dict(model_id, surfels, status), status one of DENSE_STATUS"""
+        from ._capi import mmf_dense_restore
+        n = C.c_int()
+        check(self.ctx.lib.mmf_fusion_last_dense_restores(self.handle, None, 0, C.byref(n)))
+        arr = (mmf_dense_restore * max(n.value, 1))()
+        check(self.ctx.lib.mmf_fusion_last_dense_restores(self.handle, arr, n.value, C.byref(n)))
+        return [dict(model_id=r.model_id, surfels=r.surfels, status=DENSE_STATUS[r.status]) for r in arr[:n.value]]
 
     def getPoseLog(self, index=0):
         n = C.c_int()

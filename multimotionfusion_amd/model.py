@@ -124,6 +124,28 @@ class Model:
         p = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(16))
         check(self.ctx.lib.mmf_model_export_ply(self.handle, str(path).encode(), fptr(p)))
 
+    def importCloud(self, records, pose=None, confidence=0.0, time=0):
+        """the inverse of exportCloud: record i (modeldb.CLOUD_DTYPE) becomes surfel i under `pose` (None: identity) with the
+        given confidence and initTime = timestamp = time; REPLACES the store's content.  One launch."""
+        from .modeldb import CLOUD_DTYPE
+        r = np.ascontiguousarray(records, CLOUD_DTYPE).reshape(-1)
+        p = None if pose is None else np.ascontiguousarray(np.asarray(pose, np.float32).reshape(16))
+        check(self.ctx.lib.mmf_model_import_cloud(self.handle, None if p is None else fptr(p), r.ctypes.data, len(r),
+                                                  float(confidence), int(time)))
+
+    def importLastLaunches(self):
+        return self.ctx.lib.mmf_model_import_last_launches(self.handle)
+
+    def importPly(self, path, pose=None, confidence=0.0, time=0):
+        """the records of a binary PLY cloud (exportModelPLY's file) through importCloud"""
+        p = None if pose is None else np.ascontiguousarray(np.asarray(pose, np.float32).reshape(16))
+        check(self.ctx.lib.mmf_model_import_ply(self.handle, str(path).encode(), None if p is None else fptr(p),
+                                                float(confidence), int(time)))
+
+    def setTimestamps(self, time):
+        """timestamp = time for every surfel (into a frame's prediction window); initTime and everything else stay"""
+        check(self.ctx.lib.mmf_model_set_timestamps(self.handle, int(time)))
+
     def uploadMap(self, surfels):
         s = np.ascontiguousarray(np.asarray(surfels, np.float32).reshape(-1, 12))
         check(self.ctx.lib.mmf_model_upload_map(self.handle, fptr(s), s.shape[0]))
