@@ -305,7 +305,9 @@ int mmf_model_id(mmf_model *m);
  * The segmentation RESULT is handed in per frame (mmf_segmentation: gSLICr + dense CRF of the reference's
  * front-end), pulled through a callback at the point where the reference calls performSegmentation (:412), computed
  * from the frame's raw label image (Segmentation.cpp:89-147: mmf_fusion_set_mask_segmentation, below) or by the built-in
- * dense CRF (mmf_fusion_set_crf_segmentation, below).  Relocalisation and loop closure stay in the reference's front-end.
+ * dense CRF (mmf_fusion_set_crf_segmentation, below).  Of relocalisation the fern keyframe database is here
+ * (mmf_fusion_set_fern_database, below: stage one, observational); pose recovery, loss detection and loop closure stay in the
+ * reference's front-end.
  * Every model runs on its own stream ("lane"); every public call returns with the fusion's own
  * stream (the context's) ordered after all lanes.
  * ------------------------------------------------------------------------------------- */
@@ -1611,6 +1613,118 @@ int mmf_model_import_ply(mmf_model *m, const char *path, const float pose[16], f
 int mmf_model_set_timestamps(mmf_model *m, int time);
 int mmf_fusion_load_models_ex(mmf_fusion *f, const char *export_dir, unsigned flags, int *n_loaded);
 int mmf_fusion_last_dense_restores(mmf_fusion *f, mmf_dense_restore *out, int capacity, int *n);
+
+/* ---- the fern keyframe database (csrc/ferns_kernels.hpp, csrc/ferns_host.hpp) ------------------------------
+ * Stage one of relocalisation: ElasticFusion's randomised ferns (Core/Ferns.{h,cpp}) as an engine of its own -- the encoding
+ * of a frame into fern codes, the database of keyframes, the rule that adds a frame (addFrame, Ferns.cpp:72-143) and the
+ * search for the closest keyframe that is old enough (findFrame up to :203, with blockHDAware, :322-337).  What findFrame does
+ * with that keyframe -- the fern odometry and its acceptance rule (:201-238), photometricCheck, the surface constraints --,
+ * loss detection, the override of the pose, persistence and a sharded fusion are NOT here.  The arithmetic is the one
+ * DESIGN.md 4.13 writes out and tests/ferns_oracle.py restates; the engine equals it bit for bit.
+ * The inputs are a model's fill-in images as DEVICE images of the frame's size: image rgba8 [height][width][4], vert and norm
+ * f32 [height][width][4] (mmf_model_texture "fillImage", "fillVertex", "fillNormal").  The small images have w = width / 8 by
+ * h = height / 8 pixels; small pixel (i, j) is the source texel (texel((i + 0.5f) / w, width), texel((j + 0.5f) / h, height))
+ * with texel(c, n) = clamp((int)floorf(c * (float)n), 0, n - 1) (GPUResize as DESIGN.md A3 restates it; rows are not flipped:
+ * A7).  A fern is six int32 {x, y, t_r, t_g, t_b, t_d}: x in [0, w - 1], y in [0, h - 1], t_r, t_g, t_b in [0, 255], t_d in
+ * [400, max_depth_mm] (millimetres; Ferns.cpp:21-70).  With v and p the small vertex and colour at (x, y) its code is
+ *   (p.r > t_r) << 3 | (p.g > t_g) << 2 | (p.b > t_b) << 1 | (int(v.z * 1000.0f) > t_d)   when v.z > 0 (a NaN is not), else 255
+ * -- one float multiplication, a truncating conversion; a product of 2^31 or more, where the reference's conversion is
+ * undefined, counts as greater.  good = the number of codes that are not 255.  For a stored keyframe j
+ *   co[j] = #{i : cur[i] != 255 and db[j][i] == cur[i]},   maxCo = (float)min(good_cur, good_j),
+ *   dissim[j] = (maxCo - (float)co[j]) / maxCo   (one subtraction, one correctly rounded division; 0 / 0 is NaN, which no
+ *   comparison accepts).
+ * add:  minimum = FLT_MAX, lowered by strict < over every j in ascending order, and only if good_cur > 0; the frame becomes
+ *   keyframe n iff (minimum > threshold || n == 0) && good_cur > 0, with its codes, good, pose, time and small images.
+ * find: the same minimum over the j with time - time_j > min_time_gap; the lowest such j on a tie, -1 if there is none;
+ *   similarity = (codes equal among the ferns good in both) / (float)(ferns good in both), NaN when there are none; the
+ *   keyframe is a candidate iff similarity > min_similarity.
+ * Unlike the reference's the database has a capacity: a frame the add rule accepts while it is full is dropped and counted.
+ * The reference seeds its ferns with time(0): there is nothing to be equal to, so the table comes from the caller.
+ *   mmf_ferns_default_config num 500 (MultiMotionFusion.cpp:33), max_depth_mm 15000 (:33: depthCut * 1000, with the GUI's depth
+ *                        cutoff of 15 m, GUI/Tools/GUI.h:203, MainController.cpp:515), capacity 1024, min_time_gap 300
+ *                        (Ferns.cpp:193), threshold 0.3095 (MultiMotionFusion.h:57), min_similarity 0.3 (Ferns.cpp:203)
+ *   mmf_ferns_make_table a table of num ferns for w x h small images from `seed`, deterministically (a splitmix64 sequence,
+ *                        per fern x, y, t_r, t_g, t_b, t_d, each lo + next % (hi - lo + 1)): host arithmetic, no device
+ *   mmf_ferns_create     MMF_ERR_INVALID -- before any device is touched -- for a width or height under 8, num outside
+ *                        [1, 16384], max_depth_mm < 400, capacity < 1, a NaN threshold, a null table or a fern outside its
+ *                        ranges.  The table is copied.  Device memory: capacity * (num + w h 36) bytes and change.
+ *   mmf_ferns_reset      empties the database and zeroes the drop count
+ *   mmf_ferns_set_threshold   the threshold of the add rule from the next process call on (the reference hands it to every
+ *                        addFrame call)
+ *   mmf_ferns_process    flags MMF_FERNS_FIND, MMF_FERNS_ADD or both; with both the frame is encoded and searched once and find
+ *                        sees the database before this frame's add.  Asynchronous on the context's stream: three launches
+ *                        whatever num, the number of keyframes and the size, no host wait, no copy to the host; the number of
+ *                        keyframes and the drop count live on the device and the decision to append is taken there.  pose: 16
+ *                        floats, row major.  MMF_ERR_INVALID for a null image or pose and for flags outside {1, 2, 3}.
+ *   mmf_ferns_result     the last process call's record, through pinned memory; waits for the stream.  Without MMF_FERNS_ADD
+ *                        add_minimum is FLT_MAX and added 0; without MMF_FERNS_FIND closest is -1.  closest_dissim is FLT_MAX
+ *                        and closest_similarity, closest_pose and closest_time are 0 while closest is -1.  MMF_ERR_STATE before
+ *                        the first process call (and after a reset).
+ *   mmf_ferns_keyframe   keyframe id: DEVICE pointers to its small images -- image rgba8 [h][w][4], vert and norm dense f32
+ *                        [h][w][4], as mmf_odom_init_icp_model / mmf_odom_init_icp_from_prediction take them -- its pose,
+ *                        time and good codes.  Any out pointer may be NULL.  Waits for the stream; MMF_ERR_INVALID for an id
+ *                        that is not stored.  The pointers stay valid until the engine is destroyed.
+ *   mmf_ferns_download   to HOST memory, for tests: "image" u8 [h][w][4], "vert" / "norm" f32 [h][w][4], "codes" u8 [num] (the
+ *                        current frame); "co" i32 / "dissim" f32 [capacity] (the last search: entries from the count at that
+ *                        search on are stale); "db_codes" u8 [capacity][num], "db_times" / "db_good" i32 [capacity].  bytes
+ *                        must be the array's size.  Synchronous.
+ *   mmf_ferns_last_launches   kernel launches of the last process call: 3
+ * Inside processFrame (off by default):
+ *   mmf_fusion_set_fern_database  cfg != NULL: behind the end-of-frame predict(), where the reference's processFerns() stands
+ *                        (MultiMotionFusion.cpp:824; commented out there), every frame runs process(FIND | ADD) on the camera
+ *                        model's fill-in images, its pose and the frame's tick, in an engine of the fusion's own (a second call
+ *                        replaces it), on a stream of its own behind the point of the camera model's stream where those images
+ *                        are complete, joined by the fusion's stream before the call returns.  table == NULL: the table of
+ *                        mmf_ferns_make_table with seed 0.  The reference's findFrame reads the images of the mid-frame predict()
+ *                        (:675-685), which this library does not enqueue: the hook queries the end-of-frame images instead.
+ *                        Observational: poses, maps and masks are the same bits either way.  NULL (the default): off -- the
+ *                        engine, its stream and events are freed and no frame allocates, enqueues or waits for anything.
+ *                        mmf_fusion_reset empties the database.  MMF_ERR_INVALID as mmf_ferns_create; MMF_ERR_STATE on a
+ *                        sharded fusion (world > 1; mmf_fusion_set_shard refuses a fusion with the hook on) and on a fusion
+ *                        whose camera model has no fill-in.
+ *   mmf_fusion_last_fern_result   as mmf_ferns_result, for the last frame.  MMF_ERR_STATE while the hook is off and before the
+ *                        first frame.
+ *   mmf_fusion_fern_database      the hook's engine (for mmf_ferns_keyframe, mmf_ferns_download), NULL while the hook is off */
+#define MMF_FERNS_FIND 1
+#define MMF_FERNS_ADD 2
+typedef struct mmf_ferns mmf_ferns;
+typedef struct {
+    int num;              /* ferns */
+    int max_depth_mm;     /* the upper end of a fern's depth threshold, millimetres */
+    int capacity;         /* keyframes */
+    int min_time_gap;     /* find: only keyframes with time - time_j > min_time_gap */
+    float threshold;      /* add: the frame is kept when its lowest dissimilarity is above this */
+    float min_similarity; /* find: the closest keyframe is a candidate above this */
+} mmf_ferns_config;
+typedef struct {
+    int added;           /* this frame became keyframe count - 1 */
+    int dropped_total;   /* frames the add rule accepted while the database was full, since creation / reset */
+    int count;           /* keyframes stored, behind this call */
+    int good_codes;      /* of the current frame */
+    float add_minimum;   /* add's minimum; FLT_MAX when no keyframe lowered it */
+    int closest;         /* find's keyframe, -1: none */
+    float closest_dissim;
+    float closest_similarity;
+    int candidate;       /* closest >= 0 and closest_similarity > min_similarity */
+    float closest_pose[16];
+    int closest_time;
+} mmf_ferns_result_t;
+int mmf_ferns_default_config(mmf_ferns_config *cfg);
+int mmf_ferns_make_table(unsigned long long seed, int num, int w, int h, int max_depth_mm, int *table_out);
+int mmf_ferns_create(mmf_ctx *ctx, int width, int height, const mmf_ferns_config *cfg, const int *table, mmf_ferns **out);
+void mmf_ferns_destroy(mmf_ferns *ferns);
+int mmf_ferns_reset(mmf_ferns *ferns);
+int mmf_ferns_set_threshold(mmf_ferns *ferns, float threshold);
+int mmf_ferns_process(mmf_ferns *ferns, const void *image_rgba_dev, const void *vert_dev, const void *norm_dev, const float pose[16],
+                      int time, int flags);
+int mmf_ferns_result(mmf_ferns *ferns, mmf_ferns_result_t *out);
+int mmf_ferns_keyframe(mmf_ferns *ferns, int id, const void **image_dev, const void **vert_dev, const void **norm_dev, float pose[16],
+                       int *time, int *good_codes);
+int mmf_ferns_download(mmf_ferns *ferns, const char *name, void *host_dst, size_t bytes);
+int mmf_ferns_last_launches(mmf_ferns *ferns);
+int mmf_fusion_set_fern_database(mmf_fusion *f, const mmf_ferns_config *cfg, const int *table);
+int mmf_fusion_last_fern_result(mmf_fusion *f, mmf_ferns_result_t *out);
+mmf_ferns *mmf_fusion_fern_database(mmf_fusion *f);
 
 #ifdef __cplusplus
 }

@@ -151,6 +151,17 @@ class mmf_flowseg_summary(C.Structure):
                 ("models", mmf_segmentation_model * 32), ("area2", C.c_int * 32), ("first_cell", C.c_int * 32)]
 
 
+class mmf_ferns_config(C.Structure):
+    _fields_ = [("num", C.c_int), ("max_depth_mm", C.c_int), ("capacity", C.c_int), ("min_time_gap", C.c_int),
+                ("threshold", C.c_float), ("min_similarity", C.c_float)]
+
+
+class mmf_ferns_result_t(C.Structure):
+    _fields_ = [("added", C.c_int), ("dropped_total", C.c_int), ("count", C.c_int), ("good_codes", C.c_int),
+                ("add_minimum", C.c_float), ("closest", C.c_int), ("closest_dissim", C.c_float), ("closest_similarity", C.c_float),
+                ("candidate", C.c_int), ("closest_pose", C.c_float * 16), ("closest_time", C.c_int)]
+
+
 class mmf_flowcrf_input(C.Structure):
     _fields_ = [("n_models", C.c_int), ("allow_new", C.c_int), ("new_id", C.c_uint), ("ids", C.POINTER(C.c_ubyte)),
                 ("T_start", C.POINTER(C.c_float)), ("T_end", C.POINTER(C.c_float)), ("vertex", C.POINTER(C.c_void_p)),
@@ -469,6 +480,20 @@ SIGNATURES = {
     "mmf_model_set_timestamps": (_i, [_vp, _i]),
     "mmf_fusion_load_models_ex": (_i, [_vp, C.c_char_p, C.c_uint, _ip]),
     "mmf_fusion_last_dense_restores": (_i, [_vp, C.POINTER(mmf_dense_restore), _i, _ip]),
+    "mmf_ferns_default_config": (_i, [C.POINTER(mmf_ferns_config)]),
+    "mmf_ferns_make_table": (_i, [C.c_ulonglong, _i, _i, _i, _i, _ip]),
+    "mmf_ferns_create": (_i, [_vp, _i, _i, C.POINTER(mmf_ferns_config), _ip, C.POINTER(_vp)]),
+    "mmf_ferns_destroy": (None, [_vp]),
+    "mmf_ferns_reset": (_i, [_vp]),
+    "mmf_ferns_set_threshold": (_i, [_vp, _f]),
+    "mmf_ferns_process": (_i, [_vp, _vp, _vp, _vp, _fp, _i, _i]),
+    "mmf_ferns_result": (_i, [_vp, C.POINTER(mmf_ferns_result_t)]),
+    "mmf_ferns_keyframe": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _fp, _ip, _ip]),
+    "mmf_ferns_download": (_i, [_vp, C.c_char_p, _vp, _sz]),
+    "mmf_ferns_last_launches": (_i, [_vp]),
+    "mmf_fusion_set_fern_database": (_i, [_vp, C.POINTER(mmf_ferns_config), _ip]),
+    "mmf_fusion_last_fern_result": (_i, [_vp, C.POINTER(mmf_ferns_result_t)]),
+    "mmf_fusion_fern_database": (_vp, [_vp]),
 }
 
 _lib = None

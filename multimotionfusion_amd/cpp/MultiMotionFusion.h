@@ -24,6 +24,7 @@
 #include "RigidRANSAC.h"
 #include "PointTracker.h"
 #include "SuperPoint.h"
+#include "Ferns.h"
 
 // FrameData (Core/FrameData.h:25-43) without OpenCV: one frame in HOST memory, as the log readers deliver it
 struct FrameData {
@@ -662,10 +663,49 @@ class MultiMotionFusion {
     void setEnableMultipleModels(bool v) { mmf::check(mmf_fusion_set_enable_multiple_models(f_, v), "setEnableMultipleModels"); }
     void setTick(const int& v) { mmf::check(mmf_fusion_set_tick(f_, v), "setTick"); }
     void scheduleDeactivation(const ModelPointer& m) { mmf::check(mmf_fusion_schedule_deactivation(f_, (int)m->getID()), "scheduleDeactivation"); }
-    // settings of subsystems that stay in the reference's front-end (spawning policy beyond the CRF, redetection, ferns):
+    // settings of subsystems that stay in the reference's front-end (spawning policy beyond the CRF, redetection):
     // recorded, not interpreted here.  The CRF and spawn settings are recorded too and forwarded to the built-in
     // segmentation (mmf_fusion_set_crf_segmentation).
-    void setFernThresh(const float& v) { other_["fernThresh"] = v; }
+    // fernThresh: recorded, and handed to the fern database while that hook is on (setFernDatabase)
+    void setFernThresh(const float& v) {
+        other_["fernThresh"] = v;
+        if (fern_on_) mmf::check(mmf_ferns_set_threshold(mmf_fusion_fern_database(f_), v), "mmf_ferns_set_threshold");
+    }
+    // The fern keyframe database behind every frame's final predict(), where the reference's processFerns() stands
+    // (MultiMotionFusion.cpp:824; mmf_fusion_set_fern_database): ferns(500, depthCut * 1000, ..) (:33) with the
+    // recorded fernThresh, on the camera model's fill-in images.  Observational -- stage one of relocalisation: no pose, map or
+    // mask depends on it, getLost() stays false.  Off until switched on; setFernDatabase(true) again starts an empty database.
+    void setFernDatabase(bool v) {
+        mmf_ferns_config c;
+        mmf::check(mmf_ferns_default_config(&c), "mmf_ferns_default_config");
+        const int depth_mm = (int)(refresh().depth_cutoff * 1000.f);
+        c.max_depth_mm = depth_mm > 400 ? depth_mm : 400;
+        if (other_.count("fernThresh")) c.threshold = other_["fernThresh"];
+        ferns_.reset();
+        mmf::check(mmf_fusion_set_fern_database(f_, v ? &c : nullptr, nullptr), "mmf_fusion_set_fern_database");
+        other_["fernDatabase"] = v, fern_on_ = v;
+        if (v) ferns_.reset(new Ferns(mmf_fusion_fern_database(f_), width_, height_, c.num, c.max_depth_mm));
+    }
+    // getFerns() (MultiMotionFusion.h:106): the hook's database; only while the hook is on
+    Ferns& getFerns() {
+        if (!ferns_) mmf::check(MMF_ERR_STATE, "getFerns: the fern database is off (setFernDatabase)");
+        return *ferns_;
+    }
+    // the database's record of the last frame (mmf_fusion_last_fern_result); `valid` false while the hook is off and before
+    // the first frame
+    struct FernResult {
+        bool valid = false;
+        mmf_ferns_result_t record{};
+    };
+    FernResult getLastFernResult() {
+        FernResult out;
+        if (!fern_on_) return out;
+        const int rc = mmf_fusion_last_fern_result(f_, &out.record);
+        if (rc == MMF_ERR_STATE) return out;
+        mmf::check(rc, "mmf_fusion_last_fern_result");
+        out.valid = true;
+        return out;
+    }
     void setModelSpawnOffset(const unsigned& v) {
         other_["modelSpawnOffset"] = (float)v, crf_.model_spawn_offset = (int)v, mask_.model_spawn_offset = (int)v;
         flowseg_.model_spawn_offset = (int)v;
@@ -859,7 +899,7 @@ class MultiMotionFusion {
     const std::map<std::string, float>& frontEndSettings() const { return other_; }
 
     // ----- getters (:186-216)
-    const bool& getLost() { return lost_; }  // relocalisation stays in the reference: never lost here
+    const bool& getLost() { return lost_; }  // loss detection and pose recovery stay in the reference: never lost here
     int getTick() const { return mmf_fusion_tick(f_); }
     int getTimeDelta() { return refresh().time_delta; }
     float getMaxDepthProcessed() { return refresh().max_depth_processed; }
@@ -947,6 +987,8 @@ class MultiMotionFusion {
     bool flow_on_ = false;
     bool flow_inference_on_ = false;
     bool flow_seg_on_ = false;
+    bool fern_on_ = false;
+    std::unique_ptr<Ferns> ferns_;  // a view of the hook's engine
     mmf_flowseg_config flowseg_{};
     std::unique_ptr<tracker::PointTracker> tracker_;
     unsigned char* kp_rgb_ = nullptr;

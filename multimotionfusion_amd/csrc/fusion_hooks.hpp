@@ -1,7 +1,7 @@
 // fusion_hooks.hpp -- where a frame's segmentation comes from (callback, built-in CRF, the frame's label image) and the side
 // engines that run on streams of their own beside the tracking chains (super-pixel engine, optical flow, flow-CRF
-// inference): their setters and getters, fusion_crf_segment / fusion_mask_segment, and the frame_superpixels_* and
-// frame_flow_* stages of processFrame.  Textually included by mmf_hip.hip behind fusion_state.hpp.
+// inference, fern keyframe database): their setters and getters, fusion_crf_segment / fusion_mask_segment, and the
+// frame_superpixels_*, frame_flow_* and frame_ferns stages of processFrame.  Textually included by mmf_hip.hip behind fusion_state.hpp.
 #pragma once
 
 extern "C" int mmf_fusion_set_segmentation_callback(mmf_fusion* f, mmf_segmentation_fn fn, void* user) {
@@ -442,5 +442,59 @@ static int fusion_flow_segment(mmf_fusion* f, mmf_segmentation* out) {
     s.has_new_label = s.has_new_label && !f->fseg.cfg.inhibit_new ? 1 : 0;
     fusion_seg_result(f, s.has_new_label, f->fseg.models, out);
     f->fseg.last = s, f->fseg.has = true;
+    return MMF_OK;
+}
+
+// The fern keyframe database hook: cfg != NULL creates the fusion's own engine for its frame size (a second call replaces it:
+// an empty database), NULL frees it with its stream and events.  Off by default; while off no frame allocates, enqueues or
+// waits for anything of it.  The configuration and the table are checked before the device is touched.
+extern "C" int mmf_fusion_set_fern_database(mmf_fusion* f, const mmf_ferns_config* cfg, const int* table) {
+    MMF_REQUIRE(f != nullptr, "mmf_fusion_set_fern_database: null fusion object");
+    std::vector<int> own;
+    if (cfg) {
+        if (int rc = ferns_check_config(f->width, f->height, cfg, table, "mmf_fusion_set_fern_database")) return rc;
+        if (f->shard_world > 1) return fail(MMF_ERR_STATE, "mmf_fusion_set_fern_database: not available on a sharded fusion");
+        if (!f->models[0]->fill_in) return fail(MMF_ERR_STATE, "mmf_fusion_set_fern_database: the camera model has no fill-in images");
+        if (!table) {
+            own.resize((size_t)cfg->num * 6);
+            if (int rc = mmf_ferns_make_table(0ull, cfg->num, f->width / 8, f->height / 8, cfg->max_depth_mm, own.data())) return rc;
+            table = own.data();
+        }
+    }
+    MMF_HIP_TRY(hipSetDevice(f->ctx->device));
+    f->ferns.reset();
+    if (!cfg) return MMF_OK;
+    if (int rc = ferns_create_impl(f->ctx, f->width, f->height, cfg, table, &f->ferns.engine, "mmf_fusion_set_fern_database")) return rc;
+    const hipError_t e = f->ferns.lane.create();
+    if (e != hipSuccess) {
+        f->ferns.reset();
+        return fail(MMF_ERR_HIP, std::string("mmf_fusion_set_fern_database: ") + hipGetErrorString(e));
+    }
+    return MMF_OK;
+}
+extern "C" int mmf_fusion_last_fern_result(mmf_fusion* f, mmf_ferns_result_t* out) {
+    MMF_REQUIRE(f != nullptr && out != nullptr, "mmf_fusion_last_fern_result: null argument");
+    if (!f->ferns.engine) return fail(MMF_ERR_STATE, "mmf_fusion_last_fern_result: the fern database is off (mmf_fusion_set_fern_database)");
+    if (!f->ferns.has) return fail(MMF_ERR_STATE, "mmf_fusion_last_fern_result: no frame has run since the hook went on or the last reset");
+    return mmf_ferns_result(f->ferns.engine, out);
+}
+extern "C" mmf_ferns* mmf_fusion_fern_database(mmf_fusion* f) { return f ? f->ferns.engine : nullptr; }
+
+// processFerns() (MultiMotionFusion.cpp:824, :856-860) with the query of findFrame (:682-685) in front of it: process(FIND | ADD)
+// on the camera model's fill-in images, its pose and the frame's tick.  Behind the end-of-frame predict(): the lane opens on the
+// camera model's stream, where that prediction has just been enqueued; the fusion's stream joins the lane at the end of the
+// call, in front of whatever rewrites those images.
+static int frame_ferns(mmf_fusion* f) {
+    FusionModel* cam = f->models[0];
+    const mmf_model* m = cam->model;
+    float pose[16];
+    mmf_model_get_pose(cam->model, pose);
+    MMF_HIP_TRY(f->ferns.lane.open(cam->lane->stream));  // (pending: a frame that failed between the enqueue and the join)
+    MMF_HIP_TRY(f->ferns.lane.enter());
+    int rc = ferns_process_on(f->ferns.engine, m->fill_image, m->fill_vertex, m->fill_normal, pose, f->tick, MMF_FERNS_FIND | MMF_FERNS_ADD,
+                              f->ferns.lane.stream.get(), "mmf_fusion_process_frame (fern database)");
+    if (rc) return rc;
+    MMF_HIP_TRY(f->ferns.lane.close());
+    f->ferns.has = true;
     return MMF_OK;
 }

@@ -9,8 +9,9 @@
 // The segmentation is handed in per frame (mmf_segmentation: the reference's gSLICr + dense CRF), pulled through a
 // callback at the point where the reference calls performSegmentation (:412), computed from the frame's raw label image
 // (mask_kernels.hpp, mmf_fusion_set_mask_segmentation: the `frame.mask` branch of Segmentation.cpp:89-147, which comes
-// first as it does there) or by the built-in dense CRF (crf_kernels.hpp, mmf_fusion_set_crf_segmentation).  What stays
-// with the caller: relocalisation, ferns, deformation (closeLoops / reloc off).
+// first as it does there) or by the built-in dense CRF (crf_kernels.hpp, mmf_fusion_set_crf_segmentation).  Of relocalisation
+// the fern keyframe database runs here, off by default and observational (frame_ferns, mmf_fusion_set_fern_database); what
+// stays with the caller: pose recovery from a keyframe, loss detection, deformation (closeLoops / reloc off).
 //
 // MI355X mapping: every model owns a LANE (a child context: its own stream + reduction scratch), so the
 // latency-bound Gauss-Newton chains of different models (19 x two small launches each) overlap on the device;
@@ -223,6 +224,7 @@ struct FrameRun {
     bool superpixels = false;  // the super-pixel engine runs for this frame (its lane is open)
     bool flow = false;         // the optical-flow engine runs for this frame (its lane is open) ...
     bool flow_enqueued = false;  // ... and its launches are on the flow stream
+    bool ferns = false;        // the fern database ran for this frame (its lane is closed, not yet joined)
 
     // MMF_HOST_TRACE=1: where the calling thread is, in us after the call began (averages over 100 calls)
     void stamp(mmf_fusion* f, int i) const {
@@ -1121,11 +1123,17 @@ static int fusion_process_frame_impl(mmf_fusion* f, const mmf_frame* fr) {
     rc = frame_predict(f, r);
     if (rc) return rc;
     r.stamp(f, 4);
+    if (f->ferns.engine) {  // processFerns() (:824): behind predict(), with the tick the frame ran under
+        rc = frame_ferns(f);
+        if (rc) return rc;
+        r.ferns = true;
+    }
     f->tick++;  // :825
     frame_log_poses(f, r);
     rc = frame_end(f, r);
     if (rc) return rc;
     if (r.flow_enqueued) MMF_HIP_TRY(f->flow.lane.join(f->ctx->stream));
+    if (r.ferns) MMF_HIP_TRY(f->ferns.lane.join(f->ctx->stream));
     r.stamp(f, 5);
     if (r.host_trace && ++f->trace_calls % 100 == 0) {
         std::fprintf(stderr, "host us from call start: next image side enqueued %.0f, lanes waiting %.0f, preparation enqueued %.0f (batched chains), chains enqueued %.0f, "

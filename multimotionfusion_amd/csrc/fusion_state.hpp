@@ -131,6 +131,20 @@ struct FlowSegmentation {
     ~FlowSegmentation() { reset(); }
 };
 
+// the fern keyframe database (mmf_fusion_set_fern_database; ferns_host.hpp): behind the end-of-frame predict(), on a lane of
+// its own; observational.  Nothing exists while the hook is off
+struct FernHook {
+    mmf_ferns* engine = nullptr;  // owned
+    SideLane lane;                // begin: the camera model's fill-in images of this frame are complete
+    bool has = false;             // a frame has run since the hook went on / the last reset
+    void reset() {
+        ferns_destroy_on(engine, lane.stream.get());  // (once the context's stream and the lane have run dry)
+        engine = nullptr, has = false;
+        lane.reset();
+    }
+    ~FernHook() { reset(); }
+};
+
 // keypoint redetection of inactive models (MultiMotionFusion.cpp:489-559; redetect_host.hpp): off unless switched on
 struct Redetection {
     bool on = false;
@@ -296,6 +310,7 @@ struct mmf_fusion {
     FlowHook flow;         // the optical-flow hook
     FlowInference fi;      // the flow inference.  Behind `flow`: it is released before the flow engine and the flow's stream
     FlowSegmentation fseg; // the flow_crf mode: the blob stage behind the inference
+    FernHook ferns;        // the fern keyframe database
     std::vector<mmf_dense_restore> dense_restores;  // modeldb_host.hpp: per model of the last load call
     Redetection rd;        // redetection: view store, verifier, keypoint hand-over
     Keypoints kp;          // tracker, keypoint front end, view-pose log
@@ -508,6 +523,7 @@ extern "C" int mmf_fusion_set_shard(mmf_fusion* f, int rank, int world) {
     if (world > 1 && f->rd.on) return fail(MMF_ERR_STATE, "mmf_fusion_set_shard: redetection is on (sharded redetection is not supported)");
     if (world > 1 && f->rd.verifier_mode) return fail(MMF_ERR_STATE, "mmf_fusion_set_shard: the redetection verifier is on (not supported on a shard)");
     if (world > 1 && f->flow.engine) return fail(MMF_ERR_STATE, "mmf_fusion_set_shard: the optical-flow hook is on (not supported on a shard)");
+    if (world > 1 && f->ferns.engine) return fail(MMF_ERR_STATE, "mmf_fusion_set_shard: the fern database is on (not supported on a shard)");
     if (world > 1 && f->kp.backdate_history) return fail(MMF_ERR_STATE, "mmf_fusion_set_shard: track back-dating is on (not supported on a shard)");
     f->shard_rank = rank, f->shard_world = world;
     // models created ahead of their use (preallocateModels): the ones this rank will not own shrink to bookkeeping
@@ -666,6 +682,11 @@ extern "C" int mmf_fusion_reset(mmf_fusion* f) {
     if (f->flow.engine) {  // the next frame is the first of a sequence: it yields no flow
         (void)mmf_flow_reset(f->flow.engine);
         f->flow.has = f->fi.has = false;
+    }
+    if (f->ferns.engine) {  // the keyframes belonged to the map that ends here (every frame's lane has been joined by this stream)
+        int rc = ferns_reset_on(f->ferns.engine, f->ctx->stream);
+        if (rc) return rc;
+        f->ferns.has = false;
     }
     f->tick = 1;
     return MMF_OK;

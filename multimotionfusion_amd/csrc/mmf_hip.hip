@@ -1640,6 +1640,10 @@ extern "C" int mmf_debug_set_stamps(void* dev_buf) {
 #include "flowseg_kernels.hpp"
 #include "flowseg_host.hpp"
 
+// ---- the fern keyframe database (ferns_kernels.hpp, ferns_host.hpp; Core/Ferns.cpp) ----
+#include "ferns_kernels.hpp"
+#include "ferns_host.hpp"
+
 // =============================================================================================
 // Orchestrator: MultiMotionFusion::processFrame / predict (Core/MultiMotionFusion.cpp:207-854, 863-875)
 // =============================================================================================

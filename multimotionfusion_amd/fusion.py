@@ -404,6 +404,40 @@ class MultiMotionFusion:
         out["has_result"] = bool(has.value)
         return out
 
+    def setFernDatabase(self, config=True, table=None):
+        """the fern keyframe database (ferns.FernDatabase's engine): behind every frame's final predict() the
+        camera model's fill-in images are encoded, searched for the closest keyframe that is old enough, and added when they
+        differ enough from every keyframe -- on a stream of its own.  True: the reference's settings; a ferns.FernsConfig:
+        those; table: int32 [num, 6] ferns (None: ferns.make_table with seed 0); False / None (the default state): off, the
+        engine is freed.  Observational: poses, maps and masks do not depend on it."""
+        from .ferns import FernsConfig, _table_arg
+        if config is None or config is False:
+            check(self.ctx.lib.mmf_fusion_set_fern_database(self.handle, None, None))
+            self._ferns_cfg = None
+            return
+        cfg = FernsConfig() if config is True else config
+        tab = None if table is None else _table_arg(table, cfg.num)
+        check(self.ctx.lib.mmf_fusion_set_fern_database(self.handle, C.byref(cfg.c), None if tab is None else tab.ctypes.data_as(C.POINTER(C.c_int))))
+        self._ferns_cfg = cfg
+
+    def getLastFernResult(self):
+        """the database's record of the last frame as a dict (ferns.result_dict): added, dropped_total, count, good_codes,
+        add_minimum, closest, closest_dissim, closest_similarity, candidate, closest_pose, closest_time"""
+        from .ferns import result_dict
+        r = _capi.mmf_ferns_result_t()
+        check(self.ctx.lib.mmf_fusion_last_fern_result(self.handle, C.byref(r)))
+        return result_dict(r)
+
+    def getFernDatabase(self):
+        """the hook's engine, to read from (keyframe, download, result, last_launches); None while the hook is off.  The
+        handle belongs to the fusion: it is valid until the next setFernDatabase call."""
+        from .ferns import _Engine
+        h = self.ctx.lib.mmf_fusion_fern_database(self.handle)
+        cfg = getattr(self, "_ferns_cfg", None)
+        if not h or cfg is None:
+            return None
+        return _Engine(self.ctx, C.c_void_p(h), self.width, self.height, cfg.num, cfg.capacity)
+
     def getLastSegmentation(self):
         """segmentation.last() of this fusion: unaries, Q, raw and filtered maps, model data, range, B4 flag"""
         import torch
